@@ -9,10 +9,12 @@ GPU) owns its own frames (weak scaling); with N > 1 every step's results (left k
 descriptors, counts, mvuRight, mvDepth) are all-gathered over RCCL/xGMI, overlapped with the
 next step's compute.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").
+Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").  A plain run sets up, warms up, times the K steps and prints the
+headline; --full adds the CPU baseline, the other workloads, the oracle checks and the per-stage / roofline / end-to-end /
+tracking blocks.  --dump-outputs DIR writes what the last timed step computed as .npy files.
 """
 import argparse
 import importlib
@@ -238,9 +240,10 @@ def cpu_baseline(w, h, nf, stereo, budget_s=20.0):
     }
 
 
-def measure(fe, steps, warmup, ramp, world, dist, dev, torch):
-    """Ramp + warm-up + K timed steps of fe (barrier + synchronize on both sides, MAX over ranks) + an untimed
-    stage-profile pass.  Returns dict(dt, fast_ms, stage_ms, ncalls, match_ms, last_results)."""
+def measure(fe, steps, warmup, ramp, world, dist, dev, torch, full=True):
+    """Ramp + warm-up + K timed steps of fe (barrier + synchronize on both sides, MAX over ranks); full = True adds the FAST-stage
+    events inside the timed region, the long_run pass and an untimed stage-profile pass.  Returns dict(dt, fast_ms, stage_ms, ncalls,
+    match_ms, last_results); without `full` only dt and last are filled."""
     ex = fe.ex
     # clock ramp (untimed, not counted as warm-up steps): at least `ramp` steps AND at least half a second of GPU load - a box that
     # sat idle needs that long before the clocks hold (one fresh box in a dozen measured 9 % low behind a 0.13-s ramp)
@@ -256,7 +259,8 @@ def measure(fe, steps, warmup, ramp, world, dist, dev, torch):
     fe.drain()
     # Timed region: only the dominant kernel (the FAST stage: k_fast_strips) is bracketed by HIP events on its launch stream.  Every
     # recorded event idles the GPU for ~4.5 us, so the full stage breakdown is taken in a separate untimed pass below.
-    ex.set_profiling(3)     # the FAST stage of every 4th timed step (two events idle the GPU for ~9 us)
+    if full:
+        ex.set_profiling(3)     # the FAST stage of every 4th timed step (two events idle the GPU for ~9 us)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -272,6 +276,9 @@ def measure(fe, steps, warmup, ramp, world, dist, dev, torch):
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if not full:                                    # a plain run: the outputs of the last timed step, nothing else
+        return {"dt": dt, "fast_ms": None, "stage_ms": None, "ncalls": None, "match_ms": None,
+                "last": fe.results((warmup + steps - 1) % fe.ring.nbuf), "nprof": 0, "gathered": None, "long_run": None}
     fast_ms = float(ex.stage_ms()[0][1])            # FAST stage, averaged over the K timed steps
     # a short K (the driver's command: 20 steps = 13 ms) is one sample of a noisy quantity: the same loop once more over >= 100 steps,
     # reported beside `value` as `long_run` (never as `value`: the contract times exactly K steps)
@@ -539,6 +546,49 @@ def roofline_block(fe, m, workload, B, value, world, traffic_lookup=True):
     return roof, navg
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(fe, last, path, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what the timed path handed its caller in the LAST timed step (this rank's frames), as float32 .npy files in
+    `path`: keypoints [n, 7] (x, y, size, angle, response, octave, class_id), descriptors [n, 32] (byte values), keypoint_counts
+    [images] and, for stereo, mvuRight / mvDepth [n of the left images] and stereo_matches [frames].  Images run left 0..B-1, then
+    right 0..B-1; keypoints of consecutive images follow each other.  frames [frames dumped] names the frames: all of them, or a
+    fixed seeded sample when the whole step would exceed `limit` bytes.  Returns the file names written."""
+    imgs, st = last
+    B = fe.B
+    per_kp = 4 * (7 + 32 + (2 if fe.stereo else 0))
+    sides = 2 if fe.stereo else 1
+    nkp = [sum(len(imgs[s * B + b][0]) for s in range(sides)) for b in range(B)]
+    frames = list(range(B))
+    if sum(nkp) * per_kp + 16 * B > limit:
+        order = np.random.default_rng(0).permutation(B)
+        keep, tot = [], 0
+        for b in order:
+            if tot + nkp[b] * per_kp + 16 > limit:
+                break
+            keep.append(int(b))
+            tot += nkp[b] * per_kp + 16
+        frames = sorted(keep)
+    order = [s * B + b for s in range(sides) for b in frames]
+    kps = [imgs[i][0] for i in order]
+    out = {
+        "frames": np.array(frames, np.float32),
+        "keypoint_counts": np.array([len(k) for k in kps], np.float32),
+        "keypoints": np.concatenate([np.stack([k[f].astype(np.float32) for f in ("x", "y", "size", "angle", "response", "octave", "class_id")], 1)
+                                     .reshape(-1, 7) for k in kps]),
+        "descriptors": np.concatenate([imgs[i][1].astype(np.float32).reshape(-1, 32) for i in order]),
+    }
+    if fe.stereo:
+        out["mvuRight"] = np.concatenate([st[b][0].astype(np.float32) for b in frames])
+        out["mvDepth"] = np.concatenate([st[b][1].astype(np.float32) for b in frames])
+        out["stereo_matches"] = np.array([st[b][2] for b in frames], np.float32)
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(name + ".npy" for name in out)
+
+
 def launch_ranks(n):
     """`python bench.py --gpus N` without an outer launcher: start the N ranks as CHILD processes of torch.distributed.run (one
     per GPU, rendezvous on 127.0.0.1 at a free port) with this command line, relay what they print - rank 0's single JSON line
@@ -585,6 +635,14 @@ def main():
     ap.add_argument("--total-frames", type=int, default=0,
                     help="T > 0: ONE batch of T frames per step sharded over the ranks (batching.shard_range), i.e. strong "
                          "scaling; BASELINE config 4 = --workload mono_1920x1080_4000feat --total-frames 512 --gpus 8")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the CPU baseline, the other workloads, the oracle checks, the roofline / stage "
+                         "breakdown (FAST-stage events in the timed steps, an untimed stage-profile pass), long_run, end_to_end and the "
+                         "tracking front end; the --no-* options below leave parts of it out.  Without it a run sets up, warms up, times "
+                         "the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (keypoints, descriptors, counts, mvuRight, mvDepth; float32 .npy, "
+                         "at most 64 MB) into DIR")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-gather", action="store_true", help="skip the result all-gather when N > 1")
     ap.add_argument("--force-gather", action="store_true",
@@ -626,6 +684,10 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (default); gloo only to rehearse N > 1 on a box with fewer GPUs than ranks")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    full = args.full
+    verify = full and not args.no_verify
     os.environ["ORBX_TEST_GAUSS_FLAVOUR"] = args.gauss_flavour      # the oracle that checks the run, spawned workers and ranks included
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
@@ -656,7 +718,7 @@ def main():
     left, right = make_frames(w, h, B, seed0, stereo, workers, kind)
     seeds = [seed0 + i for i in range(B)]
     others = []
-    if world == 1 and not args.no_other_workloads and not strong and args.streams == 1:
+    if full and world == 1 and not args.no_other_workloads and not strong and args.streams == 1:
         for name, ob in OTHER_WORKLOADS:
             if name == args.workload:
                 continue
@@ -670,7 +732,7 @@ def main():
                 oseeds = [5000 + i for i in range(ob)]
             others.append((name, ob, ol, orr, oseeds))
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if full and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(w, h, nf, stereo)
 
     pkg = importlib.import_module("orb_slam2v2-1_amd")
@@ -729,7 +791,8 @@ def main():
                            gather_via_host=(args.backend != "nccl"), prefetch=not args.no_prefetch, lag_stereo=not args.no_lag_stereo, gather_B=gB,
                            stereo_late=(args.stereo_order == "late"), fast_alone=args.fast_alone, force_gather=force_gather)
     fe.upload(left, right)
-    m = measure(fe, args.steps, args.warmup, args.ramp_steps, world, dist, dev, torch)
+    m = measure(fe, args.steps, args.warmup, args.ramp_steps, world, dist, dev, torch, full=full)
+    dumped = dump_outputs(fe, m["last"], args.dump_outputs) if args.dump_outputs and rank == 0 else None
     gather_leg = measure_gather_leg(fe, torch) if force_gather else None
     dt, stage_ms = m["dt"], m["stage_ms"]
 
@@ -749,9 +812,9 @@ def main():
             fe3.step(i)
         fe3.drain()
         dt3 = time.perf_counter() - t3
-        bad3 = [] if args.no_verify else verify_against_oracle(fe3, fe3.results((args.steps - 1) % 3), seeds, [0, B - 1])
+        bad3 = verify_against_oracle(fe3, fe3.results((args.steps - 1) % 3), seeds, [0, B - 1]) if verify else []
         overlapped = {"streams": 3, "value": round(B * args.steps / dt3, 2), "unit": "frames/s",
-                      "ms_per_step": round(dt3 / args.steps * 1e3, 4), "steps": args.steps, "verified": (None if args.no_verify else not bad3),
+                      "ms_per_step": round(dt3 / args.steps * 1e3, 4), "steps": args.steps, "verified": (not bad3 if verify else None),
                       "note": "independent steps alternate over 3 handles on 3 streams; kernels share the GPU, so "
                               "per-kernel durations are not isolated - informational, not the headline value"}
         del fe3
@@ -769,9 +832,12 @@ def main():
     if rank == 0:
         frames_per_step = args.total_frames if strong else world * B
         value = frames_per_step * args.steps / dt
-        roof, navg = roofline_block(fe, m, args.workload, B, value, world)
-        verified, vnote = None, "skipped (--no-verify)"
-        if not args.no_verify:
+        if full:
+            roof, navg = roofline_block(fe, m, args.workload, B, value, world)
+        else:
+            roof, navg = None, float(np.mean([len(k) for k, _ in m["last"][0]]))
+        verified, vnote = None, "skipped (--no-verify)" if full else "skipped (the oracle check runs with --full)"
+        if verify:
             vf = sorted({0, B // 2, B - 1})
             bad = verify_against_oracle(fe, m["last"], seeds, vf, kind)
             verified = not bad
@@ -779,7 +845,7 @@ def main():
                      "bit for bit, angles within 1e-4%s" % (vf, ", mvuRight / mvDepth / match counts bit for bit" if stereo else "")
                      ) if verified else "; ".join(bad[:5])
         gathered_verified, gnote = None, None
-        if m["gathered"] is not None and not args.no_verify:
+        if m["gathered"] is not None and verify:
             pick = (lambda nb: range(nb)) if args.verify_all_gathered else (lambda nb: sorted({0, nb - 1}))
             gbad, nchk = verify_gathered(fe, m["gathered"], ranks, pick, kind)
             gathered_verified = not gbad
@@ -807,40 +873,45 @@ def main():
                        "world_size_observed": world_seen, "ranks": ranks,
                        "avg_keypoints_per_image": round(navg, 1), "gauss_flavour": args.gauss_flavour,
                        "handle_options": handle_options},
-            "roofline": roof,
-            "long_run": None if m.get("long_run") is None else {
-                "steps": m["long_run"][0], "value": round(B * m["long_run"][0] / m["long_run"][1], 2), "unit": "frames/s",
-                "ms_per_step": round(m["long_run"][1] / m["long_run"][0] * 1e3, 4),
-                "note": "the same loop over 100 steps right after the timed region (K < 100 is a short sample); informational, not `value`"},
-            "stage_ms_per_call": {"pyramid": round(float(stage_ms[0]), 4), "fast": round(float(stage_ms[1]), 4),
-                                  "quadtree": round(float(stage_ms[2]), 4), "describe": round(float(stage_ms[3]), 4),
-                                  "extract_total": round(float(stage_ms[4]), 4), "stereo_match": round(m["match_ms"], 4),
-                                  "images_per_call": fe.nimg, "calls_averaged": m["ncalls"],
-                                  "fast_timed_region": round(m["fast_ms"], 4),
-                                  "note": "stage breakdown from an untimed pass of %d steps after the timed region, every stage alone on the GPU "
-                                          "(in the timed steps %s on a side stream behind the FAST stage of step i, beside its gather / quad-tree / descriptor "
-                                          "kernels - and the matcher beside the next FAST stage -, which makes those longer and the step shorter than the sum here); "
-                                          "roofline.kernel_ms is the FAST stage (%s) over the %d timed steps" % (
-                                              m["nprof"], "the stereo matcher of step i-1 and the pyramid of step i+1 run" if fe.lag else
-                                              "the pyramid of step i+1 runs" if fe.prefetch else "nothing runs", roof["kernel"], args.steps)},
         }
-        if world == 1 and S == 1 and not args.no_end_to_end:
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped}
+        if full:
+            out.update({
+                "roofline": roof,
+                "long_run": None if m.get("long_run") is None else {
+                    "steps": m["long_run"][0], "value": round(B * m["long_run"][0] / m["long_run"][1], 2), "unit": "frames/s",
+                    "ms_per_step": round(m["long_run"][1] / m["long_run"][0] * 1e3, 4),
+                    "note": "the same loop over 100 steps right after the timed region (K < 100 is a short sample); informational, not `value`"},
+                "stage_ms_per_call": {"pyramid": round(float(stage_ms[0]), 4), "fast": round(float(stage_ms[1]), 4),
+                                      "quadtree": round(float(stage_ms[2]), 4), "describe": round(float(stage_ms[3]), 4),
+                                      "extract_total": round(float(stage_ms[4]), 4), "stereo_match": round(m["match_ms"], 4),
+                                      "images_per_call": fe.nimg, "calls_averaged": m["ncalls"],
+                                      "fast_timed_region": round(m["fast_ms"], 4),
+                                      "note": "stage breakdown from an untimed pass of %d steps after the timed region, every stage alone on the GPU "
+                                              "(in the timed steps %s on a side stream behind the FAST stage of step i, beside its gather / quad-tree / descriptor "
+                                              "kernels - and the matcher beside the next FAST stage -, which makes those longer and the step shorter than the sum here); "
+                                              "roofline.kernel_ms is the FAST stage (%s) over the %d timed steps" % (
+                                                  m["nprof"], "the stereo matcher of step i-1 and the pyramid of step i+1 run" if fe.lag else
+                                                  "the pyramid of step i+1 runs" if fe.prefetch else "nothing runs", roof["kernel"], args.steps)},
+            })
+        if full and world == 1 and S == 1 and not args.no_end_to_end:
             # beside the headline (never `value`): the step fed from host memory, PCIe both ways inside the clock
             fe2 = fe      # the same front end (its results were captured above); a second handle's streams measured 10-15 % slower here
             dte, laste = measure_end_to_end(fe2, left, right, args.steps, 10, torch)
-            bade = [] if args.no_verify else verify_against_oracle(fe2, laste, seeds, sorted({0, B - 1}), kind)
+            bade = verify_against_oracle(fe2, laste, seeds, sorted({0, B - 1}), kind) if verify else []
             up = fe2.nimg * w * h
             down = sum(t.numel() * t.element_size() for t in fe2._hs.out[0].values())
             out["end_to_end"] = {
                 "value": round(B * args.steps / dte, 2), "unit": "frames/s", "ms_per_step": round(dte / args.steps * 1e3, 4), "steps": args.steps,
                 "h2d_bytes_per_step": up, "d2h_bytes_per_step": down, "h2d_GBps": round(up * args.steps / dte / 1e9, 2),
-                "d2h_GBps": round(down * args.steps / dte / 1e9, 2), "verified": None if args.no_verify else not bade,
+                "d2h_GBps": round(down * args.steps / dte / 1e9, 2), "verified": not bade if verify else None,
                 "note": "frames start in PINNED host memory and results (keypoints, descriptors, counts, mvuRight, mvDepth at full "
                         "capacity) end in pinned host memory; one hipMemcpyAsync per camera and batch on an upload stream, three image "
                         "buffers in HBM, downloads on a third stream, all overlapped with the kernels of the neighbouring batches; the host "
                         "waits for the results of step i - 3 before it submits batch i + 2; clock from the first upload to the last "
                         "result's arrival.  NOT the headline value (which starts with frames in HBM)"}
-        if world == 1 and not args.no_tracking and args.workload.startswith("kitti_stereo_1241x376_1000"):
+        if full and world == 1 and not args.no_tracking and args.workload.startswith("kitti_stereo_1241x376_1000"):
             try:
                 out["tracking_front_end"] = tracking_front_end()
             except Exception as e:      # a broken side block must not take the headline line with it
@@ -862,7 +933,7 @@ def main():
                 oval = ob * osteps / om["dt"]
                 oroof, onavg = roofline_block(ofe, om, name, ob, oval, 1, traffic_lookup=False)
                 okind = "natural" if name in NATURAL else "dense"
-                obad = [] if args.no_verify else verify_against_oracle(ofe, om["last"], oseeds, [0, ob - 1], okind)
+                obad = verify_against_oracle(ofe, om["last"], oseeds, [0, ob - 1], okind) if verify else []
                 ow_out[name] = {"value": round(oval, 2), "unit": "frames/s" if ost else "images/s", "frames_per_step": ob,
                                 "steps": osteps, "repeats": "value / ms_per_step: the BETTER of 2 runs of %d steps; value_mean_of_2 / ms_per_step_mean_of_2: their mean" % osteps,
                                 "ms_per_step": round(om["dt"] / osteps * 1e3, 4),
@@ -871,7 +942,7 @@ def main():
                                 "roofline_frac": oroof["frac"], "pipeline_frac": oroof["pipeline_frac"],
                                 "avg_keypoints_per_image": round(onavg, 1),
                                 "stage_ms_alone": {k: round(float(v), 4) for k, v in zip(("pyramid", "fast", "quadtree", "describe"), om["stage_ms"][:4])},
-                                "verified": None if args.no_verify else not obad}
+                                "verified": not obad if verify else None}
                 if okind == "natural":
                     # the corner-sparse workload with and without k_fast_strips' exact row pre-test (developer knob 16 = 1: off)
                     pkg.set_default_option(16, 1)

@@ -32,7 +32,7 @@ def _run_bench(nranks, extra, timeout=900):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nranks), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(nranks), "--backend", "gloo",
-           "--no-cpu-baseline", "--ramp-steps", "0", "--gen-workers", "6", "--verify-all-gathered"] + extra
+           "--no-cpu-baseline", "--ramp-steps", "0", "--gen-workers", "6", "--verify-all-gathered", "--full"] + extra
     p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout, text=True)
     assert p.returncode == 0, "bench.py failed (%d)\n%s\n%s" % (p.returncode, p.stdout[-2000:], p.stderr[-4000:])
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -70,7 +70,7 @@ def test_bench_self_launch_two_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--ramp-steps", "0", "--gen-workers", "6"]
+           "--full", "--no-cpu-baseline", "--ramp-steps", "0", "--gen-workers", "6"]
     p = subprocess.run(cmd + ["--batch", "8"], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, text=True)
     assert p.returncode == 0, "bench.py failed (%d)\n%s\n%s" % (p.returncode, p.stdout[-2000:], p.stderr[-4000:])
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

@@ -39,7 +39,7 @@ def test_pipelined_step_all_gather_over_rccl_one_rank_rotating_batches():
 def test_bench_force_gather_line():
     out = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-gather", "--batch", "16", "--steps", "7", "--warmup", "2",
                 "--ramp-steps", "0", "--no-cpu-baseline", "--no-other-workloads", "--no-tracking", "--no-end-to-end", "--gen-workers", "6",
-                "--verify-all-gathered"])
+                "--verify-all-gathered", "--full"])
     cfg = out["config"]
     assert out["n_gpus"] == 1 and "RCCL" in cfg["parallelism"] and "one-rank" in cfg["parallelism"], cfg["parallelism"]
     assert out["verified"] is True, out["verified_note"]

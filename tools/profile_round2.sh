@@ -1,13 +1,14 @@
 #!/bin/bash
 # second half of profile_round.sh alone (kernel stats + PMC passes), for when the bench line is already there
 set -e
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$GRAFT_REPO_ROOT/gpurun_out
 ( while sleep 45; do date >> $out/heartbeat.log; done ) &
 hb=$!
 trap "kill $hb 2>/dev/null" EXIT
 cd /tmp && export TMPDIR=/tmp
 rm -rf $out/prof_bench
-timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_bench -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-other-workloads --no-verify --gen-workers 1 > $out/prof_bench.log 2>&1
+timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_bench -- python3 $root/bench.py --full --no-cpu-baseline --no-other-workloads --no-verify --gen-workers 1 > $out/prof_bench.log 2>&1
 cp $(ls $out/prof_bench/*/*kernel_stats.csv | head -1) $out/kernel_stats.csv
 python3 $GRAFT_REPO_ROOT/tools/step_timeline.py $out/prof_bench 3 > $out/step_timeline.txt
 rm -f $out/prof_bench/*/*kernel_trace.csv

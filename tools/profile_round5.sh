@@ -6,9 +6,9 @@ set -e
 out=$GRAFT_REPO_ROOT/gpurun_out
 cd $GRAFT_REPO_ROOT
 if [ "$1" = "1" ]; then
-python3 bench.py > $out/r05_bench.json 2> $out/r05_bench.err
-python3 bench.py --steps 20 --warmup 5 > $out/r05_bench_20_steps.json 2> $out/r05_bench_20_steps.err
-python3 bench.py --force-gather --no-cpu-baseline --no-other-workloads --no-tracking --no-end-to-end > $out/r05_bench_force_gather_rccl.json 2> $out/r05_bench_force_gather.err
+python3 bench.py --full > $out/r05_bench.json 2> $out/r05_bench.err
+python3 bench.py --full --steps 20 --warmup 5 > $out/r05_bench_20_steps.json 2> $out/r05_bench_20_steps.err
+python3 bench.py --full --force-gather --no-cpu-baseline --no-other-workloads --no-tracking --no-end-to-end > $out/r05_bench_force_gather_rccl.json 2> $out/r05_bench_force_gather.err
 PMC=1 SQ=1 PMC_WORKLOAD=kitti_stereo_1241x376_1000feat PMC_BATCH=64 PMC_IMAGES=128 bash tools/profile_workload.sh r05_headline --workload kitti_stereo_1241x376_1000feat
 else
 PMC=1 SQ=1 PMC_WORKLOAD=mono_1920x1080_4000feat PMC_BATCH=64 PMC_IMAGES=64 bash tools/profile_workload.sh r05_fullhd --workload mono_1920x1080_4000feat --batch 64
