@@ -44,6 +44,35 @@ int orbm_debug_features_in_area(const orbx_keypoint_t *kun, int n, const orbm_gr
  * host angles in [0, 2 pi]; the descriptor kernel uses exactly this routine. */
 int orbx_debug_sincosf(const float *angles, int n, float *sin_out, float *cos_out, int device);
 
+/* Which code the matchers of the calling host thread ran (the size thresholds of the guided searches and of the stereo matcher pick
+ * different kernels, LDS plans and fall-backs; the results never depend on the choice, so only these hooks can tell them apart).
+ * orbm_debug_match_path: the last guided search of this thread (orbm_search_for_initialization, orbm_search_by_projection_mp / _frame
+ * (+ _device), orbm_search_local_points (+ _device), orbm_match_windows): out[0] = the resolver that produced the result
+ * (ORBM_PATH_RES_*), out[1] = why the fast path fell back to the exact kernels (ORBM_PATH_FB_*), out[2] = the dynamic LDS bytes the
+ * fast path's resolver requested (0: it launched none).  A call that returned before any kernel (no queries, no keypoints, an
+ * argument error) leaves RES_NONE. */
+#define ORBM_PATH_RES_NONE 0
+#define ORBM_PATH_RES_PAR_Q2 1   /* k_resolve_par, 2 queries per thread (m <= 2048) */
+#define ORBM_PATH_RES_PAR_Q4 2   /* k_resolve_par, 4 queries per thread (2048 < m <= 4096) */
+#define ORBM_PATH_RES_WAVE 3     /* the single-wave speculative resolvers (k_resolve_mp / _frame / _windows / _init) */
+#define ORBM_PATH_RES_EXACT 4    /* the exact one-workgroup kernels */
+#define ORBM_PATH_FB_NONE 0
+#define ORBM_PATH_FB_N 1         /* n > 30000 keypoints */
+#define ORBM_PATH_FB_INIT_SIZE 2 /* SearchForInitialization: n2 > 7000 or n1 > 65535 (LDS plan of k_resolve_init) */
+#define ORBM_PATH_FB_CAND_CAP 3  /* a query had more than CAND_CAP (512) candidates */
+#define ORBM_PATH_FB_QK 4        /* a query ran out of its QK (8) kept candidates */
+#define ORBM_PATH_FB_LDS 5       /* hipFuncSetAttribute or the launch of k_resolve_par was refused */
+#define ORBM_PATH_FB_OPTION 6    /* ORBM_OPT_EXACT_KERNELS */
+int orbm_debug_match_path(int64_t *out);
+/* The plan of the fast path, launching nothing: mode 0 = SearchByProjection(F, MPs), 1 = SearchByProjection(cur, last), 2 = projected
+ * windows, 3 = SearchForInitialization (m = n1, n = n2); for the thread's resolver option and the device.  out[0] = ORBM_PATH_RES_*
+ * (EXACT: the fast path falls back before its resolver), out[1] = the resolver's dynamic LDS bytes, out[2] = the static LDS of that
+ * kernel instance (hipFuncGetAttributes), out[3] = the device's LDS limit per workgroup. */
+int orbm_debug_resolve_plan(int mode, int m, int n, int device, int64_t *out);
+/* The last stereo matcher call of this thread (orbm_stereo, orbm_stereo_batch_device(_prev), orbx_stereo_frame(_view)):
+ * out[0] = the median / finish step kept the SAD values in LDS (cap <= SM_LDS_CAP), out[1] = bhShift, out[2] = nbins (row bins of
+ * level 0), out[3] = 1 iff a left keypoint of that call had more than ST_CAND candidates and restarted its list. */
+int orbm_debug_stereo_path(int32_t *out);
 
 #ifdef __cplusplus
 }

@@ -53,7 +53,11 @@ EXPORTS = [
 ]
 # what include/orbx_dev.h declares on top: exported by the developer build only
 DEV_EXPORTS = ["orbx_debug_level_points", "orbx_debug_sincosf", "orbx_debug_blur_patches", "orbm_debug_features_in_area",
-               "orbx_debug_blurred_level", "orbx_debug_octree_fallbacks"]
+               "orbx_debug_blurred_level", "orbx_debug_octree_fallbacks", "orbm_debug_match_path", "orbm_debug_resolve_plan",
+               "orbm_debug_stereo_path"]
+# include/orbx_dev.h: ORBM_PATH_RES_* / ORBM_PATH_FB_* (orbm_debug_match_path, orbm_debug_resolve_plan)
+RES_NONE, RES_PAR_Q2, RES_PAR_Q4, RES_WAVE, RES_EXACT = 0, 1, 2, 3, 4
+FB_NONE, FB_N, FB_INIT_SIZE, FB_CAND_CAP, FB_QK, FB_LDS, FB_OPTION = 0, 1, 2, 3, 4, 5, 6
 
 
 class OrbxError(RuntimeError):
@@ -179,6 +183,12 @@ def lib(developer=False):
     return _lib
 
 
+def matcher_lib():
+    """The library the matcher functions of this module call: the developer build while default_developer is True (`hooks` fixture),
+    so that the path hooks below and orbm_set_thread_option act on the library that ran the call (both are per library)."""
+    return lib(default_developer)
+
+
 def _load(path, dev):
     if not os.path.exists(path):
         raise OrbxError(ORBX_ERR_NO_DEVICE, "HIP library %s is missing: run `python __graft_entry__.py` "
@@ -260,6 +270,9 @@ def _load(path, dev):
         L.orbx_debug_octree_fallbacks.argtypes = [vp, vp, i32]
         L.orbx_debug_blurred_level.argtypes = [vp, i32, i32, vp, i32, vp]
         L.orbm_debug_features_in_area.argtypes = [vp, i32, C.POINTER(GridGeom), f32, f32, f32, i32, i32, vp, C.POINTER(i32), i32]
+        L.orbm_debug_match_path.argtypes = [vp]
+        L.orbm_debug_resolve_plan.argtypes = [i32, i32, i32, i32, vp]
+        L.orbm_debug_stereo_path.argtypes = [vp]
     L.orbx_last_error.restype = C.c_char_p
     L.orbx_version.restype = C.c_char_p
     L._orbx_developer = bool(dev)
@@ -268,7 +281,7 @@ def _load(path, dev):
 
 def _check(rc, L=None):
     if rc != 0:
-        raise OrbxError(rc, (L or lib()).orbx_last_error().decode())
+        raise OrbxError(rc, (L or matcher_lib()).orbx_last_error().decode())
 
 
 def _p(a):
@@ -569,6 +582,28 @@ def debug_features_in_area(kun, geom, x, y, r, min_level=-1, max_level=-1, devic
     return out[:n.value].copy()
 
 
+def debug_match_path():
+    """Test hook: what the last guided search of this thread ran in the developer build -> (resolver RES_*, fall-back FB_*, dynamic LDS)."""
+    out = np.zeros(3, np.int64)
+    _check(lib(True).orbm_debug_match_path(_p(out)), lib(True))
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def debug_resolve_plan(mode, m, n, device=0):
+    """Test hook, launches nothing: the fast path's resolver for mode (0 map points, 1 last frame, 2 windows, 3 initialization), m queries
+    and n keypoints -> (resolver RES_*, dynamic LDS, static LDS of that kernel, the device's LDS limit per workgroup)."""
+    out = np.zeros(4, np.int64)
+    _check(lib(True).orbm_debug_resolve_plan(int(mode), int(m), int(n), int(device), _p(out)), lib(True))
+    return tuple(int(v) for v in out)
+
+
+def debug_stereo_path():
+    """Test hook: the last stereo matcher call of this thread in the developer build -> (useLds, bhShift, nbins, restarted)."""
+    out = np.zeros(4, np.int32)
+    _check(lib(True).orbm_debug_stereo_path(_p(out)), lib(True))
+    return tuple(int(v) for v in out)
+
+
 def debug_sincosf(angles, device=0):
     """Test hook: the device's cosf / sinf restatement -> (sin, cos) float32 arrays."""
     a = np.ascontiguousarray(angles, np.float32)
@@ -586,9 +621,10 @@ def stereo_batch_device(ex_left, ex_right, B, left_slot0, right_slot0, d_kl, d_d
                         mbf, mb, d_uright, d_depth, d_nmatch, stream=0, prev=False):
     """Device-resident Frame::ComputeStereoMatches for B frames (raw device pointers).  prev: on the pyramids of the
     extraction call before the last one (orbm_stereo_batch_device_prev)."""
-    fn = lib().orbm_stereo_batch_device_prev if prev else lib().orbm_stereo_batch_device
+    L = ex_left._L   # (the handles belong to one build of the library)
+    fn = L.orbm_stereo_batch_device_prev if prev else L.orbm_stereo_batch_device
     _check(fn(ex_left._h, ex_right._h, B, left_slot0, right_slot0, d_kl, d_dl, d_nl, d_kr, d_dr, d_nr, cap, float(mbf), float(mb),
-              d_uright, d_depth, d_nmatch, stream))
+              d_uright, d_depth, d_nmatch, stream), L)
 
 
 def compute_stereo_matches(ex_left, ex_right, kl, dl, kr, dr, mbf, mb):
@@ -596,13 +632,13 @@ def compute_stereo_matches(ex_left, ex_right, kl, dl, kr, dr, mbf, mb):
 
     ex_left / ex_right must have just extracted the left / right image (their pyramids are
     read on the device)."""
-    L = lib()
+    L = ex_left._L   # (the handles belong to one build of the library)
     kl = np.ascontiguousarray(kl, KP_DTYPE); kr = np.ascontiguousarray(kr, KP_DTYPE)
     dl = np.ascontiguousarray(dl, np.uint8); dr = np.ascontiguousarray(dr, np.uint8)
     ur = np.full(len(kl), -1, np.float32); dp = np.full(len(kl), -1, np.float32)
     n = C.c_int(0)
     _check(L.orbm_stereo(ex_left._h, ex_right._h, _p(kl), _p(dl), len(kl), _p(kr), _p(dr), len(kr),
-                         float(mbf), float(mb), _p(ur), _p(dp), C.byref(n)))
+                         float(mbf), float(mb), _p(ur), _p(dp), C.byref(n)), L)
     return ur, dp, n.value
 
 
@@ -621,7 +657,7 @@ class ORBmatcher:
     def DescriptorDistance(a, b):
         a = np.ascontiguousarray(a, np.uint8); b = np.ascontiguousarray(b, np.uint8)
         assert a.size == 32 and b.size == 32
-        return lib().orbm_hamming(_p(a), _p(b))
+        return matcher_lib().orbm_hamming(_p(a), _p(b))
 
     def SearchForInitialization(self, k1, d1, k2, d2, geom2, vbPrevMatched, windowSize=10):
         """(src/ORBmatcher.cc:405-520) -> (nmatches, vnMatches12, vbPrevMatched')"""
@@ -630,7 +666,7 @@ class ORBmatcher:
         prev = np.ascontiguousarray(vbPrevMatched, np.float32).copy()
         m12 = np.full(len(k1), -1, np.int32)
         n = C.c_int(0)
-        _check(lib().orbm_search_for_initialization(_p(k1), _p(d1), len(k1), _p(k2), _p(d2), len(k2), C.byref(geom2),
+        _check(matcher_lib().orbm_search_for_initialization(_p(k1), _p(d1), len(k1), _p(k2), _p(d2), len(k2), C.byref(geom2),
                                                     _p(prev), _p(m12), int(windowSize), self.mfNNratio,
                                                     int(self.mbCheckOrientation), self.device, C.byref(n)))
         return n.value, m12, prev
@@ -644,7 +680,7 @@ class ORBmatcher:
         fm = np.ascontiguousarray(frame_mp, np.int32).copy()
         eo = None if ext_obs is None else np.ascontiguousarray(ext_obs, np.int32)
         n = C.c_int(0)
-        _check(lib().orbm_search_by_projection_mp(_p(kun), _p(desc), _p(uright), len(kun), C.byref(geom), _p(sf),
+        _check(matcher_lib().orbm_search_by_projection_mp(_p(kun), _p(desc), _p(uright), len(kun), C.byref(geom), _p(sf),
                                                   len(sf), _p(mps), _p(mp_desc), len(mps), _p(fm), _p(eo), float(th),
                                                   self.mfNNratio, self.device, C.byref(n)))
         return n.value, fm
@@ -660,7 +696,7 @@ class ORBmatcher:
         cm = np.ascontiguousarray(cur_mp, np.int32).copy()
         eo = None if ext_obs is None else np.ascontiguousarray(ext_obs, np.int32)
         n = C.c_int(0)
-        _check(lib().orbm_search_by_projection_frame(_p(kun), _p(desc), _p(uright), len(kun), C.byref(geom), _p(sf),
+        _check(matcher_lib().orbm_search_by_projection_frame(_p(kun), _p(desc), _p(uright), len(kun), C.byref(geom), _p(sf),
                                                      len(sf), C.byref(cam), _p(Tc), _p(Tl), _p(last), _p(last_desc),
                                                      len(last), _p(cm), _p(eo), float(th), int(bMono),
                                                      int(self.mbCheckOrientation), self.device, C.byref(n)))
@@ -677,7 +713,7 @@ def search_by_projection_frame_device(d_kun, d_desc, d_uright, n, geom, scale_fa
     cm = np.ascontiguousarray(cur_mp, np.int32).copy()
     eo = None if ext_obs is None else np.ascontiguousarray(ext_obs, np.int32)
     nm = C.c_int(0)
-    _check(lib().orbm_search_by_projection_frame_device(d_kun, d_desc, d_uright, int(n), C.byref(geom), _p(sf), len(sf), C.byref(cam),
+    _check(matcher_lib().orbm_search_by_projection_frame_device(d_kun, d_desc, d_uright, int(n), C.byref(geom), _p(sf), len(sf), C.byref(cam),
                                                         _p(Tc), _p(Tl), _p(last), d_last_desc, len(last), _p(cm), _p(eo), float(th),
                                                         int(bMono), int(check_orientation), int(device), C.byref(nm), stream))
     return nm.value, cm
@@ -693,7 +729,7 @@ def search_local_points_device(d_kun, d_desc, d_uright, n, geom, sf, pts, mp_des
     eo = None if ext_obs is None else np.ascontiguousarray(ext_obs, np.int32)
     proj = np.zeros(len(pts), MP_DTYPE)
     nm = C.c_int(0)
-    _check(lib().orbm_search_local_points_device(d_kun, d_desc, d_uright, int(n), C.byref(geom), _p(sf), len(sf), _p(pts), _p(md),
+    _check(matcher_lib().orbm_search_local_points_device(d_kun, d_desc, d_uright, int(n), C.byref(geom), _p(sf), len(sf), _p(pts), _p(md),
                                                  len(pts), _p(T), C.byref(cam), float(viewing_cos_limit), _p(thr), _p(fm), _p(eo),
                                                  float(th), float(nnratio), int(device), C.byref(nm), _p(proj), stream))
     return nm.value, fm, proj
@@ -709,7 +745,7 @@ def match_windows(kun, desc, uright, geom, queries, query_desc, holder, ext_bloc
     h = np.ascontiguousarray(holder, np.int32).copy()
     eb = None if ext_blocks is None else np.ascontiguousarray(ext_blocks, np.int32)
     n = C.c_int(0)
-    _check(lib().orbm_match_windows(_p(kun), _p(desc), _p(ur), len(kun), C.byref(geom),
+    _check(matcher_lib().orbm_match_windows(_p(kun), _p(desc), _p(ur), len(kun), C.byref(geom),
                                     None if geom_assign is None else C.byref(geom_assign), _p(q), _p(qd), len(q), _p(h),
                                     _p(eb), int(max_dist), int(check_orientation), int(device), C.byref(n)))
     return n.value, h
@@ -722,7 +758,7 @@ def best_in_windows(kun, desc, uright, geom, queries, query_desc, inv_level_sigm
     q = np.ascontiguousarray(queries, WINDOW_DTYPE); qd = np.ascontiguousarray(query_desc, np.uint8)
     s2 = None if inv_level_sigma2 is None else np.ascontiguousarray(inv_level_sigma2, np.float32)
     bi = np.full(len(q), -1, np.int32); bd = np.full(len(q), 256, np.int32)
-    _check(lib().orbm_best_in_windows(_p(kun), _p(desc), _p(ur), len(kun), C.byref(geom),
+    _check(matcher_lib().orbm_best_in_windows(_p(kun), _p(desc), _p(ur), len(kun), C.byref(geom),
                                       None if geom_assign is None else C.byref(geom_assign), _p(q), _p(qd), len(q), _p(s2),
                                       0 if s2 is None else len(s2), _p(bi), _p(bd), int(device)))
     return bi, bd
@@ -734,7 +770,7 @@ def distinctive_descriptors(desc, offsets, device=0):
     off = np.ascontiguousarray(offsets, np.int32)
     m = len(off) - 1
     br = np.zeros(m, np.int32); bm = np.zeros(m, np.int32)
-    _check(lib().orbm_distinctive_descriptors(_p(desc), _p(off), m, _p(br), _p(bm), int(device)))
+    _check(matcher_lib().orbm_distinctive_descriptors(_p(desc), _p(off), m, _p(br), _p(bm), int(device)))
     return br, bm
 
 
@@ -745,7 +781,7 @@ WORLDPOINT_DTYPE = np.dtype([("valid", "<i4"), ("wx", "<f4"), ("wy", "<f4"), ("w
 def predict_scale_thresholds(log_scale_factor, nlevels):
     """orbm_predict_scale_thresholds (host code, no GPU): MapPoint::PredictScale as nlevels-1 float thresholds"""
     t = np.zeros(max(nlevels - 1, 1), np.float32)
-    _check(lib().orbm_predict_scale_thresholds(float(log_scale_factor), int(nlevels), _p(t)))
+    _check(matcher_lib().orbm_predict_scale_thresholds(float(log_scale_factor), int(nlevels), _p(t)))
     return t[:nlevels - 1]
 
 
@@ -754,7 +790,7 @@ def is_in_frustum(pts, Tcw, cam, geom, viewing_cos_limit, thresholds, nlevels, d
     pts = np.ascontiguousarray(pts, WORLDPOINT_DTYPE); T = np.ascontiguousarray(Tcw, np.float32)
     thr = np.ascontiguousarray(thresholds, np.float32)
     out = np.zeros(len(pts), MP_DTYPE)
-    _check(lib().orbm_is_in_frustum(_p(pts), len(pts), _p(T), C.byref(cam), C.byref(geom), float(viewing_cos_limit), _p(thr),
+    _check(matcher_lib().orbm_is_in_frustum(_p(pts), len(pts), _p(T), C.byref(cam), C.byref(geom), float(viewing_cos_limit), _p(thr),
                                     int(nlevels), _p(out), int(device)))
     return out
 
@@ -770,7 +806,7 @@ def search_local_points(kun, desc, uright, geom, sf, pts, mp_desc, Tcw, cam, vie
     eo = None if ext_obs is None else np.ascontiguousarray(ext_obs, np.int32)
     proj = np.zeros(len(pts), MP_DTYPE)
     n = C.c_int(0)
-    _check(lib().orbm_search_local_points(_p(kun), _p(desc), _p(ur), len(kun), C.byref(geom), _p(sf), len(sf), _p(pts), _p(md),
+    _check(matcher_lib().orbm_search_local_points(_p(kun), _p(desc), _p(ur), len(kun), C.byref(geom), _p(sf), len(sf), _p(pts), _p(md),
                                           len(pts), _p(T), C.byref(cam), float(viewing_cos_limit), _p(thr), _p(fm), _p(eo),
                                           float(th), float(nnratio), int(device), C.byref(n), _p(proj)))
     return n.value, fm, proj

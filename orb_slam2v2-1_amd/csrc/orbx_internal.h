@@ -190,6 +190,12 @@ int fast_best_in_windows(const orbx_keypoint_t *kun, const uint8_t *desc, const 
 int fast_distinctive_descriptors(const uint8_t *desc, const int32_t *offsets, int npoints, int32_t *best_row,
                                  int32_t *best_median, int device);
 extern thread_local int t_matchExact;   // orbm_set_thread_option(ORBM_OPT_EXACT_KERNELS): this thread's guided searches take the exact one-workgroup kernels
+// What the last guided search / stereo call of this host thread ran (codes: ORBM_PATH_* of include/orbx_dev.h); written by both builds,
+// read by the developer build's orbm_debug_match_path / orbm_debug_stereo_path
+struct MatchPath { int resolver, fallback; long long lds; };
+struct StereoPath { int useLds, bhShift, nbins, device; };
+extern thread_local MatchPath t_matchPath;
+extern thread_local StereoPath t_stereoPath;
 
 // XCD-aware block -> (image, block-in-image) map for grids of (blocks per image, images).  Workgroups are dealt round-robin
 // to the 8 XCDs in linear-id order and every XCD has its own L2, so with the identity map neighbouring blocks - which

@@ -20,6 +20,10 @@
 thread_local int t_matchExact = 0;
 thread_local int t_matchResolver = 0;
 thread_local int t_matchStreamSync = 0;
+thread_local MatchPath t_matchPath = {ORBM_PATH_RES_NONE, ORBM_PATH_FB_NONE, 0};
+thread_local StereoPath t_stereoPath = {0, 0, 0, -1};
+// a guided search starts its path record (include/orbx_dev.h: orbm_debug_match_path); the fast path and the exact kernels fill it in
+static inline void path_begin() { t_matchPath = {ORBM_PATH_RES_NONE, t_matchExact ? ORBM_PATH_FB_OPTION : ORBM_PATH_FB_NONE, 0}; }
 extern "C" int orbm_set_thread_option(int key, int value) {
     if ((key != ORBM_OPT_EXACT_KERNELS && key != ORBM_OPT_RESOLVER && key != ORBM_OPT_STREAM_SYNC) || (value != 0 && value != 1)) { orbx_set_error("orbm_set_thread_option: key %d / value %d", key, value); return ORBX_ERR_ARG; }
     (key == ORBM_OPT_EXACT_KERNELS ? t_matchExact : key == ORBM_OPT_RESOLVER ? t_matchResolver : t_matchStreamSync) = value;
@@ -180,6 +184,9 @@ __global__ __launch_bounds__(SB_T) void k_stereo_bins(StereoLevels lv, const orb
 // one wave per left keypoint: row-band candidate test (:498-508, :535), level and
 // disparity-range tests (:548-553), Hamming argmin (first minimum in iR order, :558-562),
 // then the 11x11 SAD over 11 shifts (:577-607), parabola (:613-620), disparity (:623-636).
+#ifdef ORBX_DEVELOPER
+__device__ int g_stRestart;   // developer build: a left keypoint of the last call restarted its candidate list (orbm_debug_stereo_path)
+#endif
 __global__ __launch_bounds__(64 * ST_WAVES) void k_stereo_match(
     StereoLevels lv, const uint8_t *__restrict__ pyrL, size_t pyrImgL, const uint8_t *__restrict__ pyrR,
     size_t pyrImgR, const orbx_keypoint_t *__restrict__ kl, const uint8_t *__restrict__ dl,
@@ -240,6 +247,9 @@ __global__ __launch_bounds__(64 * ST_WAVES) void k_stereo_match(
             const u64 m = __ballot(pass);
             if (m) {
                 if (cnt + __popcll(m) > ST_CAND) {   // list full (wave-uniform): score what is staged, start over
+#ifdef ORBX_DEVELOPER
+                    if (lane == 0) atomicOr(&g_stRestart, 1);
+#endif
                     wave_sync();
                     for (int c = lane; c < cnt; c += 64) {
                         const int jR = cl[c];
@@ -577,11 +587,17 @@ static int stereo_batch_impl(orbx_extractor_t *hl, orbx_extractor_t *hr, int B, 
     hipStream_t st = (hipStream_t)stream;  // NULL = the HIP default (null) stream
     dim3 grid((cap + ST_WAVES - 1) / ST_WAVES, B);
     (void)hipGetLastError();
+    const int useLds = cap <= SM_LDS_CAP;
+    t_stereoPath = {useLds, bhShift, nbins, hl->device};
+#ifdef ORBX_DEVELOPER
+    void *restartFlag = nullptr;
+    ORBX_HIP(hipGetSymbolAddress(&restartFlag, HIP_SYMBOL(g_stRestart)));
+    ORBX_HIP(hipMemsetAsync(restartFlag, 0, sizeof(int), st));
+#endif
     hipLaunchKernelGGL(k_stereo_bins, dim3(B), dim3(SB_T), 0, st, lv, d_kr, hl->st_rc, d_nr, cap, bhShift, nbins, hl->st_binStart, hl->st_items);
     hipLaunchKernelGGL(k_stereo_match, grid, dim3(64 * ST_WAVES), 0, st, lv, pyrL + (size_t)left_slot0 * hl->pyrImgBytes, hl->pyrImgBytes,
                        pyrR + (size_t)right_slot0 * hr->pyrImgBytes, hr->pyrImgBytes, d_kl, d_dl, d_nl, d_kr, d_dr, d_nr, cap, mbf, mb, d_uright, d_depth,
                        hl->st_sad, hl->st_rc, hl->st_binStart, hl->st_items, bhShift, nbins);
-    const int useLds = cap <= SM_LDS_CAP;
     if (finish_rec)   // one frame, latency path: median step + the whole record to pinned host memory, one launch
     {
         const int uBegin = finish_tail_only ? (120 * cap) >> 4 : 0;
@@ -788,6 +804,20 @@ extern "C" int orbm_debug_features_in_area(const orbx_keypoint_t *kun, int n, co
     *n_out = (int)v.size();
     return ORBX_OK;
 }
+extern "C" int orbm_debug_match_path(int64_t *out) {
+    if (!out) { orbx_set_error("orbm_debug_match_path: bad arguments"); return ORBX_ERR_ARG; }
+    out[0] = t_matchPath.resolver; out[1] = t_matchPath.fallback; out[2] = t_matchPath.lds;
+    return ORBX_OK;
+}
+extern "C" int orbm_debug_stereo_path(int32_t *out) {
+    if (!out || t_stereoPath.device < 0) { orbx_set_error("orbm_debug_stereo_path: bad arguments or no stereo call on this thread"); return ORBX_ERR_ARG; }
+    ORBX_HIP(hipSetDevice(t_stereoPath.device));
+    ORBX_HIP(hipDeviceSynchronize());   // (the callers have waited for their results already; the flag is read behind every stream)
+    int restarted = 0;
+    ORBX_HIP(hipMemcpyFromSymbol(&restarted, HIP_SYMBOL(g_stRestart), sizeof(int), 0, hipMemcpyDeviceToHost));
+    out[0] = t_stereoPath.useLds; out[1] = t_stereoPath.bhShift; out[2] = t_stereoPath.nbins; out[3] = restarted;
+    return ORBX_OK;
+}
 #endif   // ORBX_DEVELOPER
 
 // ---- SearchForInitialization: one workgroup, F1 keypoints in order (the steal / gate on
@@ -872,12 +902,14 @@ extern "C" int orbm_search_for_initialization(const orbx_keypoint_t *k1, const u
         return ORBX_ERR_ARG;
     }
     *nmatches = 0;
+    path_begin();
     if (n1 == 0) return ORBX_OK;
     if (!t_matchExact && n2 > 0) {
         const int frc = fast_search_for_initialization(k1, d1, n1, k2, d2, n2, g2, prev_matched, matches12, window, nnratio,
                                                        check_orientation, device, nmatches);
         if (frc <= 0) return frc;  // done or error; > 0: exact fallback below
     }
+    t_matchPath.resolver = ORBM_PATH_RES_EXACT;
     StagePlan pl;
     const size_t o_k1 = pl.take(sizeof(orbx_keypoint_t) * n1), o_d1 = pl.take((size_t)32 * n1), o_k2 = pl.take(sizeof(orbx_keypoint_t) * n2),
                  o_d2 = pl.take((size_t)32 * n2), o_prev = pl.take(sizeof(float) * 2 * n1);
@@ -1018,6 +1050,7 @@ static int search_local_points_impl(const orbx_keypoint_t *kun, const uint8_t *d
         return ORBX_ERR_ARG;
     }
     *nmatches = 0;
+    path_begin();
     if (m == 0) return ORBX_OK;
     std::vector<orbm_mappoint_t> tmp;
     if (!proj_out) { tmp.resize(m); proj_out = tmp.data(); }
@@ -1032,6 +1065,7 @@ static int search_local_points_impl(const orbx_keypoint_t *kun, const uint8_t *d
         if (rc) return rc;
     }
     if (frc <= 0) return frc;
+    t_matchPath.resolver = ORBM_PATH_RES_EXACT;
     return exact_search_by_projection_mp(kun, desc, uright, n, g, scale_factors, nlevels, proj_out, mp_desc, m, frame_mp, ext_obs,
                                          th, nnratio, device, nmatches, dev);
 }
@@ -1066,6 +1100,7 @@ extern "C" int orbm_search_by_projection_mp(const orbx_keypoint_t *kun, const ui
         return ORBX_ERR_ARG;
     }
     *nmatches = 0;
+    path_begin();
     if (n == 0 || m == 0) return ORBX_OK;
     for (int i = 0; i < m; i++)
         if (mps[i].in_view && (mps[i].level < 0 || mps[i].level >= nlevels)) {
@@ -1077,6 +1112,7 @@ extern "C" int orbm_search_by_projection_mp(const orbx_keypoint_t *kun, const ui
                                                      frame_mp, ext_obs, th, nnratio, device, nmatches);
         if (frc <= 0) return frc;
     }
+    t_matchPath.resolver = ORBM_PATH_RES_EXACT;
     return exact_search_by_projection_mp(kun, desc, uright, n, g, scale_factors, nlevels, mps, mp_desc, m, frame_mp, ext_obs,
                                          th, nnratio, device, nmatches);
 }
@@ -1241,6 +1277,7 @@ static int search_by_projection_frame_impl(const orbx_keypoint_t *kun, const uin
         return ORBX_ERR_ARG;
     }
     *nmatches = 0;
+    path_begin();
     if (n == 0 || nlast == 0) return ORBX_OK;
     for (int i = 0; i < nlast; i++)
         if (last[i].has_mp && (last[i].octave < 0 || last[i].octave >= nlevels)) {
@@ -1253,6 +1290,7 @@ static int search_by_projection_frame_impl(const orbx_keypoint_t *kun, const uin
                                                         check_orientation, device, nmatches, dev);
         if (frc <= 0) return frc;
     }
+    t_matchPath.resolver = ORBM_PATH_RES_EXACT;
     StagePlan pl;   // dev: kun / desc / uright / last_desc are device arrays, used in place
     const size_t o_k = pl.take(dev ? 0 : sizeof(orbx_keypoint_t) * n), o_d = pl.take(dev ? 0 : (size_t)32 * n), o_u = pl.take(dev ? 0 : 4 * (size_t)n),
                  o_sf = pl.take(4 * (size_t)nlevels), o_T = pl.take(4 * 32), o_l = pl.take(sizeof(orbm_lastpoint_t) * nlast),
@@ -1421,6 +1459,7 @@ extern "C" int orbm_match_windows(const orbx_keypoint_t *kun, const uint8_t *des
         return ORBX_ERR_ARG;
     }
     *nmatches = 0;
+    path_begin();
     if (n == 0 || m == 0) return ORBX_OK;
     for (int i = 0; i < n; i++)
         if (holder[i] < -2 || holder[i] >= m) { orbx_set_error("holder[%d] = %d out of range", i, holder[i]); return ORBX_ERR_ARG; }
@@ -1429,6 +1468,7 @@ extern "C" int orbm_match_windows(const orbx_keypoint_t *kun, const uint8_t *des
                                            check_orientation, device, nmatches);
         if (frc <= 0) return frc;
     }
+    t_matchPath.resolver = ORBM_PATH_RES_EXACT;
     StagePlan pl;
     const size_t o_k = pl.take(sizeof(orbx_keypoint_t) * n), o_d = pl.take((size_t)32 * n), o_q = pl.take(sizeof(orbm_window_query_t) * m),
                  o_qd = pl.take((size_t)32 * m), o_u = pl.take(uright ? 4 * (size_t)n : 0), o_eb = pl.take(ext_blocks ? 4 * (size_t)n : 0),

@@ -3,6 +3,7 @@
 // sequential resolution).
 #pragma once
 #include "orbx_internal.h"
+#include "orbx_dev.h"   // (the ORBM_PATH_* codes of the path record)
 #include <limits.h>
 
 #define TH_HIGH 100

@@ -20,6 +20,8 @@
 #include <stdlib.h>
 #include <time.h>
 #include <algorithm>
+#include <atomic>
+#include <mutex>
 
 #define QK 8
 #define CAND_CAP 512  // candidates staged per query in LDS before the top-QK selection
@@ -211,7 +213,7 @@ __global__ __launch_bounds__(64) void k_resolve_mp(const u64 *__restrict__ keys,
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     __builtin_amdgcn_wave_barrier();
     int nm = 0;
-    bool overflow = false;
+    int overflow = 0;   // bit 0: a query had more than CAND_CAP candidates, bit 1: one ran out of its QK (out[1])
     u64 kn[QK];   // the next chunk's queries, requested a chunk ahead (see k_resolve_frame)
     int ncn = 0, obsn = 0;
     auto fetch = [&](int q) {
@@ -229,7 +231,7 @@ __global__ __launch_bounds__(64) void k_resolve_mp(const u64 *__restrict__ keys,
         for (int r = 0; r < QK; r++) k[r] = kn[r];
         const int nc = qi < m ? ncn : 0, obs = obsn;
         if (c0 + 64 < m) fetch(c0 + 64 + lane);   // wave-uniform
-        if (nc > CAND_CAP) overflow = true;  // k_cand dropped candidates: its top-QK is not trustworthy
+        if (nc > CAND_CAP) overflow |= 1;  // k_cand dropped candidates: its top-QK is not trustworthy
         u64 pending = __ballot(qi < m && nc > 0);
         while (pending) {
             const bool act = (pending >> lane) & 1ull;
@@ -256,7 +258,7 @@ __global__ __launch_bounds__(64) void k_resolve_mp(const u64 *__restrict__ keys,
             const u64 cm = __ballot(conflict);
             const u64 commit = cm ? (pending & ((1ull << __builtin_ctzll(cm)) - 1ull)) : pending;
             const bool mineCommits = (commit >> lane) & 1ull;
-            if (mineCommits && ranout) overflow = true;
+            if (mineCommits && ranout) overflow |= 2;
             if (mineCommits && accept) {
                 frame_mp[best] = qi;       // :122
                 if (obs > 0) blocked[best] = 1;
@@ -268,8 +270,8 @@ __global__ __launch_bounds__(64) void k_resolve_mp(const u64 *__restrict__ keys,
         }
     }
     nm = wave_sum_i32(nm);
-    const u64 ov = __ballot(overflow);
-    if (lane == 0) { out[0] = nm; out[1] = ov ? 1 : 0; }
+    const int ov = (__ballot(overflow & 1) ? 1 : 0) | (__ballot(overflow & 2) ? 2 : 0);
+    if (lane == 0) { out[0] = nm; out[1] = ov; }
 }
 
 // ---- B2. SearchForInitialization: resolution  (src/ORBmatcher.cc:433-512)
@@ -291,13 +293,13 @@ __global__ __launch_bounds__(64) void k_resolve_init(const u64 *__restrict__ key
     __builtin_amdgcn_wave_barrier();
     const float factor = 1.0f / HISTO_LENGTH;
     int nm = 0;
-    bool overflow = false;
+    int overflow = 0;   // bit 0: a query had more than CAND_CAP candidates, bit 1: one ran out of its QK (out[1])
     for (int c0 = 0; c0 < n1; c0 += 64) {
         const int qi = c0 + lane;
         int nc = 0;
         if (qi < n1) nc = ncand[qi];
         const u64 *kl = keys + (size_t)(qi < n1 ? qi : 0) * CAND_CAP;  // whole candidate list, sorted
-        if (nc > CAND_CAP) overflow = true;
+        if (nc > CAND_CAP) overflow |= 1;
         nc = min(nc, CAND_CAP);
         int resume = 0;  // entries before the current best stay gated for good: re-decisions resume there
         u64 pending = __ballot(qi < n1 && nc > 0);
@@ -322,7 +324,7 @@ __global__ __launch_bounds__(64) void k_resolve_init(const u64 *__restrict__ key
             const u64 cm = __ballot(conflict);
             const u64 commit = cm ? (pending & ((1ull << __builtin_ctzll(cm)) - 1ull)) : pending;
             const bool mineCommits = (commit >> lane) & 1ull;
-            if (mineCommits && ranout) overflow = true;
+            if (mineCommits && ranout) overflow |= 2;
             if (mineCommits && accept) {
                 const int old = m21[best];
                 if (old >= 0) { m12[old] = -1; nm--; }   // steal (:463-467)
@@ -355,8 +357,8 @@ __global__ __launch_bounds__(64) void k_resolve_init(const u64 *__restrict__ key
     for (int i = lane; i < n1; i += 64)
         if (m12[i] >= 0) { prev[2 * i] = k2[m12[i]].x; prev[2 * i + 1] = k2[m12[i]].y; }
     nm = wave_sum_i32(nm);
-    const u64 ov = __ballot(overflow);
-    if (lane == 0) { out[0] = nm; out[1] = ov ? 1 : 0; }
+    const int ov = (__ballot(overflow & 1) ? 1 : 0) | (__ballot(overflow & 2) ? 2 : 0);
+    if (lane == 0) { out[0] = nm; out[1] = ov; }
 }
 
 // ---- B3. SearchByProjection(cur, last): resolution  (src/ORBmatcher.cc:1399-1469)
@@ -377,7 +379,7 @@ __global__ __launch_bounds__(64) void k_resolve_frame(const u64 *__restrict__ ke
     __builtin_amdgcn_wave_barrier();
     const float factor = 1.0f / HISTO_LENGTH;
     int nm = 0, nh = 0;
-    bool overflow = false;
+    int overflow = 0;   // bit 0: a query had more than CAND_CAP candidates, bit 1: one ran out of its QK (out[1])
     // a chunk's queries are requested one chunk ahead: the wave is alone in its workgroup, and with the loads at the head of the
     // chunk every 64 queries waited for a memory round trip of their own (2000 queries: 32 x 1.6 us of a 53-us kernel)
     u64 kn[QK];
@@ -400,7 +402,7 @@ __global__ __launch_bounds__(64) void k_resolve_frame(const u64 *__restrict__ ke
         const int nc = qi < nlast ? ncn : 0, obs = obsn;
         const float ang = angn;
         if (c0 + 64 < nlast) fetch(c0 + 64 + lane);   // wave-uniform
-        if (nc > CAND_CAP) overflow = true;
+        if (nc > CAND_CAP) overflow |= 1;
         u64 pending = __ballot(qi < nlast && nc > 0);
         while (pending) {
             const bool act = (pending >> lane) & 1ull;
@@ -417,7 +419,7 @@ __global__ __launch_bounds__(64) void k_resolve_frame(const u64 *__restrict__ ke
             const u64 cm = __ballot(conflict);
             const u64 commit = cm ? (pending & ((1ull << __builtin_ctzll(cm)) - 1ull)) : pending;
             const bool mineCommits = (commit >> lane) & 1ull;
-            if (mineCommits && ranout) overflow = true;
+            if (mineCommits && ranout) overflow |= 2;
             const bool doit = mineCommits && accept;
             const u64 dm = __ballot(doit);
             if (doit) {
@@ -451,8 +453,8 @@ __global__ __launch_bounds__(64) void k_resolve_frame(const u64 *__restrict__ ke
         }
     }
     nm = wave_sum_i32(nm);
-    const u64 ov = __ballot(overflow);
-    if (lane == 0) { out[0] = nm; out[1] = ov ? 1 : 0; }
+    const int ov = (__ballot(overflow & 1) ? 1 : 0) | (__ballot(overflow & 2) ? 2 : 0);
+    if (lane == 0) { out[0] = nm; out[1] = ov; }
 }
 
 // ---- B4. generic projected-window matcher: resolution (top-1, any blocking holder; :1539-1570)
@@ -473,7 +475,7 @@ __global__ __launch_bounds__(64) void k_resolve_windows(const u64 *__restrict__ 
     __builtin_amdgcn_wave_barrier();
     const float factor = 1.0f / HISTO_LENGTH;
     int nm = 0, nh = 0;
-    bool overflow = false;
+    int overflow = 0;   // bit 0: a query had more than CAND_CAP candidates, bit 1: one ran out of its QK (out[1])
     for (int c0 = 0; c0 < m; c0 += 64) {
         const int qi = c0 + lane;
         u64 k[QK];
@@ -486,7 +488,7 @@ __global__ __launch_bounds__(64) void k_resolve_windows(const u64 *__restrict__ 
 #pragma unroll
             for (int r = 0; r < QK; r++) k[r] = keys[(size_t)qi * QK + r];
         }
-        if (nc > CAND_CAP) overflow = true;
+        if (nc > CAND_CAP) overflow |= 1;
         u64 pending = __ballot(qi < m && nc > 0);
         while (pending) {
             const bool act = (pending >> lane) & 1ull;
@@ -503,7 +505,7 @@ __global__ __launch_bounds__(64) void k_resolve_windows(const u64 *__restrict__ 
             const u64 cm = __ballot(conflict);
             const u64 commit = cm ? (pending & ((1ull << __builtin_ctzll(cm)) - 1ull)) : pending;
             const bool mineCommits = (commit >> lane) & 1ull;
-            if (mineCommits && ranout) overflow = true;
+            if (mineCommits && ranout) overflow |= 2;
             const bool doit = mineCommits && accept;
             const u64 dm = __ballot(doit);
             if (doit) {
@@ -537,8 +539,8 @@ __global__ __launch_bounds__(64) void k_resolve_windows(const u64 *__restrict__ 
         }
     }
     nm = wave_sum_i32(nm);
-    const u64 ov = __ballot(overflow);
-    if (lane == 0) { out[0] = nm; out[1] = ov ? 1 : 0; }
+    const int ov = (__ballot(overflow & 1) ? 1 : 0) | (__ballot(overflow & 2) ? 2 : 0);
+    if (lane == 0) { out[0] = nm; out[1] = ov; }
 }
 
 // ---- B'. the resolution as a FIXED POINT, by one workgroup of RP_T threads instead of one wave (round 5).
@@ -578,7 +580,7 @@ __global__ __launch_bounds__(RP_T) void k_resolve_par(const u64 *__restrict__ ke
     // (the candidates live in LDS, not in registers: 4 queries x 8 candidates per thread beside the decision's own state spilled)
     int nc[RP_Q], blk[RP_Q], claim[RP_Q];
     float ang[RP_Q];
-    bool overflow = false;
+    int overflow = 0;   // bit 0: a query had more than CAND_CAP candidates, bit 1: one ran out of its QK (out[1])
 #pragma unroll
     for (int r = 0; r < RP_Q; r++) {
         const int qi = tid + r * RP_T;
@@ -600,7 +602,7 @@ __global__ __launch_bounds__(RP_T) void k_resolve_par(const u64 *__restrict__ ke
             }
             ((uint4 *)(cq + (size_t)QK * qi))[0] = make_uint4(e[0], e[1], e[2], e[3]);
             ((uint4 *)(cq + (size_t)QK * qi))[1] = make_uint4(e[4], e[5], e[6], e[7]);
-            if (nc[r] > CAND_CAP) overflow = true;   // k_cand dropped candidates: its top-QK is not trustworthy
+            if (nc[r] > CAND_CAP) overflow |= 1;   // k_cand dropped candidates: its top-QK is not trustworthy
         }
     }
     __shared__ int hnw[RP_T / 64][32];
@@ -691,7 +693,7 @@ __global__ __launch_bounds__(RP_T) void k_resolve_par(const u64 *__restrict__ ke
 #pragma unroll
     for (int r = 0; r < RP_Q; r++) {
         bin[r] = -1;
-        if (ranout[r]) overflow = true;
+        if (ranout[r]) overflow |= 2;
         if (claim[r] >= 0) {
             atomicMax(&bt[claim[r]], (uint32_t)(tid + r * RP_T) + 1u);
             nm++;
@@ -742,7 +744,8 @@ __global__ __launch_bounds__(RP_T) void k_resolve_par(const u64 *__restrict__ ke
     }
     nm = wave_sum_i32(nm);
     if ((tid & 63) == 0 && nm) atomicAdd(&sh_nm, nm);
-    if (__ballot(overflow) && (tid & 63) == 0) sh_ov = 1;
+    const int ovw = (__ballot(overflow & 1) ? 1 : 0) | (__ballot(overflow & 2) ? 2 : 0);
+    if (ovw && (tid & 63) == 0) atomicOr(&sh_ov, ovw);
     // (a system-scope fence in every wave costs ~0.3 us each and they serialise: +4 us on this kernel.  The results go to UNCACHED host
     // memory: once a wave's stores are acknowledged - s_waitcnt vmcnt(0) - they are on the host; one wave then fences and signals.)
     if (doneFlag) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // my stores into the pinned mirror have arrived before the barrier ...
@@ -1054,24 +1057,87 @@ static int arena_wait(hipStream_t st, int seq) {
 }
 static inline int resolve_par_q(int m) { return m <= 2 * RP_T ? 2 : 4; }
 static inline size_t resolve_par_lds(int m, int n) { return sizeof(uint32_t) * ((size_t)QK * RP_T * resolve_par_q(m) + 2 * (size_t)n + (size_t)(n + 31) / 32); }
-static inline bool use_resolve_par(int m, int n) { return t_matchResolver == 0 && m <= RP_T * RP_QMAX && n <= 30000 && resolve_par_lds(m, n) <= 158 * 1024; }
-#define RESOLVE_PAR_LAUNCH(MODE, M_, ...)                                                                                   \
-    do {                                                                                                                  \
-        const size_t lds_ = resolve_par_lds((M_), n);                                                                     \
-        if (resolve_par_q(M_) == 2) {                                                                                     \
-            if (lds_ > 48 * 1024) ORBX_HIP(hipFuncSetAttribute((const void *)k_resolve_par<MODE, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_)); \
-            hipLaunchKernelGGL((k_resolve_par<MODE, 2>), dim3(1), dim3(RP_T), lds_, st, __VA_ARGS__);                     \
-        } else {                                                                                                          \
-            if (lds_ > 48 * 1024) ORBX_HIP(hipFuncSetAttribute((const void *)k_resolve_par<MODE, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_)); \
-            hipLaunchKernelGGL((k_resolve_par<MODE, 4>), dim3(1), dim3(RP_T), lds_, st, __VA_ARGS__);                     \
-        }                                                                                                                 \
-    } while (0)
+static inline size_t resolve_wave_lds(int n) { return 2 * (size_t)((n + 15) & ~15); }   // k_resolve_mp / _frame / _windows: blocked[n] + claim table[n]
+static inline size_t resolve_init_lds(int n2) { return sizeof(int32_t) * 2 * (size_t)n2 + (size_t)((n2 + 15) & ~15); }
+static const void *resolve_par_fn(int mode, int q) {
+    static const void *const fn[3][2] = {{(const void *)k_resolve_par<0, 2>, (const void *)k_resolve_par<0, 4>},
+                                         {(const void *)k_resolve_par<1, 2>, (const void *)k_resolve_par<1, 4>},
+                                         {(const void *)k_resolve_par<2, 2>, (const void *)k_resolve_par<2, 4>}};
+    return fn[mode][q == 4];
+}
+// LDS budget of k_resolve_par: a workgroup gets the device's per-workgroup LDS limit, and every instance takes its static __shared__
+// arrays out of that before the dynamic part (the dynamic budget is limit - static, per instance).  Queried once per device and instance.
+#define RP_MAX_DEVICES 64
+struct RpBudget { size_t limit, stat[3][2]; };
+static RpBudget g_rpBudget[RP_MAX_DEVICES];
+static std::atomic<int> g_rpBudgetState[RP_MAX_DEVICES];   // 0: not queried, 1: valid, -1: a query failed (no k_resolve_par on this device)
+static std::mutex g_rpBudgetMutex;
+static const RpBudget *resolve_par_budget(int device) {
+    if (device < 0 || device >= RP_MAX_DEVICES) return nullptr;
+    int state = g_rpBudgetState[device].load(std::memory_order_acquire);
+    if (state == 0) {
+        std::lock_guard<std::mutex> lock(g_rpBudgetMutex);
+        state = g_rpBudgetState[device].load(std::memory_order_relaxed);
+        if (state == 0) {
+            RpBudget b = {};
+            int cur = -1, lim = 0, optin = 0;
+            bool ok = hipGetDevice(&cur) == hipSuccess && hipSetDevice(device) == hipSuccess &&
+                      hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, device) == hipSuccess;
+            if (ok && hipDeviceGetAttribute(&optin, hipDeviceAttributeSharedMemPerBlockOptin, device) != hipSuccess) optin = 0;
+            b.limit = (size_t)std::max(lim, optin);
+            for (int mode = 0; ok && mode < 3; mode++)
+                for (int qi = 0; ok && qi < 2; qi++) {
+                    hipFuncAttributes fa;
+                    ok = hipFuncGetAttributes(&fa, resolve_par_fn(mode, qi ? 4 : 2)) == hipSuccess;
+                    b.stat[mode][qi] = ok ? fa.sharedSizeBytes : 0;
+                }
+            if (cur >= 0) (void)hipSetDevice(cur);
+            (void)hipGetLastError();
+            g_rpBudget[device] = b;
+            state = ok && b.limit > 0 ? 1 : -1;
+            g_rpBudgetState[device].store(state, std::memory_order_release);
+        }
+    }
+    return state == 1 ? &g_rpBudget[device] : nullptr;
+}
+// the dynamic LDS k_resolve_par<mode, Q(m)> may request on this device (0: none)
+static size_t resolve_par_dyn_max(int mode, int m, int device) {
+    const RpBudget *b = resolve_par_budget(device);
+    if (!b) return 0;
+    const size_t st = b->stat[mode][resolve_par_q(m) == 4];
+    return b->limit > st ? b->limit - st : 0;
+}
+static inline bool use_resolve_par(int mode, int m, int n, int device) {
+    return t_matchResolver == 0 && m <= RP_T * RP_QMAX && n <= 30000 && resolve_par_lds(m, n) <= resolve_par_dyn_max(mode, m, device);
+}
+// Launch k_resolve_par<MODE, Q(m)>.  ORBX_FAST_FALLBACK when the runtime refuses the LDS size or the launch (the error is cleared:
+// the caller waits for the kernels in front and lets the exact kernels run); a negative error when a launch in front failed.
+template <int MODE, typename... Args>
+static int resolve_par_launch(int m, int n, hipStream_t st, Args... args) {
+    ORBX_HIP(hipGetLastError());
+    const int q = resolve_par_q(m);
+    const size_t lds = resolve_par_lds(m, n);
+    if (lds > 48 * 1024 && hipFuncSetAttribute(resolve_par_fn(MODE, q), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        (void)hipGetLastError();
+        return ORBX_FAST_FALLBACK;
+    }
+    if (q == 2) hipLaunchKernelGGL((k_resolve_par<MODE, 2>), dim3(1), dim3(RP_T), lds, st, args...);
+    else hipLaunchKernelGGL((k_resolve_par<MODE, 4>), dim3(1), dim3(RP_T), lds, st, args...);
+    if (hipGetLastError() != hipSuccess) return ORBX_FAST_FALLBACK;
+    t_matchPath.resolver = q == 2 ? ORBM_PATH_RES_PAR_Q2 : ORBM_PATH_RES_PAR_Q4;
+    t_matchPath.lds = (long long)lds;
+    return ORBX_OK;
+}
+// out[1] of a resolver -> the fall-back reason of the path record
+static inline int resolve_fallback(int ov) { return (ov & 1) ? ORBM_PATH_FB_CAND_CAP : ORBM_PATH_FB_QK; }
+static inline void path_wave(size_t lds) { t_matchPath.resolver = ORBM_PATH_RES_WAVE; t_matchPath.lds = (long long)lds; }
+static inline int path_fallback(int reason) { t_matchPath.fallback = reason; return ORBX_FAST_FALLBACK; }
 
 // Returns ORBX_OK (results written), ORBX_FAST_FALLBACK, or a negative error.
 int fast_search_for_initialization(const orbx_keypoint_t *k1, const uint8_t *d1, int n1, const orbx_keypoint_t *k2,
                                    const uint8_t *d2, int n2, const orbm_grid_geom_t *g2, float *prev, int32_t *m12,
                                    int window, float nnratio, int check_ori, int device, int *nmatches) {
-    if (n2 > 7000 || n1 > 65535) return ORBX_FAST_FALLBACK;  // LDS plan of k_resolve_init (9 B per F2 keypoint, 64 KB)
+    if (n2 > 7000 || n1 > 65535) return path_fallback(ORBM_PATH_FB_INIT_SIZE);  // LDS plan of k_resolve_init (9 B per F2 keypoint, 64 KB)
     const size_t need = (size_t)(n1 + n2) * (28 + 32 + 64 + 16) + (size_t)n1 * (CAND_CAP * 8 + 64) + 65536;
     int rc = arena_begin(device, need);
     if (rc) return rc;
@@ -1088,13 +1154,14 @@ int fast_search_for_initialization(const orbx_keypoint_t *k1, const uint8_t *d1,
     hipLaunchKernelGGL(k_compact_kps, dim3((n2 + 255) / 256), dim3(256), 0, st, dk2, n2, *g2, dckp);
     hipLaunchKernelGGL(k_queries_init, dim3((n1 + 255) / 256), dim3(256), 0, st, dk1, dprev, n1, window, dq);
     hipLaunchKernelGGL(k_cand<true>, dim3(std::max(n1, 1)), dim3(256), 0, st, dq, dd1, n1, dckp, dd2, n2, *g2, dkeys, dnc);
-    hipLaunchKernelGGL(k_resolve_init, dim3(1), dim3(64), sizeof(int32_t) * 2 * (size_t)n2 + (size_t)((n2 + 15) & ~15), st, dkeys, dnc, dk1, dk2, n1, n2,
+    hipLaunchKernelGGL(k_resolve_init, dim3(1), dim3(64), resolve_init_lds(n2), st, dkeys, dnc, dk1, dk2, n1, n2,
                        dprev, dm12, dbin, nnratio, check_ori, dout);
     ORBX_HIP(hipGetLastError());
+    path_wave(resolve_init_lds(n2));
     DOWN(dout, 2); DOWN(dprev, 2 * (size_t)n1); DOWN(dm12, n1);
     ORBX_HIP(hipStreamSynchronize(st));
     const int32_t *out = arena_host(dout);
-    if (out[1]) return ORBX_FAST_FALLBACK;
+    if (out[1]) return path_fallback(resolve_fallback(out[1]));
     memcpy(prev, arena_host(dprev), sizeof(float) * 2 * (size_t)n1);
     memcpy(m12, arena_host(dm12), sizeof(int32_t) * (size_t)n1);
     *nmatches = out[0];
@@ -1129,10 +1196,11 @@ int fast_search_by_projection_mp(const orbx_keypoint_t *kun, const uint8_t *desc
                                  const uint8_t *mp_desc, int m, int32_t *frame_mp, const int32_t *ext_obs, float th,
                                  float nnratio, int device, int *nmatches, const FrustumArgs *world, orbm_mappoint_t *proj_out,
                                  const DevFrame *dev) {
-    if (n > 30000 && !world) return ORBX_FAST_FALLBACK;
+    if (n > 30000 && !world) return path_fallback(ORBM_PATH_FB_N);
     const size_t need = (size_t)n * (28 + 32 + 32 + 16) + (size_t)m * (28 + 32 + QK * 8 + 64 + sizeof(orbm_worldpoint_t)) + 65536;
     int rc = arena_begin(device, need);
     if (rc) return rc;
+    const bool usePar = use_resolve_par(0, m, n, device);   // (before the call's first launch: the first query of the LDS budget)
     int waitSeq = 0;   // > 0: the call's last kernel stores this number into the completion word (arena_wait)
     // dev: the frame's keypoints / descriptors / mvuRight are already in HBM (outputs of orbx_extract_batch_device and
     // orbm_stereo_batch_device) and the kernels run on the caller's stream, behind the kernels that produce them
@@ -1164,21 +1232,28 @@ int fast_search_by_projection_mp(const orbx_keypoint_t *kun, const uint8_t *desc
         if (n > 30000) {
             ORBX_HIP(hipStreamSynchronize(st));
             if (proj_out) memcpy(proj_out, arena_host(dmp), sizeof(orbm_mappoint_t) * (size_t)m);
-            return ORBX_FAST_FALLBACK;
+            return path_fallback(ORBM_PATH_FB_N);
         }
     } else { UP(dmp, mps, m); FLUSH_UP(); }
     const int mx = std::max(n, m);
     uint4 *dckp = arena_get<uint4>(n);
     hipLaunchKernelGGL(k_queries_mp, dim3((mx + 255) / 256), dim3(256), 0, st, dmp, m, zsf, th, dq, zfm, zeo, n, dk, du, *g, dckp);
     hipLaunchKernelGGL(k_cand<false>, dim3(std::max(m, 1)), dim3(256), 0, st, dq, zmd, m, dckp, dd, n, *g, dkeys, dnc);
-    if (use_resolve_par(m, n)) {   // results land in the pinned mirror straight from the kernel
+    if (usePar) {   // results land in the pinned mirror straight from the kernel
         waitSeq = ++g_ar.seq;
-        RESOLVE_PAR_LAUNCH(0, m, dkeys, dnc, (const void *)dmp, dk, m, n, zfm, zfm, (int32_t *)nullptr, nnratio, 0, 0, dout, arena_hostdev(dout), g_ar.dflag, waitSeq);
-        ORBX_HIP(hipGetLastError());
+        rc = resolve_par_launch<0>(m, n, st, dkeys, dnc, (const void *)dmp, dk, m, n, zfm, zfm, (int32_t *)nullptr, nnratio, 0, 0, dout,
+                                   arena_hostdev(dout), g_ar.dflag, waitSeq);
+        if (rc < 0) return rc;
+        if (rc == ORBX_FAST_FALLBACK) {   // refused: the kernels in front finish, the projections go out, the exact kernels run
+            ORBX_HIP(hipStreamSynchronize(st));
+            if (world && proj_out) memcpy(proj_out, arena_host(dmp), sizeof(orbm_mappoint_t) * (size_t)m);
+            return path_fallback(ORBM_PATH_FB_LDS);
+        }
     } else {
         ORBX_HIP(hipMemcpyAsync(dfm, arena_host(dfm), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));   // this resolver works on the device copy
-        hipLaunchKernelGGL(k_resolve_mp, dim3(1), dim3(64), 2 * (size_t)((n + 15) & ~15), st, dkeys, dnc, dmp, m, n, dfm, nnratio, dout);
+        hipLaunchKernelGGL(k_resolve_mp, dim3(1), dim3(64), resolve_wave_lds(n), st, dkeys, dnc, dmp, m, n, dfm, nnratio, dout);
         ORBX_HIP(hipGetLastError());
+        path_wave(resolve_wave_lds(n));
         DOWN(dout, 2); DOWN(dfm, n);
     }
     rc = arena_wait(st, waitSeq);
@@ -1186,7 +1261,7 @@ int fast_search_by_projection_mp(const orbx_keypoint_t *kun, const uint8_t *desc
     if (world && proj_out) memcpy(proj_out, arena_host(dmp), sizeof(orbm_mappoint_t) * (size_t)m);
     const int32_t *out = arena_host(dout);
     if (getenv("ORBX_TRACE_RESOLVE")) fprintf(stderr, "k_resolve_par<mp>: %d queries, %d keypoints, %d rounds; developer build: loads %.1f us, rounds %.1f us, epilogue %.1f us\n", m, n, out[2], (out[3] >> 20) / 10.0, ((out[3] >> 10) & 1023) / 10.0, (out[3] & 1023) / 10.0);
-    if (out[1]) return ORBX_FAST_FALLBACK;
+    if (out[1]) return path_fallback(resolve_fallback(out[1]));
     memcpy(frame_mp, arena_host(dfm), sizeof(int32_t) * (size_t)n);
     *nmatches = out[0];
     return ORBX_OK;
@@ -1197,13 +1272,14 @@ int fast_search_by_projection_frame(const orbx_keypoint_t *kun, const uint8_t *d
                                     const float *Tc16, const float *Tl16, const orbm_lastpoint_t *last,
                                     const uint8_t *last_desc, int nlast, int32_t *cur_mp, const int32_t *ext_obs,
                                     float th, int mono, int check_ori, int device, int *nmatches, const DevFrame *dev) {
-    if (n > 30000) return ORBX_FAST_FALLBACK;
+    if (n > 30000) return path_fallback(ORBM_PATH_FB_N);
     static const bool traceHost = getenv("ORBX_TRACE_HOST") != nullptr;   // developer aid: host-side time stamps of this call on stderr
     timespec ts0, ts1, ts2, ts3;
     if (traceHost) clock_gettime(CLOCK_MONOTONIC, &ts0);
     const size_t need = (size_t)n * (28 + 32 + 32 + 16) + (size_t)nlast * (28 + 32 + QK * 8 + 64 + 8) + 65536;
     int rc = arena_begin(device, need);
     if (rc) return rc;
+    const bool usePar = use_resolve_par(1, nlast, n, device);   // (before the call's first launch: the first query of the LDS budget)
     int waitSeq = 0;
     hipStream_t st = dev ? dev->stream : g_ar.st;   // dev: kun / desc / uright / last_desc are device arrays (see fast_search_by_projection_mp)
     orbx_keypoint_t *dk = dev ? const_cast<orbx_keypoint_t *>(kun) : arena_get<orbx_keypoint_t>(n);
@@ -1231,16 +1307,22 @@ int fast_search_by_projection_frame(const orbx_keypoint_t *kun, const uint8_t *d
     hipLaunchKernelGGL(k_queries_frame, dim3((mx + 255) / 256), dim3(256), 0, st, zl, nlast, zsf, *cam, *g, zT, zT + 16, th,
                        mono, dq, zcm, zeo, n, dk, du, dckp, dqm);
     hipLaunchKernelGGL(k_cand<false>, dim3(std::max(nlast, 1)), dim3(256), 0, st, dq, dld, nlast, dckp, dd, n, *g, dkeys, dnc);
-    if (use_resolve_par(nlast, n)) {
+    if (usePar) {
         waitSeq = ++g_ar.seq;
-        RESOLVE_PAR_LAUNCH(1, nlast, dkeys, dnc, (const void *)dqm, dk, nlast, n, zcm, zcm, (int32_t *)nullptr, 0.0f, 0, check_ori, dout, arena_hostdev(dout), g_ar.dflag, waitSeq);
-        ORBX_HIP(hipGetLastError());
+        rc = resolve_par_launch<1>(nlast, n, st, dkeys, dnc, (const void *)dqm, dk, nlast, n, zcm, zcm, (int32_t *)nullptr, 0.0f, 0, check_ori,
+                                   dout, arena_hostdev(dout), g_ar.dflag, waitSeq);
+        if (rc < 0) return rc;
+        if (rc == ORBX_FAST_FALLBACK) {
+            ORBX_HIP(hipStreamSynchronize(st));
+            return path_fallback(ORBM_PATH_FB_LDS);
+        }
     } else {
         ORBX_HIP(hipMemcpyAsync(dcm, arena_host(dcm), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
         ORBX_HIP(hipMemcpyAsync(dl, arena_host(dl), sizeof(orbm_lastpoint_t) * (size_t)nlast, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_resolve_frame, dim3(1), dim3(64), 2 * (size_t)((n + 15) & ~15), st, dkeys, dnc, dl, dk, nlast, n, dcm,
+        hipLaunchKernelGGL(k_resolve_frame, dim3(1), dim3(64), resolve_wave_lds(n), st, dkeys, dnc, dl, dk, nlast, n, dcm,
                            dhi, dhb, check_ori, dout);
         ORBX_HIP(hipGetLastError());
+        path_wave(resolve_wave_lds(n));
         DOWN(dout, 2); DOWN(dcm, n);
     }
     if (traceHost) clock_gettime(CLOCK_MONOTONIC, &ts2);
@@ -1253,7 +1335,7 @@ int fast_search_by_projection_frame(const orbx_keypoint_t *kun, const uint8_t *d
     }
     const int32_t *out = arena_host(dout);
     if (getenv("ORBX_TRACE_RESOLVE")) fprintf(stderr, "k_resolve_par<frame>: %d queries, %d keypoints, %d rounds; developer build: loads %.1f us, rounds %.1f us, epilogue %.1f us\n", nlast, n, out[2], (out[3] >> 20) / 10.0, ((out[3] >> 10) & 1023) / 10.0, (out[3] & 1023) / 10.0);
-    if (out[1]) return ORBX_FAST_FALLBACK;
+    if (out[1]) return path_fallback(resolve_fallback(out[1]));
     memcpy(cur_mp, arena_host(dcm), sizeof(int32_t) * (size_t)n);
     *nmatches = out[0];
     return ORBX_OK;
@@ -1263,10 +1345,11 @@ int fast_match_windows(const orbx_keypoint_t *kun, const uint8_t *desc, const fl
                        const orbm_grid_geom_t *g, const orbm_grid_geom_t *ga, const orbm_window_query_t *q,
                        const uint8_t *qdesc, int m,
                        int32_t *holder, const int32_t *ext_blocks, int max_dist, int check_ori, int device, int *nmatches) {
-    if (n > 30000) return ORBX_FAST_FALLBACK;
+    if (n > 30000) return path_fallback(ORBM_PATH_FB_N);
     const size_t need = (size_t)n * (28 + 32 + 32 + 16) + (size_t)m * (40 + 32 + QK * 8 + 96) + 65536;
     int rc = arena_begin(device, need);
     if (rc) return rc;
+    const bool usePar = use_resolve_par(2, m, n, device);   // (before the call's first launch: the first query of the LDS budget)
     hipStream_t st = g_ar.st;
     orbx_keypoint_t *dk = arena_get<orbx_keypoint_t>(n);
     uint8_t *dd = arena_get<uint8_t>((size_t)32 * n), *dqd = arena_get<uint8_t>((size_t)32 * m);
@@ -1290,18 +1373,24 @@ int fast_match_windows(const orbx_keypoint_t *kun, const uint8_t *desc, const fl
     hipLaunchKernelGGL(k_queries_windows, dim3((mx + 255) / 256), dim3(256), 0, st, dw, m, dq, dh,
                        ext_blocks ? deb : (const int32_t *)nullptr, n, dk, du, *ga, dckp);
     hipLaunchKernelGGL(k_cand<false>, dim3(std::max(m, 1)), dim3(256), 0, st, dq, dqd, m, dckp, dd, n, *g, dkeys, dnc);
-    if (use_resolve_par(m, n)) {
-        RESOLVE_PAR_LAUNCH(2, m, dkeys, dnc, (const void *)dw, dk, m, n, dh, dh, arena_hostdev(dh), 0.0f, max_dist, check_ori, dout, arena_hostdev(dout), (int32_t *)nullptr, 0);
-        ORBX_HIP(hipGetLastError());
+    if (usePar) {
+        rc = resolve_par_launch<2>(m, n, st, dkeys, dnc, (const void *)dw, dk, m, n, dh, dh, arena_hostdev(dh), 0.0f, max_dist, check_ori, dout,
+                                   arena_hostdev(dout), (int32_t *)nullptr, 0);
+        if (rc < 0) return rc;
+        if (rc == ORBX_FAST_FALLBACK) {
+            ORBX_HIP(hipStreamSynchronize(st));
+            return path_fallback(ORBM_PATH_FB_LDS);
+        }
     } else {
-        hipLaunchKernelGGL(k_resolve_windows, dim3(1), dim3(64), 2 * (size_t)((n + 15) & ~15), st, dkeys, dnc, dw, dk, m, n, dh, dhi,
+        hipLaunchKernelGGL(k_resolve_windows, dim3(1), dim3(64), resolve_wave_lds(n), st, dkeys, dnc, dw, dk, m, n, dh, dhi,
                            dhb, max_dist, check_ori, dout);
         ORBX_HIP(hipGetLastError());
+        path_wave(resolve_wave_lds(n));
         DOWN(dout, 2); DOWN(dh, n);
     }
     ORBX_HIP(hipStreamSynchronize(st));
     const int32_t *out = arena_host(dout);
-    if (out[1]) return ORBX_FAST_FALLBACK;
+    if (out[1]) return path_fallback(resolve_fallback(out[1]));
     memcpy(holder, arena_host(dh), sizeof(int32_t) * (size_t)n);
     *nmatches = out[0];
     return ORBX_OK;
@@ -1462,3 +1551,31 @@ int fast_distinctive_descriptors(const uint8_t *desc, const int32_t *offsets, in
     if (best_median) memcpy(best_median, arena_host(dbm), sizeof(int32_t) * (size_t)npoints);
     return ORBX_OK;
 }
+
+#ifdef ORBX_DEVELOPER   // ---- developer build only (include/orbx_dev.h): the fast path's plan for a size, no launch
+extern "C" int orbm_debug_resolve_plan(int mode, int m, int n, int device, int64_t *out) {
+    if (mode < 0 || mode > 3 || m < 0 || n < 0 || !out) { orbx_set_error("orbm_debug_resolve_plan: bad arguments"); return ORBX_ERR_ARG; }
+    const RpBudget *b = resolve_par_budget(device);
+    if (!b) { orbx_set_error("orbm_debug_resolve_plan: no LDS limits for device %d", device); return ORBX_ERR_NO_DEVICE; }
+    ORBX_HIP(hipSetDevice(device));
+    int64_t res = ORBM_PATH_RES_WAVE, lds = 0, stat = 0;
+    const void *fn = nullptr;
+    if (t_matchExact || (mode == 3 ? n > 7000 || m > 65535 : n > 30000)) res = ORBM_PATH_RES_EXACT;
+    else if (mode == 3) { lds = (int64_t)resolve_init_lds(n); fn = (const void *)k_resolve_init; }
+    else if (use_resolve_par(mode, m, n, device)) {
+        res = resolve_par_q(m) == 2 ? ORBM_PATH_RES_PAR_Q2 : ORBM_PATH_RES_PAR_Q4;
+        lds = (int64_t)resolve_par_lds(m, n);
+        stat = (int64_t)b->stat[mode][resolve_par_q(m) == 4];
+    } else {
+        lds = (int64_t)resolve_wave_lds(n);
+        fn = mode == 0 ? (const void *)k_resolve_mp : mode == 1 ? (const void *)k_resolve_frame : (const void *)k_resolve_windows;
+    }
+    if (fn) {
+        hipFuncAttributes fa;
+        ORBX_HIP(hipFuncGetAttributes(&fa, fn));
+        stat = (int64_t)fa.sharedSizeBytes;
+    }
+    out[0] = res; out[1] = lds; out[2] = stat; out[3] = (int64_t)b->limit;
+    return ORBX_OK;
+}
+#endif   // ORBX_DEVELOPER

@@ -81,11 +81,12 @@ def matcher_path(request, pkg):
     """The implementations of the guided searches: parallel candidates + the whole-workgroup fixed-point resolution (default,
     round 5), parallel candidates + the single-wave speculative resolution (rounds 1-4), and the exact one-workgroup kernels
     both fall back to."""
-    pkg.lib().orbm_set_thread_option(2, 1 if request.param == "exact" else 0)
-    pkg.lib().orbm_set_thread_option(3, 1 if request.param == "fast_wave" else 0)
+    L = pkg.matcher_lib()   # (thread options are per library: the one the matcher functions call)
+    L.orbm_set_thread_option(2, 1 if request.param == "exact" else 0)
+    L.orbm_set_thread_option(3, 1 if request.param == "fast_wave" else 0)
     yield request.param
-    pkg.lib().orbm_set_thread_option(2, 0)
-    pkg.lib().orbm_set_thread_option(3, 0)
+    L.orbm_set_thread_option(2, 0)
+    L.orbm_set_thread_option(3, 0)
 
 
 def test_search_for_initialization(pkg, oracle, synth, matcher_path):
