@@ -260,6 +260,49 @@ typedef struct {
 } orbx_stereo_view_t;
 int orbx_stereo_frame_view(orbx_extractor_t *h, const uint8_t *left, const uint8_t *right, int w, int hgt, int stride,
                            float mbf, float mb, orbx_stereo_view_t *view);
+/* ---- RGB-D frames: Tracking::GrabImageRGBD (src/Tracking.cc:315-345) + the RGB-D Frame constructor's feature part
+ * (src/Frame.cc:119-171: ExtractORB, UndistortKeyPoints :419-449, ComputeStereoFromRGBD :658-679).
+ * Camera: mK (fx fy cx cy), mDistCoef (k1 k2 p1 p2 [k3]; a 4-element mDistCoef has k3 = 0) and mbf.  Keypoints are undistorted
+ * (cv::undistortPoints, restated in double) unless k1 == 0 - the reference's own test, even when p1 / p2 are not 0. */
+typedef struct {
+    float fx, fy, cx, cy;
+    float k1, k2, p1, p2, k3;
+    float mbf;
+} orbx_rgbd_camera_t;
+/* depth image element types: OpenCV's type codes CV_16U / CV_32F */
+#define ORBX_DEPTH_U16 2
+#define ORBX_DEPTH_F32 5
+
+/* cvtColor(RGB2GRAY / BGR2GRAY / RGBA2GRAY / BGRA2GRAY) of B colour images in HBM, asynchronous on `stream`:
+ * Y = (R*4899 + G*9617 + B*1868 + 8192) >> 14 (OpenCV's 8-bit RGB2Gray).  channels 3 or 4; rgb != 0: channel 0 is red, else blue.
+ * Image b at d_color + b*image_stride_bytes, rows `stride` bytes apart; gray image b at d_gray + b*gray_image_stride_bytes, rows
+ * gray_stride bytes apart. */
+int orbx_gray_from_color_device(const uint8_t *d_color, int B, int w, int hgt, int channels, int rgb, int stride,
+                                size_t image_stride_bytes, uint8_t *d_gray, int gray_stride, size_t gray_image_stride_bytes,
+                                void *stream);
+/* UndistortKeyPoints + ComputeStereoFromRGBD for the DEVICE outputs of orbx_extract_batch_device (d_kps [B][cap], d_counts [B]),
+ * asynchronous on `stream`.  d_kun [B][cap] (mvKeysUn), d_uright / d_depth_out [B][cap] (mvuRight / mvDepth); rows past each frame's
+ * count are not written.  Depth image b at d_depth + b*depth_image_stride_bytes, rows depth_stride bytes apart, w x hgt elements of
+ * depth_type; the depth at a keypoint is d = imDepth(int(y), int(x)) at the DISTORTED position, converted as GrabImageRGBD does:
+ * d = (float)raw * depth_map_factor unless depth_type is F32 and |depth_map_factor - 1| <= 1e-5.  d > 0: mvDepth = d,
+ * mvuRight = kun.x - mbf/d; else (0, negative, NaN, outside the image) -1 / -1.  d_depth == NULL: the monocular constructor's tail
+ * (src/Frame.cc:174-228): mvKeysUn and -1 / -1. */
+int orbm_rgbd_batch_device(const orbx_keypoint_t *d_kps, const int32_t *d_counts, int B, int cap, const void *d_depth,
+                           int depth_type, int w, int hgt, int depth_stride, size_t depth_image_stride_bytes,
+                           float depth_map_factor, const orbx_rgbd_camera_t *cam, orbx_keypoint_t *d_kun, float *d_uright,
+                           float *d_depth_out, void *stream);
+/* One RGB-D frame host to host (synchronous): GrabImageRGBD's conversions + the RGB-D Frame constructor's feature part.
+ * img: 8-bit, channels 1 (gray, used as is), 3 or 4 (rgb as above), `stride` bytes per row.  depth: w x hgt of depth_type,
+ * depth_stride bytes per row, or NULL (monocular tail).  depth_map_factor: mDepthMapFactor (= 1 / DepthMapFactor of the settings).
+ * Out (cap rows each): kp / desc (mvKeys, mDescriptors), kun (mvKeysUn), uright, depth_out (mvuRight, mvDepth), *n.
+ * The colour conversion and the extraction run on the handle's stream with the gray image in handle-owned scratch, the depth image
+ * goes up on a side stream meanwhile.  Empty image: ORBX_OK, *n = 0.  Bad channels, depth type or NULL camera: ORBX_ERR_ARG.
+ * More than cap keypoints: clamped, ORBX_ERR_CAPACITY. */
+int orbx_rgbd_frame(orbx_extractor_t *h, const uint8_t *img, int channels, int rgb, int w, int hgt, int stride,
+                    const void *depth, int depth_type, int depth_stride, float depth_map_factor,
+                    const orbx_rgbd_camera_t *cam, int cap, orbx_keypoint_t *kp, uint8_t *desc, int *n,
+                    orbx_keypoint_t *kun, float *uright, float *depth_out);
+
 /* Pinned host memory for image / capture buffers (cv::Mat can wrap it: cv::Mat(rows, cols, CV_8UC1, ptr)); NULL on failure. */
 void *orbx_host_alloc(size_t bytes);
 void orbx_host_free(void *p);

@@ -50,6 +50,7 @@ EXPORTS = [
     "orbm_search_by_projection_frame_device", "orbm_search_local_points_device", "orbx_fast_kernels", "orbx_extract_batch_device_prefetch", "orbx_stream_wait_fast_stage", "orbx_side_stream", "orbm_stereo_batch_device_prev",
     "orbx_side_stream_for", "orbx_stereo_frame", "orbx_set_pyramid_buffers",
     "orbx_stereo_frame_view", "orbx_host_alloc", "orbx_host_free",
+    "orbx_gray_from_color_device", "orbm_rgbd_batch_device", "orbx_rgbd_frame",
 ]
 # what include/orbx_dev.h declares on top: exported by the developer build only
 DEV_EXPORTS = ["orbx_debug_level_points", "orbx_debug_sincosf", "orbx_debug_blur_patches", "orbm_debug_features_in_area",
@@ -83,6 +84,17 @@ class GridGeom(C.Structure):
 class Camera(C.Structure):
     _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
                 ("mbf", C.c_float), ("mb", C.c_float)]
+
+
+class RGBDCamera(C.Structure):
+    """orbx_rgbd_camera_t: mK, mDistCoef (k1 k2 p1 p2 k3; k3 = 0 for a 4-element mDistCoef) and mbf of an RGB-D Frame."""
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("k1", C.c_float), ("k2", C.c_float),
+                ("p1", C.c_float), ("p2", C.c_float), ("k3", C.c_float), ("mbf", C.c_float)]
+
+
+# depth image element types of orbx_rgbd_frame / orbm_rgbd_batch_device (OpenCV's CV_16U / CV_32F)
+DEPTH_U16, DEPTH_F32 = 2, 5
+_DEPTH_TYPES = {np.dtype(np.uint16): DEPTH_U16, np.dtype(np.float32): DEPTH_F32}
 
 
 def grid_geom(w, h):
@@ -219,6 +231,10 @@ def _load(path, dev):
     L.orbx_stereo_frame.argtypes = [vp, vp, vp, i32, i32, i32, f32, f32, i32, vp, vp, C.POINTER(i32), vp, vp, C.POINTER(i32), vp, vp,
                                     C.POINTER(i32)]
     L.orbx_stereo_frame_view.argtypes = [vp, vp, vp, i32, i32, i32, f32, f32, vp]
+    L.orbx_gray_from_color_device.argtypes = [vp, i32, i32, i32, i32, i32, i32, sz, vp, i32, sz, vp]
+    L.orbm_rgbd_batch_device.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, sz, f32, C.POINTER(RGBDCamera), vp, vp, vp, vp]
+    L.orbx_rgbd_frame.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, f32, C.POINTER(RGBDCamera), i32, vp, vp,
+                                  C.POINTER(i32), vp, vp, vp]
     L.orbx_host_alloc.argtypes = [sz]
     L.orbx_host_alloc.restype = vp
     L.orbx_host_free.argtypes = [vp]
@@ -455,6 +471,39 @@ class ORBextractor:
         return {"kl": kl[:a].copy(), "dl": dl[:a].copy(), "kr": kr[:b].copy(), "dr": dr[:b].copy(), "uright": ur[:a].copy(),
                 "depth": dp[:a].copy(), "nmatch": nm.value}
 
+    def rgbd_frame(self, img, depth, cam, depth_map_factor=1.0, rgb=True, cap=None):
+        """One RGB-D frame host to host in one call (orbx_rgbd_frame): GrabImageRGBD's conversions + the RGB-D Frame constructor's
+        feature part.  img: uint8 [h, w] (gray), [h, w, 3] or [h, w, 4] (rgb: channel 0 is red); depth: uint16 / float32 [h, w] or
+        None (the monocular constructor's tail: uright = depth = -1); cam: RGBDCamera; depth_map_factor: mDepthMapFactor
+        -> dict(kp, desc, kun, uright, depth)."""
+        img = np.asarray(img)
+        assert img.dtype == np.uint8 and (img.ndim == 2 or (img.ndim == 3 and img.shape[2] in (3, 4))), "CV_8UC1/3/4 expected"
+        hgt, w = img.shape[:2]
+        ch = 1 if img.ndim == 2 else img.shape[2]
+        if img.size and (img.strides[-1] != 1 or (ch > 1 and img.strides[1] != ch) or img.strides[0] < w * ch):
+            img = np.ascontiguousarray(img)   # (a row-strided view is passed as it is)
+        dp_ptr, dtype, dstride = None, DEPTH_F32, 0
+        if depth is not None:
+            depth = np.asarray(depth)
+            assert depth.shape == (hgt, w) and depth.dtype in _DEPTH_TYPES, "CV_16U / CV_32F depth of the image's size expected"
+            if depth.strides[1] != depth.itemsize or depth.strides[0] < w * depth.itemsize:
+                depth = np.ascontiguousarray(depth)
+            dp_ptr, dtype, dstride = depth.ctypes.data, _DEPTH_TYPES[depth.dtype], depth.strides[0]
+        if cap is None:
+            cap = (self.max_keypoints() if self._shape == (hgt, w) else self.nfeatures + 3 * self.nlevels + 8 * 64) + 8
+        kp, kun = np.zeros(cap, KP_DTYPE), np.zeros(cap, KP_DTYPE)
+        desc = np.zeros((cap, 32), np.uint8)
+        ur, dp = np.zeros(cap, np.float32), np.zeros(cap, np.float32)
+        n = C.c_int()
+        rc = self._L.orbx_rgbd_frame(self._h, _p(img) if img.size else None, ch, int(bool(rgb)), w, hgt, img.strides[0] if img.size else 0,
+                                     dp_ptr, dtype, dstride, float(depth_map_factor), C.byref(cam), int(cap), _p(kp), _p(desc), C.byref(n),
+                                     _p(kun), _p(ur), _p(dp))
+        self._ck(rc)
+        if img.size:
+            self._shape = (hgt, w)
+        a = n.value
+        return {"kp": kp[:a].copy(), "desc": desc[:a].copy(), "kun": kun[:a].copy(), "uright": ur[:a].copy(), "depth": dp[:a].copy()}
+
     def stereo_frame_view(self, left, right, mbf, mb, shape=None, stride=None):
         """The latency form of stereo_frame (orbx_stereo_frame_view): no copy commands, results in the handle's pinned record.
         left / right: uint8 numpy arrays [h, w] (pageable: staged by the call), or objects with data_ptr() (torch tensors - pinned
@@ -625,6 +674,21 @@ def stereo_batch_device(ex_left, ex_right, B, left_slot0, right_slot0, d_kl, d_d
     fn = L.orbm_stereo_batch_device_prev if prev else L.orbm_stereo_batch_device
     _check(fn(ex_left._h, ex_right._h, B, left_slot0, right_slot0, d_kl, d_dl, d_nl, d_kr, d_dr, d_nr, cap, float(mbf), float(mb),
               d_uright, d_depth, d_nmatch, stream), L)
+
+
+def gray_from_color_device(d_color, B, w, h, channels, rgb, stride, image_stride, d_gray, gray_stride, gray_image_stride, stream=0):
+    """cvtColor(RGB[A]/BGR[A]2GRAY) of B colour images in HBM (orbx_gray_from_color_device; raw device pointers)."""
+    _check(lib().orbx_gray_from_color_device(d_color, int(B), int(w), int(h), int(channels), int(bool(rgb)), int(stride), int(image_stride),
+                                             d_gray, int(gray_stride), int(gray_image_stride), stream))
+
+
+def rgbd_batch_device(d_kps, d_counts, B, cap, d_depth, depth_type, w, h, depth_stride, depth_image_stride, depth_map_factor, cam,
+                      d_kun, d_uright, d_depth_out, stream=0):
+    """UndistortKeyPoints + ComputeStereoFromRGBD of B frames on the device outputs of extract_batch_device
+    (orbm_rgbd_batch_device; raw device pointers, d_depth None / 0 = the monocular tail)."""
+    _check(lib().orbm_rgbd_batch_device(d_kps, d_counts, int(B), int(cap), d_depth or None, int(depth_type), int(w), int(h),
+                                        int(depth_stride), int(depth_image_stride), float(depth_map_factor), C.byref(cam), d_kun,
+                                        d_uright, d_depth_out, stream))
 
 
 def compute_stereo_matches(ex_left, ex_right, kl, dl, kr, dr, mbf, mb):

@@ -201,6 +201,7 @@ extern "C" int orbx_destroy(orbx_extractor_t *h) {
     if (h->last_valid) hipStreamSynchronize(h->last_stream);
     if (h->st_stream) hipStreamSynchronize(h->st_stream);
     orbx_internal_free_stereo_scratch(h);
+    orbx_internal_free_rgbd_scratch(h);
     free_plan(h);
     hipFree(h->d_in); hipFree(h->d_kps); hipFree(h->d_desc); hipFree(h->d_counts); hipFree(h->d_dbgBlur);
     hipFree(h->d_sfr); if (h->h_sfr) hipHostFree(h->h_sfr);

@@ -145,10 +145,12 @@ struct orbx_extractor {
     int ev_head;
     double acc_ms[ORBX_NUM_STAGES];
     long acc_n;
+    struct RgbdScratch *rgbd;   // orbx_rgbd_frame: colour / gray / depth images and the frame's results (orbx_rgbd.hip), NULL until first used
 };
 
 // extractor internals used by the matcher side
 void orbx_internal_free_stereo_scratch(orbx_extractor *h);   // orbx_match.hip
+void orbx_internal_free_rgbd_scratch(orbx_extractor *h);     // orbx_rgbd.hip
 // ComputeStereoMatches of the frame in image slots 0 / 1 of h with the record layout of orbx_stereo_frame_view (orbx_match.hip)
 int orbx_internal_stereo_frame_record(orbx_extractor *h, uint8_t *d_rec, uint8_t *rec_hostdev, int cap, float mbf, float mb, hipStream_t st, bool recordsOnHost,
                                       int32_t *doneFlag, int doneSeq, int *flagArmed);

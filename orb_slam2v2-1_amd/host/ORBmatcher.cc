@@ -754,6 +754,61 @@ int ExtractStereoFrameHIP(Frame &F, const cv::Mat &imLeft, const cv::Mat &imRigh
     return nm;
 }
 
+int ExtractRGBDFrameHIP(Frame &F, const cv::Mat &im, const cv::Mat &imDepth, float depthMapFactor, bool bRGB) {
+    F.mvKeys.clear(); F.mvKeysUn.clear(); F.mDescriptors.release();
+    F.mvuRight.clear(); F.mvDepth.clear(); F.N = 0;
+    if (!F.mpORBextractorLeft || !F.mpORBextractorLeft->ok() || im.empty()) return 0;
+    const int ch = im.channels();
+    if (im.depth() != CV_8U || (ch != 1 && ch != 3 && ch != 4)) {
+        std::fprintf(stderr, "ExtractRGBDFrame: CV_8UC1 / 3 / 4 image expected\n");
+        return -1;
+    }
+    const bool hasDepth = !imDepth.empty();
+    if (hasDepth && (imDepth.cols != im.cols || imDepth.rows != im.rows || (imDepth.type() != CV_16U && imDepth.type() != CV_32F))) {
+        std::fprintf(stderr, "ExtractRGBDFrame: CV_16U / CV_32F depth of the image's size expected\n");
+        return -1;
+    }
+    if (F.mK.rows != 3 || F.mK.cols != 3 || F.mDistCoef.rows * F.mDistCoef.cols < 4) {
+        std::fprintf(stderr, "ExtractRGBDFrame: mK (3x3) and mDistCoef (4 or 5 elements) must be set\n");
+        return -1;
+    }
+    orbx_rgbd_camera_t cam;
+    cam.fx = F.mK.at<float>(0, 0); cam.fy = F.mK.at<float>(1, 1); cam.cx = F.mK.at<float>(0, 2); cam.cy = F.mK.at<float>(1, 2);
+    const float *dc = F.mDistCoef.ptr<float>(0);   // (a 4x1 / 5x1 column: continuous)
+    cam.k1 = dc[0]; cam.k2 = dc[1]; cam.p1 = dc[2]; cam.p2 = dc[3];
+    cam.k3 = F.mDistCoef.rows * F.mDistCoef.cols >= 5 ? dc[4] : 0.f;   // src/Tracking.cc:66-77
+    cam.mbf = F.mbf;
+    orbx_extractor_t *h = F.mpORBextractorLeft->handle();
+    const int cap = orbx_max_keypoints(h) + 256;
+    std::vector<orbx_keypoint_t> kp(cap), kun(cap);
+    cv::Mat desc(cap, 32, CV_8U);
+    std::vector<float> ur(cap), dp(cap);
+    int n = 0;
+    const int rc = orbx_rgbd_frame(h, im.ptr(0), ch, bRGB ? 1 : 0, im.cols, im.rows, (int)im.step, hasDepth ? imDepth.ptr(0) : nullptr,
+                                   hasDepth ? imDepth.type() : ORBX_DEPTH_F32, hasDepth ? (int)imDepth.step : 0, depthMapFactor, &cam, cap,
+                                   kp.data(), desc.ptr(0), &n, kun.data(), ur.data(), dp.data());
+    if (rc != ORBX_OK) {
+        std::fprintf(stderr, "ExtractRGBDFrame: %s\n", orbx_last_error());
+        return -1;
+    }
+    auto key = [](const orbx_keypoint_t &s) {
+        cv::KeyPoint k;
+        k.pt.x = s.x; k.pt.y = s.y; k.size = s.size; k.angle = s.angle; k.response = s.response;
+        k.octave = s.octave; k.class_id = s.class_id;
+        return k;
+    };
+    F.mvKeys.reserve(n); F.mvKeysUn.reserve(n);
+    for (int i = 0; i < n; i++) { F.mvKeys.push_back(key(kp[i])); F.mvKeysUn.push_back(key(kun[i])); }
+    if (n > 0) {
+        F.mDescriptors.create(n, 32, CV_8U);
+        for (int i = 0; i < n; i++) std::memcpy(F.mDescriptors.ptr(i), desc.ptr(i), 32);
+    }
+    F.N = n;
+    F.mvuRight.assign(ur.begin(), ur.begin() + n);
+    F.mvDepth.assign(dp.begin(), dp.begin() + n);
+    return n;
+}
+
 int ComputeStereoMatchesHIP(Frame &F) {
     const int N = F.N, Nr = (int)F.mvKeysRight.size();
     F.mvuRight = std::vector<float>(N, -1.0f);  // :483-484

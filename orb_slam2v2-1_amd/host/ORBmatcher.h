@@ -92,6 +92,16 @@ int ComputeStereoMatchesHIP(Frame &F);
 // Returns the number of stereo matches (< 0: error, outputs empty).
 int ExtractStereoFrameHIP(Frame &F, const cv::Mat &imLeft, const cv::Mat &imRight);
 
+// The RGB-D Frame constructor's feature part in ONE GPU call (src/Frame.cc:119-171): ExtractORB(0, imGray), UndistortKeyPoints and
+// ComputeStereoFromRGBD, plus - for a raw capture - GrabImageRGBD's conversions (src/Tracking.cc:315-336).  Fills F.mvKeys /
+// mvKeysUn / mDescriptors / N / mvuRight / mvDepth from F.mpORBextractorLeft, F.mK, F.mDistCoef and F.mbf.  im: CV_8UC1, CV_8UC3 or
+// CV_8UC4 (bRGB: channel 0 is red, mbRGB); imDepth: CV_16U or CV_32F (empty: the monocular constructor's mvuRight = mvDepth = -1);
+// depthMapFactor: mDepthMapFactor.  Both forms give the same results:
+//   in the Frame constructor, on what Tracking converted:  ExtractRGBDFrameHIP(*this, imGray, imDepth, 1.0f, true);
+//   in GrabImageRGBD, on the raw capture (no cvtColor, no convertTo on the CPU): ExtractRGBDFrameHIP(F, imRGB, imD, mDepthMapFactor, mbRGB);
+// Returns N (< 0: error, outputs empty).
+int ExtractRGBDFrameHIP(Frame &F, const cv::Mat &im, const cv::Mat &imDepth, float depthMapFactor, bool bRGB);
+
 // Tracking::SearchLocalPoints (src/Tracking.cc:1305-1339) from "Project points in frame" on: Frame::isInFrustum
 // (src/Frame.cc:284-340) of every local map point that was not seen in this frame and is not bad, then
 // ORBmatcher(nnratio).SearchByProjection(F, vpLocalMapPoints, th) — both in ONE GPU call.  Leaves on each point

@@ -12,8 +12,13 @@
 #include <cmath>
 
 #define CV_8U 0
+#define CV_16U 2
 #define CV_32F 5
+#define CV_MAKETYPE(depth, cn) ((depth) + (((cn) - 1) << 3))
 #define CV_8UC1 CV_8U
+#define CV_8UC3 CV_MAKETYPE(CV_8U, 3)
+#define CV_8UC4 CV_MAKETYPE(CV_8U, 4)
+#define CV_16UC1 CV_16U
 #define CV_32FC1 CV_32F
 
 namespace cv {
@@ -34,7 +39,7 @@ struct KeyPoint {  // field order of cv::KeyPoint (reference: include/BoostArchi
     KeyPoint() : size(0), angle(-1), response(0), octave(0), class_id(-1) {}
 };
 
-// 2-D, single-channel, reference-counted matrix: enough for gray images, N x 32 descriptor
+// 2-D, reference-counted matrix: enough for gray / colour / depth images, N x 32 descriptor
 // tables and 4x4 / 3x1 float poses.
 class Mat {
 public:
@@ -54,6 +59,8 @@ public:
     void release() { buf_.reset(); data = nullptr; rows = cols = 0; step = 0; }
     bool empty() const { return data == nullptr || rows == 0 || cols == 0; }
     int type() const { return type_; }
+    int depth() const { return type_ & 7; }
+    int channels() const { return (type_ >> 3) + 1; }
     size_t elemSize() const { return esz(type_); }
     Mat clone() const {
         Mat m(rows, cols, type_);
@@ -77,7 +84,10 @@ public:
         return m;
     }
 private:
-    static size_t esz(int type) { return type == CV_32F ? 4 : 1; }
+    static size_t esz(int type) {
+        const int d = type & 7;
+        return (size_t)((type >> 3) + 1) * (d == CV_32F ? 4 : d == CV_16U ? 2 : 1);
+    }
     int type_;
     std::shared_ptr<uchar> buf_;
 };

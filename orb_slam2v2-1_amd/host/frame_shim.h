@@ -74,6 +74,7 @@ public:
     }
     ORBextractor *mpORBextractorLeft, *mpORBextractorRight;
     static float fx, fy, cx, cy;
+    cv::Mat mK, mDistCoef;   // calibration (include/Frame.h): 3x3 and 4x1 / 5x1 CV_32F
     float mbf, mb;
     int N;
     std::vector<cv::KeyPoint> mvKeys, mvKeysRight, mvKeysUn;
