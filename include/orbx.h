@@ -303,6 +303,44 @@ int orbx_rgbd_frame(orbx_extractor_t *h, const uint8_t *img, int channels, int r
                     const orbx_rgbd_camera_t *cam, int cap, orbx_keypoint_t *kp, uint8_t *desc, int *n,
                     orbx_keypoint_t *kun, float *uright, float *depth_out);
 
+/* ---- Stereo rectification of raw pairs: the stereo node's cv::initUndistortRectifyMap once per camera and cv::remap(INTER_LINEAR)
+ * of both images per frame (ros_stereo.cc:106-107, 161-162), then Tracking::GrabImageStereo's cvtColor (src/Tracking.cc:275-310).
+ * A rectifier holds one camera's maps on one device (DESIGN.md §3 items 9-11 restate the arithmetic).  It is immutable after
+ * creation: any thread or stream may use it. */
+typedef struct orbx_rectifier orbx_rectifier_t;
+/* initUndistortRectifyMap(K, D, R, P3x3, Size(w, hgt), CV_32FC1): K, R, P3x3 row-major 3x3 (P3x3 = the first three columns of the
+ * settings' P), D: nD = 4, 5 or 8 coefficients (k1 k2 p1 p2 [k3 [k4 k5 k6]]).  Map size 1..4095 each way.  A singular P3x3 * R,
+ * another nD, a bad size or device: ORBX_ERR_ARG. */
+int orbx_rectifier_create(const double K[9], const double *D, int nD, const double R[9], const double P3x3[9], int w, int hgt,
+                          int device, orbx_rectifier_t **out);
+int orbx_rectifier_destroy(orbx_rectifier_t *r);
+/* The CV_32F maps (M1 = x, M2 = y) as initUndistortRectifyMap returns them, w * hgt floats each, row-major; either may be NULL. */
+int orbx_rectifier_maps(const orbx_rectifier_t *r, float *mapx, float *mapy);
+/* Output tiles, tiles that gather their taps from memory (the footprint does not fit in LDS), device bytes held.  Any may be NULL. */
+int orbx_rectifier_info(const orbx_rectifier_t *r, int *tiles, int *gather_tiles, size_t *device_bytes);
+/* remap(src, dst, M1, M2, INTER_LINEAR, BORDER_CONSTANT 0) of B raw 8-bit images in HBM, asynchronous on `stream`: images [0, B0)
+ * through r0, [B0, B) through r1 (a rectifier no image uses may be NULL; both have one map size and device).  Source image b at
+ * d_src + b*image_stride_bytes, sw x sh pixels of `channels` (1, 3, 4) bytes, rows `stride` bytes apart; the source may be larger or
+ * smaller than the map.  Output: the map's size, gray (3 / 4 channels: RGB[A]/BGR[A]2GRAY of the remapped pixel, rgb != 0: channel 0
+ * is red) at d_gray + b*gray_image_stride_bytes, rows gray_stride bytes apart. */
+int orbx_rectify_device(const orbx_rectifier_t *r0, const orbx_rectifier_t *r1, int B0, const uint8_t *d_src, int B, int sw, int sh,
+                        int channels, int rgb, int stride, size_t image_stride_bytes, uint8_t *d_gray, int gray_stride,
+                        size_t gray_image_stride_bytes, void *stream);
+/* orbx_stereo_frame on a RAW pair: both images (w x hgt, `channels` 1 / 3 / 4, rows `stride` bytes apart) go up once, are rectified
+ * by rl / rr (map size w x hgt, the handle's device) into handle scratch in HBM and converted to gray, then extracted and matched as
+ * orbx_stereo_frame does.  Results equal orbx_stereo_frame on the rectified gray pair.  NULL rectifier, bad channels, map size,
+ * device or stride: ORBX_ERR_ARG.  Empty image: ORBX_OK with zero counts.  Synchronous. */
+int orbx_stereo_frame_rectified(orbx_extractor_t *h, const orbx_rectifier_t *rl, const orbx_rectifier_t *rr, const uint8_t *left,
+                                const uint8_t *right, int channels, int rgb, int w, int hgt, int stride, float mbf, float mb, int cap,
+                                orbx_keypoint_t *kl, uint8_t *dl, int *nl, orbx_keypoint_t *kr, uint8_t *dr, int *nr, float *uright,
+                                float *depth, int *nmatch);
+/* The latency form on a raw pair: the images are read where they lie (pinned host or device memory; pageable memory is staged once
+ * into pinned memory of the handle), rectified into handle scratch in HBM, then orbx_stereo_frame_view runs on the gray pair - the
+ * same record, alternation and validity.  Errors as orbx_stereo_frame_rectified.  Synchronous. */
+int orbx_stereo_frame_view_rectified(orbx_extractor_t *h, const orbx_rectifier_t *rl, const orbx_rectifier_t *rr, const uint8_t *left,
+                                     const uint8_t *right, int channels, int rgb, int w, int hgt, int stride, float mbf, float mb,
+                                     orbx_stereo_view_t *view);
+
 /* Pinned host memory for image / capture buffers (cv::Mat can wrap it: cv::Mat(rows, cols, CV_8UC1, ptr)); NULL on failure. */
 void *orbx_host_alloc(size_t bytes);
 void orbx_host_free(void *p);

@@ -51,6 +51,8 @@ EXPORTS = [
     "orbx_side_stream_for", "orbx_stereo_frame", "orbx_set_pyramid_buffers",
     "orbx_stereo_frame_view", "orbx_host_alloc", "orbx_host_free",
     "orbx_gray_from_color_device", "orbm_rgbd_batch_device", "orbx_rgbd_frame",
+    "orbx_rectifier_create", "orbx_rectifier_destroy", "orbx_rectifier_maps", "orbx_rectifier_info", "orbx_rectify_device",
+    "orbx_stereo_frame_rectified", "orbx_stereo_frame_view_rectified",
 ]
 # what include/orbx_dev.h declares on top: exported by the developer build only
 DEV_EXPORTS = ["orbx_debug_level_points", "orbx_debug_sincosf", "orbx_debug_blur_patches", "orbm_debug_features_in_area",
@@ -235,6 +237,14 @@ def _load(path, dev):
     L.orbm_rgbd_batch_device.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, sz, f32, C.POINTER(RGBDCamera), vp, vp, vp, vp]
     L.orbx_rgbd_frame.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, f32, C.POINTER(RGBDCamera), i32, vp, vp,
                                   C.POINTER(i32), vp, vp, vp]
+    L.orbx_rectifier_create.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, C.POINTER(vp)]
+    L.orbx_rectifier_destroy.argtypes = [vp]
+    L.orbx_rectifier_maps.argtypes = [vp, vp, vp]
+    L.orbx_rectifier_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(sz)]
+    L.orbx_rectify_device.argtypes = [vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, sz, vp, i32, sz, vp]
+    L.orbx_stereo_frame_rectified.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, i32, vp, vp, C.POINTER(i32), vp, vp,
+                                              C.POINTER(i32), vp, vp, C.POINTER(i32)]
+    L.orbx_stereo_frame_view_rectified.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp]
     L.orbx_host_alloc.argtypes = [sz]
     L.orbx_host_alloc.restype = vp
     L.orbx_host_free.argtypes = [vp]
@@ -528,6 +538,68 @@ class ORBextractor:
                 "dr": view(v.dr, b * 32, np.uint8).reshape(b, 32), "uright": view(v.uright, a, np.float32),
                 "depth": view(v.depth, a, np.float32), "nmatch": v.nmatch, "view": v}
 
+    @staticmethod
+    def _raw_image(a, name):
+        """uint8 [h, w] or [h, w, 3|4] host array -> (array, channels, row stride in bytes); row-strided views are passed as they are."""
+        a = np.asarray(a)
+        assert a.dtype == np.uint8 and (a.ndim == 2 or (a.ndim == 3 and a.shape[2] in (3, 4))), name + ": CV_8UC1/3/4 expected"
+        ch = 1 if a.ndim == 2 else a.shape[2]
+        if a.size and (a.strides[-1] != 1 or (ch > 1 and a.strides[1] != ch) or a.strides[0] < a.shape[1] * ch):
+            a = np.ascontiguousarray(a)
+        return a, ch, (a.strides[0] if a.size else 0)
+
+    def stereo_frame_rectified(self, rect_left, rect_right, left, right, mbf, mb, rgb=True):
+        """stereo_frame on a RAW pair (orbx_stereo_frame_rectified): ros_stereo's remap of both images with the two StereoRectifier
+        maps, GrabImageStereo's cvtColor for colour input, then extraction and ComputeStereoMatches.  left / right: uint8 [h, w] or
+        [h, w, 3|4] with one row stride (rgb: channel 0 is red) -> dict(kl, dl, kr, dr, uright, depth, nmatch)."""
+        left, ch, stride = self._raw_image(left, "left")
+        right, chr_, stride_r = self._raw_image(right, "right")
+        assert left.shape == right.shape and ch == chr_, "left and right differ in shape"
+        if stride_r != stride:
+            left, right = np.ascontiguousarray(left), np.ascontiguousarray(right)
+            stride = left.strides[0] if left.size else 0
+        hgt, w = left.shape[:2]
+        cap = (self.max_keypoints() if self._shape == (hgt, w) else self.nfeatures + 3 * self.nlevels + 8 * 64) + 8
+        kl, kr = np.zeros(cap, KP_DTYPE), np.zeros(cap, KP_DTYPE)
+        dl, dr = np.zeros((cap, 32), np.uint8), np.zeros((cap, 32), np.uint8)
+        ur, dp = np.zeros(cap, np.float32), np.zeros(cap, np.float32)
+        nl, nr, nm = C.c_int(), C.c_int(), C.c_int()
+        self._ck(self._L.orbx_stereo_frame_rectified(self._h, _rect_handle(rect_left), _rect_handle(rect_right),
+                                                     _p(left) if left.size else None, _p(right) if right.size else None, ch,
+                                                     int(bool(rgb)), w, hgt, stride, float(mbf), float(mb), cap, _p(kl), _p(dl),
+                                                     C.byref(nl), _p(kr), _p(dr), C.byref(nr), _p(ur), _p(dp), C.byref(nm)))
+        if left.size:
+            self._shape = (hgt, w)
+        a, b = nl.value, nr.value
+        return {"kl": kl[:a].copy(), "dl": dl[:a].copy(), "kr": kr[:b].copy(), "dr": dr[:b].copy(), "uright": ur[:a].copy(),
+                "depth": dp[:a].copy(), "nmatch": nm.value}
+
+    def stereo_frame_view_rectified(self, rect_left, rect_right, left, right, mbf, mb, rgb=True, shape=None, channels=None, stride=None):
+        """The latency form on a RAW pair (orbx_stereo_frame_view_rectified).  left / right: uint8 numpy arrays [h, w] / [h, w, 3|4]
+        (pageable: staged by the call), objects with data_ptr() (torch tensors - pinned host or device memory, [h, w] or [h, w, c]),
+        or raw addresses (then shape = (h, w) and channels).  Returns what stereo_frame_view returns."""
+        def addr(a):
+            if isinstance(a, int):
+                return a, None, a
+            if hasattr(a, "data_ptr"):
+                return a.data_ptr(), tuple(a.shape), a
+            a = np.ascontiguousarray(a, np.uint8)
+            return a.ctypes.data, a.shape, a
+        la, ra = addr(left), addr(right)
+        shp = la[1]
+        hgt, w = shape if shape is not None else shp[:2]
+        ch = channels if channels is not None else (1 if shp is None or len(shp) == 2 else shp[2])
+        v = StereoView()
+        self._ck(self._L.orbx_stereo_frame_view_rectified(self._h, _rect_handle(rect_left), _rect_handle(rect_right), la[0], ra[0],
+                                                          int(ch), int(bool(rgb)), w, hgt, w * ch if stride is None else int(stride),
+                                                          float(mbf), float(mb), C.byref(v)))
+        self._shape = (hgt, w)
+        a, b = v.nl, v.nr
+        view = lambda p, n, dt: np.frombuffer((C.c_char * (n * np.dtype(dt).itemsize)).from_address(p), dt) if n > 0 else np.zeros(0, dt)
+        return {"kl": view(v.kl, a, KP_DTYPE), "dl": view(v.dl, a * 32, np.uint8).reshape(a, 32), "kr": view(v.kr, b, KP_DTYPE),
+                "dr": view(v.dr, b * 32, np.uint8).reshape(b, 32), "uright": view(v.uright, a, np.float32),
+                "depth": view(v.depth, a, np.float32), "nmatch": v.nmatch, "view": v}
+
     def set_pyramid_buffers(self, n):
         """2 (default) or 3 pyramid buffers (orbx_set_pyramid_buffers)."""
         self._ck(self._L.orbx_set_pyramid_buffers(self._h, int(n)))
@@ -689,6 +761,64 @@ def rgbd_batch_device(d_kps, d_counts, B, cap, d_depth, depth_type, w, h, depth_
     _check(lib().orbm_rgbd_batch_device(d_kps, d_counts, int(B), int(cap), d_depth or None, int(depth_type), int(w), int(h),
                                         int(depth_stride), int(depth_image_stride), float(depth_map_factor), C.byref(cam), d_kun,
                                         d_uright, d_depth_out, stream))
+
+
+class StereoRectifier:
+    """One camera of a raw stereo rig: cv::initUndistortRectifyMap(K, D, R, P[:, :3], (w, h), CV_32FC1) on the device
+    (orbx_rectifier_create; ros_stereo.cc:106-107).  K, R: 3x3; P: 3x3 or 3x4 (the first three columns are used); D: 4, 5 or 8
+    coefficients.  Immutable; maps() returns (M1, M2) as float32 [h, w], info() the tile counts and device bytes."""
+
+    def __init__(self, K, D, R, P, w, h, device=0):
+        self._L = lib()
+        self._r = None
+        K = np.ascontiguousarray(np.asarray(K, np.float64).reshape(3, 3))
+        R = np.ascontiguousarray(np.asarray(R, np.float64).reshape(3, 3))
+        P = np.asarray(P, np.float64)
+        assert P.shape in ((3, 3), (3, 4)), "P: 3x3 or 3x4"
+        P = np.ascontiguousarray(P[:, :3])
+        D = np.ascontiguousarray(np.asarray(D, np.float64).ravel())
+        r = C.c_void_p()
+        _check(self._L.orbx_rectifier_create(_p(K), _p(D) if D.size else None, int(D.size), _p(R), _p(P), int(w), int(h), int(device),
+                                             C.byref(r)), self._L)
+        self._r = r
+        self.w, self.h, self.device = int(w), int(h), int(device)
+
+    @property
+    def handle(self):
+        return self._r.value
+
+    def maps(self):
+        mx, my = np.zeros((self.h, self.w), np.float32), np.zeros((self.h, self.w), np.float32)
+        _check(self._L.orbx_rectifier_maps(self._r, _p(mx), _p(my)), self._L)
+        return mx, my
+
+    def info(self):
+        t, g, b = C.c_int(), C.c_int(), C.c_size_t()
+        _check(self._L.orbx_rectifier_info(self._r, C.byref(t), C.byref(g), C.byref(b)), self._L)
+        return {"tiles": t.value, "gather_tiles": g.value, "device_bytes": b.value}
+
+    def close(self):
+        if self._r:
+            self._L.orbx_rectifier_destroy(self._r)
+            self._r = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _rect_handle(r):
+    return None if r is None else (r.handle if isinstance(r, StereoRectifier) else r)
+
+
+def rectify_device(r0, r1, B0, d_src, B, sw, sh, channels, rgb, stride, image_stride, d_gray, gray_stride, gray_image_stride, stream=0):
+    """remap(INTER_LINEAR) + RGB[A]/BGR[A]2GRAY of B raw images in HBM (orbx_rectify_device; raw device pointers): images [0, B0)
+    through r0, [B0, B) through r1 (StereoRectifier or None where no image uses it)."""
+    _check(lib().orbx_rectify_device(_rect_handle(r0), _rect_handle(r1), int(B0), d_src, int(B), int(sw), int(sh), int(channels),
+                                     int(bool(rgb)), int(stride), int(image_stride), d_gray, int(gray_stride), int(gray_image_stride),
+                                     stream), lib())
 
 
 def compute_stereo_matches(ex_left, ex_right, kl, dl, kr, dr, mbf, mb):

@@ -202,6 +202,7 @@ extern "C" int orbx_destroy(orbx_extractor_t *h) {
     if (h->st_stream) hipStreamSynchronize(h->st_stream);
     orbx_internal_free_stereo_scratch(h);
     orbx_internal_free_rgbd_scratch(h);
+    orbx_internal_free_rect_scratch(h);
     free_plan(h);
     hipFree(h->d_in); hipFree(h->d_kps); hipFree(h->d_desc); hipFree(h->d_counts); hipFree(h->d_dbgBlur);
     hipFree(h->d_sfr); if (h->h_sfr) hipHostFree(h->h_sfr);
@@ -1406,22 +1407,16 @@ extern "C" int orbx_extract_batch(orbx_extractor_t *h, const uint8_t *const *img
 // matcher (src/Frame.cc:78-84: ExtractORB(0, imLeft) || ExtractORB(1, imRight), then ComputeStereoMatches, :481-655).  Both images
 // go up, are extracted as one batch of two on this handle (slots 0 / 1), matched on the device, and everything comes down behind ONE
 // synchronisation: no second extractor, no re-upload of the keypoints the extractor just produced.
-extern "C" int orbx_stereo_frame(orbx_extractor_t *h, const uint8_t *left, const uint8_t *right, int w, int hgt, int stride,
-                                 float mbf, float mb, int cap, orbx_keypoint_t *kl, uint8_t *dl, int *nl, orbx_keypoint_t *kr,
-                                 uint8_t *dr, int *nr, float *uright, float *depth, int *nmatch) {
-    if (!h || !kl || !dl || !nl || !kr || !dr || !nr || !uright || !depth || cap < 1) {
-        orbx_set_error("orbx_stereo_frame: bad arguments");
-        return ORBX_ERR_ARG;
-    }
-    *nl = 0; *nr = 0;
-    if (nmatch) *nmatch = 0;
-    if (!left || !right || w <= 0 || hgt <= 0) return ORBX_OK;   // empty image (:1046-1047)
-    if (stride < w) { orbx_set_error("stride < width"); return ORBX_ERR_ARG; }
+// The body of orbx_stereo_frame: host images `left` / `right` are uploaded into the handle's staging first; d_pair != NULL: the pair
+// is in HBM already (image 1 at d_pair + pair_img_bytes, work queued on the handle's stream before this call produces it).
+static int stereo_frame_run(orbx_extractor *h, const uint8_t *left, const uint8_t *right, const uint8_t *d_pair, int w, int hgt,
+                            int stride, size_t pair_img_bytes, float mbf, float mb, int cap, orbx_keypoint_t *kl, uint8_t *dl, int *nl,
+                            orbx_keypoint_t *kr, uint8_t *dr, int *nr, float *uright, float *depth, int *nmatch) {
     ORBX_HIP(hipSetDevice(h->device));
     int rc = ensure_plan(h, w, hgt, 2);
     if (rc) return rc;
     const size_t span = (size_t)stride * (hgt - 1) + w, img_bytes = (span + 255) & ~(size_t)255;
-    rc = ensure_staging(h, img_bytes * 2, 2, cap);
+    rc = ensure_staging(h, d_pair ? 0 : img_bytes * 2, 2, cap);
     if (rc) return rc;
     const int dcap = h->out_cap;
     if (h->sfr_cap < dcap) {
@@ -1433,9 +1428,12 @@ extern "C" int orbx_stereo_frame(orbx_extractor_t *h, const uint8_t *left, const
         h->sfr_cap = dcap;
     }
     hipStream_t st = h->stream;
-    ORBX_HIP(hipMemcpyAsync(h->d_in, left, span, hipMemcpyHostToDevice, st));
-    ORBX_HIP(hipMemcpyAsync(h->d_in + img_bytes, right, span, hipMemcpyHostToDevice, st));
-    rc = launch_pipeline(h, h->d_in, 2, w, hgt, stride, img_bytes, h->d_kps, h->d_desc, h->d_counts, dcap, st);
+    if (!d_pair) {
+        ORBX_HIP(hipMemcpyAsync(h->d_in, left, span, hipMemcpyHostToDevice, st));
+        ORBX_HIP(hipMemcpyAsync(h->d_in + img_bytes, right, span, hipMemcpyHostToDevice, st));
+    }
+    rc = launch_pipeline(h, d_pair ? d_pair : h->d_in, 2, w, hgt, stride, d_pair ? pair_img_bytes : img_bytes, h->d_kps, h->d_desc,
+                         h->d_counts, dcap, st);
     if (rc) return rc;
     float *d_ur = h->d_sfr, *d_dp = h->d_sfr + dcap;
     int32_t *d_nm = (int32_t *)(h->d_sfr + 2 * (size_t)dcap);
@@ -1469,6 +1467,27 @@ extern "C" int orbx_stereo_frame(orbx_extractor_t *h, const uint8_t *left, const
     return status;
 }
 
+extern "C" int orbx_stereo_frame(orbx_extractor_t *h, const uint8_t *left, const uint8_t *right, int w, int hgt, int stride,
+                                 float mbf, float mb, int cap, orbx_keypoint_t *kl, uint8_t *dl, int *nl, orbx_keypoint_t *kr,
+                                 uint8_t *dr, int *nr, float *uright, float *depth, int *nmatch) {
+    if (!h || !kl || !dl || !nl || !kr || !dr || !nr || !uright || !depth || cap < 1) {
+        orbx_set_error("orbx_stereo_frame: bad arguments");
+        return ORBX_ERR_ARG;
+    }
+    *nl = 0; *nr = 0;
+    if (nmatch) *nmatch = 0;
+    if (!left || !right || w <= 0 || hgt <= 0) return ORBX_OK;   // empty image (:1046-1047)
+    if (stride < w) { orbx_set_error("stride < width"); return ORBX_ERR_ARG; }
+    return stereo_frame_run(h, left, right, nullptr, w, hgt, stride, 0, mbf, mb, cap, kl, dl, nl, kr, dr, nr, uright, depth, nmatch);
+}
+
+int orbx_internal_stereo_frame_device(orbx_extractor *h, const uint8_t *d_pair, int w, int hgt, int stride, size_t img_bytes, float mbf,
+                                      float mb, int cap, orbx_keypoint_t *kl, uint8_t *dl, int *nl, orbx_keypoint_t *kr, uint8_t *dr,
+                                      int *nr, float *uright, float *depth, int *nmatch) {
+    return stereo_frame_run(h, nullptr, nullptr, d_pair, w, hgt, stride, img_bytes, mbf, mb, cap, kl, dl, nl, kr, dr, nr, uright, depth,
+                            nmatch);
+}
+
 // ---- the latency form: one stereo frame, no copy commands (include/orbx.h: orbx_stereo_frame_view)
 extern "C" void *orbx_host_alloc(size_t bytes) {
     void *p = nullptr;
@@ -1478,7 +1497,7 @@ extern "C" void *orbx_host_alloc(size_t bytes) {
 extern "C" void orbx_host_free(void *p) { if (p) (void)hipHostFree(p); }
 
 // the address a kernel reads the image at, or NULL when the memory is ordinary pageable host memory
-static const uint8_t *device_visible(const uint8_t *p) {
+const uint8_t *orbx_internal_device_visible(const uint8_t *p) {
     hipPointerAttribute_t a;
     memset(&a, 0, sizeof(a));
     if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return nullptr; }   // (older runtimes: an error for unregistered memory)
@@ -1513,7 +1532,7 @@ extern "C" int orbx_stereo_frame_view(orbx_extractor_t *h, const uint8_t *left, 
         h->fv_cap = cap;
     }
     const size_t span = (size_t)stride * (hgt - 1) + w, img_bytes = (span + 255) & ~(size_t)255;
-    const uint8_t *dl = device_visible(left), *dr = device_visible(right);
+    const uint8_t *dl = orbx_internal_device_visible(left), *dr = orbx_internal_device_visible(right);
     if (!dl || !dr) {   // pageable memory: one memcpy per image into the handle's pinned staging buffer, read from there
         if (h->fv_stage_bytes < 2 * img_bytes) {
             ORBX_HIP(hipStreamSynchronize(h->stream));

@@ -146,17 +146,25 @@ struct orbx_extractor {
     double acc_ms[ORBX_NUM_STAGES];
     long acc_n;
     struct RgbdScratch *rgbd;   // orbx_rgbd_frame: colour / gray / depth images and the frame's results (orbx_rgbd.hip), NULL until first used
+    struct RectScratch *rect;   // orbx_stereo_frame(_view)_rectified: raw pair, its pinned staging, rectified gray pair (orbx_rectify.hip), NULL until first used
 };
 
 // extractor internals used by the matcher side
 void orbx_internal_free_stereo_scratch(orbx_extractor *h);   // orbx_match.hip
 void orbx_internal_free_rgbd_scratch(orbx_extractor *h);     // orbx_rgbd.hip
+void orbx_internal_free_rect_scratch(orbx_extractor *h);     // orbx_rectify.hip
+// orbx_stereo_frame on a pair already in HBM on the handle's device (image 1 at d_pair + img_bytes), queued on the handle's stream (orbx_extract.hip)
+int orbx_internal_stereo_frame_device(orbx_extractor *h, const uint8_t *d_pair, int w, int hgt, int stride, size_t img_bytes, float mbf,
+                                      float mb, int cap, orbx_keypoint_t *kl, uint8_t *dl, int *nl, orbx_keypoint_t *kr, uint8_t *dr,
+                                      int *nr, float *uright, float *depth, int *nmatch);
 // ComputeStereoMatches of the frame in image slots 0 / 1 of h with the record layout of orbx_stereo_frame_view (orbx_match.hip)
 int orbx_internal_stereo_frame_record(orbx_extractor *h, uint8_t *d_rec, uint8_t *rec_hostdev, int cap, float mbf, float mb, hipStream_t st, bool recordsOnHost,
                                       int32_t *doneFlag, int doneSeq, int *flagArmed);
 void orbx_internal_release_match_scratch();                  // orbx_match.hip      (thread-local staging pair)
 void orbx_internal_release_arena();                          // orbx_match_fast.hip (thread-local arena)
 void orbx_internal_release_bow_scratch();                    // orbx_bow.hip        (thread-local scratch)
+// the address a kernel reads an image at (device, pinned or managed memory), or NULL for ordinary pageable host memory (orbx_extract.hip)
+const uint8_t *orbx_internal_device_visible(const uint8_t *p);
 int orbx_internal_level(const orbx_extractor *h, int level, int *w, int *hgt, int *pstride,
                         unsigned long long *poff);
 

@@ -714,23 +714,8 @@ int ComputeDistinctiveDescriptorsHIP(const std::vector<MapPoint *> &vpMapPoints,
     return n;
 }
 
-int ExtractStereoFrameHIP(Frame &F, const cv::Mat &imLeft, const cv::Mat &imRight) {
-    F.mvKeys.clear(); F.mvKeysRight.clear(); F.mDescriptors.release(); F.mDescriptorsRight.release();
-    F.mvuRight.clear(); F.mvDepth.clear(); F.N = 0;
-    if (!F.mpORBextractorLeft || !F.mpORBextractorLeft->ok() || imLeft.empty() || imRight.empty()) return 0;
-    if (imLeft.cols != imRight.cols || imLeft.rows != imRight.rows || imLeft.step != imRight.step) {
-        std::fprintf(stderr, "ExtractStereoFrame: left and right image differ in size or stride\n");
-        return -1;
-    }
-    orbx_extractor_t *h = F.mpORBextractorLeft->handle();
-    // the latency form (include/orbx.h: orbx_stereo_frame_view): no copy command in either direction - the first kernel reads the images
-    // where they lie (pinned capture buffers from orbx_host_alloc are read over the bus; a pageable cv::Mat is staged by the call) and the
-    // last kernel writes the frame's record into pinned memory of the handle, which `v` points into until the call after the next
-    orbx_stereo_view_t v;
-    if (orbx_stereo_frame_view(h, imLeft.ptr(0), imRight.ptr(0), imLeft.cols, imLeft.rows, (int)imLeft.step, F.mbf, F.mb, &v) != ORBX_OK) {
-        std::fprintf(stderr, "ExtractStereoFrame: %s\n", orbx_last_error());
-        return -1;
-    }
+// fills the stereo Frame's feature members from the record of a latency call
+static int fill_stereo_frame(Frame &F, const orbx_stereo_view_t &v) {
     const int nl = v.nl, nr = v.nr, nm = v.nmatch;
     auto fill = [](const orbx_keypoint_t *src, const uint8_t *dsrc, int n, std::vector<cv::KeyPoint> &keys, cv::Mat &desc) {
         keys.reserve(n);
@@ -752,6 +737,76 @@ int ExtractStereoFrameHIP(Frame &F, const cv::Mat &imLeft, const cv::Mat &imRigh
     F.mvuRight.assign(v.uright, v.uright + nl);       // -1 where unmatched, as :483-484 initialise them
     F.mvDepth.assign(v.depth, v.depth + nl);
     return nm;
+}
+
+int ExtractStereoFrameHIP(Frame &F, const cv::Mat &imLeft, const cv::Mat &imRight) {
+    F.mvKeys.clear(); F.mvKeysRight.clear(); F.mDescriptors.release(); F.mDescriptorsRight.release();
+    F.mvuRight.clear(); F.mvDepth.clear(); F.N = 0;
+    if (!F.mpORBextractorLeft || !F.mpORBextractorLeft->ok() || imLeft.empty() || imRight.empty()) return 0;
+    if (imLeft.cols != imRight.cols || imLeft.rows != imRight.rows || imLeft.step != imRight.step) {
+        std::fprintf(stderr, "ExtractStereoFrame: left and right image differ in size or stride\n");
+        return -1;
+    }
+    orbx_extractor_t *h = F.mpORBextractorLeft->handle();
+    // the latency form (include/orbx.h: orbx_stereo_frame_view): no copy command in either direction - the first kernel reads the images
+    // where they lie (pinned capture buffers from orbx_host_alloc are read over the bus; a pageable cv::Mat is staged by the call) and the
+    // last kernel writes the frame's record into pinned memory of the handle, which `v` points into until the call after the next
+    orbx_stereo_view_t v;
+    if (orbx_stereo_frame_view(h, imLeft.ptr(0), imRight.ptr(0), imLeft.cols, imLeft.rows, (int)imLeft.step, F.mbf, F.mb, &v) != ORBX_OK) {
+        std::fprintf(stderr, "ExtractStereoFrame: %s\n", orbx_last_error());
+        return -1;
+    }
+    return fill_stereo_frame(F, v);
+}
+
+// K / D / R / P as doubles, row-major (CV_64F or CV_32F, one channel); false: another type
+static bool mat_doubles(const cv::Mat &m, std::vector<double> &out) {
+    out.clear();
+    if (m.empty() || m.channels() != 1 || (m.depth() != CV_64F && m.depth() != CV_32F)) return false;
+    for (int r = 0; r < m.rows; r++)
+        for (int c = 0; c < m.cols; c++) out.push_back(m.depth() == CV_64F ? m.at<double>(r, c) : (double)m.at<float>(r, c));
+    return true;
+}
+
+StereoRectifierHIP::StereoRectifierHIP(const cv::Mat &K, const cv::Mat &D, const cv::Mat &R, const cv::Mat &P, cv::Size size)
+    : mpR(nullptr), mSize(size) {
+    std::vector<double> k, d, r, p;
+    if (!mat_doubles(K, k) || !mat_doubles(D, d) || !mat_doubles(R, r) || !mat_doubles(P, p) || k.size() != 9 || r.size() != 9 ||
+        P.rows != 3 || (P.cols != 3 && P.cols != 4)) {
+        std::fprintf(stderr, "StereoRectifierHIP: K, R 3x3, P 3x3 / 3x4 and D of CV_64F / CV_32F expected\n");
+        return;
+    }
+    double p3[9];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) p3[3 * i + j] = p[(size_t)P.cols * i + j];   // P.rowRange(0,3).colRange(0,3)
+    const char *dev = std::getenv("ORBX_DEVICE");
+    if (orbx_rectifier_create(k.data(), d.data(), (int)d.size(), r.data(), p3, size.width, size.height, dev ? std::atoi(dev) : 0,
+                              &mpR) != ORBX_OK) {
+        std::fprintf(stderr, "StereoRectifierHIP: %s\n", orbx_last_error());
+        mpR = nullptr;
+    }
+}
+
+StereoRectifierHIP::~StereoRectifierHIP() { orbx_rectifier_destroy(mpR); }
+
+int ExtractStereoFrameHIP(Frame &F, const cv::Mat &rawLeft, const cv::Mat &rawRight, const StereoRectifierHIP &L,
+                          const StereoRectifierHIP &R, bool bRGB) {
+    F.mvKeys.clear(); F.mvKeysRight.clear(); F.mDescriptors.release(); F.mDescriptorsRight.release();
+    F.mvuRight.clear(); F.mvDepth.clear(); F.N = 0;
+    if (!F.mpORBextractorLeft || !F.mpORBextractorLeft->ok() || rawLeft.empty() || rawRight.empty()) return 0;
+    const int ch = rawLeft.channels();
+    if (rawLeft.type() != rawRight.type() || rawLeft.depth() != CV_8U || (ch != 1 && ch != 3 && ch != 4) || rawLeft.cols != rawRight.cols ||
+        rawLeft.rows != rawRight.rows || rawLeft.step != rawRight.step || !L.ok() || !R.ok()) {
+        std::fprintf(stderr, "ExtractStereoFrame: two CV_8UC1/3/4 images of one size and step and two built rectifiers expected\n");
+        return -1;
+    }
+    orbx_stereo_view_t v;
+    if (orbx_stereo_frame_view_rectified(F.mpORBextractorLeft->handle(), L.handle(), R.handle(), rawLeft.ptr(0), rawRight.ptr(0), ch,
+                                         bRGB ? 1 : 0, rawLeft.cols, rawLeft.rows, (int)rawLeft.step, F.mbf, F.mb, &v) != ORBX_OK) {
+        std::fprintf(stderr, "ExtractStereoFrame: %s\n", orbx_last_error());
+        return -1;
+    }
+    return fill_stereo_frame(F, v);
 }
 
 int ExtractRGBDFrameHIP(Frame &F, const cv::Mat &im, const cv::Mat &imDepth, float depthMapFactor, bool bRGB) {

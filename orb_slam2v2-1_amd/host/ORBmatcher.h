@@ -92,6 +92,31 @@ int ComputeStereoMatchesHIP(Frame &F);
 // Returns the number of stereo matches (< 0: error, outputs empty).
 int ExtractStereoFrameHIP(Frame &F, const cv::Mat &imLeft, const cv::Mat &imRight);
 
+// One camera of a raw stereo rig on the GPU: what the stereo node builds with cv::initUndistortRectifyMap(K, D, R, P.rowRange(0,3).
+// colRange(0,3), size, CV_32F, M1, M2) (ros_stereo.cc:106-107), in that argument order.  K, R: 3x3; P: 3x3 or 3x4 (the first three
+// columns are used); D: 4, 5 or 8 coefficients; CV_64F (as the settings store them) or CV_32F.  Immutable once built; ok() tells
+// whether it was (the maps of the device, orbx_rectifier_maps, otherwise the reason on stderr).
+class StereoRectifierHIP {
+public:
+    StereoRectifierHIP(const cv::Mat &K, const cv::Mat &D, const cv::Mat &R, const cv::Mat &P, cv::Size size);
+    ~StereoRectifierHIP();
+    bool ok() const { return mpR != nullptr; }
+    const orbx_rectifier_t *handle() const { return mpR; }
+    cv::Size size() const { return mSize; }
+private:
+    StereoRectifierHIP(const StereoRectifierHIP &);
+    StereoRectifierHIP &operator=(const StereoRectifierHIP &);
+    orbx_rectifier_t *mpR;
+    cv::Size mSize;
+};
+
+// The same as ExtractStereoFrameHIP on a RAW pair (ros_stereo.cc:158-163 + Tracking::GrabImageStereo, src/Tracking.cc:275-310):
+// both images are remapped with L / R (INTER_LINEAR) and - CV_8UC3 / CV_8UC4 - converted to gray (bRGB: channel 0 is red, mbRGB)
+// on the GPU, then extracted and matched.  rawLeft / rawRight: CV_8UC1/3/4 of the rectifiers' size, one type and row step.
+// Returns the number of stereo matches (< 0: error, outputs empty).
+int ExtractStereoFrameHIP(Frame &F, const cv::Mat &rawLeft, const cv::Mat &rawRight, const StereoRectifierHIP &L,
+                          const StereoRectifierHIP &R, bool bRGB);
+
 // The RGB-D Frame constructor's feature part in ONE GPU call (src/Frame.cc:119-171): ExtractORB(0, imGray), UndistortKeyPoints and
 // ComputeStereoFromRGBD, plus - for a raw capture - GrabImageRGBD's conversions (src/Tracking.cc:315-336).  Fills F.mvKeys /
 // mvKeysUn / mDescriptors / N / mvuRight / mvDepth from F.mpORBextractorLeft, F.mK, F.mDistCoef and F.mbf.  im: CV_8UC1, CV_8UC3 or

@@ -14,12 +14,14 @@
 #define CV_8U 0
 #define CV_16U 2
 #define CV_32F 5
+#define CV_64F 6
 #define CV_MAKETYPE(depth, cn) ((depth) + (((cn) - 1) << 3))
 #define CV_8UC1 CV_8U
 #define CV_8UC3 CV_MAKETYPE(CV_8U, 3)
 #define CV_8UC4 CV_MAKETYPE(CV_8U, 4)
 #define CV_16UC1 CV_16U
 #define CV_32FC1 CV_32F
+#define CV_64FC1 CV_64F
 
 namespace cv {
 typedef unsigned char uchar;
@@ -31,6 +33,11 @@ template <typename T> struct Point_ {
 typedef Point_<int> Point;
 typedef Point_<int> Point2i;
 typedef Point_<float> Point2f;
+struct Size {
+    int width, height;
+    Size() : width(0), height(0) {}
+    Size(int w, int h) : width(w), height(h) {}
+};
 
 struct KeyPoint {  // field order of cv::KeyPoint (reference: include/BoostArchiver.h:47-57)
     Point2f pt;
@@ -86,7 +93,7 @@ public:
 private:
     static size_t esz(int type) {
         const int d = type & 7;
-        return (size_t)((type >> 3) + 1) * (d == CV_32F ? 4 : d == CV_16U ? 2 : 1);
+        return (size_t)((type >> 3) + 1) * (d == CV_64F ? 8 : d == CV_32F ? 4 : d == CV_16U ? 2 : 1);
     }
     int type_;
     std::shared_ptr<uchar> buf_;
