@@ -341,6 +341,48 @@ int orbx_stereo_frame_view_rectified(orbx_extractor_t *h, const orbx_rectifier_t
                                      const uint8_t *right, int channels, int rgb, int w, int hgt, int stride, float mbf, float mb,
                                      orbx_stereo_view_t *view);
 
+/* ---- Dense RGB-D keyframe clouds: PointCloudMapping::generatePointCloud (src/pointcloudmapping.cc:83-114) and the
+ * pcl::VoxelGrid<PointXYZRGBA> filter saveOctomap puts every keyframe's cloud through (:117-127), DESIGN.md §3 items 12-13.
+ * Plane segmentation, the axis swap, octomap insertion and PCD output (:139-279) stay with the caller. */
+typedef struct {
+    float x, y, z;
+    uint8_t b, g, r, a;   /* "b" is channel 0 of the colour image whatever its order, as the reference names it (:99-101) */
+} orbx_cloud_point_t;     /* 16 bytes */
+typedef struct orbx_cloudmapper orbx_cloudmapper_t;
+/* PointCloudMapping(resolution): leaf = (float)resolution of voxel.setLeafSize; step: every step-th pixel of every step-th row (the
+ * reference: 3); alpha: the a of every generated point (what PCL's default constructor leaves there differs between releases).
+ * leaf <= 0, step < 1, alpha outside 0..255: ORBX_ERR_ARG, checked before the device is touched.  The mapper owns grow-only scratch
+ * in HBM; its calls come from one stream at a time. */
+int orbx_cloudmapper_create(float leaf, int step, int alpha, int device, orbx_cloudmapper_t **out);
+int orbx_cloudmapper_destroy(orbx_cloudmapper_t *m);
+/* points a w x hgt image can give at most: ceil(w / step) * ceil(hgt / step) (0: bad arguments) */
+int orbx_cloud_capacity(int w, int hgt, int step);
+/* generatePointCloud of B keyframes of one size and camera in HBM, asynchronous on `stream`.  Depth image b at d_depth +
+ * b*depth_image_stride_bytes, rows depth_stride bytes apart, converted as GrabImageRGBD does (see orbm_rgbd_batch_device); colour image
+ * b at d_color + b*color_image_stride_bytes, `channels` (3 or 4) bytes per pixel: b, g, r = bytes 0, 1, 2 of pixel n (the reference
+ * indexes n*3 whatever the channel count, i.e. reads the wrong pixel of a 4-channel image).  A sample is kept unless d < 0.01 or
+ * d > 10 (as doubles: a NaN depth is KEPT and gives a NaN point); z = d, x = (n - cx) * z / fx, y = (m - cy) * z / fy in float; then
+ * p = Twc * (x, y, z, 1) in double, rounded to float.  Twc16: HOST, B x 16 doubles, row-major - the caller's
+ * toSE3Quat(GetPose()).inverse().matrix(); it is read before the call returns.  Out: d_points [B][cap] in scan order, d_counts [B];
+ * a count above cap is clamped. */
+int orbx_cloud_generate_device(orbx_cloudmapper_t *m, const void *d_depth, int depth_type, int depth_stride,
+                               size_t depth_image_stride_bytes, float depth_map_factor, const uint8_t *d_color, int channels,
+                               int color_stride, size_t color_image_stride_bytes, int B, int w, int hgt, float fx, float fy, float cx,
+                               float cy, const double *Twc16, orbx_cloud_point_t *d_points, int cap, int32_t *d_counts, void *stream);
+/* VoxelGrid::applyFilter (leaf = the mapper's, downsample_all_data, no filter field) of B clouds in HBM, asynchronous on `stream`:
+ * cloud b = the first min(d_counts[b], cap) rows of d_points + b*cap.  Points with a non-finite coordinate are dropped; one point per
+ * occupied cell in ascending cell index, x y z and r g b a each the float sum over the cell's points in input order divided by their
+ * number (colours truncated).  d_out [B][out_cap] (not d_points), d_out_counts [B]: clamped to out_cap; -1 where the grid has more
+ * than INT32_MAX cells (PCL warns and returns its input: nothing is written). */
+int orbx_cloud_voxel_device(orbx_cloudmapper_t *m, const orbx_cloud_point_t *d_points, const int32_t *d_counts, int B, int cap,
+                            orbx_cloud_point_t *d_out, int out_cap, int32_t *d_out_counts, void *stream);
+/* One keyframe host to host (synchronous): the images go up, then generate and filter as above.  raw_out (may be NULL) / n_raw (may
+ * be NULL): the generated cloud; out / n: the filtered one - the generated one where the grid overflows, as PCL returns it; cap rows
+ * each.  Empty image: ORBX_OK with zero counts.  More than cap points: clamped, ORBX_ERR_CAPACITY. */
+int orbx_keyframe_cloud(orbx_cloudmapper_t *m, const uint8_t *color, int channels, int color_stride, const void *depth,
+                        int depth_type, int depth_stride, float depth_map_factor, int w, int hgt, float fx, float fy, float cx, float cy,
+                        const double *Twc16, int cap, orbx_cloud_point_t *raw_out, int *n_raw, orbx_cloud_point_t *out, int *n);
+
 /* Pinned host memory for image / capture buffers (cv::Mat can wrap it: cv::Mat(rows, cols, CV_8UC1, ptr)); NULL on failure. */
 void *orbx_host_alloc(size_t bytes);
 void orbx_host_free(void *p);

@@ -33,6 +33,9 @@ LASTPT_DTYPE = np.dtype([("has_mp", "<i4"), ("wx", "<f4"), ("wy", "<f4"), ("wz",
 WINDOW_DTYPE = np.dtype([("valid", "<i4"), ("u", "<f4"), ("v", "<f4"), ("radius", "<f4"), ("min_level", "<i4"),
                          ("max_level", "<i4"), ("angle", "<f4"), ("blocks", "<i4"), ("ur_c", "<f4"), ("ur_tol", "<f4")])
 
+# orbx_cloud_point_t: a point of a dense keyframe cloud (pcl::PointXYZRGBA's fields; "b" is channel 0 of the colour image)
+CLOUD_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("b", "u1"), ("g", "u1"), ("r", "u1"), ("a", "u1")])
+
 ORBX_OK, ORBX_ERR_ARG, ORBX_ERR_NO_DEVICE, ORBX_ERR_HIP, ORBX_ERR_CAPACITY, ORBX_ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5
 NUM_STAGES = 5
 
@@ -53,6 +56,8 @@ EXPORTS = [
     "orbx_gray_from_color_device", "orbm_rgbd_batch_device", "orbx_rgbd_frame",
     "orbx_rectifier_create", "orbx_rectifier_destroy", "orbx_rectifier_maps", "orbx_rectifier_info", "orbx_rectify_device",
     "orbx_stereo_frame_rectified", "orbx_stereo_frame_view_rectified",
+    "orbx_cloudmapper_create", "orbx_cloudmapper_destroy", "orbx_cloud_capacity", "orbx_cloud_generate_device",
+    "orbx_cloud_voxel_device", "orbx_keyframe_cloud",
 ]
 # what include/orbx_dev.h declares on top: exported by the developer build only
 DEV_EXPORTS = ["orbx_debug_level_points", "orbx_debug_sincosf", "orbx_debug_blur_patches", "orbm_debug_features_in_area",
@@ -245,6 +250,13 @@ def _load(path, dev):
     L.orbx_stereo_frame_rectified.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, i32, vp, vp, C.POINTER(i32), vp, vp,
                                               C.POINTER(i32), vp, vp, C.POINTER(i32)]
     L.orbx_stereo_frame_view_rectified.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp]
+    L.orbx_cloudmapper_create.argtypes = [f32, i32, i32, i32, C.POINTER(vp)]
+    L.orbx_cloudmapper_destroy.argtypes = [vp]
+    L.orbx_cloud_capacity.argtypes = [i32, i32, i32]
+    L.orbx_cloud_generate_device.argtypes = [vp, vp, i32, i32, sz, f32, vp, i32, i32, sz, i32, i32, i32, f32, f32, f32, f32, vp, vp, i32, vp, vp]
+    L.orbx_cloud_voxel_device.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, vp]
+    L.orbx_keyframe_cloud.argtypes = [vp, vp, i32, i32, vp, i32, i32, f32, i32, i32, f32, f32, f32, f32, vp, i32, vp, C.POINTER(i32), vp,
+                                      C.POINTER(i32)]
     L.orbx_host_alloc.argtypes = [sz]
     L.orbx_host_alloc.restype = vp
     L.orbx_host_free.argtypes = [vp]
@@ -819,6 +831,76 @@ def rectify_device(r0, r1, B0, d_src, B, sw, sh, channels, rgb, stride, image_st
     _check(lib().orbx_rectify_device(_rect_handle(r0), _rect_handle(r1), int(B0), d_src, int(B), int(sw), int(sh), int(channels),
                                      int(bool(rgb)), int(stride), int(image_stride), d_gray, int(gray_stride), int(gray_image_stride),
                                      stream), lib())
+
+
+def cloud_capacity(w, h, step=3):
+    """ceil(w / step) * ceil(h / step): the points one w x h keyframe can give (orbx_cloud_capacity)."""
+    return lib().orbx_cloud_capacity(int(w), int(h), int(step))
+
+
+class CloudMapper:
+    """PointCloudMapping(resolution) on the device (orbx_cloudmapper_create; src/pointcloudmapping.cc:29-34, 83-127): generatePointCloud
+    of RGB-D keyframes and the pcl::VoxelGrid filter saveOctomap runs on each.  leaf: the voxel's edge (System.cc passes 0.1); step:
+    every step-th pixel of every step-th row; alpha: the a of every generated point.  Points are CLOUD_DTYPE rows."""
+
+    def __init__(self, leaf=0.1, step=3, alpha=255, device=0):
+        self._L = lib()
+        self._m = None
+        m = C.c_void_p()
+        _check(self._L.orbx_cloudmapper_create(float(leaf), int(step), int(alpha), int(device), C.byref(m)), self._L)
+        self._m = m
+        self.leaf, self.step, self.alpha, self.device = float(np.float32(leaf)), int(step), int(alpha), int(device)
+
+    def close(self):
+        if self._m:
+            self._L.orbx_cloudmapper_destroy(self._m)
+            self._m = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def capacity(self, w, h):
+        return self._L.orbx_cloud_capacity(int(w), int(h), self.step)
+
+    def generate_device(self, d_depth, depth_type, depth_stride, depth_image_stride, depth_map_factor, d_color, channels, color_stride,
+                        color_image_stride, B, w, h, fx, fy, cx, cy, Twc, d_points, cap, d_counts, stream=0):
+        """generatePointCloud of B keyframes in HBM (orbx_cloud_generate_device; raw device pointers).  Twc: host, B x 4 x 4 doubles
+        (the inverse pose matrices); d_points [B][cap] CLOUD_DTYPE rows in scan order, d_counts [B] int32.  Asynchronous."""
+        T = np.ascontiguousarray(np.asarray(Twc, np.float64).reshape(int(B), 16))
+        _check(self._L.orbx_cloud_generate_device(self._m, d_depth, int(depth_type), int(depth_stride), int(depth_image_stride),
+                                                  float(depth_map_factor), d_color, int(channels), int(color_stride),
+                                                  int(color_image_stride), int(B), int(w), int(h), float(fx), float(fy), float(cx),
+                                                  float(cy), _p(T), d_points, int(cap), d_counts, stream), self._L)
+
+    def voxel_device(self, d_points, d_counts, B, cap, d_out, out_cap, d_out_counts, stream=0):
+        """The voxel-grid centroid filter of B clouds in HBM (orbx_cloud_voxel_device; raw device pointers).  d_out_counts [B]: the
+        voxels of each cloud, -1 where the grid overflows (PCL returns its input there).  Asynchronous."""
+        _check(self._L.orbx_cloud_voxel_device(self._m, d_points, d_counts, int(B), int(cap), d_out, int(out_cap), d_out_counts, stream),
+               self._L)
+
+    def keyframe_cloud(self, color, depth, fx, fy, cx, cy, Twc, depth_map_factor=1.0, cap=None):
+        """One keyframe host to host (orbx_keyframe_cloud).  color: uint8 [h, w, 3|4]; depth: uint16 / float32 [h, w]; Twc: 4 x 4
+        doubles -> (raw, filtered) CLOUD_DTYPE arrays: generatePointCloud's cloud and what VoxelGrid makes of it."""
+        color, ch, cstride = ORBextractor._raw_image(color, "color")
+        assert ch in (3, 4), "CV_8UC3 / CV_8UC4 colour expected"
+        depth = np.asarray(depth)
+        hgt, w = color.shape[:2]
+        assert depth.shape == (hgt, w) and depth.dtype in _DEPTH_TYPES, "CV_16U / CV_32F depth of the image's size expected"
+        if depth.size and (depth.strides[1] != depth.itemsize or depth.strides[0] < w * depth.itemsize):
+            depth = np.ascontiguousarray(depth)
+        T = np.ascontiguousarray(np.asarray(Twc, np.float64).reshape(16))
+        if cap is None:
+            cap = max(self.capacity(w, hgt), 1)
+        raw, out = np.zeros(cap, CLOUD_DTYPE), np.zeros(cap, CLOUD_DTYPE)
+        nr, n = C.c_int(), C.c_int()
+        _check(self._L.orbx_keyframe_cloud(self._m, _p(color) if color.size else None, ch, cstride, _p(depth) if depth.size else None,
+                                           _DEPTH_TYPES[depth.dtype], depth.strides[0] if depth.size else 0, float(depth_map_factor), w,
+                                           hgt, float(fx), float(fy), float(cx), float(cy), _p(T), int(cap), _p(raw), C.byref(nr), _p(out),
+                                           C.byref(n)), self._L)
+        return raw[:nr.value].copy(), out[:n.value].copy()
 
 
 def compute_stereo_matches(ex_left, ex_right, kl, dl, kr, dr, mbf, mb):
