@@ -342,8 +342,9 @@ int orbx_stereo_frame_view_rectified(orbx_extractor_t *h, const orbx_rectifier_t
                                      orbx_stereo_view_t *view);
 
 /* ---- Dense RGB-D keyframe clouds: PointCloudMapping::generatePointCloud (src/pointcloudmapping.cc:83-114) and the
- * pcl::VoxelGrid<PointXYZRGBA> filter saveOctomap puts every keyframe's cloud through (:117-127), DESIGN.md §3 items 12-13.
- * Plane segmentation, the axis swap, octomap insertion and PCD output (:139-279) stay with the caller. */
+ * pcl::VoxelGrid<PointXYZRGBA> filter saveOctomap puts every keyframe's cloud through (:117-127); further
+ * down the map's occupancy octree (the axis swap, octomap insertion and writeBinary, :198-278, items 14-15).  Plane segmentation,
+ * whose result the reference never uses, and PCD input / output (:139-185) stay with the caller. */
 typedef struct {
     float x, y, z;
     uint8_t b, g, r, a;   /* "b" is channel 0 of the colour image whatever its order, as the reference names it (:99-101) */
@@ -382,6 +383,47 @@ int orbx_cloud_voxel_device(orbx_cloudmapper_t *m, const orbx_cloud_point_t *d_p
 int orbx_keyframe_cloud(orbx_cloudmapper_t *m, const uint8_t *color, int channels, int color_stride, const void *depth,
                         int depth_type, int depth_stride, float depth_map_factor, int w, int hgt, float fx, float fy, float cx, float cy,
                         const double *Twc16, int cap, orbx_cloud_point_t *raw_out, int *n_raw, orbx_cloud_point_t *out, int *n);
+
+/* ---- The dense map's occupancy octree: what saveOctomap writes with tree.writeBinary (src/pointcloudmapping.cc:198-278), DESIGN.md
+ * §3 items 14-15.  Every point goes through pcl::transformPointCloud with a float 4x4 (default: the reference's axis swap
+ * x' = z, y' = -x, z' = -y), then octomap::OcTree(res).updateNode(point, true); writeBinary sets every occupied leaf to the clamping
+ * maximum and prunes, so the file is a function of the SET of occupied depth-16 cells alone.  A point with a non-finite coordinate,
+ * or whose key leaves [0, 65535] on an axis (|coordinate| beyond 32768 * res), is dropped and counted. */
+typedef struct {
+    uint16_t kx, ky, kz;   /* octomap key of the leaf's minimum corner: the low 16 - depth bits are zero */
+    uint16_t depth;        /* 1 .. 16; 16: one cell of edge res */
+} orbx_octree_leaf_t;      /* 8 bytes */
+typedef struct {
+    int64_t points_in;       /* points of all segments (counts clamped to [0, cap]) */
+    int64_t points_dropped;  /* non-finite, or outside the tree */
+    int64_t cells;           /* occupied depth-16 cells (distinct keys) */
+    int64_t leaves;          /* leaves after pruning */
+    int64_t tree_size;       /* OcTree::size() after pruning: inner nodes + leaves, root included; 0 for an empty map */
+    int64_t data_bytes;      /* bytes after the header's "data" line: 2 per inner node */
+    int32_t overflow;        /* 1: data_cap or leaf_cap was too small (the sizes above are still the true ones) */
+    int32_t reserved;
+} orbx_octree_info_t;        /* 56 bytes */
+/* The tree of a map in HBM, asynchronous on `stream`; the host reads nothing between the kernels.  The map is the union of B
+ * segments: the first clamp(d_counts[b], 0, cap) rows of d_points + b*cap - the layout orbx_cloud_voxel_device writes, so its output
+ * feeds this call without a host trip.  (A voxel count of -1, "the grid overflowed, PCL returns its input", contributes nothing here:
+ * a caller who wants that frame's unfiltered cloud in the map passes it as a segment of its own.)  B * cap <= 2^27.
+ * M16f: HOST, 16 floats row-major, read before return; NULL: the axis swap.  Rows 0..2 are evaluated in float, every product and sum
+ * rounded, left to right: x' = M00*x + M01*y + M02*z + M03.  res > 0 and finite, else ORBX_ERR_ARG (arguments are checked before the
+ * device is touched).
+ * d_data [data_cap] bytes: the .bt file's data section - two bytes per inner node in preorder.  d_leaves [leaf_cap] (NULL: skipped):
+ * the leaves after pruning in preorder.  d_info: one orbx_octree_info_t.  Nothing is written at or past a capacity; a capacity that
+ * is too small sets info.overflow, and the sizes reported are still the true ones.  Scratch: the mapper's, grow-only. */
+int orbx_octree_device(orbx_cloudmapper_t *m, const orbx_cloud_point_t *d_points, const int32_t *d_counts, int B, int cap,
+                       const float *M16f, double res, uint8_t *d_data, int64_t data_cap, orbx_octree_leaf_t *d_leaves, int64_t leaf_cap,
+                       orbx_octree_info_t *d_info, void *stream);
+/* Host to host, synchronous: the COMPLETE .bt file (header + data) of n points into out; *n_bytes: its size.  out_cap too small:
+ * ORBX_ERR_CAPACITY with *n_bytes the size needed (out may be NULL when out_cap is 0).  n == 0: the header with "size 0" (no device
+ * is needed for that).  info may be NULL. */
+int orbx_octomap_bt(orbx_cloudmapper_t *m, const orbx_cloud_point_t *points, int n, const float *M16f, double res, uint8_t *out,
+                    size_t out_cap, size_t *n_bytes, orbx_octree_info_t *info);
+/* an upper bound of the file's size for n points: 2 * (15 n + 1) data bytes (every cell with a path of its own below the root) plus
+ * 192 for the header; n < 0: 0 */
+size_t orbx_octomap_bytes_bound(int64_t n);
 
 /* Pinned host memory for image / capture buffers (cv::Mat can wrap it: cv::Mat(rows, cols, CV_8UC1, ptr)); NULL on failure. */
 void *orbx_host_alloc(size_t bytes);

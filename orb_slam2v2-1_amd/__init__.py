@@ -36,6 +36,11 @@ WINDOW_DTYPE = np.dtype([("valid", "<i4"), ("u", "<f4"), ("v", "<f4"), ("radius"
 # orbx_cloud_point_t: a point of a dense keyframe cloud (pcl::PointXYZRGBA's fields; "b" is channel 0 of the colour image)
 CLOUD_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("b", "u1"), ("g", "u1"), ("r", "u1"), ("a", "u1")])
 
+# orbx_octree_leaf_t: a leaf of the pruned occupancy octree (octomap key of its minimum corner, depth 1..16)
+OCTREE_LEAF_DTYPE = np.dtype([("kx", "<u2"), ("ky", "<u2"), ("kz", "<u2"), ("depth", "<u2")])
+# the reference's transform_trans * transform_rot_x * transform_rot_y (src/pointcloudmapping.cc:198-223): x' = z, y' = -x, z' = -y
+OCTOMAP_AXIS_SWAP = np.array([[0, 0, 1, 0], [-1, 0, 0, 0], [0, -1, 0, 0], [0, 0, 0, 1]], np.float32)
+
 ORBX_OK, ORBX_ERR_ARG, ORBX_ERR_NO_DEVICE, ORBX_ERR_HIP, ORBX_ERR_CAPACITY, ORBX_ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5
 NUM_STAGES = 5
 
@@ -58,6 +63,7 @@ EXPORTS = [
     "orbx_stereo_frame_rectified", "orbx_stereo_frame_view_rectified",
     "orbx_cloudmapper_create", "orbx_cloudmapper_destroy", "orbx_cloud_capacity", "orbx_cloud_generate_device",
     "orbx_cloud_voxel_device", "orbx_keyframe_cloud",
+    "orbx_octree_device", "orbx_octomap_bt", "orbx_octomap_bytes_bound",
 ]
 # what include/orbx_dev.h declares on top: exported by the developer build only
 DEV_EXPORTS = ["orbx_debug_level_points", "orbx_debug_sincosf", "orbx_debug_blur_patches", "orbm_debug_features_in_area",
@@ -80,6 +86,15 @@ class StereoView(C.Structure):
                 ("kl", C.c_void_p), ("kr", C.c_void_p), ("dl", C.c_void_p), ("dr", C.c_void_p), ("uright", C.c_void_p), ("depth", C.c_void_p),
                 ("d_kl", C.c_void_p), ("d_kr", C.c_void_p), ("d_dl", C.c_void_p), ("d_dr", C.c_void_p), ("d_uright", C.c_void_p),
                 ("d_depth", C.c_void_p)]
+
+
+class OctreeInfo(C.Structure):
+    """orbx_octree_info_t (orbx_octree_device / orbx_octomap_bt)."""
+    _fields_ = [("points_in", C.c_int64), ("points_dropped", C.c_int64), ("cells", C.c_int64), ("leaves", C.c_int64),
+                ("tree_size", C.c_int64), ("data_bytes", C.c_int64), ("overflow", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f, _ in self._fields_ if f != "reserved"}
 
 
 class GridGeom(C.Structure):
@@ -257,6 +272,10 @@ def _load(path, dev):
     L.orbx_cloud_voxel_device.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, vp]
     L.orbx_keyframe_cloud.argtypes = [vp, vp, i32, i32, vp, i32, i32, f32, i32, i32, f32, f32, f32, f32, vp, i32, vp, C.POINTER(i32), vp,
                                       C.POINTER(i32)]
+    L.orbx_octree_device.argtypes = [vp, vp, vp, i32, i32, vp, C.c_double, vp, C.c_int64, vp, C.c_int64, vp, vp]
+    L.orbx_octomap_bt.argtypes = [vp, vp, i32, vp, C.c_double, vp, sz, C.POINTER(sz), C.POINTER(OctreeInfo)]
+    L.orbx_octomap_bytes_bound.argtypes = [C.c_int64]
+    L.orbx_octomap_bytes_bound.restype = sz
     L.orbx_host_alloc.argtypes = [sz]
     L.orbx_host_alloc.restype = vp
     L.orbx_host_free.argtypes = [vp]
@@ -901,6 +920,35 @@ class CloudMapper:
                                            hgt, float(fx), float(fy), float(cx), float(cy), _p(T), int(cap), _p(raw), C.byref(nr), _p(out),
                                            C.byref(n)), self._L)
         return raw[:nr.value].copy(), out[:n.value].copy()
+
+    @staticmethod
+    def _xform(M):
+        """None (the reference's axis swap) or a 4 x 4 float32 matrix -> the 16 floats orbx_octree_device reads, or None."""
+        return None if M is None else np.ascontiguousarray(np.asarray(M, np.float32).reshape(16))
+
+    def octree_device(self, d_points, d_counts, B, cap, M, resolution, d_data, data_cap, d_leaves, leaf_cap, d_info, stream=0):
+        """The occupancy octree of a map in HBM (orbx_octree_device; raw device pointers): the union of B segments of CLOUD_DTYPE rows
+        as voxel_device writes them -> d_data: the .bt file's data bytes, d_leaves (0: skipped): OCTREE_LEAF_DTYPE rows in preorder,
+        d_info: one orbx_octree_info_t (OctreeInfo).  M: None for the reference's axis swap, or 4 x 4 floats.  Asynchronous."""
+        M = self._xform(M)
+        _check(self._L.orbx_octree_device(self._m, d_points, d_counts, int(B), int(cap), _p(M), float(resolution), d_data or None,
+                                          int(data_cap), d_leaves or None, int(leaf_cap), d_info, stream), self._L)
+
+    def octomap_bt(self, points, M=None, resolution=0.1):
+        """saveOctomap's tree of a host map (orbx_octomap_bt): CLOUD_DTYPE rows -> (the bytes of the .bt file octomap::OcTree::writeBinary
+        would write, info dict: points_in, points_dropped, cells, leaves, tree_size, data_bytes, overflow)."""
+        points = np.ascontiguousarray(points, CLOUD_DTYPE)
+        M = self._xform(M)
+        n, info, nb = len(points), OctreeInfo(), C.c_size_t()
+        out = np.empty(192 + 2 * n, np.uint8)   # room for 1 inner node per point (a surface has about a third); the exact size otherwise
+        for _ in range(2):
+            rc = self._L.orbx_octomap_bt(self._m, _p(points) if n else None, n, _p(M), float(resolution), _p(out), out.size,
+                                         C.byref(nb), C.byref(info))
+            if rc != ORBX_ERR_CAPACITY:
+                break
+            out = np.empty(nb.value, np.uint8)
+        _check(rc, self._L)
+        return out[:nb.value].tobytes(), info.as_dict()
 
 
 def compute_stereo_matches(ex_left, ex_right, kl, dl, kr, dr, mbf, mb):

@@ -12,14 +12,10 @@
 // summed through LDS, k_cloud_scan turns the per-workgroup counts of a frame into offsets, and the pass that writes repeats the
 // ballots and stores at offset + rank.  No atomic takes part in any position, so the order is the input's.
 // The arithmetic is restated in DESIGN.md §3 and, in numpy, in tests/cloud_ref.py.
-#include "orbx_internal.h"
+#include "orbx_cloud_dev.h"
 #include <math.h>
 #include <algorithm>
 
-#define CL_THREADS 256
-#define CL_ITERS 4
-#define CL_TILE (CL_THREADS * CL_ITERS)   // elements per workgroup
-#define CL_SEGS (CL_TILE / 64)            // wave-sized segments per workgroup, in element order: segment = iteration * 4 + wave
 #define VE_FLIGHT 16                      // points k_vox_emit loads ahead of its sequential sums
 #define CL_POSES 16                       // poses per launch of k_cloud_emit (kernel arguments: 16 x 12 doubles = 1.5 KB)
 
@@ -50,63 +46,10 @@ __device__ __forceinline__ uint32_t f2o(float f) {
 __device__ __forceinline__ float o2f(uint32_t o) {
     return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
 }
-__device__ __forceinline__ bool finite_bits(float f) {
-    return (__float_as_uint(f) & 0x7f800000u) != 0x7f800000u;
-}
 // a word other workgroups update with atomics, as the L2 holds it now (a stale value only costs an atomic more)
 __device__ __forceinline__ uint32_t peek(const uint32_t *p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ uint64_t lanes_below() {
-    return (1ull << (threadIdx.x & 63)) - 1ull;
-}
-
-// Ranks of the workgroup's elements: flag[k] of iteration k (element base + k * 256 + threadIdx.x) -> rank[k] among the flagged
-// elements of the workgroup, in element order; returns the workgroup's count.  segs: CL_SEGS ints of LDS.
-__device__ __forceinline__ int block_ranks(const bool (&flag)[CL_ITERS], int (&rank)[CL_ITERS], int *segs) {
-    const int wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < CL_ITERS; k++) {
-        const uint64_t m = __ballot(flag[k]);
-        rank[k] = __popcll(m & lanes_below());
-        if ((threadIdx.x & 63) == 0) segs[k * 4 + wv] = __popcll(m);
-    }
-    __syncthreads();
-    int total = 0;
-#pragma unroll
-    for (int s = 0; s < CL_SEGS; s++) {
-        const int c = segs[s];
-#pragma unroll
-        for (int k = 0; k < CL_ITERS; k++)
-            if (s < k * 4 + wv) rank[k] += c;
-        total += c;
-    }
-    __syncthreads();
-    return total;
-}
-
-// exclusive scan of one value per lane over the 256 lanes; lds: 4 ints
-__device__ __forceinline__ int block_excl_scan(int v, int *lds, int &total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) lds[wv] = inc;
-    __syncthreads();
-    int base = 0;
-    total = 0;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        if (i < wv) base += lds[i];
-        total += lds[i];
-    }
-    __syncthreads();
-    return base + inc - v;
-}
-
 // Per-workgroup counts [B][nblk] -> exclusive offsets in place, the frame's total to tot[b].  One workgroup per frame.
 // outCounts (may be NULL): min(total, clampCap), or -1 for a frame whose grid overflowed.
 __global__ __launch_bounds__(CL_THREADS) void k_cloud_scan(int32_t *__restrict__ blk, int nblk, int32_t *__restrict__ tot,
@@ -207,10 +150,6 @@ __global__ void k_vox_init(VoxMeta *__restrict__ meta, int B, uint32_t *__restri
     for (int k = 0; k < 3; k++) { meta[b].mn[k] = 0xffffffffu; meta[b].mx[k] = 0u; meta[b].minb[k] = 0; }
     meta[b].mul1 = meta[b].mul2 = 0u;
     meta[b].overflow = 0;
-}
-
-__device__ __forceinline__ int frame_points(const int32_t *counts, int b, int cap) {
-    return min(max(counts[b], 0), cap);
 }
 
 // finite points per workgroup, and their extents (integer atomic min / max at the L2: the result does not depend on the order)
@@ -522,34 +461,7 @@ __global__ __launch_bounds__(CL_THREADS) void k_vox_emit(const orbx_cloud_point_
     }
 }
 
-// ---- host side
-
-struct orbx_cloudmapper {
-    float leaf; int step, alpha, device;
-    // grow-only scratch of the device calls (one stream at a time uses a mapper)
-    uint8_t *d_blk; size_t blkBytes;       // int32 [B][workgroups]: counts, then offsets
-    uint8_t *d_tot; size_t totBytes;       // int32 [2][B]: valid samples / finite points, voxels
-    uint8_t *d_meta; size_t metaBytes;     // VoxMeta [B] + the batch's largest key
-    uint8_t *d_pairs; size_t pairBytes;    // uint32 keys [2][B * cap] | values [2][B * cap]
-    uint8_t *d_hist; size_t histBytes;     // uint32 [B][workgroups][256]
-    uint8_t *d_digit; size_t digitBytes;   // uint32 [B][256]
-    // orbx_keyframe_cloud
-    hipStream_t stream;
-    uint8_t *d_color; size_t colorBytes;
-    uint8_t *d_depth; size_t depthBytes;
-    uint8_t *d_raw; size_t rawBytes;
-    uint8_t *d_out; size_t outBytes;
-    uint8_t *d_cnt; size_t cntBytes;
-};
-
-static int reserve(uint8_t **p, size_t *have, size_t need) {
-    need = ((need + 255) & ~(size_t)255) + 256;
-    if (*have >= need) return ORBX_OK;
-    hipFree(*p); *p = nullptr; *have = 0;   // (hipFree waits for the device: no kernel still reads the old block)
-    ORBX_HIP(hipMalloc(p, need));
-    *have = need;
-    return ORBX_OK;
-}
+// ---- host side (the mapper handle: orbx_cloud_dev.h)
 
 extern "C" int orbx_cloudmapper_create(float leaf, int step, int alpha, int device, orbx_cloudmapper_t **out) {
     if (!out || !(leaf > 0.0f) || !(leaf < INFINITY) || step < 1 || alpha < 0 || alpha > 255 || device < 0) {
@@ -584,6 +496,7 @@ extern "C" int orbx_cloudmapper_destroy(orbx_cloudmapper_t *m) {
     hipSetDevice(m->device);
     if (m->stream) { hipStreamSynchronize(m->stream); hipStreamDestroy(m->stream); }
     hipFree(m->d_blk); hipFree(m->d_tot); hipFree(m->d_meta); hipFree(m->d_pairs); hipFree(m->d_hist); hipFree(m->d_digit);
+    hipFree(m->d_octCodes); hipFree(m->d_octBlk); hipFree(m->d_octHist); hipFree(m->d_octState);
     hipFree(m->d_color); hipFree(m->d_depth); hipFree(m->d_raw); hipFree(m->d_out); hipFree(m->d_cnt);
     delete m;
     return ORBX_OK;

@@ -1,4 +1,5 @@
-// PointCloudMapping.cc — see PointCloudMapping.h.  Host glue only: every point is computed by orbx_keyframe_cloud.
+// PointCloudMapping.cc — see PointCloudMapping.h.  Host glue only: every point is computed by orbx_keyframe_cloud, every byte of the
+// tree by orbx_octomap_bt.
 #include "PointCloudMapping.h"
 #include <cstdio>
 #include <cstdlib>
@@ -59,6 +60,41 @@ int PointCloudMappingHIP::insertKeyFrame(float fx, float fy, float cx, float cy,
     if (n < 0) return n;
     globalMap.insert(globalMap.end(), tmp.begin(), tmp.end());   // *globalMap += *tmp (:126)
     return n;
+}
+
+long long PointCloudMappingHIP::octomapBinary(std::vector<uint8_t> &out, double octree_resolution) {
+    out.clear();
+    if (!mpMapper || globalMap.size() > 0x7fffffffu) return -1;
+    const int n = (int)globalMap.size();
+    // room for one inner node per point (a surface has about a third as many); the exact size, which the call reports, otherwise
+    out.resize(192 + 2 * (size_t)n);
+    orbx_octree_info_t info;
+    size_t bytes = 0;
+    int rc = orbx_octomap_bt(mpMapper, globalMap.data(), n, nullptr, octree_resolution, out.data(), out.size(), &bytes, &info);
+    if (rc == ORBX_ERR_CAPACITY) {
+        out.resize(bytes);
+        rc = orbx_octomap_bt(mpMapper, globalMap.data(), n, nullptr, octree_resolution, out.data(), out.size(), &bytes, &info);
+    }
+    if (rc != ORBX_OK) {
+        std::fprintf(stderr, "PointCloudMappingHIP: %s\n", orbx_last_error());
+        out.clear();
+        return -1;
+    }
+    out.resize(bytes);
+    return (long long)info.tree_size;
+}
+
+long long PointCloudMappingHIP::saveOctomap(const char *oct_name, double octree_resolution) {
+    std::vector<uint8_t> bytes;
+    const long long size = octomapBinary(bytes, octree_resolution);
+    if (size < 0 || !oct_name) return -1;
+    FILE *f = std::fopen(oct_name, "wb");
+    if (!f) {
+        std::fprintf(stderr, "PointCloudMappingHIP: cannot write %s\n", oct_name);
+        return -1;
+    }
+    const bool ok = std::fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
+    return (std::fclose(f) == 0 && ok) ? size : -1;
 }
 
 void PointCloudMappingHIP::Reset() { globalMap.clear(); }

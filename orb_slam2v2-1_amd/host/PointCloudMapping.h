@@ -1,12 +1,14 @@
-// PointCloudMapping.h — the data-parallel part of the reference's dense map (include/pointcloudmapping.h, src/pointcloudmapping.cc:
-// 29-34, 83-127) on an MI355X through include/orbx.h: generatePointCloud of an RGB-D keyframe and the pcl::VoxelGrid filter
-// saveOctomap puts it through.  Plane segmentation, the axis swap, octomap insertion and PCD output (:139-279) stay with the caller,
-// and so does the pose: Twc16 is what the reference computes with its own Eigen,
+// PointCloudMapping.h — the reference's dense map (include/pointcloudmapping.h, src/pointcloudmapping.cc:29-34, 83-127, 198-278) on
+// an MI355X through include/orbx.h: generatePointCloud of an RGB-D keyframe, the pcl::VoxelGrid filter saveOctomap puts it through,
+// and what saveOctomap makes of the accumulated map: the axis swap, octomap::OcTree insertion and the .bt file of writeBinary.
+// Plane segmentation (its result is printed and never used) and PCD input / output (:139-185) stay with the caller, and so does the
+// pose: Twc16 is what the reference computes with its own Eigen,
 //     Eigen::Isometry3d T = ORB_SLAM2::Converter::toSE3Quat(kf->GetPose());  Eigen::Matrix4d Twc = T.inverse().matrix();
 // handed over row-major (Twc16[4 * i + j] = Twc(i, j)).
 #ifndef POINTCLOUDMAPPING_HIP_H
 #define POINTCLOUDMAPPING_HIP_H
 
+#include <stdint.h>
 #include <vector>
 #include "cv_shim.h"
 #include "orbx.h"
@@ -31,6 +33,13 @@ public:
     // One keyframe as saveOctomap treats it: generatePointCloud, voxel.filter, *globalMap += *tmp.  Returns the number of points
     // appended (< 0: error, globalMap unchanged).
     int insertKeyFrame(float fx, float fy, float cx, float cy, const double *Twc16, const cv::Mat &color, const cv::Mat &depth);
+
+    // The tail of saveOctomap (:198-278) on globalMap: transformPointCloud with the axis swap, OcTree tree(octree_resolution) (the
+    // reference: 0.1), updateNode per point, writeBinary(oct_name).  Returns the tree's size() after pruning (0: an empty map, the
+    // file is the header alone), < 0 on error (nothing is written then).
+    long long saveOctomap(const char *oct_name, double octree_resolution = 0.1);
+    // the same bytes in memory; the return value as above
+    long long octomapBinary(std::vector<uint8_t> &out, double octree_resolution = 0.1);
 
     // a new map: globalMap is emptied (the mapper and its device scratch stay)
     void Reset();
