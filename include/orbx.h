@@ -716,7 +716,10 @@ int orbv_transform(const orbv_vocabulary_t *v, const uint8_t *desc, int n, int l
  * best <= max_dist && (float)best < nnratio * (float)second (second = smallest distance among the other
  * candidates, 256 if none); with check_orientation the matches outside the three largest 30-degree bins of
  * (q_angle - c_angle) are dropped at the end.  A feature belongs to one node only, so nodes are independent:
- * one wavefront per node.  match_q[nq]: candidate feature index or -1. */
+ * one wavefront per node; a feature index that appears twice in q_items or twice in c_items is ORBX_ERR_ARG.
+ * A node may hold at most 4096 candidates (one taken-bit each in a 64-bit register per lane): more is
+ * ORBX_ERR_UNSUPPORTED.  On either error match_q is all -1 and *nmatches is 0.
+ * match_q[nq]: candidate feature index or -1. */
 int orbm_search_by_bow(const uint8_t *q_desc, const float *q_angle, const uint8_t *q_valid, int nq,
                        const uint8_t *c_desc, const float *c_angle, const uint8_t *c_valid, int nc,
                        const int32_t *node_qstart, const int32_t *q_items, const int32_t *node_cstart,
@@ -731,7 +734,9 @@ int orbm_search_by_bow(const uint8_t *q_desc, const float *q_angle, const uint8_
  * sqrt(100*scale_factors[octave2]) away from the epipole (ex, ey) (:742-748), then CheckDistEpipolarLine
  * (:140-157: squared distance to the line x1'F12 < 3.84*level_sigma2[octave2]); a passing candidate becomes the
  * best — so among equal distances the LAST passing one wins.  F12_9: row-major 3x3.  Rotation consistency as in
- * orbm_search_by_bow.  match_q[nq]: candidate feature index or -1. */
+ * orbm_search_by_bow, and so are the limits: a repeated index in q_items or in c_items is ORBX_ERR_ARG, more than
+ * 4096 candidates in one node ORBX_ERR_UNSUPPORTED, match_q all -1 and *nmatches 0 on either.
+ * match_q[nq]: candidate feature index or -1. */
 int orbm_search_for_triangulation(const orbx_keypoint_t *kp1, const uint8_t *q_desc, const uint8_t *q_flags, int nq,
                                   const orbx_keypoint_t *kp2, const uint8_t *c_desc, const uint8_t *c_flags, int nc,
                                   const int32_t *node_qstart, const int32_t *q_items, const int32_t *node_cstart,

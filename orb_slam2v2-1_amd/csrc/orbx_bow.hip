@@ -268,6 +268,18 @@ __global__ __launch_bounds__(256) void k_bow_orient(const float *__restrict__ qa
     if (tid == 0) *nmatches = cnt;
 }
 
+// every listed index in range and listed once: a feature belongs to one node only, which is what lets the per-node taken
+// bits of the kernels stand for the reference's global vpMapPointMatches[] / vbMatched2[]
+static int check_items(const char *fn, const char *name, const int32_t *items, int count, int n, std::vector<uint8_t> &seen) {
+    seen.assign(n, 0);
+    for (int i = 0; i < count; i++) {
+        if (items[i] < 0 || items[i] >= n) { orbx_set_error("%s[%d] out of range", name, i); return ORBX_ERR_ARG; }
+        if (seen[items[i]]) { orbx_set_error("%s: %s[%d] repeats feature %d", fn, name, i, items[i]); return ORBX_ERR_ARG; }
+        seen[items[i]] = 1;
+    }
+    return ORBX_OK;
+}
+
 extern "C" int orbm_search_by_bow(const uint8_t *q_desc, const float *q_angle, const uint8_t *q_valid, int nq,
                                   const uint8_t *c_desc, const float *c_angle, const uint8_t *c_valid, int nc,
                                   const int32_t *node_qstart, const int32_t *q_items, const int32_t *node_cstart,
@@ -285,8 +297,8 @@ extern "C" int orbm_search_by_bow(const uint8_t *q_desc, const float *q_angle, c
     if (node_qstart[0] != 0 || node_cstart[0] != 0 || tq < 0 || tc < 0 || (tq > 0 && !q_items) || (tc > 0 && !c_items)) { orbx_set_error("orbm_search_by_bow: bad node lists"); return ORBX_ERR_ARG; }
     for (int j = 0; j < nnodes; j++)
         if (node_qstart[j + 1] < node_qstart[j] || node_cstart[j + 1] < node_cstart[j]) { orbx_set_error("orbm_search_by_bow: node lists not monotonic at %d", j); return ORBX_ERR_ARG; }
-    for (int i = 0; i < tq; i++) if (q_items[i] < 0 || q_items[i] >= nq) { orbx_set_error("q_items[%d] out of range", i); return ORBX_ERR_ARG; }
-    for (int i = 0; i < tc; i++) if (c_items[i] < 0 || c_items[i] >= nc) { orbx_set_error("c_items[%d] out of range", i); return ORBX_ERR_ARG; }
+    std::vector<uint8_t> seen;
+    if (check_items("orbm_search_by_bow", "q_items", q_items, tq, nq, seen) || check_items("orbm_search_by_bow", "c_items", c_items, tc, nc, seen)) return ORBX_ERR_ARG;
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t o = off; off += ALN(bytes); return o; };
     const size_t o_qd = take((size_t)nq * 32), o_qa = take((size_t)nq * 4), o_qv = take(nq), o_cd = take((size_t)nc * 32),
@@ -403,8 +415,8 @@ extern "C" int orbm_search_for_triangulation(const orbx_keypoint_t *kp1, const u
     if (node_qstart[0] != 0 || node_cstart[0] != 0 || tq < 0 || tc < 0 || (tq > 0 && !q_items) || (tc > 0 && !c_items)) { orbx_set_error("orbm_search_for_triangulation: bad node lists"); return ORBX_ERR_ARG; }
     for (int j = 0; j < nnodes; j++)
         if (node_qstart[j + 1] < node_qstart[j] || node_cstart[j + 1] < node_cstart[j]) { orbx_set_error("orbm_search_for_triangulation: node lists not monotonic at %d", j); return ORBX_ERR_ARG; }
-    for (int i = 0; i < tq; i++) if (q_items[i] < 0 || q_items[i] >= nq) { orbx_set_error("q_items[%d] out of range", i); return ORBX_ERR_ARG; }
-    for (int i = 0; i < tc; i++) if (c_items[i] < 0 || c_items[i] >= nc) { orbx_set_error("c_items[%d] out of range", i); return ORBX_ERR_ARG; }
+    std::vector<uint8_t> seen;
+    if (check_items("orbm_search_for_triangulation", "q_items", q_items, tq, nq, seen) || check_items("orbm_search_for_triangulation", "c_items", c_items, tc, nc, seen)) return ORBX_ERR_ARG;
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t o = off; off += ALN(bytes); return o; };
     const size_t o_k1 = take((size_t)nq * sizeof(orbx_keypoint_t)), o_qd = take((size_t)nq * 32), o_qf = take(nq), o_qa = take((size_t)nq * 4),
