@@ -7,10 +7,10 @@
 //                                  (:117-127): finite-point extents, cell index, stable sort by cell, one centroid per cell
 //   orbx_keyframe_cloud            one keyframe host to host
 //
-// Ordered compaction, used three times (valid samples, finite points, segment heads): every workgroup of 256 lanes owns 1024
-// consecutive elements as 16 wave-sized segments; a ballot + popcount ranks a lane inside its segment, the 16 segment counts are
-// summed through LDS, k_cloud_scan turns the per-workgroup counts of a frame into offsets, and the pass that writes repeats the
-// ballots and stores at offset + rank.  No atomic takes part in any position, so the order is the input's.
+// Ordered compaction (orbx_cloud_dev.h) is used three times - valid samples, finite points, heads of the sorted runs - over per-frame
+// tiles: grid (workgroups of a frame, B), frame b's elements at b * cap, k_cloud_scan the scan of a frame's counts.  The sort is that
+// header's too, of (cell index, input index) pairs: its histogram is frame-major, [B][workgroups][256], scanned by one lane per digit
+// (k_radix_scan), and the passes that run are the 8-bit digits of the batch's largest key (batchMax).
 // The arithmetic is restated in DESIGN.md §3 and, in numpy, in tests/cloud_ref.py.
 #include "orbx_cloud_dev.h"
 #include <math.h>
@@ -57,19 +57,10 @@ __global__ __launch_bounds__(CL_THREADS) void k_cloud_scan(int32_t *__restrict__
                                                            const VoxMeta *__restrict__ meta) {
     __shared__ int lds[4];
     const int b = blockIdx.x;
-    int32_t *c = blk + (size_t)b * nblk;
-    int carry = 0;
-    for (int i0 = 0; i0 < nblk; i0 += CL_THREADS) {
-        const int i = i0 + threadIdx.x;
-        const int v = i < nblk ? c[i] : 0;
-        int total;
-        const int ex = block_excl_scan(v, lds, total);
-        if (i < nblk) c[i] = carry + ex;
-        carry += total;
-    }
+    const int total = scan_counts(blk + (size_t)b * nblk, nblk, lds);
     if (threadIdx.x == 0) {
-        tot[b] = carry;
-        if (outCounts) outCounts[b] = (meta && meta[b].overflow) ? -1 : min(carry, clampCap);
+        tot[b] = total;
+        if (outCounts) outCounts[b] = (meta && meta[b].overflow) ? -1 : min(total, clampCap);
     }
 }
 
@@ -97,7 +88,7 @@ __global__ __launch_bounds__(CL_THREADS) void k_cloud_count(GenArgs a, int32_t *
     int rank[CL_ITERS];
 #pragma unroll
     for (int k = 0; k < CL_ITERS; k++) {
-        const int s = base + k * CL_THREADS + threadIdx.x;
+        const int s = tile_elem(base, k);
         float d; int m, n;
         flag[k] = s < a.ns && cloud_sample(a, b, s, d, m, n);
     }
@@ -115,7 +106,7 @@ __global__ __launch_bounds__(CL_THREADS) void k_cloud_emit(GenArgs a, CloudPoses
     float dep[CL_ITERS];
 #pragma unroll
     for (int k = 0; k < CL_ITERS; k++) {
-        const int s = base + k * CL_THREADS + threadIdx.x;
+        const int s = tile_elem(base, k);
         dep[k] = 0.f; pm[k] = pn[k] = 0;
         flag[k] = s < a.ns && cloud_sample(a, b, s, dep[k], pm[k], pn[k]);
     }
@@ -163,7 +154,7 @@ __global__ __launch_bounds__(CL_THREADS) void k_vox_minmax(const orbx_cloud_poin
     uint32_t mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
 #pragma unroll
     for (int k = 0; k < CL_ITERS; k++) {
-        const int i = base + k * CL_THREADS + threadIdx.x;
+        const int i = tile_elem(base, k);
         flag[k] = false;
         if (i < n) {
             const orbx_cloud_point_t p = pts[(size_t)b * cap + i];
@@ -180,11 +171,8 @@ __global__ __launch_bounds__(CL_THREADS) void k_vox_minmax(const orbx_cloud_poin
     if (total == 0) return;
 #pragma unroll
     for (int c = 0; c < 3; c++) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            mn[c] = min(mn[c], (uint32_t)__shfl_xor((int)mn[c], o, 64));
-            mx[c] = max(mx[c], (uint32_t)__shfl_xor((int)mx[c], o, 64));
-        }
+        mn[c] = wave_reduce(mn[c], [](uint32_t x, uint32_t y) { return min(x, y); });
+        mx[c] = wave_reduce(mx[c], [](uint32_t x, uint32_t y) { return max(x, y); });
     }
     // the four waves' extents meet in LDS: one atomic per word and workgroup (atomics on one word run one at a time at the L2)
     if ((threadIdx.x & 63) == 0) {
@@ -245,7 +233,7 @@ __global__ __launch_bounds__(CL_THREADS) void k_vox_keys(const orbx_cloud_point_
     uint32_t key[CL_ITERS], kmax = 0u;
 #pragma unroll
     for (int k = 0; k < CL_ITERS; k++) {
-        const int i = base + k * CL_THREADS + threadIdx.x;
+        const int i = tile_elem(base, k);
         flag[k] = false; key[k] = 0u;
         if (i < n) {
             const orbx_cloud_point_t p = pts[(size_t)b * cap + i];
@@ -266,10 +254,9 @@ __global__ __launch_bounds__(CL_THREADS) void k_vox_keys(const orbx_cloud_point_
         if (!flag[k]) continue;
         const size_t o = (size_t)b * cap + off + rank[k];
         keys[o] = key[k];
-        vals[o] = (uint32_t)(base + k * CL_THREADS + threadIdx.x);
+        vals[o] = (uint32_t)tile_elem(base, k);
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) kmax = max(kmax, (uint32_t)__shfl_xor((int)kmax, o, 64));
+    kmax = wave_reduce(kmax, [](uint32_t x, uint32_t y) { return max(x, y); });
     if ((threadIdx.x & 63) == 0) kred[threadIdx.x >> 6] = kmax;
     __syncthreads();
     // only the number of 8-bit digits matters: a workgroup sends its key only if that has more of them than the word holds
@@ -279,12 +266,9 @@ __global__ __launch_bounds__(CL_THREADS) void k_vox_keys(const orbx_cloud_point_
     }
 }
 
-// LSD radix sort of (key, value) by key, 8 bits a pass, stable, every frame of the batch in one launch.  Pass p runs only while
-// the batch's largest key has bits at or above 8p (batchMax, read on the device); it reads buffer p & 1 and writes the other, so after the
-// passes that ran the sorted pairs sit in buffer (passes & 1).
-__device__ __forceinline__ int radix_passes(const uint32_t *batchMax) {
-    return radix_digits(*batchMax);
-}
+// The sort of (key, value) by key, every frame of the batch in one launch.  Pass p runs only while the batch's largest key has bits
+// at or above 8p (batchMax, read on the device); it reads buffer p & 1 and writes the other, so after the passes that ran the
+// sorted pairs sit in buffer (passes & 1).
 __device__ __forceinline__ int sort_points(const VoxMeta *meta, const int32_t *nfin, int b) {
     return meta[b].overflow ? 0 : nfin[b];
 }
@@ -293,18 +277,11 @@ __global__ __launch_bounds__(CL_THREADS) void k_radix_hist(int pass, const uint3
                                                           const VoxMeta *__restrict__ meta, const int32_t *__restrict__ nfin,
                                                           const uint32_t *__restrict__ batchMax, uint32_t *__restrict__ hist) {
     __shared__ uint32_t h[256];
-    if (pass >= radix_passes(batchMax)) return;
+    if (pass >= radix_digits(*batchMax)) return;
     const int b = blockIdx.y, base = blockIdx.x * CL_TILE, n = sort_points(meta, nfin, b);
     if (base >= n) return;
     const uint32_t *keys = keys2 + (size_t)(pass & 1) * N + (size_t)b * cap;
-    h[threadIdx.x] = 0u;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < CL_ITERS; k++) {
-        const int i = base + k * CL_THREADS + threadIdx.x;
-        if (i < n) atomicAdd(&h[(keys[i] >> (8 * pass)) & 255u], 1u);
-    }
-    __syncthreads();
+    radix_tile_hist(keys, n, base, pass, h);
     hist[((size_t)b * gridDim.x + blockIdx.x) * 256 + threadIdx.x] = h[threadIdx.x];
 }
 
@@ -314,7 +291,7 @@ __global__ __launch_bounds__(CL_THREADS) void k_radix_scan(int pass, int nblk, c
                                                           const int32_t *__restrict__ nfin, const uint32_t *__restrict__ batchMax,
                                                           uint32_t *__restrict__ hist, uint32_t *__restrict__ digitBase) {
     __shared__ int lds[4];
-    if (pass >= radix_passes(batchMax)) return;
+    if (pass >= radix_digits(*batchMax)) return;
     const int b = blockIdx.x, n = sort_points(meta, nfin, b);
     const int nact = (n + CL_TILE - 1) / CL_TILE;
     uint32_t *h = hist + (size_t)b * nblk * 256 + threadIdx.x;
@@ -333,53 +310,25 @@ __global__ __launch_bounds__(CL_THREADS) void k_radix_scatter(int pass, uint32_t
                                                              const uint32_t *__restrict__ batchMax, const uint32_t *__restrict__ hist,
                                                              const uint32_t *__restrict__ digitBase) {
     __shared__ uint32_t seg[CL_SEGS][256];   // [segment][digit]: count, then first position
-    if (pass >= radix_passes(batchMax)) return;
+    if (pass >= radix_digits(*batchMax)) return;
     const int b = blockIdx.y, base = blockIdx.x * CL_TILE, n = sort_points(meta, nfin, b);
     if (base >= n) return;
     const size_t src = (size_t)(pass & 1) * N + (size_t)b * cap, dst = (size_t)((pass + 1) & 1) * N + (size_t)b * cap;
-    const int wv = threadIdx.x >> 6;
     for (int s = 0; s < CL_SEGS; s++) seg[s][threadIdx.x] = 0u;
     __syncthreads();
     uint32_t key[CL_ITERS], val[CL_ITERS];
-    int rank[CL_ITERS];
     bool flag[CL_ITERS];
 #pragma unroll
     for (int k = 0; k < CL_ITERS; k++) {
-        const int i = base + k * CL_THREADS + threadIdx.x;
+        const int i = tile_elem(base, k);
         flag[k] = i < n;
         key[k] = flag[k] ? keys2[src + i] : 0u;
         val[k] = flag[k] ? vals2[src + i] : 0u;
-        const uint32_t d = (key[k] >> (8 * pass)) & 255u;
-        uint64_t same = __ballot(flag[k]);   // the segment's lanes with this lane's digit
-#pragma unroll
-        for (int bit = 0; bit < 8; bit++) {
-            const bool one = (d >> bit) & 1u;
-            const uint64_t m = __ballot(one);
-            same &= one ? m : ~m;
-        }
-        rank[k] = __popcll(same & lanes_below());
-        if (flag[k] && rank[k] == 0) seg[k * 4 + wv][d] = (uint32_t)__popcll(same);
     }
-    __syncthreads();
-    {   // lane d: first position of digit d for every segment, in segment order
-        uint32_t run = digitBase[(size_t)b * 256 + threadIdx.x] + hist[((size_t)b * gridDim.x + blockIdx.x) * 256 + threadIdx.x];
-        for (int s = 0; s < CL_SEGS; s++) {
-            const uint32_t c = seg[s][threadIdx.x];
-            seg[s][threadIdx.x] = run;
-            run += c;
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < CL_ITERS; k++) {
-        if (!flag[k]) continue;
-        const uint32_t d = (key[k] >> (8 * pass)) & 255u;
-        const uint32_t o = seg[k * 4 + wv][d] + (uint32_t)rank[k];
-        if (o < (uint32_t)n) {   // (always: kept as the store's bound)
-            keys2[dst + o] = key[k];
-            vals2[dst + o] = val[k];
-        }
-    }
+    radix_tile_scatter(
+        key, flag, pass, n, seg,
+        [&] { return digitBase[(size_t)b * 256 + threadIdx.x] + hist[((size_t)b * gridDim.x + blockIdx.x) * 256 + threadIdx.x]; },
+        [&](int k, uint32_t o) { keys2[dst + o] = key[k]; vals2[dst + o] = val[k]; });
 }
 
 // heads of the runs of equal keys, per workgroup
@@ -388,14 +337,10 @@ __global__ __launch_bounds__(CL_THREADS) void k_vox_heads(const uint32_t *__rest
                                                          const uint32_t *__restrict__ batchMax, int32_t *__restrict__ blk) {
     __shared__ int segs[CL_SEGS];
     const int b = blockIdx.y, base = blockIdx.x * CL_TILE, n = sort_points(meta, nfin, b);
-    const uint32_t *keys = keys2 + (size_t)(radix_passes(batchMax) & 1) * N + (size_t)b * cap;
+    const uint32_t *keys = keys2 + (size_t)(radix_digits(*batchMax) & 1) * N + (size_t)b * cap;
     bool flag[CL_ITERS];
     int rank[CL_ITERS];
-#pragma unroll
-    for (int k = 0; k < CL_ITERS; k++) {
-        const int i = base + k * CL_THREADS + threadIdx.x;
-        flag[k] = i < n && (i == 0 || keys[i] != keys[i - 1]);
-    }
+    run_heads(keys, n, base, flag);
     const int total = block_ranks(flag, rank, segs);
     if (threadIdx.x == 0) blk[(size_t)b * gridDim.x + blockIdx.x] = total;
 }
@@ -410,21 +355,17 @@ __global__ __launch_bounds__(CL_THREADS) void k_vox_emit(const orbx_cloud_point_
     __shared__ int segs[CL_SEGS];
     const int b = blockIdx.y, base = blockIdx.x * CL_TILE, n = sort_points(meta, nfin, b);
     if (base >= n) return;
-    const size_t o = (size_t)(radix_passes(batchMax) & 1) * N + (size_t)b * cap;
+    const size_t o = (size_t)(radix_digits(*batchMax) & 1) * N + (size_t)b * cap;
     const uint32_t *keys = keys2 + o, *vals = vals2 + o;
     bool flag[CL_ITERS];
     int rank[CL_ITERS];
-#pragma unroll
-    for (int k = 0; k < CL_ITERS; k++) {
-        const int i = base + k * CL_THREADS + threadIdx.x;
-        flag[k] = i < n && (i == 0 || keys[i] != keys[i - 1]);
-    }
+    run_heads(keys, n, base, flag);
     block_ranks(flag, rank, segs);
     const int off = blk[(size_t)b * gridDim.x + blockIdx.x];
     for (int k = 0; k < CL_ITERS; k++) {
         const int r = off + rank[k];
         if (!flag[k] || r >= outCap) continue;
-        const int i = base + k * CL_THREADS + threadIdx.x;
+        const int i = tile_elem(base, k);
         const uint32_t key = keys[i];
         // the run's end: the keys are sorted, so a doubling search and a bisection find it in O(log length) dependent loads
         int lo = i, stride = 1;

@@ -19,9 +19,11 @@
 // Preorder positions are prefix sums of these counts over i; the two bytes of an inner node come from the eight child boundaries,
 // found by bisection inside the node's run.  Sixteen levels are never materialised: the scratch is the sort's two buffers.
 //
-// Ordered compaction and the launch conventions are orbx_cloud.hip's: 256 lanes own 1024 consecutive elements, a count launch,
-// a scan of the per-workgroup counts, a write launch; no atomic decides a position; the sizes live in a device record (OctState),
-// launches are sized for the worst case and return early; the host reads nothing between the kernels.
+// Ordered compaction and the sort's core are orbx_cloud_dev.h's, here over the flat [B * cap] map: one-dimensional grids, k_oct_scan
+// the scan of a count array.  The sort is of the bare 64-bit codes; its histogram is digit-major, [256][workgroups], and scanned by one
+// workgroup per digit (k_oct_hscan), since a map has thousands of workgroups where a keyframe has tens; the passes that run are the
+// digits in which two codes differ (codeOr ^ codeAnd).  The sizes live in a device record (OctState), launches are sized for the
+// worst case and return early; the host reads nothing between the kernels.
 #include "orbx_cloud_dev.h"
 #include <math.h>
 #include <algorithm>
@@ -103,7 +105,7 @@ __global__ __launch_bounds__(CL_THREADS) void k_oct_keys_count(const orbx_cloud_
 #pragma unroll
     for (int k = 0; k < CL_ITERS; k++) {
         unsigned long long code;
-        flag[k] = oct_point_code(pts, counts, cap, ntot, base + k * CL_THREADS + threadIdx.x, M, resFactor, code);
+        flag[k] = oct_point_code(pts, counts, cap, ntot, tile_elem(base, k), M, resFactor, code);
     }
     const int total = block_ranks(flag, rank, segs);
     if (threadIdx.x == 0) blk[blockIdx.x] = total;
@@ -114,18 +116,9 @@ __global__ __launch_bounds__(CL_THREADS) void k_oct_keys_count(const orbx_cloud_
 __global__ __launch_bounds__(CL_THREADS) void k_oct_scan(int32_t *__restrict__ blk, int nblk, const int32_t *__restrict__ nElems,
                                                         int32_t *__restrict__ tot) {
     __shared__ int lds[4];
-    int32_t *c = blk + (size_t)blockIdx.x * nblk;
     const int nact = nElems ? min(nblk, (*nElems + CL_TILE - 1) / CL_TILE) : nblk;
-    int carry = 0;
-    for (int i0 = 0; i0 < nact; i0 += CL_THREADS) {
-        const int i = i0 + threadIdx.x;
-        const int v = i < nact ? c[i] : 0;
-        int total;
-        const int ex = block_excl_scan(v, lds, total);
-        if (i < nact) c[i] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) tot[blockIdx.x] = carry;
+    const int total = scan_counts(blk + (size_t)blockIdx.x * nblk, nact, lds);
+    if (threadIdx.x == 0) tot[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(CL_THREADS) void k_oct_keys_write(const orbx_cloud_point_t *__restrict__ pts, const int32_t *__restrict__ counts,
@@ -141,7 +134,7 @@ __global__ __launch_bounds__(CL_THREADS) void k_oct_keys_write(const orbx_cloud_
 #pragma unroll
     for (int k = 0; k < CL_ITERS; k++) {
         code[k] = 0ull;
-        flag[k] = oct_point_code(pts, counts, cap, ntot, base + k * CL_THREADS + threadIdx.x, M, resFactor, code[k]);
+        flag[k] = oct_point_code(pts, counts, cap, ntot, tile_elem(base, k), M, resFactor, code[k]);
         if (flag[k]) { vor |= code[k]; vand &= code[k]; }
     }
     const int total = block_ranks(flag, rank, segs);
@@ -150,11 +143,8 @@ __global__ __launch_bounds__(CL_THREADS) void k_oct_keys_write(const orbx_cloud_
 #pragma unroll
     for (int k = 0; k < CL_ITERS; k++)
         if (flag[k] && off + rank[k] < ntot) codes[off + rank[k]] = code[k];   // (always below ntot: kept as the store's bound)
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        vor |= (unsigned long long)__shfl_xor((long long)vor, o, 64);
-        vand &= (unsigned long long)__shfl_xor((long long)vand, o, 64);
-    }
+    vor = wave_reduce(vor, [](unsigned long long x, unsigned long long y) { return x | y; });
+    vand = wave_reduce(vand, [](unsigned long long x, unsigned long long y) { return x & y; });
     if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = vor; red[threadIdx.x >> 6][1] = vand; }
     __syncthreads();
     // OR / AND do not depend on the order; a workgroup whose bits the words hold already sends nothing (a stale read costs an atomic more)
@@ -169,7 +159,7 @@ __global__ __launch_bounds__(CL_THREADS) void k_oct_keys_write(const orbx_cloud_
     }
 }
 
-// ---- radix sort of the codes: six passes of 8 bits over the 48; pass p runs iff two codes differ in its digit, reads buffer
+// ---- the sort of the codes: six passes of 8 bits over the 48; pass p runs iff two codes differ in its digit, reads buffer
 // oct_src(p) and writes the other, so the sorted codes end in buffer oct_src(6)
 __device__ __forceinline__ bool oct_pass_runs(const OctState *st, int pass) {
     return (((st->codeOr ^ st->codeAnd) >> (8 * pass)) & 255ull) != 0ull;
@@ -188,14 +178,7 @@ __global__ __launch_bounds__(CL_THREADS) void k_oct_hist(int pass, const unsigne
     const int base = blockIdx.x * CL_TILE, n = st->nValid;
     if (base >= n || !oct_pass_runs(st, pass)) return;
     const unsigned long long *codes = codes2 + (size_t)oct_src(st, pass) * ntot;
-    h[threadIdx.x] = 0u;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < CL_ITERS; k++) {
-        const int i = base + k * CL_THREADS + threadIdx.x;
-        if (i < n) atomicAdd(&h[(uint32_t)(codes[i] >> (8 * pass)) & 255u], 1u);
-    }
-    __syncthreads();
+    radix_tile_hist(codes, n, base, pass, h);
     hist[(size_t)threadIdx.x * nblk + blockIdx.x] = h[threadIdx.x];
 }
 
@@ -206,17 +189,8 @@ __global__ __launch_bounds__(CL_THREADS) void k_oct_hscan(int pass, const OctSta
     const int n = st->nValid;
     if (n <= 0 || !oct_pass_runs(st, pass)) return;
     const int nact = min(nblk, (n + CL_TILE - 1) / CL_TILE);
-    uint32_t *h = hist + (size_t)blockIdx.x * nblk;
-    int carry = 0;
-    for (int i0 = 0; i0 < nact; i0 += CL_THREADS) {
-        const int i = i0 + threadIdx.x;
-        const int v = i < nact ? (int)h[i] : 0;
-        int total;
-        const int ex = block_excl_scan(v, lds, total);
-        if (i < nact) h[i] = (uint32_t)(carry + ex);
-        carry += total;
-    }
-    if (threadIdx.x == 0) digitTot[blockIdx.x] = (uint32_t)carry;
+    const int total = scan_counts((int32_t *)hist + (size_t)blockIdx.x * nblk, nact, lds);   // (counts of at most 2^27 codes)
+    if (threadIdx.x == 0) digitTot[blockIdx.x] = (uint32_t)total;
 }
 
 __global__ __launch_bounds__(CL_THREADS) void k_oct_scatter(int pass, unsigned long long *__restrict__ codes2, int ntot,
@@ -229,46 +203,20 @@ __global__ __launch_bounds__(CL_THREADS) void k_oct_scatter(int pass, unsigned l
     const int sb = oct_src(st, pass);
     const unsigned long long *src = codes2 + (size_t)sb * ntot;
     unsigned long long *dst = codes2 + (size_t)(sb ^ 1) * ntot;
-    const int wv = threadIdx.x >> 6;
     for (int s = 0; s < CL_SEGS; s++) seg[s][threadIdx.x] = 0u;
     int total;
     const uint32_t digitBase = (uint32_t)block_excl_scan((int)digitTot[threadIdx.x], lds, total);   // (its barriers also publish the zeros)
     unsigned long long key[CL_ITERS];
-    int rank[CL_ITERS];
     bool flag[CL_ITERS];
 #pragma unroll
     for (int k = 0; k < CL_ITERS; k++) {
-        const int i = base + k * CL_THREADS + threadIdx.x;
+        const int i = tile_elem(base, k);
         flag[k] = i < n;
         key[k] = flag[k] ? src[i] : 0ull;
-        const uint32_t d = (uint32_t)(key[k] >> (8 * pass)) & 255u;
-        uint64_t same = __ballot(flag[k]);   // the segment's lanes with this lane's digit
-#pragma unroll
-        for (int bit = 0; bit < 8; bit++) {
-            const bool one = (d >> bit) & 1u;
-            const uint64_t m = __ballot(one);
-            same &= one ? m : ~m;
-        }
-        rank[k] = __popcll(same & lanes_below());
-        if (flag[k] && rank[k] == 0) seg[k * 4 + wv][d] = (uint32_t)__popcll(same);
     }
-    __syncthreads();
-    {   // lane d: first position of digit d for every segment, in segment order
-        uint32_t run = digitBase + hist[(size_t)threadIdx.x * nblk + blockIdx.x];
-        for (int s = 0; s < CL_SEGS; s++) {
-            const uint32_t c = seg[s][threadIdx.x];
-            seg[s][threadIdx.x] = run;
-            run += c;
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < CL_ITERS; k++) {
-        if (!flag[k]) continue;
-        const uint32_t d = (uint32_t)(key[k] >> (8 * pass)) & 255u;
-        const uint32_t o = seg[k * 4 + wv][d] + (uint32_t)rank[k];
-        if (o < (uint32_t)n) dst[o] = key[k];   // (always: kept as the store's bound)
-    }
+    radix_tile_scatter(
+        key, flag, pass, n, seg, [&] { return digitBase + hist[(size_t)threadIdx.x * nblk + blockIdx.x]; },
+        [&](int k, uint32_t o) { dst[o] = key[k]; });
 }
 
 // ---- the distinct codes
@@ -283,13 +231,7 @@ __global__ __launch_bounds__(CL_THREADS) void k_oct_heads(unsigned long long *__
     const unsigned long long *codes = codes2 + (size_t)sb * ntot;
     bool flag[CL_ITERS];
     int rank[CL_ITERS];
-    unsigned long long key[CL_ITERS];
-#pragma unroll
-    for (int k = 0; k < CL_ITERS; k++) {
-        const int i = base + k * CL_THREADS + threadIdx.x;
-        key[k] = i < n ? codes[i] : 0ull;
-        flag[k] = i < n && (i == 0 || key[k] != codes[i - 1]);
-    }
+    run_heads(codes, n, base, flag);
     const int total = block_ranks(flag, rank, segs);
     if (!WRITE) {
         if (threadIdx.x == 0) blk[blockIdx.x] = total;
@@ -299,7 +241,7 @@ __global__ __launch_bounds__(CL_THREADS) void k_oct_heads(unsigned long long *__
     const int off = blk[blockIdx.x];
 #pragma unroll
     for (int k = 0; k < CL_ITERS; k++)
-        if (flag[k] && off + rank[k] < n) out[off + rank[k]] = key[k];   // (always below n: kept as the store's bound)
+        if (flag[k] && off + rank[k] < n) out[off + rank[k]] = codes[tile_elem(base, k)];   // (always below n: kept as the store's bound)
 }
 
 // ---- the pruned tree, read off the distinct sorted codes c[0..n)
@@ -335,7 +277,7 @@ __global__ __launch_bounds__(CL_THREADS) void k_oct_nodes(const unsigned long lo
     int v = 0;
 #pragma unroll
     for (int k = 0; k < CL_ITERS; k++) {
-        const int i = base + k * CL_THREADS + threadIdx.x;
+        const int i = tile_elem(base, k);
         if (i < n) {
             int D, F; bool leaf;
             oct_element(c, n, i, D, F, leaf);
@@ -386,7 +328,7 @@ __global__ __launch_bounds__(CL_THREADS) void k_oct_emit(const unsigned long lon
     bool leaf[CL_ITERS];
 #pragma unroll
     for (int k = 0; k < CL_ITERS; k++) {
-        const int i = base + k * CL_THREADS + threadIdx.x;
+        const int i = tile_elem(base, k);
         D[k] = F[k] = 0; leaf[k] = false;
         if (i < n) oct_element(c, n, i, D[k], F[k], leaf[k]);
     }
@@ -403,7 +345,7 @@ __global__ __launch_bounds__(CL_THREADS) void k_oct_emit(const unsigned long lon
 #pragma unroll
         for (int k = 0; k < CL_ITERS; k++) {
             if (!leaf[k] || loff + lrank[k] >= leafCap) continue;
-            const unsigned long long ci = c[base + k * CL_THREADS + threadIdx.x];
+            const unsigned long long ci = c[tile_elem(base, k)];
             orbx_octree_leaf_t l;
             l.kx = (uint16_t)oct_compact(ci); l.ky = (uint16_t)oct_compact(ci >> 1); l.kz = (uint16_t)oct_compact(ci >> 2);
             l.depth = (uint16_t)F[k];
@@ -416,7 +358,7 @@ __global__ __launch_bounds__(CL_THREADS) void k_oct_emit(const unsigned long lon
         for (int k = 0; k < CL_ITERS; k++)
             for (int d = D[k]; d < F[k]; d++) {
                 const int p = ipos[k] + d - D[k] - w0;
-                if (p >= 0 && p < OE_WINDOW) work[p] = (uint16_t)(((k * CL_THREADS + threadIdx.x) << 4) | d);
+                if (p >= 0 && p < OE_WINDOW) work[p] = (uint16_t)((tile_elem(0, k) << 4) | d);
             }
         __syncthreads();
         const int cnt = min(nodes - w0, OE_WINDOW);

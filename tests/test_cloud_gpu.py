@@ -301,6 +301,23 @@ def test_voxel_batch_whose_frames_need_different_pass_counts(pkg, torch):
         assert_same(got[b], refs[b][0], "frame %d" % b)
 
 
+@pytest.mark.parametrize("leaf", [0.25, 0.02])
+def test_voxel_frame_of_257_workgroups_beside_one(pkg, torch, leaf):
+    """A frame of more than 256 workgroups: the scan of the per-workgroup counts goes a second round with a carry, and frame 1's rows
+    of the per-workgroup counts and histograms sit 257 entries in."""
+    clouds = [random_cloud((1 << 18) + 37), random_cloud(65, 1)]
+    cap = max(len(c) for c in clouds)
+    assert (cap + 1023) // 1024 == 257
+    if leaf == 0.02:
+        _, idx, _ = R.voxel_indices(clouds[0], F32(leaf))
+        assert int(idx.max()) >= 1 << 24   # all four passes run
+    refs = [R.voxel(c, F32(leaf)) for c in clouds]
+    got, n = gpu_voxel(pkg, torch, pkg.CloudMapper(leaf, 3, 255), clouds)
+    assert list(n) == [r[1] for r in refs]
+    for b in range(2):
+        assert_same(got[b], refs[b][0], "frame %d" % b)
+
+
 def test_voxel_overflow_frame_beside_normal_frames(pkg, torch):
     leaf = 1e-4
     small = R.make_cloud((random_cloud(1025, 2)["x"][:, None] * [1, 0.5, 0.25] * F32(0.004)).astype(F32))   # a few centimetres across
