@@ -74,6 +74,23 @@ int orbm_debug_resolve_plan(int mode, int m, int n, int device, int64_t *out);
  * level 0), out[3] = 1 iff a left keypoint of that call had more than ST_CAND candidates and restarted its list. */
 int orbm_debug_stereo_path(int32_t *out);
 
+/* The launch rule of an extraction call (csrc/orbx_plan.h: plan_chunk), by itself: no HIP call, no handle, works without a GPU.
+ * in = PlanInput, out = ChunkPlan, as flat int32 arrays in the structs' field order:
+ *   in  (ORBX_DEBUG_PLAN_INPUT_INTS):  B, nl, totalStrips, stripLevels, octBigMask, lastChunks, prof, profFast, skipPyr, pfUsed,
+ *        evPyrDone, dbgBlur, sliceScratch, fastTileStride, fastScoreStride, sparseRecent, ncells[16], opt[32]
+ *   out (ORBX_DEBUG_CHUNK_PLAN_INTS):  usePyr, strips, stripLevels, fastCells, es, histOct, multiWg, fused, gather, bigMask, wideOct,
+ *        compact, sparseForm, sparsePerCell, rowFlags, sparseHint (0 nobody, 1 k_octree_pyr, 2 k_gather), earlyLv, aSplit,
+ *        octForm (0 exact alone, 1 big = multi-workgroup, 2 early, 3 split, 4 single), sweepSlices, sweepShared, orderKernel,
+ *        fastDoneAt (-1 never, 0 behind FAST, 1 behind the quad-tree, 2 behind the descriptors, 3 together with FAST), fastPhase, octPhase,
+ *        octStop, descLdsPad (bytes), nslice[16]
+ * n_in / n_out must be exactly those counts.  ORBX_ERR_UNSUPPORTED (and the invariant's text in orbx_last_error) when the plan breaks a
+ * constraint the kernels rely on - launch_chunk then launches nothing.
+ * orbx_debug_last_plan: the ChunkPlan that chunk 0 of the handle's last extraction call executed (a copy kept in the handle). */
+#define ORBX_DEBUG_PLAN_INPUT_INTS 64
+#define ORBX_DEBUG_CHUNK_PLAN_INTS 43
+int orbx_debug_plan_chunk(const int32_t *in, int n_in, int32_t *out, int n_out);
+int orbx_debug_last_plan(const orbx_extractor_t *h, int32_t *out, int n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -68,7 +68,15 @@ EXPORTS = [
 # what include/orbx_dev.h declares on top: exported by the developer build only
 DEV_EXPORTS = ["orbx_debug_level_points", "orbx_debug_sincosf", "orbx_debug_blur_patches", "orbm_debug_features_in_area",
                "orbx_debug_blurred_level", "orbx_debug_octree_fallbacks", "orbm_debug_match_path", "orbm_debug_resolve_plan",
-               "orbm_debug_stereo_path"]
+               "orbm_debug_stereo_path", "orbx_debug_plan_chunk", "orbx_debug_last_plan"]
+# include/orbx_dev.h: PlanInput / ChunkPlan of the launch rule as flat int32 arrays (orbx_debug_plan_chunk, orbx_debug_last_plan), field order
+PLAN_INPUT_FIELDS = ["B", "nl", "totalStrips", "stripLevels", "octBigMask", "lastChunks", "prof", "profFast", "skipPyr", "pfUsed", "evPyrDone",
+                     "dbgBlur", "sliceScratch", "fastTileStride", "fastScoreStride", "sparseRecent"]   # + ncells[16] + opt[32]
+CHUNK_PLAN_FIELDS = ["usePyr", "strips", "stripLevels", "fastCells", "es", "histOct", "multiWg", "fused", "gather", "bigMask", "wideOct", "compact",
+                     "sparseForm", "sparsePerCell", "rowFlags", "sparseHint", "earlyLv", "aSplit", "octForm", "sweepSlices", "sweepShared",
+                     "orderKernel", "fastDoneAt", "fastPhase", "octPhase", "octStop", "descLdsPad"]   # + nslice[16]
+OCT_EXACT, OCT_BIG, OCT_EARLY, OCT_SPLIT, OCT_SINGLE = 0, 1, 2, 3, 4      # ChunkPlan.octForm
+HINT_NONE, HINT_OCT_SRC, HINT_GATHER = 0, 1, 2                            # ChunkPlan.sparseHint
 # include/orbx_dev.h: ORBM_PATH_RES_* / ORBM_PATH_FB_* (orbm_debug_match_path, orbm_debug_resolve_plan)
 RES_NONE, RES_PAR_Q2, RES_PAR_Q4, RES_WAVE, RES_EXACT = 0, 1, 2, 3, 4
 FB_NONE, FB_N, FB_INIT_SIZE, FB_CAND_CAP, FB_QK, FB_LDS, FB_OPTION = 0, 1, 2, 3, 4, 5, 6
@@ -330,6 +338,8 @@ def _load(path, dev):
         L.orbm_debug_match_path.argtypes = [vp]
         L.orbm_debug_resolve_plan.argtypes = [i32, i32, i32, i32, vp]
         L.orbm_debug_stereo_path.argtypes = [vp]
+        L.orbx_debug_plan_chunk.argtypes = [vp, i32, vp, i32]
+        L.orbx_debug_last_plan.argtypes = [vp, vp, i32]
     L.orbx_last_error.restype = C.c_char_p
     L.orbx_version.restype = C.c_char_p
     L._orbx_developer = bool(dev)
@@ -712,6 +722,13 @@ class ORBextractor:
             self._L.orbx_debug_blur_patches(self._h, 0, None, 0)
         return k, d, out[:len(k)]
 
+    def debug_last_plan(self):
+        """Test hook: the launch plan chunk 0 of the last extraction call executed -> dict of CHUNK_PLAN_FIELDS (+ "nslice")."""
+        self._hooks()
+        out = np.zeros(len(CHUNK_PLAN_FIELDS) + 16, np.int32)
+        self._ck(self._L.orbx_debug_last_plan(self._h, _p(out), len(out)))
+        return _plan_dict(out)
+
     def set_profiling(self, mode=1):
         """0/False off, 1/True events at every stage boundary, 2 only around k_fast_cells (see orbx.h)."""
         self._ck(self._L.orbx_set_profiling(self._h, int(mode)))
@@ -747,6 +764,26 @@ def debug_resolve_plan(mode, m, n, device=0):
     out = np.zeros(4, np.int64)
     _check(lib(True).orbm_debug_resolve_plan(int(mode), int(m), int(n), int(device), _p(out)), lib(True))
     return tuple(int(v) for v in out)
+
+
+def _plan_dict(out):
+    d = {k: int(v) for k, v in zip(CHUNK_PLAN_FIELDS, out)}
+    d["nslice"] = tuple(int(v) for v in out[len(CHUNK_PLAN_FIELDS):])
+    return d
+
+
+def debug_plan_chunk(ncells=(), opt=None, **fields):
+    """Test hook, no HIP call (works without a GPU): the launch rule on a PlanInput given as keywords of PLAN_INPUT_FIELDS (default 0),
+    per-level `ncells` and `opt` = {option key: value} -> (status, dict of CHUNK_PLAN_FIELDS + "nslice")."""
+    a = np.zeros(len(PLAN_INPUT_FIELDS) + 16 + 32, np.int32)
+    for k, v in fields.items():
+        a[PLAN_INPUT_FIELDS.index(k)] = int(v)
+    a[len(PLAN_INPUT_FIELDS):len(PLAN_INPUT_FIELDS) + len(ncells)] = ncells
+    for k, v in (opt or {}).items():
+        a[len(PLAN_INPUT_FIELDS) + 16 + int(k)] = int(v)
+    out = np.zeros(len(CHUNK_PLAN_FIELDS) + 16, np.int32)
+    rc = lib(True).orbx_debug_plan_chunk(_p(a), len(a), _p(out), len(out))
+    return rc, _plan_dict(out)
 
 
 def debug_stereo_path():

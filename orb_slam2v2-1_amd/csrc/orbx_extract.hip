@@ -678,9 +678,6 @@ __global__ void k_nop() {}
 // reflected-border branches; a branch-free version would still move 2.4 bytes per pixel: ~0.08 ms), so even the best case wins
 // ~0.05 of 0.89 ms at 2000 features and nothing at 1000.
 #define ORBX_BLUR_THR 100000000
-// a level whose last call kept fewer FAST candidates per 30-px cell than this is "corner-sparse" (the benchmark's dense frames: ~60;
-// smooth natural scenes: 2-4)
-#define ORBX_SPARSE_PER_CELL 16
 static unsigned blur_plan(const orbx_extractor *h, BlurPlan &bp, int &totalTiles) {
     unsigned mask = 0;
     totalTiles = 0;
@@ -805,60 +802,87 @@ static ChunkView chunk_view(const orbx_extractor *h, const uint8_t *d_imgs, size
     return v;
 }
 
+// What plan_chunk reads, taken from the handle: a chunk of B images of a call cut into nch chunks.
+static PlanInput plan_input(const orbx_extractor *h, int B, int nch, bool prof, bool profFast, bool skipPyr, bool evPyrDone) {
+    PlanInput in = {};
+    in.B = B; in.nl = h->nlevels; in.totalStrips = h->totalStrips; in.stripLevels = (int32_t)h->stripLevels; in.octBigMask = (int32_t)h->octBigMask;
+    in.lastChunks = nch; in.prof = prof; in.profFast = profFast; in.skipPyr = skipPyr; in.pfUsed = h->pfUsed != 0; in.evPyrDone = evPyrDone;
+    in.dbgBlur = h->d_dbgBlur != nullptr; in.sliceScratch = h->d_octPartBest != nullptr;
+    in.fastTileStride = h->fastTileStride; in.fastScoreStride = h->fastScoreStride;
+    // the quad-tree of image slot 0 stores the call's sequence number into a host-mapped word when it flags a corner-sparse level
+    in.sparseRecent = h->h_sparseSeen && (uint32_t)h->callSeq - (uint32_t)*(volatile int32_t *)h->h_sparseSeen <= 16u;   // (sequence numbers wrap: unsigned distance)
+    for (int l = 0; l < h->nlevels; l++) in.ncells[l] = h->geom[l].ncells;
+    memcpy(in.opt, h->opt, sizeof(in.opt));
+    return in;
+}
+
+// the quad-tree kernels in their 512- or 1024-thread build (ChunkPlan::wideOct), on STREAM
+#define ORBX_OCT_LAUNCH_ON(STREAM, KERN, KERNW, GRID, LDS, ...)                                                         \
+    do {                                                                                                                \
+        if (p.wideOct) {                                                                                                \
+            ORBX_HIP(hipFuncSetAttribute((const void *)KERNW, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS))); \
+            hipLaunchKernelGGL(KERNW, GRID, dim3(OCT_T_WIDE), LDS, STREAM, __VA_ARGS__);                                \
+        } else {                                                                                                        \
+            ORBX_HIP(hipFuncSetAttribute((const void *)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS)));  \
+            hipLaunchKernelGGL(KERN, GRID, dim3(OCT_T), LDS, STREAM, __VA_ARGS__);                                      \
+        }                                                                                                               \
+    } while (0)
+// k_octree_pyr of the levels [LV0, LV0 + grid.y): its arguments but for the phase-stop knobs, the first level and the key source
+#define ORBX_OCT_PYR_ON(STREAM, GRID, STOP, PHASE, LV0, SRC)                                                                        \
+    ORBX_OCT_LAUNCH_ON(STREAM, k_octree_pyr, k_octree_pyr_wide, GRID, ldsOct, h->d_geom, nl, v.cand, h->keysPerImg, v.candCnt, v.lvlKp, \
+                       h->lvlKpCap, v.lvlCnt, h->d_tab, h->maxNodeCap, pow2, h->octPyrWords, v.octFallback, STOP, v.nodeOf, scratch,   \
+                       PHASE, 0u, LV0, SRC)
+// k_fast_cells: the instance of the plan's compile-time tile stride, with (SP) or without the compaction queue
+#define ORBX_LAUNCH_FAST(EST, SP, LDSW)                                                                                  \
+    hipLaunchKernelGGL((k_fast_cells<EST, SP>), dim3((h->totalCells + FAST_WAVES - 1) / FAST_WAVES, B), dim3(64 * FAST_WAVES), \
+                       (size_t)(LDSW) * FAST_WAVES, st, v.pyr, h->pyrImgBytes, h->d_geom, nl, h->totalCells, v.cellCnt, v.cellRaw, v.slots, \
+                       h->slotsPerImg, h->ini_th, h->min_th, h->fastTileStride, h->fastScoreStride, h->fastTileRows, \
+                       (LDSW), p.fastPhase, cb, (unsigned)p.stripLevels, v.sparse, (SP) ? FastHist{} : fhist)
+#define ORBX_LAUNCH_FAST_ES(SP, LDSW)                         \
+    switch (p.es) {                                           \
+    case 44: ORBX_LAUNCH_FAST(44, SP, LDSW); break;           \
+    case 48: ORBX_LAUNCH_FAST(48, SP, LDSW); break;           \
+    case 52: ORBX_LAUNCH_FAST(52, SP, LDSW); break;           \
+    default: ORBX_LAUNCH_FAST(0, SP, LDSW); break;            \
+    }
+
 // One chunk (B images from v) through the whole pipeline on stream st.  ev / prof / profFast: this chunk carries the stage events;
-// evPyrDone (may be NULL) is recorded behind the chunk's pyramid.
-static void launch_pyramid(orbx_extractor *h, const uint8_t *d_imgs, uint8_t *pyr, int B, int stride, size_t img_stride, hipStream_t st);
+// evPyrDone (may be NULL) is recorded behind the chunk's pyramid.  Every decision is plan_chunk's (orbx_plan.h): this function reads
+// no option, it executes the plan.
 static int launch_chunk(orbx_extractor *h, const ChunkView &v, int B, int stride, size_t img_stride, int cap, hipStream_t st,
                         hipEvent_t *ev, bool prof, bool profFast, hipEvent_t evPyrDone, bool skipPyr) {
+    ChunkPlan p;
+    int rc = plan_chunk(plan_input(h, B, h->lastChunks, prof, profFast, skipPyr, evPyrDone != nullptr), &p);
+    if (rc) return rc;   // (a plan that breaks an invariant of the kernels launches nothing)
+    if (v.b0 == 0) h->lastPlan = p;
     const int nl = h->nlevels;
     CellBases cb;
     for (int l = 0; l <= ORBX_MAX_LEVELS; l++) cb.v[l] = l < nl ? h->geom[l].cellBase : h->totalCells;
-    const uint8_t *d_imgs = v.imgs;
+    StripBases sb;
+    for (int l = 0; l <= ORBX_MAX_LEVELS; l++) sb.v[l] = h->stripBase[l];
     orbx_keypoint_t *d_kps = v.kps; uint8_t *d_desc = v.desc; int32_t *d_counts = v.counts;
-    int aSplit = 0;   // > 0: split call, the levels [0, aSplit) and [aSplit, nl) take different streams behind k_gather
     if (prof) ORBX_HIP(hipEventRecord(ev[0], st));
     if (!skipPyr) {   // K1 (skipped when the pyramid was built ahead: then its level-wide blur was, too)
-        launch_pyramid(h, d_imgs, v.pyr, B, stride, img_stride, st);
+        launch_pyramid(h, v.imgs, v.pyr, B, stride, img_stride, st);
         unsigned m = 0;
-        int rc = launch_blur(h, h->d_pyr, &h->d_blur, &h->blurBytes, v.b0, B, st, &m);
+        rc = launch_blur(h, h->d_pyr, &h->d_blur, &h->blurBytes, v.b0, B, st, &m);
         if (rc) return rc;
         h->blurMaskLast = m;
     }
     if (evPyrDone) ORBX_HIP(hipEventRecord(evPyrDone, st));
-    // With the pyramid built ahead nothing but a stream wait (for that pyramid) sits in front of the FAST launch, and a timing
-    // event recorded right behind a pending wait can be stamped before the wait is over: the bracket then reads wait + FAST
-    // (seen as 0.30 instead of 0.27 ms in one run out of four).  An empty kernel orders the stamp behind the wait.
-    if (profFast && skipPyr && h->opt[12] == 0) hipLaunchKernelGGL(k_nop, dim3(1), dim3(64), 0, st);
+    if (p.orderKernel) hipLaunchKernelGGL(k_nop, dim3(1), dim3(64), 0, st);
     if (profFast) ORBX_HIP(hipEventRecord(ev[1], st));
-    // (ORBX_OPT_PREFETCH_GATE = 3: a pyramid built ahead may start as soon as THIS call's FAST stage may - it then runs beside it)
-    if (h->pfUsed && evPyrDone == nullptr && h->opt[10] == 3) ORBX_HIP(hipEventRecord(h->evFastDone, st));
-    // decisions of the quad-tree stage that the FAST stage needs to know
-    // developer knob 4: 0 default, 1 = the exact form alone, 2 = EVERY level by the multi-workgroup form, 3 = none
-    const bool usePyr = h->opt[4] != 1;
-    // (round 5: a batch whose FAST stage histograms its emissions for the quad-tree - at most ORBX_HIST_IMAGES images, every level by
-    // k_fast_cells - needs no shared sweep at all: one 1920x1080 image went through gather 6 + k_octree_big 53 + 15 us)
-    const bool stripsWanted = h->totalStrips > 0 && (h->opt[6] == 0 ? (size_t)h->totalStrips * B >= 4096 : h->opt[6] == 3);
-    const bool histWanted = h->opt[23] == 0 && B <= ORBX_HIST_IMAGES && h->lastChunks == 1 && !stripsWanted && h->opt[0] == 0 && h->opt[18] != 1 &&
-                            h->opt[7] == 0 && h->opt[1] == 0;
-    const bool multiWg = h->opt[4] == 2 || (h->opt[4] != 3 && B <= 4 && h->octBigMask != 0 && !histWanted);
-    // Fused: k_octree_pyr reads the FAST stage's cell lists in place (no k_gather launch, no compacted key array: -35 us per
-    // 128 images 1241x376, -200 us per 64 images 1920x1080 in the pipelined step).  Not for the multi-workgroup form, the exact
-    // form alone and the phase-stop knobs, which sweep the compacted array (developer knob 18 = 1: never fused).
-    const bool fused = usePyr && !multiWg && (h->opt[7] == 0 || h->opt[7] == 8 || h->opt[7] == 9) && h->opt[1] == 0 && h->opt[18] != 1;   // (7 = 8 / 9, developer build: time stamps, no stop)
-    const int sparsePerCell = h->opt[16] == 2 ? 1 << 20 : ORBX_SPARSE_PER_CELL;
+    if (p.fastDoneAt == ORBX_FASTDONE_WITH_FAST) ORBX_HIP(hipEventRecord(h->evFastDone, st));
     OctSrc osrc = {};
-    if (fused) {
+    if (p.fused) {   // k_octree_pyr reads the FAST stage's cell lists in place
         osrc.cellCnt = v.cellCnt; osrc.cellRaw = v.cellRaw; osrc.slots = v.slots; osrc.slotsPerImg = h->slotsPerImg;
         osrc.totalCells = h->totalCells; osrc.iniTh = h->ini_th; osrc.minTh = h->min_th; osrc.candCntOut = v.candCnt;
-        osrc.sparseFlag = v.sparse; osrc.sparsePerCell = sparsePerCell; osrc.candOut = v.cand;
-        osrc.sparseSeen = h->opt[20] != 0 ? h->d_sparseSeen : nullptr; osrc.callSeq = h->callSeq;   // (the hint only serves the compaction forms)
+        osrc.sparseFlag = v.sparse; osrc.sparsePerCell = p.sparsePerCell; osrc.candOut = v.cand;
+        osrc.sparseSeen = p.sparseHint == ORBX_HINT_OCT_SRC ? h->d_sparseSeen : nullptr; osrc.callSeq = h->callSeq;
         h->candStale = std::max(h->candStale, v.b0 + B);
     }
-    // ORBX_OPT_OCT_HIST (0 = by batch size, 1 = never): with at most ORBX_HIST_IMAGES images and every level done by k_fast_cells, the FAST
-    // stage histograms its emissions for the quad-tree (FastHist) and k_octree_pyr loads the histogram instead of sweeping the keys
-    const bool histOct = fused && histWanted;
     FastHist fhist = {};
-    if (histOct) {
+    if (p.histOct) {   // the FAST stage histograms its emissions for the quad-tree
         fhist.cnt = h->d_histCnt; fhist.best = h->d_histBest; fhist.stride = h->histStride; fhist.tab = h->d_tab;
         osrc.histCnt = h->d_histCnt; osrc.histBest = h->d_histBest; osrc.histStride = h->histStride;
     }
@@ -868,243 +892,139 @@ static int launch_chunk(orbx_extractor *h, const ChunkView &v, int B, int stride
     for (int l = 0; l < nl; l++) maxCellsL = std::max(maxCellsL, h->geom[l].ncells);
     const int scratch = std::max(4 * h->maxNodeCap, maxCellsL + 1);
     const size_t ldsOct = std::max(h->octPyrLdsBytes, h->octLdsBytes);
-    const bool wideOct = h->opt[11] == 0 ? h->octBigMask != 0 : h->opt[11] == 2;
-    bool compact = false;   // the compaction kernel takes the corner-sparse (image, level)s of the strip levels
-    int earlyLv = 0;   // > 0: the strips of the levels [0, earlyLv) are launched first and their quad-tree starts beside the FAST of the rest
+    hipStream_t s2 = h->side[1];   // the second stream of the early quad-tree and of the split call
     {   // K2
-        // developer knob 6: 1 = every level by k_fast_cells (compile-time tile strides), 2 = ... with run-time strides
-        // a strip is a longer job than a cell (a wave walks ~33 rows): with few images the one-wave-per-cell kernel finishes
-        // sooner (13 vs 29 us for one 1241x376 image); once the strips fill the GPU they win (2.5 vs 3.1 us per image).  Same results.
-        const bool strips = h->totalStrips > 0 && (h->opt[6] == 0 ? (size_t)h->totalStrips * B >= 4096 : h->opt[6] == 3);
-        const unsigned stripLevels = strips ? h->stripLevels : 0u;
-        if (strips) {
-            StripBases sb;
-            for (int l = 0; l <= ORBX_MAX_LEVELS; l++) sb.v[l] = h->stripBase[l];
-            const int32_t *spf = h->opt[16] == 1 ? (const int32_t *)nullptr : v.sparse;   // ORBX_OPT_ROW_PRETEST: 1 = never the sparse path, 2 = always
-            // ORBX_OPT_SPARSE_FORM 1 / 2 (alternatives, measured no faster than the default row skip inside the strip kernel - DESIGN.md
-            // section 5): the corner-sparse (image, level)s - flagged by the previous call's quad-tree - leave the strip kernel and are done
-            // by a compaction kernel (below).  That costs a launch whose waves all return at once when nothing is flagged, so it is added
-            // only while the handle has recently met a sparse level: the quad-tree of image slot 0 stores the call's sequence number
-            // into a host-mapped word when it flags one (a hint that lags by the calls in flight; a wrong hint costs speed only,
-            // because both kernels take the SAME device flags).
-            compact = spf != nullptr && h->opt[20] != 0 &&
-                      (h->opt[16] == 2 || (h->h_sparseSeen && (uint32_t)h->callSeq - (uint32_t)*(volatile int32_t *)h->h_sparseSeen <= 16u));   // (sequence numbers wrap: unsigned distance)
-            // Early quad-tree (developer knob 19: a >= 2 = levels [0, a); default 0 = off): the quad-tree of the large levels is ONE
-            // workgroup per level walking a serial chain - the critical path behind FAST.  Their strips go first, in a launch of their
-            // own, and their quad-tree starts on a second stream as soon as that launch is done, beside the FAST of the remaining
-            // levels.  Parity-tested and MEASURED SLOWER at every size (64 stereo frames 1241x376: 0.635 -> 0.649 ms per step with
-            // a = 2, 0.657 with a = 3; 2000 features 0.838 -> 0.874; 1920x1080 x 64 1.254 -> 1.274; 752x480 0.599 -> 0.607): FAST loses to
-            // the quad-tree workgroups what the shorter chain behind it gains, plus two cross-stream events.  Off by default.
-            const int ea = h->opt[19];
-            if (fused && !prof && !compact && h->opt[19] >= 2 && h->opt[15] < 2 && h->lastChunks == 1 && B >= 8 && nl > ea &&
-                (h->stripLevels & ((1u << ea) - 1u)) == (1u << ea) - 1u && h->d_dbgBlur == nullptr)
-                earlyLv = ea;
-            const int sA = earlyLv ? h->stripBase[earlyLv] : 0;
-            if (earlyLv) {
-                hipLaunchKernelGGL(k_fast_strips, dim3((sA + FAST_WAVES - 1) / FAST_WAVES, B), dim3(64 * FAST_WAVES), 0, st,
-                                   v.pyr, h->pyrImgBytes, h->d_geom, nl, sA, h->totalCells, v.cellCnt, v.cellRaw,
-                                   v.slots, h->slotsPerImg, h->ini_th, h->min_th, sb, spf, 0, compact ? 1 : 0);
-                hipStream_t s2 = h->side[1];
-                ORBX_HIP(hipEventRecord(h->evGather, st));
-                ORBX_HIP(hipStreamWaitEvent(s2, h->evGather, 0));
-                if (wideOct) {
-                    ORBX_HIP(hipFuncSetAttribute((const void *)k_octree_pyr_wide, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsOct));
-                    hipLaunchKernelGGL(k_octree_pyr_wide, dim3(B, earlyLv), dim3(OCT_T_WIDE), ldsOct, s2, h->d_geom, nl, v.cand, h->keysPerImg, v.candCnt,
-                                       v.lvlKp, h->lvlKpCap, v.lvlCnt, h->d_tab, h->maxNodeCap, pow2, h->octPyrWords, v.octFallback, 0, v.nodeOf,
-                                       scratch, 0, 0u, 0, osrc);
-                } else {
-                    ORBX_HIP(hipFuncSetAttribute((const void *)k_octree_pyr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsOct));
-                    hipLaunchKernelGGL(k_octree_pyr, dim3(B, earlyLv), dim3(OCT_T), ldsOct, s2, h->d_geom, nl, v.cand, h->keysPerImg, v.candCnt,
-                                       v.lvlKp, h->lvlKpCap, v.lvlCnt, h->d_tab, h->maxNodeCap, pow2, h->octPyrWords, v.octFallback, 0, v.nodeOf,
-                                       scratch, 0, 0u, 0, osrc);
-                }
-                ORBX_HIP(hipEventRecord(h->evOctA, s2));
-            }
-            if (h->totalStrips > sA)
-                hipLaunchKernelGGL(k_fast_strips, dim3((h->totalStrips - sA + FAST_WAVES - 1) / FAST_WAVES, B), dim3(64 * FAST_WAVES), 0, st,
-                                   v.pyr, h->pyrImgBytes, h->d_geom, nl, h->totalStrips, h->totalCells, v.cellCnt, v.cellRaw,
-                                   v.slots, h->slotsPerImg, h->ini_th, h->min_th, sb, spf, sA, compact ? 1 : 0);
+        const int32_t *spf = p.rowFlags ? v.sparse : (const int32_t *)nullptr;
+        const int sA = p.earlyLv ? h->stripBase[p.earlyLv] : 0;
+        if (p.earlyLv) {   // the strips of the levels [0, earlyLv) first; their quad-tree starts beside the FAST of the rest
+            hipLaunchKernelGGL(k_fast_strips, dim3((sA + FAST_WAVES - 1) / FAST_WAVES, B), dim3(64 * FAST_WAVES), 0, st,
+                               v.pyr, h->pyrImgBytes, h->d_geom, nl, sA, h->totalCells, v.cellCnt, v.cellRaw,
+                               v.slots, h->slotsPerImg, h->ini_th, h->min_th, sb, spf, 0, p.compact ? 1 : 0);
+            ORBX_HIP(hipEventRecord(h->evGather, st));
+            ORBX_HIP(hipStreamWaitEvent(s2, h->evGather, 0));
+            ORBX_OCT_PYR_ON(s2, dim3(B, p.earlyLv), 0, 0, 0, osrc);
+            ORBX_HIP(hipEventRecord(h->evOctA, s2));
         }
-        dim3 grid((h->totalCells + FAST_WAVES - 1) / FAST_WAVES, B);
-        const int es = (h->fastScoreStride == h->fastTileStride - 8 && h->opt[6] != 2) ? h->fastTileStride : 0;
-#define ORBX_LAUNCH_FAST(EST, SP, LDSW)                                                                                  \
-    hipLaunchKernelGGL((k_fast_cells<EST, SP>), grid, dim3(64 * FAST_WAVES), (size_t)(LDSW) * FAST_WAVES, st,              \
-                       v.pyr, h->pyrImgBytes, h->d_geom, nl, h->totalCells, v.cellCnt, v.cellRaw, v.slots, \
-                       h->slotsPerImg, h->ini_th, h->min_th, h->fastTileStride, h->fastScoreStride, h->fastTileRows, \
-                       (LDSW), h->opt[0], cb, stripLevels, v.sparse, (SP) ? FastHist{} : fhist)
-        if (compact && h->opt[20] == 1) {   // the flagged (image, level)s: the strip kernel's compaction twin
-            StripBases sb;
-            for (int l = 0; l <= ORBX_MAX_LEVELS; l++) sb.v[l] = h->stripBase[l];
+        if (p.strips && h->totalStrips > sA)
+            hipLaunchKernelGGL(k_fast_strips, dim3((h->totalStrips - sA + FAST_WAVES - 1) / FAST_WAVES, B), dim3(64 * FAST_WAVES), 0, st,
+                               v.pyr, h->pyrImgBytes, h->d_geom, nl, h->totalStrips, h->totalCells, v.cellCnt, v.cellRaw,
+                               v.slots, h->slotsPerImg, h->ini_th, h->min_th, sb, spf, sA, p.compact ? 1 : 0);
+        if (p.compact && p.sparseForm == 1) {   // the flagged (image, level)s: the strip kernel's compaction twin
             hipLaunchKernelGGL(k_fast_strips_sparse, dim3((h->totalStrips + FAST_WAVES - 1) / FAST_WAVES, B), dim3(64 * FAST_WAVES), 0, st,
                                v.pyr, h->pyrImgBytes, h->d_geom, nl, h->totalStrips, h->totalCells, v.cellCnt, v.cellRaw,
                                v.slots, h->slotsPerImg, h->ini_th, h->min_th, sb, v.sparse);
-        } else if (compact) {   // ORBX_OPT_SPARSE_FORM = 2: the cell kernel's compaction form (+ the queue of 16-bit entries behind a wave's tiles)
+        } else if (p.compact) {   // ORBX_OPT_SPARSE_FORM = 2: the cell kernel's compaction form (+ the queue of 16-bit entries behind a wave's tiles)
             const int ldsw = h->fastLdsPerWave + ((32 * h->fastTileRows + 15) & ~15);
-            switch (es) {
-            case 44: ORBX_LAUNCH_FAST(44, true, ldsw); break;
-            case 48: ORBX_LAUNCH_FAST(48, true, ldsw); break;
-            case 52: ORBX_LAUNCH_FAST(52, true, ldsw); break;
-            default: ORBX_LAUNCH_FAST(0, true, ldsw); break;
-            }
+            ORBX_LAUNCH_FAST_ES(true, ldsw);
         }
-        if (stripLevels != (1u << nl) - 1u) {   // levels with wider cells (the coarsest ones of small images)
-            switch (es) {   // the strides of the usual 30-px cell grids; anything else takes the run-time-stride instance
-            case 44: ORBX_LAUNCH_FAST(44, false, h->fastLdsPerWave); break;
-            case 48: ORBX_LAUNCH_FAST(48, false, h->fastLdsPerWave); break;
-            case 52: ORBX_LAUNCH_FAST(52, false, h->fastLdsPerWave); break;
-            default: ORBX_LAUNCH_FAST(0, false, h->fastLdsPerWave); break;
-            }
-        }
-#undef ORBX_LAUNCH_FAST
+        if (p.fastCells) ORBX_LAUNCH_FAST_ES(false, h->fastLdsPerWave);
     }
     if (profFast) ORBX_HIP(hipEventRecord(ev[2], st));
-    const bool gate = h->pfUsed && evPyrDone == nullptr;   // a pyramid built ahead starts behind this FAST stage (knob 10: 1 behind the quad-tree, 2 behind the descriptors)
-    if (gate && h->opt[10] == 0) ORBX_HIP(hipEventRecord(h->evFastDone, st));
+    if (p.fastDoneAt == ORBX_FASTDONE_BEHIND_FAST) ORBX_HIP(hipEventRecord(h->evFastDone, st));
     {   // K3
-        if (!fused)
+        if (p.gather)
             hipLaunchKernelGGL(k_gather, dim3((h->totalCells + GATHER_CELLS_PER_BLOCK - 1) / GATHER_CELLS_PER_BLOCK, B),
                                dim3(256), 0, st, h->d_geom, nl, h->totalCells, v.cellCnt, v.cellRaw, v.slots,
-                               h->slotsPerImg, v.cand, h->keysPerImg, v.candCnt, h->ini_th, h->min_th, cb, v.sparse, sparsePerCell,
-                               h->opt[20] != 0 ? h->d_sparseSeen : (int32_t *)nullptr, h->callSeq);
-        // developer knob 15: a >= 2 = split call at level a (default 0: one launch sequence)
-        aSplit = (usePyr && !prof && h->lastChunks == 1 && B >= 8 && h->opt[7] == 0 && h->opt[1] == 0 && h->opt[15] >= 2 &&
-                  !multiWg && h->d_dbgBlur == nullptr)
-                     ? std::min(h->opt[15], nl - 1) : 0;   // (default: no split - measured slower)
-        if (nl < 3) aSplit = 0;
-        if (aSplit > 0) {   // scratch records of the levels [a, nl)
+                               h->slotsPerImg, v.cand, h->keysPerImg, v.candCnt, h->ini_th, h->min_th, cb, v.sparse, p.sparsePerCell,
+                               p.sparseHint == ORBX_HINT_GATHER ? h->d_sparseSeen : (int32_t *)nullptr, h->callSeq);
+        if (p.aSplit > 0) {   // scratch records of the levels [a, nl)
             const size_t need = (size_t)h->pB * cap * 60;
             if (h->splitBytes < need) {
                 ORBX_HIP(hipStreamSynchronize(st));
-                ORBX_HIP(hipStreamSynchronize(h->side[1]));
+                ORBX_HIP(hipStreamSynchronize(s2));
                 hipFree(h->d_kpsB); hipFree(h->d_descB); h->d_kpsB = nullptr; h->d_descB = nullptr; h->splitBytes = 0;
                 ORBX_HIP(hipMalloc(&h->d_kpsB, (size_t)h->pB * cap * sizeof(orbx_keypoint_t)));
                 ORBX_HIP(hipMalloc(&h->d_descB, (size_t)h->pB * cap * 32));
                 h->splitBytes = need;
             }
         }
-        if (usePyr) {   // a level whose tree outgrows the count pyramid is redone by the same block with the exact form: one launch
-            const size_t lds = std::max(h->octPyrLdsBytes, h->octLdsBytes);
-            // The multi-workgroup form shortens ONE image's critical path (a 1920x1080 level 0: 195 us alone in its workgroup); a
-            // batch already fills the GPU with one workgroup per (image, level), and the extra hand-offs then cost more than they save
-            // (batch 32 of 1920x1080: 274 us against 215), so it is taken for small batches only.  Same results either way.
-            // (only the multi-workgroup form shares levels: it sweeps the COMPACTED keys, which exist only when k_gather ran - i.e. when the call is not fused)
-            const unsigned bigMask = !multiWg ? 0u : h->opt[4] == 2 ? (1u << nl) - 1u : h->octBigMask;
+        // (k_octree_pyr: a level whose tree outgrows the count pyramid is redone by the same block with the exact form: one launch)
+        switch (p.octForm) {
+        case ORBX_OCT_EXACT:
+            ORBX_OCT_LAUNCH_ON(st, k_octree, k_octree_wide, dim3(B, nl), h->octLdsBytes, h->d_geom, nl, v.cand, v.nodeOf,
+                               h->keysPerImg, v.candCnt, v.lvlKp, h->lvlKpCap, v.lvlCnt, h->d_tab, h->maxNodeCap, pow2,
+                               scratch, p.octPhase);
+            break;
+        case ORBX_OCT_BIG: {
             OctBig big = {};
             // the kernels index this scratch by the chunk-local image: chunks that run side by side on two streams get disjoint slots
             big.part = h->d_octPart + v.octSlot0 * OCT_BIG_K * (size_t)h->octDeepMax; big.leaf = h->d_octLeaf + v.octSlot0 * (size_t)h->octPyrWords;
             big.best = h->d_octBest + v.octSlot0 * (size_t)h->maxNodeCap; big.state = h->d_octState + v.octSlot0 * 4;
             big.K = OCT_BIG_K; big.deepMax = h->octDeepMax; big.pyrMax = h->octPyrWords;
-            for (int l = 0; l < nl; l++) if ((bigMask >> l) & 1u) big.levelOf[big.nBig++] = l;
-            // 1024-thread instances for images with a large level (>= 600 FAST cells; developer knob 11: 1 = never, 2 = always)
-            const bool wide = h->opt[11] == 0 ? h->octBigMask != 0 : h->opt[11] == 2;
-#define ORBX_OCT_LAUNCH_ON(STREAM, KERN, KERNW, GRID, LDS, ...)                                                            \
-    do {                                                                                                                \
-        if (wide) {                                                                                                     \
-            ORBX_HIP(hipFuncSetAttribute((const void *)KERNW, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS))); \
-            hipLaunchKernelGGL(KERNW, GRID, dim3(OCT_T_WIDE), LDS, STREAM, __VA_ARGS__);                                \
-        } else {                                                                                                        \
-            ORBX_HIP(hipFuncSetAttribute((const void *)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS)));  \
-            hipLaunchKernelGGL(KERN, GRID, dim3(OCT_T), LDS, STREAM, __VA_ARGS__);                                      \
-        }                                                                                                               \
-    } while (0)
-#define ORBX_OCT_LAUNCH(KERN, KERNW, GRID, LDS, ...) ORBX_OCT_LAUNCH_ON(st, KERN, KERNW, GRID, LDS, __VA_ARGS__)
-            if (big.nBig > 0 && h->opt[7] == 0 && h->opt[1] == 0) {
-                // large levels: K workgroups histogram, the last one to arrive runs the passes; the same launch carries the other
-                // levels (one workgroup each, listed behind the large ones) ...
-                int nall = big.nBig;
-                for (int l = 0; l < nl; l++) if (!((bigMask >> l) & 1u)) big.levelOf[nall++] = l;
-                ORBX_OCT_LAUNCH(k_octree_big<1>, k_octree_big_wide<1>, dim3(OCT_BIG_K, nl, B), lds, h->d_geom, nl, v.cand, h->keysPerImg,
-                                v.candCnt, v.lvlKp, h->lvlKpCap, v.lvlCnt, h->d_tab, h->maxNodeCap, pow2, h->octPyrWords,
-                                v.octFallback, v.nodeOf, scratch, big);
-                // ... then K workgroups elect the best key per node, the last one writes the level's keypoints
-                ORBX_OCT_LAUNCH(k_octree_big<2>, k_octree_big_wide<2>, dim3(OCT_BIG_K, big.nBig, B), lds, h->d_geom, nl, v.cand, h->keysPerImg,
-                                v.candCnt, v.lvlKp, h->lvlKpCap, v.lvlCnt, h->d_tab, h->maxNodeCap, pow2, h->octPyrWords,
-                                v.octFallback, v.nodeOf, scratch, big);
-            } else if (earlyLv > 0) {
-                // the quad-tree of the levels [0, earlyLv) is already running on the second stream (started behind their strips)
-                ORBX_OCT_LAUNCH(k_octree_pyr, k_octree_pyr_wide, dim3(B, nl - earlyLv), lds, h->d_geom, nl, v.cand,
-                                h->keysPerImg, v.candCnt, v.lvlKp, h->lvlKpCap, v.lvlCnt, h->d_tab, h->maxNodeCap,
-                                pow2, h->octPyrWords, v.octFallback, 0, v.nodeOf, scratch, 0, 0u, earlyLv, osrc);
-                ORBX_HIP(hipStreamWaitEvent(st, h->evOctA, 0));
-            } else if (aSplit > 0) {
-                // Split call: the quad-tree of the large levels [0, a) - one workgroup per level walking a serial chain, the critical
-                // path of this stage - moves to a second stream, and the small levels [a, nl) go ahead on the caller's stream:
-                // their quad-tree, then their descriptors (a VALU-bound kernel that fills the GPU) into scratch arrays, beside that
-                // chain.  The descriptors of [0, a) follow when both are done and move the scratch records behind their own.
-                hipStream_t s2 = h->side[1];
-                ORBX_HIP(hipEventRecord(h->evGather, st));
-                ORBX_HIP(hipStreamWaitEvent(s2, h->evGather, 0));
-                ORBX_OCT_LAUNCH_ON(s2, k_octree_pyr, k_octree_pyr_wide, dim3(B, aSplit), lds, h->d_geom, nl, v.cand,
-                                   h->keysPerImg, v.candCnt, v.lvlKp, h->lvlKpCap, v.lvlCnt, h->d_tab, h->maxNodeCap,
-                                   pow2, h->octPyrWords, v.octFallback, 0, v.nodeOf, scratch, 0, 0u, 0, osrc);
-                ORBX_HIP(hipEventRecord(h->evOctA, s2));
-                ORBX_OCT_LAUNCH(k_octree_pyr, k_octree_pyr_wide, dim3(B, nl - aSplit), lds, h->d_geom, nl, v.cand,
-                                h->keysPerImg, v.candCnt, v.lvlKp, h->lvlKpCap, v.lvlCnt, h->d_tab, h->maxNodeCap,
-                                pow2, h->octPyrWords, v.octFallback, 0, v.nodeOf, scratch, 0, 0u, aSplit, osrc);
-            } else {   // no large level (or a phase-stop knob is set): one workgroup per level, one launch
-                // ... except that in a BATCH the sweep of a large level (>= 600 FAST cells) MAY be shared by two or four workgroups
-                // (ORBX_OPT_OCT_SLICES = 1; off by default): the level-0 workgroup of a 1920x1080 image is the critical path of the stage
-                // (113 us, 64 of them its sweep), and sharing the sweeps takes the stage ALONE from 120 to 90 us at batch 32 - but the pipelined
-                // step gets slower (0.6105 -> 0.6277 ms at batch 32, 1.186 -> 1.256 ms at batch 64): beside the next pyramid and the previous
-                // matcher the extra 1024-thread workgroups cost more than the shorter critical path gives back
-                OctSrc os = osrc;
-                int kmax = 1;
-                if (fused && !histOct && h->opt[26] == 1 && h->d_octPartBest && h->opt[7] == 0 && h->opt[1] == 0) {
-                    for (int l = 0; l < nl; l++) {
-                        const int k = h->geom[l].ncells >= 1600 ? 4 : h->geom[l].ncells >= 600 ? 2 : 1;
-                        os.nslice[l] = (unsigned char)k;
-                        kmax = std::max(kmax, k);
-                    }
-                    os.partCnt = h->d_octPartCnt + v.octSlot0 * OCT_MAX_SLICES * (size_t)h->octSliceStride;
-                    os.partBest = h->d_octPartBest + v.octSlot0 * OCT_MAX_SLICES * (size_t)h->octSliceStride;
-                    os.sliceState = h->d_octSliceState + v.octSlot0;
-                    os.maxSlices = OCT_MAX_SLICES; os.partStride = h->octSliceStride;
-                }
-                dim3 ogrid(B, nl);
-                if (kmax > 1) {   // linear grid: every slice of the large levels in front of the small levels
-                    os.linear = 1; os.nImages = B;
-                    int tot = 0;
-                    for (int l = 0; l <= ORBX_MAX_LEVELS; l++) { os.blkPrefix[l] = tot; if (l < nl) tot += B * std::max(1, (int)os.nslice[l]); }
-                    ogrid = dim3(tot);
-                }
-                ORBX_OCT_LAUNCH(k_octree_pyr, k_octree_pyr_wide, ogrid, lds, h->d_geom, nl, v.cand,
-                                h->keysPerImg, v.candCnt, v.lvlKp, h->lvlKpCap, v.lvlCnt, h->d_tab, h->maxNodeCap,
-                                pow2, h->octPyrWords, v.octFallback, h->opt[7], v.nodeOf, scratch, h->opt[1], 0u, 0, os);
+            for (int l = 0; l < nl; l++) if (((unsigned)p.bigMask >> l) & 1u) big.levelOf[big.nBig++] = l;
+            // large levels: K workgroups histogram, the last one to arrive runs the passes; the same launch carries the other
+            // levels (one workgroup each, listed behind the large ones) ...
+            int nall = big.nBig;
+            for (int l = 0; l < nl; l++) if (!(((unsigned)p.bigMask >> l) & 1u)) big.levelOf[nall++] = l;
+            ORBX_OCT_LAUNCH_ON(st, k_octree_big<1>, k_octree_big_wide<1>, dim3(OCT_BIG_K, nl, B), ldsOct, h->d_geom, nl, v.cand, h->keysPerImg,
+                               v.candCnt, v.lvlKp, h->lvlKpCap, v.lvlCnt, h->d_tab, h->maxNodeCap, pow2, h->octPyrWords,
+                               v.octFallback, v.nodeOf, scratch, big);
+            // ... then K workgroups elect the best key per node, the last one writes the level's keypoints
+            ORBX_OCT_LAUNCH_ON(st, k_octree_big<2>, k_octree_big_wide<2>, dim3(OCT_BIG_K, big.nBig, B), ldsOct, h->d_geom, nl, v.cand, h->keysPerImg,
+                               v.candCnt, v.lvlKp, h->lvlKpCap, v.lvlCnt, h->d_tab, h->maxNodeCap, pow2, h->octPyrWords,
+                               v.octFallback, v.nodeOf, scratch, big);
+            break;
+        }
+        case ORBX_OCT_EARLY:   // the quad-tree of the levels [0, earlyLv) is already running on the second stream (started behind their strips)
+            ORBX_OCT_PYR_ON(st, dim3(B, nl - p.earlyLv), 0, 0, p.earlyLv, osrc);
+            ORBX_HIP(hipStreamWaitEvent(st, h->evOctA, 0));
+            break;
+        case ORBX_OCT_SPLIT:
+            // Split call: the quad-tree of the large levels [0, a) - one workgroup per level walking a serial chain, the critical
+            // path of this stage - moves to a second stream, and the small levels [a, nl) go ahead on the caller's stream:
+            // their quad-tree, then their descriptors (a VALU-bound kernel that fills the GPU) into scratch arrays, beside that
+            // chain.  The descriptors of [0, a) follow when both are done and move the scratch records behind their own.
+            ORBX_HIP(hipEventRecord(h->evGather, st));
+            ORBX_HIP(hipStreamWaitEvent(s2, h->evGather, 0));
+            ORBX_OCT_PYR_ON(s2, dim3(B, p.aSplit), 0, 0, 0, osrc);
+            ORBX_HIP(hipEventRecord(h->evOctA, s2));
+            ORBX_OCT_PYR_ON(st, dim3(B, nl - p.aSplit), 0, 0, p.aSplit, osrc);
+            break;
+        default: {   // ORBX_OCT_SINGLE: one workgroup per level, one launch - or, with a shared sweep, several for a large level
+            OctSrc os = osrc;
+            if (p.sweepSlices) {
+                for (int l = 0; l < nl; l++) os.nslice[l] = (unsigned char)p.nslice[l];
+                os.partCnt = h->d_octPartCnt + v.octSlot0 * OCT_MAX_SLICES * (size_t)h->octSliceStride;
+                os.partBest = h->d_octPartBest + v.octSlot0 * OCT_MAX_SLICES * (size_t)h->octSliceStride;
+                os.sliceState = h->d_octSliceState + v.octSlot0;
+                os.maxSlices = OCT_MAX_SLICES; os.partStride = h->octSliceStride;
             }
-        } else {        // developer knob 4 = 1: the exact form alone
-            const bool wide = h->opt[11] == 0 ? h->octBigMask != 0 : h->opt[11] == 2;
-            ORBX_OCT_LAUNCH(k_octree, k_octree_wide, dim3(B, nl), h->octLdsBytes, h->d_geom, nl, v.cand, v.nodeOf,
-                            h->keysPerImg, v.candCnt, v.lvlKp, h->lvlKpCap, v.lvlCnt, h->d_tab, h->maxNodeCap, pow2,
-                            scratch, h->opt[1]);
-#undef ORBX_OCT_LAUNCH
-#undef ORBX_OCT_LAUNCH_ON
+            dim3 ogrid(B, nl);
+            if (p.sweepShared) {   // linear grid: every slice of the large levels in front of the small levels
+                os.linear = 1; os.nImages = B;
+                int tot = 0;
+                for (int l = 0; l <= ORBX_MAX_LEVELS; l++) { os.blkPrefix[l] = tot; if (l < nl) tot += B * std::max(1, (int)os.nslice[l]); }
+                ogrid = dim3(tot);
+            }
+            ORBX_OCT_PYR_ON(st, ogrid, p.octStop, p.octPhase, 0, os);
+        }
         }
     }
     if (prof) ORBX_HIP(hipEventRecord(ev[3], st));
-    if (gate && h->opt[10] == 1) ORBX_HIP(hipEventRecord(h->evFastDone, st));
+    if (p.fastDoneAt == ORBX_FASTDONE_BEHIND_OCT) ORBX_HIP(hipEventRecord(h->evFastDone, st));
     {   // K4 (one instance per flavour of the Gaussian's column rounding: the default pays nothing for the other)
         const bool sse2 = h->flavour.gauss_rounding == ORBX_GAUSS_ROUND_SSE2;
         // ORBX_OPT_DESC_LDS_PAD (KB): unused dynamic LDS per workgroup = fewer resident k_describe workgroups per CU, i.e. wave slots
         // left for the pyramid kernels that run beside it in a pipelined step (tuning only)
-        const size_t descPad = (size_t)h->opt[21] * 1024;
+        const size_t descPad = (size_t)p.descLdsPad;
         const bool ftaps = h->flavour.gauss_rounding == ORBX_GAUSS_FIXED_TAPS;
         const uint32_t taps = gauss_taps_packed(h);
-        const auto kDesc = aSplit > 0 ? (ftaps ? k_describe<ORBX_GAUSS_FIXED_TAPS, true> : sse2 ? k_describe<ORBX_GAUSS_ROUND_SSE2, true> : k_describe<ORBX_GAUSS_ROUND_HALF_UP, true>)
-                                      : (ftaps ? k_describe<ORBX_GAUSS_FIXED_TAPS, false> : sse2 ? k_describe<ORBX_GAUSS_ROUND_SSE2, false> : k_describe<ORBX_GAUSS_ROUND_HALF_UP, false>);
+        const auto kDesc = p.aSplit > 0 ? (ftaps ? k_describe<ORBX_GAUSS_FIXED_TAPS, true> : sse2 ? k_describe<ORBX_GAUSS_ROUND_SSE2, true> : k_describe<ORBX_GAUSS_ROUND_HALF_UP, true>)
+                                        : (ftaps ? k_describe<ORBX_GAUSS_FIXED_TAPS, false> : sse2 ? k_describe<ORBX_GAUSS_ROUND_SSE2, false> : k_describe<ORBX_GAUSS_ROUND_HALF_UP, false>);
         const uint8_t *blurp = h->blurMaskLast ? h->d_blur + (size_t)v.b0 * h->pyrImgBytes : nullptr;
-        if (aSplit > 0) {
+        if (p.aSplit > 0) {
             int boundA = 0, boundB = 0;
-            for (int l = 0; l < nl; l++) (l < aSplit ? boundA : boundB) += std::max(h->geom[l].N + 2, 4 * h->geom[l].nIni);
+            for (int l = 0; l < nl; l++) (l < p.aSplit ? boundA : boundB) += std::max(h->geom[l].N + 2, 4 * h->geom[l].nIni);
             const int maxoA = std::min(cap, boundA), maxoB = std::min(cap, boundB);
             orbx_keypoint_t *kB = h->d_kpsB + (size_t)v.b0 * cap;
             uint8_t *dB = h->d_descB + (size_t)v.b0 * cap * 32;
             const int nbB = (maxoB + DESC_WAVES - 1) / DESC_WAVES, nbA = (maxoA + DESC_WAVES - 1) / DESC_WAVES;
-            DescGroup gB = {aSplit, nl, 0, nbB, nullptr, nullptr};
+            DescGroup gB = {p.aSplit, nl, 0, nbB, nullptr, nullptr};
             gB.taps = taps;
             hipLaunchKernelGGL(kDesc, dim3(nbB, B), dim3(64 * DESC_WAVES), descPad, st, v.pyr, h->pyrImgBytes, h->d_geom, nl,
                                v.lvlKp, h->lvlKpCap, v.lvlCnt, kB, dB, d_counts, cap, (uint8_t *)nullptr, blurp, h->blurMaskLast, gB);
             ORBX_HIP(hipStreamWaitEvent(st, h->evOctA, 0));
-            DescGroup gA = {0, aSplit, 1, nbA, kB, dB};
+            DescGroup gA = {0, p.aSplit, 1, nbA, kB, dB};
             gA.taps = taps;
             hipLaunchKernelGGL(kDesc, dim3(nbA + (maxoB + DESC_COPY_PER_BLOCK - 1) / DESC_COPY_PER_BLOCK, B), dim3(64 * DESC_WAVES), descPad, st,
                                v.pyr, h->pyrImgBytes, h->d_geom, nl, v.lvlKp, h->lvlKpCap, v.lvlCnt, d_kps, d_desc, d_counts, cap,
@@ -1120,17 +1040,13 @@ static int launch_chunk(orbx_extractor *h, const ChunkView &v, int B, int stride
         }
     }
     if (prof) ORBX_HIP(hipEventRecord(ev[4], st));
-    if (gate && h->opt[10] == 2) ORBX_HIP(hipEventRecord(h->evFastDone, st));
+    if (p.fastDoneAt == ORBX_FASTDONE_BEHIND_DESC) ORBX_HIP(hipEventRecord(h->evFastDone, st));
     return ORBX_OK;
 }
-
-// Chunks a batch of B images is cut into (developer knob 8; default ONE).  The one rule for launch_pipeline and orbx_fast_kernels.
-static int chunk_count(const orbx_extractor *h, int B, bool prof, bool skipPyr) {
-    int nch = h->opt[8] <= 1 ? 1 : std::min(h->opt[8], ORBX_MAX_CHUNKS);
-    nch = std::min(nch, B);
-    if (prof || skipPyr || h->opt[0] || h->opt[1] || h->opt[7]) nch = 1;
-    return nch;
-}
+#undef ORBX_LAUNCH_FAST_ES
+#undef ORBX_LAUNCH_FAST
+#undef ORBX_OCT_PYR_ON
+#undef ORBX_OCT_LAUNCH_ON
 
 // A batch runs as up to ORBX_MAX_CHUNKS chunks of images.  Chunk 0 goes to the caller's stream, the others to the handle's side
 // streams, and chunk c's pyramid waits for chunk c-1's: the memory-bound pyramid and the latency-bound gather / quad-tree of one
@@ -1151,7 +1067,7 @@ static int launch_pipeline(orbx_extractor *h, const uint8_t *d_imgs, int B, int 
     }
     // developer knob 8: n >= 2 = n chunks (default: one - measured on 64 stereo frames, two chunks: 773 us against 742, the
     // latency-bound gather / quad-tree do not shrink with the chunk and the pyramid slows the FAST it overlaps by as much as it gains).
-    const int nch = chunk_count(h, B, prof, skipPyr);
+    const int nch = chunk_count(h->opt, B, prof, skipPyr);
     h->lastChunks = nch;
     h->candStale = 0;
     h->callSeq = (int)((unsigned)h->callSeq + 1u);   // wraps (compared by unsigned distance)
@@ -1731,15 +1647,37 @@ extern "C" int orbx_debug_level_points(orbx_extractor_t *h, int b, int level, in
 extern "C" int orbx_fast_kernels(const orbx_extractor_t *h, int B, int *strips, int *cells, int *images_per_launch) {
     if (!h || h->pw == 0 || B < 1) { orbx_set_error("orbx_fast_kernels: no plan yet"); return ORBX_ERR_ARG; }
     // the last call's own chunk count when it was a batch of this size (it knows whether its pyramid was built ahead), else the rule
-    const int nch = (h->last_valid && h->lastB == B) ? h->lastChunks : chunk_count(h, B, h->profiling == 1, false);
+    const int nch = (h->last_valid && h->lastB == B) ? h->lastChunks : chunk_count(h->opt, B, h->profiling == 1, false);
     B = B / nch;                                   // the first chunk is the one whose FAST stage carries the events
     if (images_per_launch) *images_per_launch = B;
-    const bool st = h->totalStrips > 0 && (h->opt[6] == 0 ? (size_t)h->totalStrips * B >= 4096 : h->opt[6] == 3);
-    const unsigned lv = st ? h->stripLevels : 0u;
-    if (strips) *strips = st ? 1 : 0;
-    if (cells) *cells = lv != (1u << h->nlevels) - 1u ? 1 : 0;
+    ChunkPlan p;
+    const int rc = plan_chunk(plan_input(h, B, nch, h->profiling == 1, h->profiling != 0, false, false), &p);
+    if (rc) return rc;
+    if (strips) *strips = p.strips;
+    if (cells) *cells = p.fastCells;
     return ORBX_OK;
 }
+
+#ifdef ORBX_DEVELOPER
+// The launch rule by itself (no HIP call, no handle): PlanInput in, ChunkPlan out, both as flat int32 arrays (include/orbx_dev.h).
+static_assert(ORBX_DEBUG_PLAN_INPUT_INTS == ORBX_PLAN_INPUT_INTS && ORBX_DEBUG_CHUNK_PLAN_INTS == ORBX_CHUNK_PLAN_INTS, "include/orbx_dev.h and orbx_plan.h disagree");
+extern "C" int orbx_debug_plan_chunk(const int32_t *in, int n_in, int32_t *out, int n_out) {
+    PlanInput pi;
+    if (!in || !out || n_in != ORBX_PLAN_INPUT_INTS || n_out != ORBX_CHUNK_PLAN_INTS) { orbx_set_error("orbx_debug_plan_chunk: bad arguments"); return ORBX_ERR_ARG; }
+    memcpy(&pi, in, sizeof(pi));
+    if (pi.B < 1 || pi.nl < 1 || pi.nl > ORBX_MAX_LEVELS) { orbx_set_error("orbx_debug_plan_chunk: bad B or nl"); return ORBX_ERR_ARG; }
+    ChunkPlan p;
+    const int rc = plan_chunk(pi, &p);
+    if (rc == ORBX_OK) memcpy(out, &p, sizeof(p));
+    return rc;
+}
+// the plan chunk 0 of the handle's last extraction call executed
+extern "C" int orbx_debug_last_plan(const orbx_extractor_t *h, int32_t *out, int n_out) {
+    if (!h || !out || n_out != ORBX_CHUNK_PLAN_INTS || !h->last_valid) { orbx_set_error("orbx_debug_last_plan: bad arguments or no call yet"); return ORBX_ERR_ARG; }
+    memcpy(out, &h->lastPlan, sizeof(h->lastPlan));
+    return ORBX_OK;
+}
+#endif
 
 #ifdef ORBX_DEVELOPER
 // Test hook for SURVEY section 8 row a8 (cv::GaussianBlur 7x7, sigma 2, fused into k_describe and never stored): the next

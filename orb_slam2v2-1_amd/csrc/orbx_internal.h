@@ -21,6 +21,7 @@
 #define ORBX_HIST_IMAGES 4     // batches up to this size: the FAST stage histograms its emissions for the quad-tree (FastHist)
 
 void orbx_set_error(const char *fmt, ...);
+#include "orbx_plan.h"   // PlanInput / ChunkPlan / plan_chunk / chunk_count: the launch rule of an extraction call
 
 #define ORBX_HIP(call)                                                                      \
     do {                                                                                    \
@@ -134,6 +135,7 @@ struct orbx_extractor {
     hipStream_t last_stream; // stream of the last batch call (NULL is a stream too: the HIP default stream)
     int last_valid;          // ... once there has been one
     int lastB;
+    ChunkPlan lastPlan;      // the plan chunk 0 of the last call executed (orbx_debug_last_plan)
     int framesStale;         // > 0: the frames of levels >= 1 of that many images have not been written (see ensure_frames)
     // scratch of Frame::ComputeStereoMatches when this handle is the LEFT extractor (orbx_match.hip: stereo_scratch_reserve)
     int32_t *st_sad; uint2 *st_rc; int32_t *st_binStart; uint4 *st_items; size_t st_n; int st_nB;

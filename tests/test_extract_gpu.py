@@ -67,9 +67,10 @@ def test_batch_matches_single(pkg, oracle, synth):
         np.testing.assert_array_equal(gd, od)
 
 
-def _compare(pkg, oracle, img, nf, sf=1.2, nl=8, ini=20, mn=7):
+def _compare(pkg, oracle, img, nf, sf=1.2, nl=8, ini=20, mn=7, plans=None):
     """One image through the HIP path, TWICE - with the FAST kernel a single image takes by default (k_fast_cells, one wave per
-    cell) and with the one a large batch takes (k_fast_strips, forced by developer knob 6 = 3) - against the oracle."""
+    cell) and with the one a large batch takes (k_fast_strips, forced by developer knob 6 = 3) - against the oracle.
+    plans: a list that receives the launch plan (orbx_debug_last_plan) of each pass, the strip pass first."""
     ex = pkg.ORBextractor(nf, sf, nl, ini, mn)
     orc = oracle.Extractor(nf, sf, nl, ini, mn)
     ok, od = orc.extract(img)
@@ -78,9 +79,14 @@ def _compare(pkg, oracle, img, nf, sf=1.2, nl=8, ini=20, mn=7):
         knob(6, 3)
         try:
             _check_against(ex, orc, ok, od, img, nl)
+            if plans is not None:
+                plans.append(ex.debug_last_plan())
         finally:
             knob(6, 0)
-    return _check_against(ex, orc, ok, od, img, nl)
+    k = _check_against(ex, orc, ok, od, img, nl)
+    if plans is not None:
+        plans.append(ex.debug_last_plan())
+    return k
 
 
 _KNOB6 = [0]   # tests that set knob 6 themselves (test_fast_cell_kernel_instances) say so here
@@ -382,11 +388,13 @@ def test_large_scale_factor(pkg, oracle, synth):
 def test_quadtree_sweep_kernel_alone(pkg, oracle, synth):
     """k_octree (one key sweep per pass) is the exact fallback of k_octree_pyr: run it alone."""
     pkg.set_default_option(4, 1)
+    plans = []
     try:
-        _compare(pkg, oracle, synth.frame(752, 480, 80), 1000)
-        _compare(pkg, oracle, synth.frame(640, 480, 81), 2000)
+        _compare(pkg, oracle, synth.frame(752, 480, 80), 1000, plans=plans)
+        _compare(pkg, oracle, synth.frame(640, 480, 81), 2000, plans=plans)
     finally:
         pkg.set_default_option(4, 0)
+    assert len(plans) == 4 and all(p["octForm"] == pkg.OCT_EXACT and not p["usePyr"] and p["gather"] and not p["fused"] for p in plans), plans
 
 
 def test_quadtree_multi_workgroup_form(pkg, oracle, synth):
@@ -400,12 +408,13 @@ def test_quadtree_multi_workgroup_form(pkg, oracle, synth):
     flat = np.full((480, 640), 77, np.uint8)                                          # no keys at all
     for knob in (2, 3):
         pkg.set_default_option(4, knob)
+        plans = []
         try:
-            _compare(pkg, oracle, synth.frame(1241, 376, 96), 1000)
-            _compare(pkg, oracle, synth.frame(640, 480, 97), 2000)
-            _compare(pkg, oracle, clustered, 1000)
-            _compare(pkg, oracle, flat, 500)
-            _compare(pkg, oracle, rng.integers(0, 256, (376, 620), dtype=np.uint8), 2000)
+            _compare(pkg, oracle, synth.frame(1241, 376, 96), 1000, plans=plans)
+            _compare(pkg, oracle, synth.frame(640, 480, 97), 2000, plans=plans)
+            _compare(pkg, oracle, clustered, 1000, plans=plans)
+            _compare(pkg, oracle, flat, 500, plans=plans)
+            _compare(pkg, oracle, rng.integers(0, 256, (376, 620), dtype=np.uint8), 2000, plans=plans)
             # a batch: the arrival counters are per (image, level) and must come back to zero for the next call
             imgs = synth.batch(752, 480, 6, k0=98)
             ex = pkg.ORBextractor(1000, 1.2, 8, 20, 7)
@@ -416,9 +425,24 @@ def test_quadtree_multi_workgroup_form(pkg, oracle, synth):
                     ok, od = orc.extract(imgs[i])
                     assert res[i][0].tobytes() == ok.tobytes() or (len(res[i][0]) == len(ok) and (res[i][1] == od).all()
                                                                      and (res[i][0]["x"] == ok["x"]).all() and (res[i][0]["y"] == ok["y"]).all())
+            plans.append(ex.debug_last_plan())
         finally:
             pkg.set_default_option(4, 0)
-    _compare(pkg, oracle, synth.frame(1920, 1080, 99), 4000)     # default rule: a single image, the larger levels take the multi-workgroup form
+        # the form that ran (orbx_debug_last_plan): knob 2 = every level multi-workgroup, on the compacted keys k_gather wrote; knob 3 = never
+        assert len(plans) == 11
+        for p in plans:
+            if knob == 2:
+                assert p["octForm"] == pkg.OCT_BIG and p["multiWg"] and p["gather"] and not p["fused"] and p["bigMask"] == 255, p
+            else:
+                assert p["octForm"] == pkg.OCT_SINGLE and not p["multiWg"] and p["bigMask"] == 0, p
+    # default rule, a single image with large levels: behind the strip kernel (forced) they take the multi-workgroup form on the keys
+    # k_gather compacted; behind the cell kernel (a single image's default) the FAST stage histograms for the quad-tree, nothing is
+    # gathered and the form must not be taken (it would sweep an array nobody wrote)
+    plans = []
+    _compare(pkg, oracle, synth.frame(1920, 1080, 99), 4000, plans=plans)
+    ps, pc = plans
+    assert ps["octForm"] == pkg.OCT_BIG and ps["multiWg"] and ps["gather"] and ps["bigMask"] != 0 and not ps["histOct"], ps
+    assert pc["octForm"] == pkg.OCT_SINGLE and pc["histOct"] and pc["fused"] and not pc["gather"] and not pc["multiWg"] and pc["bigMask"] == 0, pc
 
 
 @pytest.mark.parametrize("wide,form", [(2, 0), (2, 1), (2, 2), (1, 0), (1, 2)])
@@ -464,9 +488,15 @@ def test_fast_strips_and_cells_mix(pkg, oracle, synth):
     """Sizes whose pyramid mixes strip levels (cells <= 32 px) with wide-cell levels (640x480: levels 5 and 7 have 33- and
     37-px cells), a last strip with one / two / three cells, a last column narrower than its neighbours, and thresholds that
     make the per-cell fallback (src/ORBextractor.cc:809-816) decide differently from cell to cell."""
-    _compare(pkg, oracle, synth.frame(640, 480, 90), 1000)
+    plans = []
+    _compare(pkg, oracle, synth.frame(640, 480, 90), 1000, plans=plans)
+    ps, pc = plans                               # the strip pass runs BOTH kernels (levels 5 and 7 stay with k_fast_cells), the default pass the cell kernel alone
+    assert ps["strips"] and ps["fastCells"] and ps["stripLevels"] == 0b01011111, ps
+    assert not pc["strips"] and pc["fastCells"] and pc["stripLevels"] == 0, pc
     for w in (406, 437, 468, 499, 531):          # nCols = 12 .. 16 at level 0: every remainder of nCols mod 4
-        _compare(pkg, oracle, synth.frame(w, 300, 91 + w), 600)
+        plans = []
+        _compare(pkg, oracle, synth.frame(w, 300, 91 + w), 600, plans=plans)
+        assert plans[0]["strips"] and plans[0]["stripLevels"] & 1 and not plans[1]["strips"] and plans[1]["fastCells"], plans
     rng = np.random.default_rng(93)
     img = np.full((376, 1241), 100, np.uint8)
     for _ in range(300):                                # faint and strong squares: some cells only reach minTh
@@ -702,6 +732,8 @@ def test_split_call_level_groups(pkg, oracle, synth, split):
                     np.testing.assert_array_equal(got[f], ok[f][:n], err_msg="%s image %d cap %d" % (f, b, cap))
                 np.testing.assert_allclose(got["angle"], ok["angle"][:n], atol=1e-4, rtol=0)
                 np.testing.assert_array_equal(dd[b, :n], od[:n])
+            p = ex.debug_last_plan()             # the arrangement that ran: split at the requested level (8 levels: a <= 7), or one launch sequence
+            assert p["aSplit"] == split and (p["octForm"] == pkg.OCT_SPLIT) == (split >= 2) and p["earlyLv"] == 0, (split, p)
     finally:
         pkg.set_default_option(15, 0)
 
@@ -805,6 +837,13 @@ def test_early_quadtree_of_large_levels(pkg, oracle, synth, early):
         for rep in range(3):
             ex.extract_batch_device(d_imgs.data_ptr(), B, w, h, w, w * h, kps.data_ptr(), desc.data_ptr(), cnt.data_ptr(), cap, st)
         torch.cuda.synchronize()
+        # the arrangement that ran: the early form needs every level below `early` to be a strip level; where this image's strip levels
+        # do not reach that far the call takes the single form, and that is what is asserted
+        p = ex.debug_last_plan()
+        m = (1 << early) - 1
+        want = early if early >= 2 and p["stripLevels"] & m == m else 0
+        assert p["strips"] and p["earlyLv"] == want and (p["octForm"] == pkg.OCT_EARLY) == (want > 0) and p["fused"], (early, p)
+        assert want == early or early == 5, (early, p)      # levels 0 - 2 of 752x480 are strip levels
         k = kps.cpu().numpy().view(np.uint8).reshape(B, cap, 28)
         dd = desc.cpu().numpy()
         for b in range(B):
@@ -865,6 +904,9 @@ def test_small_batch_forms_agree(pkg, oracle, synth):
                 for k_, v_ in opts:
                     ex.set_option(k_, v_)
                 got = ex.extract_batch(imgs)
+                p = ex.debug_last_plan()         # the quad-tree loads the FAST stage's histogram at the default, never under ORBX_OPT_OCT_HIST = 1
+                assert p["histOct"] == ((23, 1) not in opts and not p["strips"]) and (not p["strips"] or w > 1900), (w, h, B, opts, p)
+                assert p["fused"] and not p["multiWg"] if p["histOct"] else True, p
                 for b in range(B):
                     assert got[b][0].tobytes() == exp[b][0].tobytes() and got[b][1].tobytes() == exp[b][1].tobytes(), (w, h, B, b, opts)
                 orc.extract(imgs[B - 1])
@@ -872,6 +914,27 @@ def test_small_batch_forms_agree(pkg, oracle, synth):
                     np.testing.assert_array_equal(ex.pyramid_level(l, b=B - 1, padded=True), orc.pyramid_level(l, padded=True), err_msg=str((w, h, B, l, opts)))
                     np.testing.assert_array_equal(ex.debug_level_points(l, 1, b=B - 1), _cands(orc.level_keypoints(l)), err_msg=str((w, h, B, l, opts)))
                 ex.close()
+
+
+def test_launch_plan_across_the_small_batch_threshold(pkg, oracle, synth):
+    """333x257 at the defaults, batches of 1, 4 and 5 images (ORBX_HIST_IMAGES = 4): orbx_fast_kernels and the plan the call executed
+    (orbx_debug_last_plan) name the same FAST kernels, the quad-tree loads the FAST stage's histogram up to four images and sweeps the
+    cell lists from five on, and every image equals the oracle."""
+    w, h, nf = 333, 257, 300
+    imgs = np.stack([synth.frame(w, h, 770 + i) for i in range(5)])
+    orc = oracle.Extractor(nf, 1.2, 8, 20, 7)
+    exp = [orc.extract(im) for im in imgs]
+    ex = pkg.ORBextractor(nf, 1.2, 8, 20, 7)
+    for B in (1, 4, 5):
+        got = ex.extract_batch(imgs[:B])
+        p = ex.debug_last_plan()
+        names = ex.fast_kernels(B)
+        assert ("k_fast_strips" in names) == bool(p["strips"]) and ("k_fast_cells" in names) == bool(p["fastCells"]), (B, names, p)
+        assert ex.fast_images_per_launch == B
+        assert p["histOct"] == (B <= 4) and p["fused"] and not p["gather"] and not p["multiWg"] and p["octForm"] == pkg.OCT_SINGLE, (B, p)
+        for b in range(B):
+            assert got[b][0].tobytes() == exp[b][0].tobytes() and got[b][1].tobytes() == exp[b][1].tobytes(), (B, b)
+    ex.close()
 
 
 def test_stereo_frame_view_equals_stereo_frame(pkg, oracle, synth):
@@ -928,6 +991,12 @@ def test_quadtree_shared_sweep_in_a_batch(pkg, oracle, synth):
             got = ex.extract_batch(imgs)
             for b in range(B):
                 assert got[b][0].tobytes() == exp[b][0].tobytes() and got[b][1].tobytes() == exp[b][1].tobytes(), (opts, rep, b)
+        p = ex.debug_last_plan()                 # the sweep really was shared: four workgroups on level 0 (>= 1600 cells), one on the coarsest
+        if (26, 1) in opts:
+            assert p["octForm"] == pkg.OCT_SINGLE and p["sweepSlices"] and p["sweepShared"] and p["nslice"][0] == 4 and p["nslice"][7] == 1, (opts, p)
+        else:
+            assert p["octForm"] == pkg.OCT_SINGLE and not p["sweepSlices"] and not p["sweepShared"] and not any(p["nslice"]), (opts, p)
+        assert p["wideOct"] == ((11, 1) not in opts) and p["fused"] and not p["histOct"], (opts, p)
         orc.extract(imgs[B - 1])
         for l in range(8):
             np.testing.assert_array_equal(ex.debug_level_points(l, 1, b=B - 1), _cands(orc.level_keypoints(l)), err_msg=str((opts, l)))
