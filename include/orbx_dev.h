@@ -91,6 +91,17 @@ int orbm_debug_stereo_path(int32_t *out);
 int orbx_debug_plan_chunk(const int32_t *in, int n_in, int32_t *out, int n_out);
 int orbx_debug_last_plan(const orbx_extractor_t *h, int32_t *out, int n_out);
 
+/* The per-thread scratch of the matchers as the CALLING host thread holds it, read only: no HIP call,
+ * nothing allocated, works without a GPU and on a thread that never called a matcher (capacities 0, devices -1).
+ *   out (ORBM_DEBUG_THREAD_SCRATCH_INTS): arena capacity in bytes, arena device (-1: none), arena call counter, 1 / 0 the arena has a
+ *        stream, 1 / 0 the arena has a completion word, staging-pair capacity, staging-pair device, BoW scratch capacity, BoW scratch
+ *        device
+ * n_out must be exactly that count.  The arena serves the fast path of the guided searches, the staging pair the exact kernels of the
+ * host-array entry points, the BoW scratch orbv_transform / orbm_search_by_bow / orbm_search_for_triangulation; capacities only grow
+ * until orbx_thread_release_scratch() returns all three to 0 / -1 (the call counter stays). */
+#define ORBM_DEBUG_THREAD_SCRATCH_INTS 9
+int orbm_debug_thread_scratch(int64_t *out, int n_out);
+
 #ifdef __cplusplus
 }
 #endif

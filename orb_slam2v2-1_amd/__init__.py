@@ -68,7 +68,10 @@ EXPORTS = [
 # what include/orbx_dev.h declares on top: exported by the developer build only
 DEV_EXPORTS = ["orbx_debug_level_points", "orbx_debug_sincosf", "orbx_debug_blur_patches", "orbm_debug_features_in_area",
                "orbx_debug_blurred_level", "orbx_debug_octree_fallbacks", "orbm_debug_match_path", "orbm_debug_resolve_plan",
-               "orbm_debug_stereo_path", "orbx_debug_plan_chunk", "orbx_debug_last_plan"]
+               "orbm_debug_stereo_path", "orbx_debug_plan_chunk", "orbx_debug_last_plan", "orbm_debug_thread_scratch"]
+# include/orbx_dev.h: the record orbm_debug_thread_scratch fills, field order
+THREAD_SCRATCH_FIELDS = ["arena_cap", "arena_device", "arena_seq", "arena_stream", "arena_word", "stage_cap", "stage_device", "bow_cap",
+                         "bow_device"]
 # include/orbx_dev.h: PlanInput / ChunkPlan of the launch rule as flat int32 arrays (orbx_debug_plan_chunk, orbx_debug_last_plan), field order
 PLAN_INPUT_FIELDS = ["B", "nl", "totalStrips", "stripLevels", "octBigMask", "lastChunks", "prof", "profFast", "skipPyr", "pfUsed", "evPyrDone",
                      "dbgBlur", "sliceScratch", "fastTileStride", "fastScoreStride", "sparseRecent"]   # + ncells[16] + opt[32]
@@ -340,6 +343,7 @@ def _load(path, dev):
         L.orbm_debug_stereo_path.argtypes = [vp]
         L.orbx_debug_plan_chunk.argtypes = [vp, i32, vp, i32]
         L.orbx_debug_last_plan.argtypes = [vp, vp, i32]
+        L.orbm_debug_thread_scratch.argtypes = [vp, i32]
     L.orbx_last_error.restype = C.c_char_p
     L.orbx_version.restype = C.c_char_p
     L._orbx_developer = bool(dev)
@@ -784,6 +788,14 @@ def debug_plan_chunk(ncells=(), opt=None, **fields):
     out = np.zeros(len(CHUNK_PLAN_FIELDS) + 16, np.int32)
     rc = lib(True).orbx_debug_plan_chunk(_p(a), len(a), _p(out), len(out))
     return rc, _plan_dict(out)
+
+
+def debug_thread_scratch():
+    """Test hook, no HIP call (works without a GPU): the calling thread's matcher scratch in the developer build -> dict of
+    THREAD_SCRATCH_FIELDS."""
+    out = np.zeros(len(THREAD_SCRATCH_FIELDS), np.int64)
+    _check(lib(True).orbm_debug_thread_scratch(_p(out), len(out)), lib(True))
+    return {k: int(v) for k, v in zip(THREAD_SCRATCH_FIELDS, out)}
 
 
 def debug_stereo_path():

@@ -163,6 +163,9 @@ void orbx_internal_release_bow_scratch() {
     if (g_bs.d) { hipSetDevice(g_bs.device); hipFree(g_bs.d); }
     g_bs.d = nullptr; g_bs.cap = 0; g_bs.device = -1;
 }
+#ifdef ORBX_DEVELOPER
+void orbx_internal_bow_scratch_info(int64_t *out2) { out2[0] = (int64_t)g_bs.cap; out2[1] = g_bs.device; }
+#endif
 #define ALN(x) (((x) + 255) & ~(size_t)255)
 
 extern "C" int orbv_transform(const orbv_vocabulary_t *v, const uint8_t *desc, int n, int levelsup, int32_t *word_id,

@@ -42,6 +42,16 @@ extern "C" int orbx_thread_release_scratch(void) {
     orbx_internal_release_bow_scratch();
     return ORBX_OK;
 }
+#ifdef ORBX_DEVELOPER
+// include/orbx_dev.h: the calling thread's three scratch records, read only (no HIP call, nothing allocated)
+extern "C" int orbm_debug_thread_scratch(int64_t *out, int n_out) {
+    if (!out || n_out != ORBM_DEBUG_THREAD_SCRATCH_INTS) { orbx_set_error("orbm_debug_thread_scratch: bad arguments"); return ORBX_ERR_ARG; }
+    orbx_internal_arena_info(out);
+    orbx_internal_match_scratch_info(out + 5);
+    orbx_internal_bow_scratch_info(out + 7);
+    return ORBX_OK;
+}
+#endif
 
 // Per-handle options (include/orbx.h): which of several kernels / launch arrangements with identical results the handle uses.
 // There is no process-global switch.  Keys 0, 1, 7 stop a kernel after phase n (ablation timing; outputs incomplete) and exist only

@@ -680,6 +680,9 @@ struct StagePlan {
 template <typename T> static inline T *stage_dev(size_t o) { return (T *)(g_sp.d + o); }
 static inline void stage_put(size_t o, const void *src, size_t bytes) { if (bytes) memcpy(g_sp.h + o, src, bytes); }
 void orbx_internal_release_match_scratch() { stage_release(); }
+#ifdef ORBX_DEVELOPER
+void orbx_internal_match_scratch_info(int64_t *out2) { out2[0] = (int64_t)g_sp.cap; out2[1] = g_sp.device; }
+#endif
 
 extern "C" int orbm_stereo(orbx_extractor_t *hl, orbx_extractor_t *hr, const orbx_keypoint_t *kl,
                            const uint8_t *dl, int nl, const orbx_keypoint_t *kr, const uint8_t *dr, int nr,

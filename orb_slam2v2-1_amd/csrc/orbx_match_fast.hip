@@ -1004,6 +1004,11 @@ void orbx_internal_release_arena() {
     g_ar.hflag = nullptr; g_ar.dflag = nullptr;
     g_ar.base = nullptr; g_ar.hbase = nullptr; g_ar.hdev = nullptr; g_ar.cap = 0; g_ar.device = -1;
 }
+#ifdef ORBX_DEVELOPER
+void orbx_internal_arena_info(int64_t *out5) {
+    out5[0] = (int64_t)g_ar.cap; out5[1] = g_ar.device; out5[2] = g_ar.seq; out5[3] = g_ar.st ? 1 : 0; out5[4] = g_ar.hflag ? 1 : 0;
+}
+#endif
 template <typename T> static T *arena_get(size_t count) {
     const size_t bytes = (count * sizeof(T) + 255) & ~(size_t)255;
     T *p = (T *)(g_ar.base + g_ar.off);

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <set>
 #include <string>
+#include <thread>
 #include <vector>
 #include "ORBextractor.h"
 #include "ORBmatcher.h"
@@ -236,34 +237,47 @@ static int distinct_mode(int argc, char **argv) {
     return n < 0 ? 5 : 0;
 }
 
-static int local_mode(int argc, char **argv) {
+// ---- local / bow / tri: each mode is read_*() (the files, once), run_*() (the body: inputs -> outputs) and write_*() (the dump and
+// the line on stdout), so that the `threads` mode can run the bodies over and over from three threads.
+struct LocalIn { int w, h, nf; float cam[5], th; std::vector<unsigned char> img, praw, draw, aux; };
+struct LocalOut {
+    int status, n, ret, nToMatch; std::vector<int> res;
+    bool operator==(const LocalOut &o) const { return status == o.status && n == o.n && ret == o.ret && nToMatch == o.nToMatch && res == o.res; }
+};
+static bool read_local(int argc, char **argv, LocalIn &in, std::string &out) {
     // argv: local img w h nf fx,fy,cx,cy,mbf pts.bin(Mp3d[m]) pdesc.bin aux.bin th out
     // aux: Tcw[16] f32; uright[n] f32; holder[n] i32 (-1 / -2 / list index); ext_obs[n] i32; obs[m] i32; seen[m] i32
-    if (argc != 12) return 2;
-    const int w = atoi(argv[3]), h = atoi(argv[4]), nf = atoi(argv[5]);
-    float cam[5];
-    sscanf(argv[6], "%f,%f,%f,%f,%f", &cam[0], &cam[1], &cam[2], &cam[3], &cam[4]);
-    std::vector<unsigned char> img = slurp(argv[2]), praw = slurp(argv[7]), draw = slurp(argv[8]), aux = slurp(argv[9]);
-    const float th = (float)atof(argv[10]);
-    const std::string out = argv[11];
-    ORBextractor ex(nf, 1.2f, 8, 20, 7);
-    if (!ex.ok()) return 3;
+    if (argc != 12) return false;
+    in.w = atoi(argv[3]); in.h = atoi(argv[4]); in.nf = atoi(argv[5]);
+    sscanf(argv[6], "%f,%f,%f,%f,%f", &in.cam[0], &in.cam[1], &in.cam[2], &in.cam[3], &in.cam[4]);
+    in.img = slurp(argv[2]); in.praw = slurp(argv[7]); in.draw = slurp(argv[8]); in.aux = slurp(argv[9]);
+    in.th = (float)atof(argv[10]);
+    out = argv[11];
+    return true;
+}
+static LocalOut run_local(const LocalIn &in) {
+    LocalOut o; o.status = 0; o.n = o.ret = o.nToMatch = 0;
+    const int w = in.w, h = in.h;
+    const float *cam = in.cam;
+    std::vector<unsigned char> img = in.img;             // (cv::Mat takes a non-const pointer)
+    ORBextractor ex(in.nf, 1.2f, 8, 20, 7);
+    if (!ex.ok()) { o.status = 3; return o; }
     Frame F;
     fill_frame(F, &ex, cv::Mat(h, w, CV_8UC1, img.data()), w, h);
     Frame::fx = cam[0]; Frame::fy = cam[1]; Frame::cx = cam[2]; Frame::cy = cam[3];
     F.mbf = cam[4]; F.mb = F.mbf / Frame::fx;
     F.mnScaleLevels = ex.GetLevels(); F.mfScaleFactor = ex.GetScaleFactor(); F.mfLogScaleFactor = log(F.mfScaleFactor);
     F.mnId = 7;
-    const int n = F.N, m = (int)(praw.size() / sizeof(Mp3d));
-    if (aux.size() != 64 + 4 * (size_t)(3 * n + 2 * m)) { fprintf(stderr, "aux size: n=%d m=%d\n", n, m); return 6; }
-    const float *fa = (const float *)aux.data();
+    const int n = F.N, m = (int)(in.praw.size() / sizeof(Mp3d));
+    if (in.aux.size() != 64 + 4 * (size_t)(3 * n + 2 * m)) { fprintf(stderr, "aux size: n=%d m=%d\n", n, m); o.status = 6; return o; }
+    const float *fa = (const float *)in.aux.data();
     F.mTcw = mat4(fa);
     const float *ur = fa + 16;
     const int *holder = (const int *)(ur + n), *eobs = holder + n, *obs = eobs + n, *seen = obs + m;
     for (int j = 0; j < n; j++) F.mvuRight[j] = ur[j];
-    const Mp3d *mp = (const Mp3d *)praw.data();
+    const Mp3d *mp = (const Mp3d *)in.praw.data();
     std::vector<MapPoint> pts, ext(n);
-    fill_points(pts, mp, draw.data(), m);
+    fill_points(pts, mp, in.draw.data(), m);
     std::vector<MapPoint *> vp(m);
     for (int i = 0; i < m; i++) {
         vp[i] = &pts[i];
@@ -276,28 +290,51 @@ static int local_mode(int argc, char **argv) {
         if (holder[j] >= 0) F.mvpMapPoints[j] = &pts[holder[j]];
         else if (holder[j] == -2) { F.mvpMapPoints[j] = &ext[j]; ext[j].nObs = eobs[j]; }
     }
-    int nToMatch = 0;
-    const int ret = SearchLocalPointsHIP(F, vp, th, 0.8f, nToMatch);
-    std::vector<int> res;
+    o.ret = SearchLocalPointsHIP(F, vp, in.th, 0.8f, o.nToMatch);
+    o.n = n;
     for (int j = 0; j < n; j++) {
         MapPoint *p = F.mvpMapPoints[j];
-        res.push_back(!p ? -1 : (p >= &pts[0] && p < &pts[0] + m) ? (int)(p - &pts[0]) : -2);
+        o.res.push_back(!p ? -1 : (p >= &pts[0] && p < &pts[0] + m) ? (int)(p - &pts[0]) : -2);
     }
-    for (int i = 0; i < m; i++) res.push_back(pts[i].mnVisible);
-    dump(out + ".i32", res.data(), res.size() * 4);
-    printf("%d %d %d\n", n, ret, nToMatch);
+    for (int i = 0; i < m; i++) o.res.push_back(pts[i].mnVisible);
+    return o;
+}
+static int write_local(const LocalOut &o, const std::string &out, const char *prefix) {
+    if (o.status) return o.status;
+    dump(out + ".i32", o.res.data(), o.res.size() * 4);
+    printf("%s%d %d %d\n", prefix, o.n, o.ret, o.nToMatch);
     return 0;
 }
+static int local_mode(int argc, char **argv) {
+    LocalIn in; std::string out;
+    if (!read_local(argc, argv, in, out)) return 2;
+    return write_local(run_local(in), out, "");
+}
 
-static int bow_mode(int argc, char **argv) {
+struct BowIn { std::string voc; float ratio; std::vector<unsigned char> d1, a1, v1, d2, a2, v2; };
+struct BowOut {
+    int status, n1, n2, nA, nB; std::vector<double> bow; std::vector<int> fv, res;
+    bool operator==(const BowOut &o) const {
+        return status == o.status && n1 == o.n1 && n2 == o.n2 && nA == o.nA && nB == o.nB && bow.size() == o.bow.size() &&
+               (bow.empty() || !memcmp(bow.data(), o.bow.data(), bow.size() * 8)) && fv == o.fv && res == o.res;
+    }
+};
+static bool read_bow(int argc, char **argv, BowIn &in, std::string &out) {
     // argv: bow voc.txt d1.bin(u8[n1][32]) a1.bin(f32[n1]) v1.bin(u8[n1]: 0 no point, 1 good, 2 bad) d2.bin a2.bin v2.bin ratio out
     // KeyFrame 1 = (d1, a1, v1); Frame / KeyFrame 2 = (d2, a2, v2).  Writes BowVec / FeatVec of both and the two SearchByBoW results.
-    if (argc != 11) return 2;
+    if (argc != 11) return false;
+    in.voc = argv[2];
+    in.d1 = slurp(argv[3]); in.a1 = slurp(argv[4]); in.v1 = slurp(argv[5]); in.d2 = slurp(argv[6]); in.a2 = slurp(argv[7]); in.v2 = slurp(argv[8]);
+    in.ratio = (float)atof(argv[9]);
+    out = argv[10];
+    return true;
+}
+static BowOut run_bow(const BowIn &in) {
+    BowOut o; o.status = 0; o.n1 = o.n2 = o.nA = o.nB = 0;
     ORBVocabulary voc;
-    if (!voc.loadFromTextFile(argv[2])) return 3;
-    std::vector<unsigned char> d1 = slurp(argv[3]), a1 = slurp(argv[4]), v1 = slurp(argv[5]), d2 = slurp(argv[6]), a2 = slurp(argv[7]), v2 = slurp(argv[8]);
-    const float ratio = (float)atof(argv[9]);
-    const std::string out = argv[10];
+    if (!voc.loadFromTextFile(in.voc)) { o.status = 3; return o; }
+    std::vector<unsigned char> d1 = in.d1, d2 = in.d2;
+    const std::vector<unsigned char> &a1 = in.a1, &v1 = in.v1, &a2 = in.a2, &v2 = in.v2;
     const int n1 = (int)v1.size(), n2 = (int)v2.size();
     KeyFrame K1, K2;
     Frame F;
@@ -311,41 +348,59 @@ static int bow_mode(int argc, char **argv) {
     for (int i = 0; i < n1; i++) { K1.mvKeysUn[i].angle = ((const float *)a1.data())[i]; if (v1[i]) { K1.mvpMapPoints[i] = &p1[i]; p1[i].mbBad = v1[i] == 2; } }
     for (int i = 0; i < n2; i++) { K2.mvKeysUn[i].angle = F.mvKeys[i].angle = ((const float *)a2.data())[i]; if (v2[i]) { K2.mvpMapPoints[i] = &p2[i]; p2[i].mbBad = v2[i] == 2; } }
     K1.ComputeBoW(); K2.ComputeBoW(); F.ComputeBoW();
-    {   // BowVec (word, value) pairs and FeatVec (node, count, items...) of keyframe 1
-        std::vector<double> bow;
-        for (DBoW2::BowVector::const_iterator it = K1.mBowVec.begin(); it != K1.mBowVec.end(); ++it) { bow.push_back((double)it->first); bow.push_back(it->second); }
-        dump(out + ".bow", bow.data(), bow.size() * 8);
-        std::vector<int> fv;
-        for (DBoW2::FeatureVector::const_iterator it = K1.mFeatVec.begin(); it != K1.mFeatVec.end(); ++it) {
-            fv.push_back((int)it->first); fv.push_back((int)it->second.size());
-            for (size_t j = 0; j < it->second.size(); j++) fv.push_back((int)it->second[j]);
-        }
-        dump(out + ".fv", fv.data(), fv.size() * 4);
+    // BowVec (word, value) pairs and FeatVec (node, count, items...) of keyframe 1
+    for (DBoW2::BowVector::const_iterator it = K1.mBowVec.begin(); it != K1.mBowVec.end(); ++it) { o.bow.push_back((double)it->first); o.bow.push_back(it->second); }
+    for (DBoW2::FeatureVector::const_iterator it = K1.mFeatVec.begin(); it != K1.mFeatVec.end(); ++it) {
+        o.fv.push_back((int)it->first); o.fv.push_back((int)it->second.size());
+        for (size_t j = 0; j < it->second.size(); j++) o.fv.push_back((int)it->second[j]);
     }
-    ORBmatcher matcher(ratio, true);
+    ORBmatcher matcher(in.ratio, true);
     std::vector<MapPoint *> mF, m12;
-    const int nA = matcher.SearchByBoW(&K1, F, mF);
-    const int nB = matcher.SearchByBoW(&K1, &K2, m12);
-    std::vector<int> res;
-    for (int i = 0; i < n2; i++) res.push_back(mF[i] ? (int)(mF[i] - &p1[0]) : -1);       // F feature -> KF1 point
-    for (int i = 0; i < n1; i++) res.push_back(m12[i] ? (int)(m12[i] - &p2[0]) : -1);     // KF1 feature -> KF2 point
-    dump(out + ".i32", res.data(), res.size() * 4);
-    printf("%d %d %d %d\n", n1, n2, nA, nB);
+    o.nA = matcher.SearchByBoW(&K1, F, mF);
+    o.nB = matcher.SearchByBoW(&K1, &K2, m12);
+    for (int i = 0; i < n2; i++) o.res.push_back(mF[i] ? (int)(mF[i] - &p1[0]) : -1);       // F feature -> KF1 point
+    for (int i = 0; i < n1; i++) o.res.push_back(m12[i] ? (int)(m12[i] - &p2[0]) : -1);     // KF1 feature -> KF2 point
+    o.n1 = n1; o.n2 = n2;
+    return o;
+}
+static int write_bow(const BowOut &o, const std::string &out, const char *prefix) {
+    if (o.status) return o.status;
+    dump(out + ".bow", o.bow.data(), o.bow.size() * 8);
+    dump(out + ".fv", o.fv.data(), o.fv.size() * 4);
+    dump(out + ".i32", o.res.data(), o.res.size() * 4);
+    printf("%s%d %d %d %d\n", prefix, o.n1, o.n2, o.nA, o.nB);
     return 0;
 }
+static int bow_mode(int argc, char **argv) {
+    BowIn in; std::string out;
+    if (!read_bow(argc, argv, in, out)) return 2;
+    return write_bow(run_bow(in), out, "");
+}
 
-static int tri_mode(int argc, char **argv) {
+struct TriIn { std::string voc; bool onlyStereo; std::vector<unsigned char> d1, k1, m1, u1, d2, k2, m2, u2, aux; };
+struct TriOut {
+    int status, n1, n2, n; std::vector<int> res;
+    bool operator==(const TriOut &o) const { return status == o.status && n1 == o.n1 && n2 == o.n2 && n == o.n && res == o.res; }
+};
+static bool read_tri(int argc, char **argv, TriIn &in, std::string &out) {
     // argv: tri voc.txt d1.bin k1.bin(orbx_keypoint_t[n1]) m1.bin(u8 has map point) ur1.bin(f32) d2.bin k2.bin m2.bin ur2.bin aux.bin onlyStereo out
     // aux: F12[9], T1w[16], T2w[16], fx, fy, cx, cy (f32)
-    if (argc != 14) return 2;
+    if (argc != 14) return false;
+    in.voc = argv[2];
+    in.d1 = slurp(argv[3]); in.k1 = slurp(argv[4]); in.m1 = slurp(argv[5]); in.u1 = slurp(argv[6]); in.d2 = slurp(argv[7]);
+    in.k2 = slurp(argv[8]); in.m2 = slurp(argv[9]); in.u2 = slurp(argv[10]); in.aux = slurp(argv[11]);
+    in.onlyStereo = atoi(argv[12]) != 0;
+    out = argv[13];
+    return true;
+}
+static TriOut run_tri(const TriIn &in) {
+    TriOut o; o.status = 0; o.n1 = o.n2 = o.n = 0;
     ORBVocabulary voc;
-    if (!voc.loadFromTextFile(argv[2])) return 3;
-    std::vector<unsigned char> d1 = slurp(argv[3]), k1 = slurp(argv[4]), m1 = slurp(argv[5]), u1 = slurp(argv[6]), d2 = slurp(argv[7]),
-                               k2 = slurp(argv[8]), m2 = slurp(argv[9]), u2 = slurp(argv[10]), aux = slurp(argv[11]);
-    const bool onlyStereo = atoi(argv[12]) != 0;
-    const std::string out = argv[13];
+    if (!voc.loadFromTextFile(in.voc)) { o.status = 3; return o; }
+    std::vector<unsigned char> d1 = in.d1, d2 = in.d2;
+    const std::vector<unsigned char> &k1 = in.k1, &m1 = in.m1, &u1 = in.u1, &k2 = in.k2, &m2 = in.m2, &u2 = in.u2;
     const int n1 = (int)m1.size(), n2 = (int)m2.size();
-    const float *fa = (const float *)aux.data();
+    const float *fa = (const float *)in.aux.data();
     KeyFrame K[2];
     std::vector<MapPoint> pts(n1 + n2);
     for (int s = 0; s < 2; s++) {
@@ -371,12 +426,57 @@ static int tri_mode(int argc, char **argv) {
     for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) F12.at<float>(r, c) = fa[r * 3 + c];
     ORBmatcher matcher(0.6f, false);   // src/LocalMapping.cc:223
     std::vector<std::pair<size_t, size_t> > pairs;
-    const int n = matcher.SearchForTriangulation(&K[0], &K[1], F12, pairs, onlyStereo);
-    std::vector<int> res;
-    for (size_t i = 0; i < pairs.size(); i++) { res.push_back((int)pairs[i].first); res.push_back((int)pairs[i].second); }
-    dump(out + ".i32", res.data(), res.size() * 4);
-    printf("%d %d %d\n", n1, n2, n);
+    o.n = matcher.SearchForTriangulation(&K[0], &K[1], F12, pairs, in.onlyStereo);
+    for (size_t i = 0; i < pairs.size(); i++) { o.res.push_back((int)pairs[i].first); o.res.push_back((int)pairs[i].second); }
+    o.n1 = n1; o.n2 = n2;
+    return o;
+}
+static int write_tri(const TriOut &o, const std::string &out, const char *prefix) {
+    if (o.status) return o.status;
+    dump(out + ".i32", o.res.data(), o.res.size() * 4);
+    printf("%s%d %d %d\n", prefix, o.n1, o.n2, o.n);
     return 0;
+}
+static int tri_mode(int argc, char **argv) {
+    TriIn in; std::string out;
+    if (!read_tri(argc, argv, in, out)) return 2;
+    return write_tri(run_tri(in), out, "");
+}
+
+// ---- threads: the three bodies above from three std::threads at once, as Tracking (SearchLocalPoints), LocalMapping
+// (SearchForTriangulation) and LoopClosing (SearchByBoW) call the classes: `iters` runs each, every result compared with the
+// thread's first, which is dumped as the single-threaded mode dumps it; each thread ends with orbx_thread_release_scratch().
+template <typename In, typename Out>
+static void loop_body(const char *name, Out (*run)(const In &), const In *in, int iters, Out *first, int *status) {
+    *status = 0;
+    for (int it = 0; it < iters && !*status; it++) {
+        Out o = run(*in);
+        if (o.status) { fprintf(stderr, "threads: thread %s, iteration %d: status %d\n", name, it, o.status); *status = o.status; }
+        else if (it == 0) *first = o;
+        else if (!(o == *first)) { fprintf(stderr, "threads: thread %s, iteration %d: the result differs from iteration 0\n", name, it); *status = 7; }
+    }
+    if (orbx_thread_release_scratch() != ORBX_OK) { fprintf(stderr, "threads: thread %s: orbx_thread_release_scratch failed\n", name); if (!*status) *status = 8; }
+}
+static int threads_mode(int argc, char **argv) {
+    // argv: threads iters local <local's arguments> tri <tri's arguments> bow <bow's arguments>
+    if (argc != 3 + 11 + 13 + 10) return 2;
+    const int iters = atoi(argv[2]);
+    char **al = argv + 2, **at = al + 11, **ab = at + 13;     // each mode reads its arguments from index 2 on
+    if (iters < 1 || std::string(al[1]) != "local" || std::string(at[1]) != "tri" || std::string(ab[1]) != "bow") return 2;
+    LocalIn li; TriIn ti; BowIn bi;
+    std::string lo, to, bo;
+    if (!read_local(12, al, li, lo) || !read_tri(14, at, ti, to) || !read_bow(11, ab, bi, bo)) return 2;
+    LocalOut l0; TriOut t0; BowOut b0;
+    int ls = 0, ts = 0, bs = 0;
+    std::thread tl(loop_body<LocalIn, LocalOut>, "local", run_local, &li, iters, &l0, &ls);
+    std::thread tt(loop_body<TriIn, TriOut>, "tri", run_tri, &ti, iters, &t0, &ts);
+    std::thread tb(loop_body<BowIn, BowOut>, "bow", run_bow, &bi, iters, &b0, &bs);
+    tl.join(); tt.join(); tb.join();
+    if (ls || ts || bs) return ls ? ls : ts ? ts : bs;
+    int rc = write_local(l0, lo, "local ");
+    if (!rc) rc = write_tri(t0, to, "tri ");
+    if (!rc) rc = write_bow(b0, bo, "bow ");
+    return rc;
 }
 
 int main(int argc, char **argv) {
@@ -388,6 +488,7 @@ int main(int argc, char **argv) {
     if (mode == "local") return local_mode(argc, argv);
     if (mode == "bow") return bow_mode(argc, argv);
     if (mode == "tri") return tri_mode(argc, argv);
+    if (mode == "threads") return threads_mode(argc, argv);
     if (mode == "extract" && argc == 7) {
         const int w = atoi(argv[3]), h = atoi(argv[4]), nf = atoi(argv[5]);
         const std::string out = argv[6];
@@ -544,6 +645,6 @@ int main(int argc, char **argv) {
         printf("%d %d\n", F.N, n);
         return 0;
     }
-    fprintf(stderr, "usage: host_driver extract|stereo|init|projmp|projkf|kf|sim3 ...\n");
+    fprintf(stderr, "usage: host_driver extract|stereo|init|projmp|projkf|kf|sim3|local|bow|tri|threads ...\n");
     return 2;
 }

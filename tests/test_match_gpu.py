@@ -3,13 +3,10 @@ counts and Hamming distances; float outputs compared exactly — same float oper
 import numpy as np
 import pytest
 
+# the scene builders live in tests/match_cases.py: the threaded worker (tests/match_threads_worker.py) replays the same scenes
+from match_cases import features as _features, mappoints_from as _mappoints_from, kfside as _kfside, local_map as _local_map
+
 pytestmark = pytest.mark.gpu
-
-
-def _features(oracle, img, nf=1000):
-    orc = oracle.Extractor(nf, 1.2, 8, 20, 7)
-    k, d = orc.extract(img)
-    return orc, k, d
 
 
 def test_hamming_host(pkg, oracle):
@@ -107,22 +104,6 @@ def test_search_for_initialization(pkg, oracle, synth, matcher_path):
         assert gn == on
         np.testing.assert_array_equal(gm12, om12)
         np.testing.assert_array_equal(gprev, oprev)
-
-
-def _mappoints_from(oracle, k, d, rng, m):
-    idx = rng.choice(len(k), size=m, replace=len(k) < m)
-    mps = np.zeros(m, oracle.MP_DTYPE)
-    mps["in_view"] = rng.random(m) > 0.1
-    mps["proj_x"] = k["x"][idx] + rng.normal(0, 1.5, m)
-    mps["proj_y"] = k["y"][idx] + rng.normal(0, 1.5, m)
-    mps["proj_xr"] = mps["proj_x"] - rng.uniform(1, 30, m)
-    mps["level"] = np.clip(k["octave"][idx] + rng.integers(-1, 2, m), 0, 7)
-    mps["view_cos"] = rng.uniform(0.99, 1.0, m)
-    mps["observations"] = rng.integers(0, 4, m)
-    md = d[idx].copy()
-    flip = rng.integers(0, 256, md.shape, dtype=np.uint8) & rng.integers(0, 256, md.shape, dtype=np.uint8) & \
-        rng.integers(0, 256, md.shape, dtype=np.uint8) & rng.integers(0, 256, md.shape, dtype=np.uint8)
-    return mps, md ^ flip
 
 
 def test_search_by_projection_mappoints(pkg, oracle, synth, matcher_path):
@@ -302,16 +283,6 @@ def test_match_windows_generic_paths_agree(pkg, oracle, synth, matcher_path):
 
 
 # ---- SURVEY §8(f) rank 1, KeyFrame side: SearchByProjection(KeyFrame*, Scw), Fuse x2, SearchBySim3
-def _kfside(oracle, synth, seed, distorted, m=1800):
-    import kf_scene as ks
-    w, h = 1241, 376
-    rng = np.random.default_rng(seed)
-    _, k, d = _features(oracle, synth.frame(w, h, 30 + seed), 1000)
-    sf = oracle.Extractor(1000, 1.2, 8, 20, 7).scale_factors
-    cam = oracle.Cam(ks.FX, ks.FY, ks.CX, ks.CY, ks.MBF, np.float32(ks.MBF) / np.float32(ks.FX))
-    return ks, w, h, rng, k, d, sf, cam, np.float32(np.log(np.float32(1.2))), m
-
-
 @pytest.mark.parametrize("distorted", [False, True])
 @pytest.mark.parametrize("gate", [False, True])
 def test_best_in_windows(pkg, oracle, synth, distorted, gate):
@@ -389,31 +360,6 @@ def test_distinctive_descriptors(pkg, oracle):
 
 
 # ---- Frame::isInFrustum on the device, alone and fused with SearchByProjection(F, MPs)
-def _local_map(pkg, oracle, synth, seed, m=3000):
-    ks, w, h, rng, k, d, sf, cam, log_sf, _ = _kfside(oracle, synth, seed, False, m)
-    T = ks.pose(rng)
-    pts3, pd, idx = ks.points_for(oracle, rng, k, d, sf, T, m, bits=3)
-    pts3["valid"] = rng.random(m) > 0.1
-    # level boundaries: make max_distance/dist land within a few ulps of sf^k for part of the points
-    R, t = T[:3, :3].astype(np.float64), T[:3, 3].astype(np.float64)
-    Ow = (-R.T @ t).astype(np.float32)
-    dist = np.sqrt(((np.stack([pts3["wx"], pts3["wy"], pts3["wz"]], 1) - Ow).astype(np.float64) ** 2).sum(1)).astype(np.float32)
-    edge = rng.random(m) < 0.3
-    kk = rng.integers(0, 8, m)
-    ulp = rng.integers(-3, 4, m)
-    target = (np.float32(1.2) ** kk).astype(np.float32)
-    md = (dist * target).astype(np.float32)
-    md = (md.view(np.int32) + ulp.astype(np.int32)).view(np.float32)
-    pts3["max_distance"] = np.where(edge, md, pts3["max_distance"])
-    pts3["min_distance"] = np.where(edge, md * np.float32(0.1), pts3["min_distance"])
-    obs = rng.integers(0, 6, m).astype(np.int32)
-    wp = np.zeros(m, pkg.WORLDPOINT_DTYPE)
-    for f in ("valid", "wx", "wy", "wz", "nx", "ny", "nz", "max_distance", "min_distance"):
-        wp[f] = pts3[f]
-    wp["observations"] = obs
-    return ks, w, h, rng, k, d, sf, cam, log_sf, T, pts3, wp, pd, obs
-
-
 def test_is_in_frustum(pkg, oracle, synth):
     """orbm_is_in_frustum vs Frame::isInFrustum (src/Frame.cc:284-340) restated with the C library's logf: every
     field identical, including the predicted level of points sitting within 3 ulps of a level boundary."""

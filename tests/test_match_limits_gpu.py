@@ -10,6 +10,9 @@ descriptors), kept inside the domain src/Frame.cc defines."""
 import numpy as np
 import pytest
 
+# the builders live in tests/match_cases.py: the threaded worker (tests/match_threads_worker.py) builds its regrow cases with them
+from match_cases import (limits_frame, flips as _flips, kps as _kps, cluster as _cluster, init_inputs, cand_cap_init_inputs)
+
 pytestmark = pytest.mark.gpu
 
 W, H = 1920, 1080
@@ -34,32 +37,7 @@ def dev_matchers(pkg, hooks):
 @pytest.fixture(scope="module")
 def frame(oracle, synth):
     """One 1920x1080 / 4000-feature extraction (the oracle's: bit-identical to the HIP extractor, tested elsewhere)."""
-    orc = oracle.Extractor(4000, 1.2, 8, 20, 7)
-    k, d = orc.extract(synth.frame(W, H, 51))
-    assert len(k) > 3000
-    return k, d, orc.scale_factors
-
-
-def _flips(rng, shape, ands=4):
-    f = rng.integers(0, 256, shape, dtype=np.uint8)
-    for _ in range(ands - 1):
-        f &= rng.integers(0, 256, shape, dtype=np.uint8)
-    return f
-
-
-def _kps(frame, n, rng):
-    """n keypoints: the extracted ones first, then jittered replicas (descriptors with sparse bit flips); the jitter stays inside the
-    extracted keypoints' bounding box, which lies inside every level's border margin."""
-    k, d, _ = frame
-    idx = np.arange(n) % len(k)
-    kk, dd = k[idx].copy(), d[idx].copy()
-    rep = np.arange(n) >= len(k)
-    r = int(rep.sum())
-    if r:
-        kk["x"][rep] = np.clip(kk["x"][rep] + rng.normal(0, 1.0, r), k["x"].min(), k["x"].max()).astype(np.float32)
-        kk["y"][rep] = np.clip(kk["y"][rep] + rng.normal(0, 1.0, r), k["y"].min(), k["y"].max()).astype(np.float32)
-        dd[rep] ^= _flips(rng, (r, 32))
-    return kk, dd
+    return limits_frame(oracle, synth)
 
 
 def _path(pkg):
@@ -410,18 +388,6 @@ def _outside(k, d, cx, cy, half):
     return k[keep], d[keep]
 
 
-def _cluster(frame, count, rng, cx=900.0, cy=500.0, half=6.0):
-    """count keypoints of octave 0 inside a square of half-width `half` around (cx, cy): one query window holds all of them."""
-    k, d, _ = frame
-    src = np.flatnonzero(k["octave"] == 0)
-    idx = src[np.arange(count) % len(src)]
-    kk, dd = k[idx].copy(), d[idx].copy()
-    kk["x"] = (cx + rng.uniform(-half, half, count)).astype(np.float32)
-    kk["y"] = (cy + rng.uniform(-half, half, count)).astype(np.float32)
-    dd ^= _flips(rng, (count, 32), 2)
-    return kk, dd
-
-
 @pytest.mark.parametrize("count", [CAND_CAP, CAND_CAP + 1])
 def test_cand_cap_windows(pkg, oracle, frame, count):
     """k_cand<false>: one query whose window holds exactly 512, then 513 eligible keypoints (513: the fast path reports the overflow
@@ -466,13 +432,7 @@ def test_cand_cap_windows(pkg, oracle, frame, count):
 def test_cand_cap_initialization(pkg, oracle, frame, count):
     """k_cand<true> (SearchForInitialization keeps the whole sorted list): one F1 keypoint whose window holds 512 / 513 F2
     keypoints."""
-    rng = np.random.default_rng(850 + count)
-    k2, d2 = _cluster(frame, count, rng)
-    k1, d1 = _kps(frame, 400, rng)
-    k1["octave"] = 0
-    k1["x"][0], k1["y"][0] = 900.0, 500.0
-    d1[0] = d2[5] ^ _flips(rng, 32, 2)
-    prev = np.stack([k1["x"], k1["y"]], 1).astype(np.float32)
+    k1, d1, k2, d2, prev = cand_cap_init_inputs(frame, count)
     on, om12, oprev = oracle.search_for_initialization(k1, d1, k2, d2, oracle.grid_geom(W, H), prev, 10, 0.9, True)
     gn, gm12, gprev = pkg.ORBmatcher(0.9, True).SearchForInitialization(k1, d1, k2, d2, pkg.grid_geom(W, H), prev, 10)
     assert gn == on
@@ -548,16 +508,7 @@ def test_ratio_test_ties(pkg, oracle, frame):
 # SearchForInitialization: n2 = 7000 / 7001
 
 def _init_case(pkg, oracle, frame, n1, n2, seed, window=30, contention=False):
-    rng = np.random.default_rng(seed)
-    k2, d2 = _kps(frame, n2, rng)
-    if contention:   # every F1 keypoint fights for the same few F2 keypoints
-        src = rng.choice(60, n1)
-        k1, d1 = k2[src].copy(), d2[src] ^ _flips(rng, (n1, 32), 3)
-    else:
-        k1, d1 = _kps(frame, n1, rng)
-    k1["octave"] = 0
-    k2["octave"] = 0
-    prev = np.stack([k1["x"], k1["y"]], 1).astype(np.float32) + rng.normal(0, 2, (n1, 2)).astype(np.float32)
+    k1, d1, k2, d2, prev = init_inputs(frame, n1, n2, seed, contention)
     on, om12, oprev = oracle.search_for_initialization(k1, d1, k2, d2, oracle.grid_geom(W, H), prev, window, 0.9, True)
     gn, gm12, gprev = pkg.ORBmatcher(0.9, True).SearchForInitialization(k1, d1, k2, d2, pkg.grid_geom(W, H), prev, window)
     assert gn == on, (gn, on, _path(pkg))
