@@ -744,6 +744,79 @@ int orbm_search_for_triangulation(const orbx_keypoint_t *kp1, const uint8_t *q_d
                                   const float *scale_factors, const float *level_sigma2, int nlevels, int max_dist,
                                   int check_orientation, int32_t *match_q, int *nmatches, int device);
 
+/* ---- the keyframe database: ORB_SLAM2::KeyFrameDatabase (src/KeyFrameDatabase.cc:31-309) over BoW vectors, and
+ * TemplatedVocabulary::score with L1Scoring (Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68), the only scoring built.
+ * A BoW vector is the content of a DBoW2::BowVector: n pairs (word id, value), ids strictly ascending.
+ * A keyframe is named by the caller's id, 0 .. ORBV_DB_MAX_KF_ID (the id -> slot table is an array; a larger id is
+ * ORBX_ERR_UNSUPPORTED, a negative one ORBX_ERR_ARG).  A query holds at most ORBV_DB_MAX_QUERY words (its ids are staged in
+ * the LDS of every workgroup; more is ORBX_ERR_UNSUPPORTED).  No inverted file is kept: a query is intersected with every
+ * keyframe of the database, one wavefront each, and the reference's list order - ascending (smallest common word,
+ * position in that word's list) - is rebuilt from a sequence number every add stamps (erase keeps the relative order of
+ * a list, so position = order of the add calls; a re-add after erase gets a new number).  Arguments are checked on the
+ * host before any HIP call.  A handle owns its memory (entry pool, growing by doubling; slot table; one pinned result
+ * buffer) and one stream; calls on one handle are serialised by a mutex inside it (the reference locks mMutex), different
+ * handles run concurrently.  The pool space and the slot of an erased keyframe are not reclaimed before orbv_db_clear.
+ * The reference's query stamps (mnLoopQuery == pKF->mnId, mnRelocQuery == F->mnId) are not modelled, so no call takes a
+ * query id: they misbehave only for a repeated query id and for id 0 against fresh keyframes, which DetectLoop (no query
+ * for the first ten keyframes) and Relocalization (frame 0 cannot relocalise) never produce. */
+#define ORBV_DB_MAX_KF_ID ((1 << 20) - 1)
+#define ORBV_DB_MAX_QUERY 8192
+#define ORBV_DB_MAX_COVISIBLE 10
+typedef struct orbv_db orbv_db_t;
+/* one LISTED keyframe of a query (lKFsSharingWords), in list order.  flags: bit 0 = scored (words > minCommonWords), bit 1 =
+ * entered lScoreAndMatch.  score: (float)score when scored; else 0 for a loop query and the keyframe's mRelocScore for a
+ * relocalisation query.  acc_score / best_kf: the covisibility accumulation, 0 / -1 without bit 1. */
+typedef struct {
+    int32_t kf_id, words;
+    uint32_t flags;
+    float score, acc_score;
+    int32_t best_kf;
+} orbv_db_hit_t;
+/* ORBVocabulary::score(v1, v2) = L1Scoring::score (ScoringObject.cpp:23-68) for a pair of vectors: over the common words in
+ * ascending id, s += fabs(vi - wi) - fabs(vi) - fabs(wi) one rounded double operation at a time, then -s / 2.0 (the
+ * lower_bound skips make the walk a merge).  Host code: no handle, no device.  Ids not strictly ascending: ORBX_ERR_ARG. */
+int orbv_score_l1(const uint32_t *w1, const double *v1, int n1, const uint32_t *w2, const double *v2, int n2, double *out);
+/* KeyFrameDatabase::KeyFrameDatabase (:33-37).  nwords = voc->size().  initial_entries: starting size of the entry pool in
+ * (id, value) pairs, 0 = the default (2^20).  No usable GPU: ORBX_ERR_NO_DEVICE; there is no CPU path. */
+int orbv_db_create(int nwords, int device, int initial_entries, orbv_db_t **out);
+void orbv_db_destroy(orbv_db_t *db);
+/* KeyFrameDatabase::add (:40-46).  n == 0 is legal (a keyframe no query can list).  Ids not strictly ascending or >= nwords,
+ * or a kf_id that is in the database: ORBX_ERR_ARG.  The keyframe starts with an empty covisible list and mRelocScore 0.0f
+ * (the reference leaves that member uninitialised, src/KeyFrame.cc:35: the value is this library's hypothesis). */
+int orbv_db_add(orbv_db_t *db, int kf_id, const uint32_t *words, const double *values, int n);
+/* KeyFrameDatabase::erase (:48-67); a kf_id that is not in the database: nothing happens, ORBX_OK.  With the keyframe go its
+ * covisible list and its mRelocScore. */
+int orbv_db_erase(orbv_db_t *db, int kf_id);
+/* KeyFrameDatabase::clear (:69-73) */
+int orbv_db_clear(orbv_db_t *db);
+/* What pKFi->GetBestCovisibilityKeyFrames(10) returns (:151, :265), as ids in that order: the caller's graph.  n > 10, a
+ * negative id, or a kf_id that is not in the database: ORBX_ERR_ARG.  An id the database does not hold at the time of a
+ * query is skipped by it (such a keyframe's stamps can never equal the query's). */
+int orbv_db_set_covisible(orbv_db_t *db, int kf_id, const int32_t *ids, int n);
+/* keyframes in the database, (id, value) pairs they hold, capacity of the pool in pairs, device memory of the handle in bytes;
+ * any pointer may be NULL */
+int orbv_db_info(const orbv_db_t *db, int *keyframes, int64_t *entries, int64_t *pool_entries, size_t *device_bytes);
+/* mpVoc->score(query, keyframe) as doubles for n keyframes of the database: the minScore loop of LoopClosing::DetectLoop
+ * (src/LoopClosing.cc:135-147).  A kf_id that is not in the database: ORBX_ERR_ARG. */
+int orbv_db_score(orbv_db_t *db, const uint32_t *qw, const double *qv, int nq, const int32_t *kf_ids, int n, double *scores);
+/* KeyFrameDatabase::DetectLoopCandidates (:76-197).  connected = pKF->GetConnectedKeyFrames() as ids (ids the database does
+ * not hold are ignored): they never enter the list.  maxCommonWords over the list, int minCommonWords = maxCommonWords*0.8f,
+ * a listed keyframe is scored iff words > minCommonWords, enters lScoreAndMatch iff (float)score >= min_score; per entry
+ * acc = best = si, then over its covisible list in order: a neighbour counts iff listed and scored by this query, acc += s2
+ * in float, s2 > best makes it the best keyframe; bestAccScore starts at min_score; retained iff acc > 0.75f*bestAccScore;
+ * cand = the best keyframes of the retained entries in list order, first occurrence only.  hits may be NULL.  A capacity too
+ * small: ORBX_ERR_ARG with the needed counts in *ncand / *nhits (nhits may be NULL).  Empty query or nothing listed: ORBX_OK,
+ * zero candidates. */
+int orbv_db_detect_loop(orbv_db_t *db, const uint32_t *qw, const double *qv, int nq, const int32_t *connected, int nconnected,
+                        float min_score, int32_t *cand, int cand_cap, int *ncand, orbv_db_hit_t *hits, int hit_cap, int *nhits);
+/* KeyFrameDatabase::DetectRelocalizationCandidates (:199-309): no connected set and no min_score (every scored keyframe
+ * enters lScoreAndMatch, bestAccScore starts at 0); a neighbour counts iff it is LISTED, and contributes its mRelocScore,
+ * which only a relocalisation query that scores the keyframe writes - for a listed neighbour this query did not score it is
+ * the value the last query that scored it left (0.0f if none did).  The scores are written before the capacities are
+ * checked; repeating the query with larger buffers writes the same values again. */
+int orbv_db_detect_reloc(orbv_db_t *db, const uint32_t *qw, const double *qv, int nq, int32_t *cand, int cand_cap, int *ncand,
+                         orbv_db_hit_t *hits, int hit_cap, int *nhits);
+
 /* The host-array matcher entry points keep grow-only device scratch, a pinned mirror and one non-blocking stream
  * PER HOST THREAD (re-entrant without locks: the reference calls matchers from Tracking, LocalMapping and LoopClosing
  * threads at once, src/LocalMapping.cc:223, src/LoopClosing.cc:249).  Nothing is freed implicitly; a thread calls

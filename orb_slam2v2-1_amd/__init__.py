@@ -40,6 +40,9 @@ CLOUD_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("b", "u1"), (
 OCTREE_LEAF_DTYPE = np.dtype([("kx", "<u2"), ("ky", "<u2"), ("kz", "<u2"), ("depth", "<u2")])
 # the reference's transform_trans * transform_rot_x * transform_rot_y (src/pointcloudmapping.cc:198-223): x' = z, y' = -x, z' = -y
 OCTOMAP_AXIS_SWAP = np.array([[0, 0, 1, 0], [-1, 0, 0, 0], [0, -1, 0, 0], [0, 0, 0, 1]], np.float32)
+# include/orbx.h: orbv_db_hit_t, one listed keyframe of a keyframe-database query (flags: bit 0 scored, bit 1 entered lScoreAndMatch)
+DB_HIT_DTYPE = np.dtype([("kf_id", "<i4"), ("words", "<i4"), ("flags", "<u4"), ("score", "<f4"), ("acc_score", "<f4"), ("best_kf", "<i4")])
+DB_MAX_KF_ID, DB_MAX_QUERY, DB_MAX_COVISIBLE = (1 << 20) - 1, 8192, 10
 
 ORBX_OK, ORBX_ERR_ARG, ORBX_ERR_NO_DEVICE, ORBX_ERR_HIP, ORBX_ERR_CAPACITY, ORBX_ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5
 NUM_STAGES = 5
@@ -64,6 +67,8 @@ EXPORTS = [
     "orbx_cloudmapper_create", "orbx_cloudmapper_destroy", "orbx_cloud_capacity", "orbx_cloud_generate_device",
     "orbx_cloud_voxel_device", "orbx_keyframe_cloud",
     "orbx_octree_device", "orbx_octomap_bt", "orbx_octomap_bytes_bound",
+    "orbv_score_l1", "orbv_db_create", "orbv_db_destroy", "orbv_db_add", "orbv_db_erase", "orbv_db_clear", "orbv_db_set_covisible",
+    "orbv_db_info", "orbv_db_score", "orbv_db_detect_loop", "orbv_db_detect_reloc",
 ]
 # what include/orbx_dev.h declares on top: exported by the developer build only
 DEV_EXPORTS = ["orbx_debug_level_points", "orbx_debug_sincosf", "orbx_debug_blur_patches", "orbm_debug_features_in_area",
@@ -323,6 +328,18 @@ def _load(path, dev):
     L.orbv_destroy.restype = None
     L.orbv_info.argtypes = [vp] + [C.POINTER(i32)] * 6
     L.orbv_transform.argtypes = [vp, vp, i32, i32, vp, vp, vp]
+    L.orbv_score_l1.argtypes = [vp, vp, i32, vp, vp, i32, vp]
+    L.orbv_db_create.argtypes = [i32, i32, i32, C.POINTER(vp)]
+    L.orbv_db_destroy.argtypes = [vp]
+    L.orbv_db_destroy.restype = None
+    L.orbv_db_add.argtypes = [vp, i32, vp, vp, i32]
+    L.orbv_db_erase.argtypes = [vp, i32]
+    L.orbv_db_clear.argtypes = [vp]
+    L.orbv_db_set_covisible.argtypes = [vp, i32, vp, i32]
+    L.orbv_db_info.argtypes = [vp, C.POINTER(i32), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(sz)]
+    L.orbv_db_score.argtypes = [vp, vp, vp, i32, vp, i32, vp]
+    L.orbv_db_detect_loop.argtypes = [vp, vp, vp, i32, vp, i32, f32, vp, i32, C.POINTER(i32), vp, i32, C.POINTER(i32)]
+    L.orbv_db_detect_reloc.argtypes = [vp, vp, vp, i32, vp, i32, C.POINTER(i32), vp, i32, C.POINTER(i32)]
     L.orbm_search_for_triangulation.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, f32, f32, vp, vp, i32, i32, i32, vp,
                                                 C.POINTER(i32), i32]
     L.orbm_search_by_bow.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, f32, i32, vp, C.POINTER(i32), i32]
@@ -1221,6 +1238,91 @@ class Vocabulary:
         w = np.zeros(n, np.int32); nid = np.zeros(n, np.int32); wt = np.zeros(n, np.float64)
         self._ck(self._L.orbv_transform(self._h, _p(d), n, int(levelsup), _p(w), _p(nid), _p(wt)))
         return w, nid, wt
+
+
+def _bow(words, values):
+    w = np.ascontiguousarray(words, np.uint32).reshape(-1); v = np.ascontiguousarray(values, np.float64).reshape(-1)
+    if len(w) != len(v):
+        raise ValueError("a BoW vector needs as many values as word ids")
+    return w, v
+
+
+def score_l1(words1, values1, words2, values2):
+    """orbv_score_l1: ORBVocabulary::score of two BoW vectors (L1Scoring), host code"""
+    w1, v1 = _bow(words1, values1); w2, v2 = _bow(words2, values2)
+    out = C.c_double(0)
+    L = lib()
+    _check(L.orbv_score_l1(_p(w1), _p(v1), len(w1), _p(w2), _p(v2), len(w2), C.byref(out)), L)
+    return out.value
+
+
+class KeyFrameDatabase:
+    """ORB_SLAM2::KeyFrameDatabase on the GPU (orbv_db_*): keyframes are the caller's ids, BoW vectors (word ids, values) arrays."""
+
+    def _ck(self, rc):
+        _check(rc, self._L)
+
+    def __init__(self, nwords, device=0, initial_entries=0):
+        self._L = lib()
+        h = C.c_void_p()
+        self._ck(self._L.orbv_db_create(int(nwords), int(device), int(initial_entries), C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._L.orbv_db_destroy(self._h)
+            self._h = None
+
+    def add(self, kf_id, words, values):
+        w, v = _bow(words, values)
+        self._ck(self._L.orbv_db_add(self._h, int(kf_id), _p(w), _p(v), len(w)))
+
+    def erase(self, kf_id):
+        self._ck(self._L.orbv_db_erase(self._h, int(kf_id)))
+
+    def clear(self):
+        self._ck(self._L.orbv_db_clear(self._h))
+
+    def set_covisible(self, kf_id, ids):
+        a = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        self._ck(self._L.orbv_db_set_covisible(self._h, int(kf_id), _p(a), len(a)))
+
+    def info(self):
+        k, e, p, b = C.c_int(0), C.c_int64(0), C.c_int64(0), C.c_size_t(0)
+        self._ck(self._L.orbv_db_info(self._h, C.byref(k), C.byref(e), C.byref(p), C.byref(b)))
+        return {"keyframes": k.value, "entries": e.value, "pool_entries": p.value, "device_bytes": b.value}
+
+    def score(self, words, values, kf_ids):
+        """orbv_db_score -> float64 score of the query against each listed keyframe"""
+        w, v = _bow(words, values)
+        ids = np.ascontiguousarray(kf_ids, np.int32).reshape(-1)
+        out = np.zeros(len(ids), np.float64)
+        self._ck(self._L.orbv_db_score(self._h, _p(w), _p(v), len(w), _p(ids), len(ids), _p(out)))
+        return out
+
+    def _detect(self, call, hits):
+        cap = hcap = max(16, self.info()["keyframes"])   # candidates and listed keyframes are keyframes of the database
+        for attempt in range(4):
+            cand = np.zeros(cap, np.int32); h = np.zeros(hcap, DB_HIT_DTYPE) if hits else None
+            nc, nh = C.c_int(0), C.c_int(0)
+            rc = call(_p(cand), cap, C.byref(nc), _p(h), hcap, C.byref(nh))
+            if rc == ORBX_ERR_ARG and (nc.value > cap or nh.value > hcap) and attempt < 3:   # keyframes added by another thread meanwhile
+                cap, hcap = max(cap, 2 * nc.value), max(hcap, 2 * nh.value)
+                continue
+            self._ck(rc)
+            break
+        return (cand[:nc.value].copy(), h[:nh.value].copy()) if hits else cand[:nc.value].copy()
+
+    def detect_loop_candidates(self, words, values, connected, min_score, hits=False):
+        """orbv_db_detect_loop -> candidate ids (and, with hits, the DB_HIT_DTYPE records of the listed keyframes in list order)"""
+        w, v = _bow(words, values)
+        c = np.ascontiguousarray(sorted(connected) if isinstance(connected, (set, frozenset)) else connected, np.int32).reshape(-1)
+        return self._detect(lambda *a: self._L.orbv_db_detect_loop(self._h, _p(w), _p(v), len(w), _p(c), len(c), float(min_score), *a), hits)
+
+    def detect_relocalization_candidates(self, words, values, hits=False):
+        """orbv_db_detect_reloc -> candidate ids (and, with hits, the records of the listed keyframes)"""
+        w, v = _bow(words, values)
+        return self._detect(lambda *a: self._L.orbv_db_detect_reloc(self._h, _p(w), _p(v), len(w), *a), hits)
 
 
 def search_by_bow(q_desc, q_angle, q_valid, c_desc, c_angle, c_valid, node_qstart, q_items, node_cstart, c_items, max_dist,

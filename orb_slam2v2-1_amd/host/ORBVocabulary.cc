@@ -3,6 +3,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <stdexcept>
 
 namespace ORB_SLAM2 {
 
@@ -54,6 +55,18 @@ void ORBVocabulary::transform(const std::vector<cv::Mat> &features, DBoW2::BowVe
             }
     }
     if (must) v.normalize(norm);
+}
+
+double ORBVocabulary::score(const DBoW2::BowVector &v1, const DBoW2::BowVector &v2) const {
+    if (m_scoring != DBoW2::L1_NORM) throw std::runtime_error("ORBVocabulary::score: only L1_NORM scoring is built");
+    std::vector<uint32_t> w1, w2;
+    std::vector<double> x1, x2;
+    for (DBoW2::BowVector::const_iterator it = v1.begin(); it != v1.end(); ++it) { w1.push_back(it->first); x1.push_back(it->second); }
+    for (DBoW2::BowVector::const_iterator it = v2.begin(); it != v2.end(); ++it) { w2.push_back(it->first); x2.push_back(it->second); }
+    double s = 0.0;
+    if (orbv_score_l1(w1.data(), x1.data(), (int)w1.size(), w2.data(), x2.data(), (int)w2.size(), &s) != ORBX_OK)
+        throw std::runtime_error(std::string("ORBVocabulary::score: ") + orbx_last_error());
+    return s;
 }
 
 }  // namespace ORB_SLAM2

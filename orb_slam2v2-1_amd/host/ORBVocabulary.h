@@ -66,6 +66,9 @@ public:
     unsigned int size() const { return (unsigned int)m_words; }
     // transform(features, v, fv, levelsup) (:1147-1214)
     void transform(const std::vector<cv::Mat> &features, DBoW2::BowVector &v, DBoW2::FeatureVector &fv, int levelsup) const;
+    // score(v1, v2) (:1211-1216) with L1Scoring (ScoringObject.cpp:23-68), the scoring ORBvoc.txt declares; host code over
+    // orbv_score_l1.  Throws std::runtime_error for a vocabulary of any other ScoringType (not built) or a malformed vector.
+    double score(const DBoW2::BowVector &v1, const DBoW2::BowVector &v2) const;
     orbv_vocabulary_t *handle() const { return mV; }
 private:
     ORBVocabulary(const ORBVocabulary &);
