@@ -817,6 +817,40 @@ int orbv_db_detect_loop(orbv_db_t *db, const uint32_t *qw, const double *qv, int
 int orbv_db_detect_reloc(orbv_db_t *db, const uint32_t *qw, const double *qv, int nq, int32_t *cand, int cand_cap, int *ncand,
                          orbv_db_hit_t *hits, int hit_cap, int *nhits);
 
+/* ---- Optimizer::PoseOptimization(Frame *) (src/Optimizer.cc:239-451): the pose-only optimisation between the tracking
+ * thread's two matcher calls (src/Tracking.cc:918, :1041, :1083, :1585-1616), on flat arrays.  One 6-DoF vertex, one unary
+ * reprojection edge per valid entry (monocular when ur < 0, else stereo), 4 rounds of <= 10 Levenberg-Marquardt iterations with
+ * the Huber kernel in the first three, classification by chi2 after every round; a restatement of the reference and the g2o
+ * classes it drives, double with the reference's float narrowings.  The whole schedule is ONE kernel
+ * launch, one workgroup per problem; two calls on the same input give the same bytes.  A singular normal matrix (fewer than
+ * 3 active edges in a later round, coincident points) is not pinned to the reference: the call terminates, returns ORBX_OK
+ * and its output is finite or unchanged.
+ *
+ * outlier[n] in/out = mvbOutlier: entries with valid == 0 keep the caller's value, the others get the last round's flag.
+ * *ngood = nInitialCorrespondences - nBad; fewer than 3 correspondences: *ngood = 0, Tcw_out = Tcw_in, the valid entries' flags
+ * cleared.  Tcw is the row-major float 4x4.  info (may be NULL): t / q the final estimate in double (q = x y z w),
+ * iterations[r] / trials[r] the LM iterations and linear solves of round r, rounds the number of rounds run.
+ * NULL pointers, n < 0, B < 0, offsets that start below 0 or decrease: ORBX_ERR_ARG, checked before the device is touched.
+ * No usable GPU: ORBX_ERR_NO_DEVICE; there is no CPU path.  Scratch, pinned mirror and stream are per host thread
+ * (orbx_thread_release_scratch). */
+typedef struct { int32_t valid; float u, v, ur; float inv_sigma2; float wx, wy, wz; } orbo_observation_t; /* 32 B; ur < 0: monocular */
+typedef struct { int32_t correspondences, bad; int32_t iterations[4], trials[4], rounds; double t[3], q[4]; } orbo_pose_info_t;
+int orbo_pose_optimization(const orbo_observation_t *obs, int n, const orbm_camera_t *cam, const float *Tcw_in16,
+                           float *Tcw_out16, uint8_t *outlier, int *ngood, orbo_pose_info_t *info /* may be NULL */, int device);
+/* B independent problems in one launch (Relocalization's candidate keyframes): offsets[B+1] into obs / outlier, cams[B],
+ * Tcw_in16 / Tcw_out16 [B][16], ngood[B], infos[B] (may be NULL).  Each problem's results are those of its single call. */
+int orbo_pose_optimization_batch(const orbo_observation_t *obs, const int32_t *offsets, int B, const orbm_camera_t *cams,
+                                 const float *Tcw_in16, float *Tcw_out16, uint8_t *outlier, int32_t *ngood,
+                                 orbo_pose_info_t *infos, int device);
+/* The frame left in HBM by extraction (see orbm_search_by_projection_frame_device): d_kun / d_uright are device arrays of n
+ * entries, the observation of entry i is (d_kun[i].x, d_kun[i].y, d_uright[i]) with inv_level_sigma2[d_kun[i].octave]
+ * (nlevels <= 16 host floats); only the 16-byte map-point records cross the bus.  Runs on `stream`; returns when the results
+ * are on the host.  Same results as orbo_pose_optimization on the downloaded arrays. */
+typedef struct { int32_t valid; float wx, wy, wz; } orbo_worldpos_t;
+int orbo_pose_optimization_device(const orbx_keypoint_t *d_kun, const float *d_uright, int n, const float *inv_level_sigma2,
+                                  int nlevels, const orbo_worldpos_t *pts, const orbm_camera_t *cam, const float *Tcw_in16,
+                                  float *Tcw_out16, uint8_t *outlier, int *ngood, orbo_pose_info_t *info, int device, void *stream);
+
 /* The host-array matcher entry points keep grow-only device scratch, a pinned mirror and one non-blocking stream
  * PER HOST THREAD (re-entrant without locks: the reference calls matchers from Tracking, LocalMapping and LoopClosing
  * threads at once, src/LocalMapping.cc:223, src/LoopClosing.cc:249).  Nothing is freed implicitly; a thread calls

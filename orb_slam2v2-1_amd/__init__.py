@@ -41,6 +41,13 @@ OCTREE_LEAF_DTYPE = np.dtype([("kx", "<u2"), ("ky", "<u2"), ("kz", "<u2"), ("dep
 # the reference's transform_trans * transform_rot_x * transform_rot_y (src/pointcloudmapping.cc:198-223): x' = z, y' = -x, z' = -y
 OCTOMAP_AXIS_SWAP = np.array([[0, 0, 1, 0], [-1, 0, 0, 0], [0, -1, 0, 0], [0, 0, 0, 1]], np.float32)
 # include/orbx.h: orbv_db_hit_t, one listed keyframe of a keyframe-database query (flags: bit 0 scored, bit 1 entered lScoreAndMatch)
+# orbo_observation_t / orbo_worldpos_t / orbo_pose_info_t (pose_optimization*)
+POSE_OBS_DTYPE = np.dtype([("valid", "<i4"), ("u", "<f4"), ("v", "<f4"), ("ur", "<f4"), ("inv_sigma2", "<f4"),
+                           ("wx", "<f4"), ("wy", "<f4"), ("wz", "<f4")])
+POSE_WORLDPOS_DTYPE = np.dtype([("valid", "<i4"), ("wx", "<f4"), ("wy", "<f4"), ("wz", "<f4")])
+POSE_INFO_DTYPE = np.dtype({"names": ["correspondences", "bad", "iterations", "trials", "rounds", "t", "q"],
+                            "formats": ["<i4", "<i4", ("<i4", 4), ("<i4", 4), "<i4", ("<f8", 3), ("<f8", 4)],
+                            "offsets": [0, 4, 8, 24, 40, 48, 72], "itemsize": 104})
 DB_HIT_DTYPE = np.dtype([("kf_id", "<i4"), ("words", "<i4"), ("flags", "<u4"), ("score", "<f4"), ("acc_score", "<f4"), ("best_kf", "<i4")])
 DB_MAX_KF_ID, DB_MAX_QUERY, DB_MAX_COVISIBLE = (1 << 20) - 1, 8192, 10
 
@@ -70,6 +77,8 @@ EXPORTS = [
     "orbv_score_l1", "orbv_db_create", "orbv_db_destroy", "orbv_db_add", "orbv_db_erase", "orbv_db_clear", "orbv_db_set_covisible",
     "orbv_db_info", "orbv_db_score", "orbv_db_detect_loop", "orbv_db_detect_reloc",
 ]
+# the optimiser section of include/orbx.h (prefix orbo_), listed apart: EXPORTS is compared with the header's orbx_ / orbm_ / orbv_ names
+POSE_EXPORTS = ["orbo_pose_optimization", "orbo_pose_optimization_batch", "orbo_pose_optimization_device"]
 # what include/orbx_dev.h declares on top: exported by the developer build only
 DEV_EXPORTS = ["orbx_debug_level_points", "orbx_debug_sincosf", "orbx_debug_blur_patches", "orbm_debug_features_in_area",
                "orbx_debug_blurred_level", "orbx_debug_octree_fallbacks", "orbm_debug_match_path", "orbm_debug_resolve_plan",
@@ -347,6 +356,9 @@ def _load(path, dev):
     L.orbm_search_local_points.argtypes = [vp, vp, vp, i32, C.POINTER(GridGeom), vp, i32, vp, vp, i32, vp, C.POINTER(Camera), f32,
                                            vp, vp, vp, f32, f32, i32, C.POINTER(i32), vp]
     L.orbm_search_local_points_device.argtypes = L.orbm_search_local_points.argtypes + [vp]
+    L.orbo_pose_optimization.argtypes = [vp, i32, C.POINTER(Camera), vp, vp, vp, C.POINTER(i32), vp, i32]
+    L.orbo_pose_optimization_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, i32]
+    L.orbo_pose_optimization_device.argtypes = [vp, vp, i32, vp, i32, vp, C.POINTER(Camera), vp, vp, vp, C.POINTER(i32), vp, i32, vp]
     L.orbm_best_in_windows.argtypes = [vp, vp, vp, i32, C.POINTER(GridGeom), C.POINTER(GridGeom), vp, vp, i32, vp, i32, vp, vp, i32]
     if dev:
         L.orbx_debug_level_points.argtypes = [vp, i32, i32, i32, vp, i32, C.POINTER(i32)]
@@ -1123,6 +1135,69 @@ def search_local_points_device(d_kun, d_desc, d_uright, n, geom, sf, pts, mp_des
                                                  len(pts), _p(T), C.byref(cam), float(viewing_cos_limit), _p(thr), _p(fm), _p(eo),
                                                  float(th), float(nnratio), int(device), C.byref(nm), _p(proj), stream))
     return nm.value, fm, proj
+
+
+def _pose_info(rec):
+    return {"correspondences": int(rec["correspondences"]), "bad": int(rec["bad"]), "rounds": int(rec["rounds"]),
+            "iterations": [int(x) for x in rec["iterations"]], "trials": [int(x) for x in rec["trials"]],
+            "t": np.array(rec["t"], np.float64), "q": np.array(rec["q"], np.float64)}
+
+
+def _as_camera(cam):
+    return cam if isinstance(cam, Camera) else Camera(*[float(c) for c in cam])
+
+
+def pose_optimization(obs, cam, Tcw, outlier=None, device=0):
+    """Optimizer::PoseOptimization (orbo_pose_optimization): obs [n] POSE_OBS_DTYPE (ur < 0: monocular), cam a Camera or
+    (fx, fy, cx, cy, mbf, mb), Tcw the float 4x4, outlier [n] = mvbOutlier (only the entries with valid == 0 matter; default zeros)
+    -> (Tcw_out [4, 4] float32, outlier' [n] uint8, ngood, info dict: correspondences, bad, rounds, iterations, trials, t, q)"""
+    obs = np.ascontiguousarray(obs, POSE_OBS_DTYPE)
+    n = len(obs)
+    T = np.ascontiguousarray(Tcw, np.float32).reshape(4, 4)
+    To = np.zeros((4, 4), np.float32)
+    out = np.zeros(n, np.uint8) if outlier is None else np.ascontiguousarray(outlier, np.uint8).copy()
+    assert len(out) == n
+    info = np.zeros(1, POSE_INFO_DTYPE)
+    ng = C.c_int(0)
+    cam = _as_camera(cam)
+    _check(matcher_lib().orbo_pose_optimization(_p(obs), n, C.byref(cam), _p(T), _p(To), _p(out), C.byref(ng), _p(info), int(device)))
+    return To, out, ng.value, _pose_info(info[0])
+
+
+def pose_optimization_batch(obs, offsets, cams, Tcw, outlier=None, device=0):
+    """orbo_pose_optimization_batch: B problems in one launch.  obs / outlier are the problems' entries back to back, offsets [B + 1]
+    into them, cams B cameras, Tcw [B, 4, 4] -> (Tcw_out [B, 4, 4], outlier', ngood [B], infos: list of B dicts)"""
+    obs = np.ascontiguousarray(obs, POSE_OBS_DTYPE)
+    off = np.ascontiguousarray(offsets, np.int32)
+    B = len(off) - 1
+    T = np.ascontiguousarray(Tcw, np.float32).reshape(B, 4, 4)
+    To = np.zeros((B, 4, 4), np.float32)
+    out = np.zeros(len(obs), np.uint8) if outlier is None else np.ascontiguousarray(outlier, np.uint8).copy()
+    assert len(out) == len(obs) and len(cams) == B
+    cs = (Camera * max(B, 1))(*[_as_camera(c) for c in cams])
+    infos = np.zeros(max(B, 1), POSE_INFO_DTYPE)
+    ng = np.zeros(max(B, 1), np.int32)
+    _check(matcher_lib().orbo_pose_optimization_batch(_p(obs), _p(off), B, C.addressof(cs), _p(T), _p(To), _p(out), _p(ng), _p(infos),
+                                                      int(device)))
+    return To, out, ng[:B], [_pose_info(infos[b]) for b in range(B)]
+
+
+def pose_optimization_device(d_kun, d_uright, n, inv_level_sigma2, pts, cam, Tcw, outlier=None, device=0, stream=None):
+    """orbo_pose_optimization_device: d_kun / d_uright are raw device pointers to the frame's undistorted keypoints and mvuRight
+    (the extractor's / stereo matcher's outputs in HBM), pts [n] POSE_WORLDPOS_DTYPE the map-point positions
+    -> (Tcw_out, outlier', ngood, info) as pose_optimization"""
+    is2 = np.ascontiguousarray(inv_level_sigma2, np.float32)
+    pts = np.ascontiguousarray(pts, POSE_WORLDPOS_DTYPE)
+    assert len(pts) == n
+    T = np.ascontiguousarray(Tcw, np.float32).reshape(4, 4)
+    To = np.zeros((4, 4), np.float32)
+    out = np.zeros(n, np.uint8) if outlier is None else np.ascontiguousarray(outlier, np.uint8).copy()
+    info = np.zeros(1, POSE_INFO_DTYPE)
+    ng = C.c_int(0)
+    cam = _as_camera(cam)
+    _check(matcher_lib().orbo_pose_optimization_device(d_kun, d_uright, int(n), _p(is2), len(is2), _p(pts), C.byref(cam), _p(T), _p(To),
+                                                       _p(out), C.byref(ng), _p(info), int(device), stream or None))
+    return To, out, ng.value, _pose_info(info[0])
 
 
 def match_windows(kun, desc, uright, geom, queries, query_desc, holder, ext_blocks=None, max_dist=100,

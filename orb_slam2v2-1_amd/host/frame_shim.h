@@ -84,7 +84,8 @@ public:
     std::vector<bool> mvbOutlier;
     static float mfGridElementWidthInv, mfGridElementHeightInv;
     cv::Mat mTcw;
-    std::vector<float> mvScaleFactors, mvInvScaleFactors;
+    void SetPose(cv::Mat Tcw) { mTcw = Tcw.clone(); }   // src/Frame.cc:262-266, without the derived Rcw / tcw / Ow the matchers do not read
+    std::vector<float> mvScaleFactors, mvInvScaleFactors, mvInvLevelSigma2;
     static float mnMinX, mnMaxX, mnMinY, mnMaxY;
     int mnScaleLevels = 0;          // src/Frame.cc:69
     float mfScaleFactor = 0.f, mfLogScaleFactor = 0.f;  // :70-71

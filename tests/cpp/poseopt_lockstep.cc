@@ -1,0 +1,62 @@
+// poseopt_lockstep.cc — the text of k_pose_opt (orb_slam2v2-1_amd/csrc/orbx_poseopt.hip) compiled for the host and run as ONE thread,
+// for tests/test_poseopt_cpu.py: with one thread the kernel sums its edges in ascending order, which is the order of
+// tests/pose_ref.py, so the two must give the same bits.  That pins the kernel's arithmetic and control flow without a GPU; what
+// it cannot show - the 256-thread summation order, the barriers, the device's sin / cos - is tests/test_poseopt_gpu.py's.
+// Build with -ffp-contract=off, as the library is.
+//   poseopt_lockstep IN OUT
+//       IN:  int32 n | orbm_camera_t | float Tcw[16] | orbo_observation_t[n] | uint8 outlier[n]
+//       OUT: float Tcw[16] | int32 ngood | orbo_pose_info_t | uint8 outlier[n]
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <vector>
+#include "orbx.h"
+
+// the HIP keywords and built-ins the kernel uses, for a grid of one block of one thread
+#define ORBX_POSEOPT_HOST
+#define ORBX_MAX_LEVELS 16
+#define __global__
+#define __device__
+#define __forceinline__ inline
+#define __shared__
+#define __launch_bounds__(x)
+#define __restrict__
+#define __align__(x)
+struct Idx3 { int x; };
+static const Idx3 threadIdx = {0}, blockIdx = {0};
+static inline void __syncthreads() {}
+static inline int atomicAdd(int *p, int v) { const int old = *p; *p += v; return old; }
+static inline double __shfl_xor(double v, int, int) { return v; }   // never reached: a wave of one lane has no butterfly steps
+uint8_t po_lds[1536 * sizeof(orbo_observation_t)];                  // the kernel's dynamic LDS (extern __shared__)
+
+#include "orbx_poseopt.hip"
+
+int main(int argc, char **argv) {
+    if (argc != 3) { fprintf(stderr, "usage: poseopt_lockstep IN OUT\n"); return 2; }
+    static_assert(sizeof(po_lds) == PO_LDS_EDGES * sizeof(orbo_observation_t), "LDS stage");
+    FILE *f = fopen(argv[1], "rb");
+    int32_t n = 0;
+    PoseProblem pr;
+    if (!f || fread(&n, 4, 1, f) != 1 || n < 0 || fread(&pr.cam, sizeof(pr.cam), 1, f) != 1 || fread(pr.Tcw, 64, 1, f) != 1) return 1;
+    pr.off = 0; pr.n = n;
+    std::vector<orbo_observation_t> obs((size_t)n + 1);
+    std::vector<uint8_t> fl((size_t)n + 1);
+    std::vector<float> chi((size_t)n + 1);
+    if (n && (fread(obs.data(), sizeof(orbo_observation_t), n, f) != (size_t)n || fread(fl.data(), 1, n, f) != (size_t)n)) return 1;
+    fclose(f);
+    PoseDevSrc src;
+    memset(&src, 0, sizeof(src));
+    src.dMono = (float)sqrt(5.991); src.dStereo = (float)sqrt(7.815);
+    float T[16];
+    int32_t ngood = 0;
+    orbo_pose_info_t info;
+    memset(&info, 0, sizeof(info));
+    k_pose_opt(&pr, obs.data(), src, fl.data(), chi.data(), T, &ngood, &info);
+    f = fopen(argv[2], "wb");
+    if (!f) return 1;
+    fwrite(T, 64, 1, f); fwrite(&ngood, 4, 1, f); fwrite(&info, sizeof(info), 1, f); fwrite(fl.data(), 1, n, f);
+    fclose(f);
+    return 0;
+}

@@ -1,0 +1,213 @@
+"""CPU: the restatement of Optimizer::PoseOptimization (tests/pose_ref.py) against properties - parity with g2o is not pinned, so the
+reference the GPU tests compare with is itself checked here: its Jacobians, that it finds the pose, that what it returns is a
+stationary point, that its flags are a chi2 test, and that the scenes reach every branch.  Then the C ABI's argument errors."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import pose_ref as R        # noqa: E402
+import pose_scene as S      # noqa: E402
+
+
+def exact_error(E, t, q):
+    """the edges' error with every operation in double (no float invz): the geometric model the Jacobians differentiate"""
+    x, y, z = R.quat_rotate(q, E.Xw) + t[:, None]
+    pu, pv = x / z * E.fx + E.cx, y / z * E.fy + E.cy
+    return np.stack([E.u - pu, E.v - pv, np.where(E.mono, 0.0, E.ur - (pu - E.bf / z))])
+
+
+def test_jacobians_match_central_differences():
+    sc = S.case("mixed300")
+    E = R.Edges(sc["obs"], sc["cam"])
+    assert E.mono.any() and (~E.mono).any()
+    t, q = R.se3_from_T(sc["Tcw0"])
+    e, X = E.error(t, q)
+    assert np.abs(e - exact_error(E, t, q)).max() < 1e-3      # the float invz moves a projection by ~1e-4 px, no more
+    J = E.jacobian(X)
+    h = 1e-6
+    for j in range(6):
+        d = np.zeros(6); d[j] = h
+        num = (exact_error(E, *R.se3_oplus(t, q, d)) - exact_error(E, *R.se3_oplus(t, q, -d))) / (2 * h)
+        # central differences: truncation h^2 |J'''| and rounding eps |e| / h ~ 1e-16 * 1e3 / 1e-6, both far below 1e-6 of |J|
+        assert np.abs(num - J[:, j]).max() <= 1e-6 * np.abs(J).max(), j
+
+
+def test_noise_free_scene_returns_the_true_pose():
+    """Observations given in double (a float pixel is already 6e-5 off) and monocular (the stereo error's float invz is noise of
+    its own): the four rounds then end within 1e-9 of the pose that made the observations."""
+    sc = S.make(11, 200, mono=1.0, noise=0.0)
+    E = R.Edges(sc["obs"], sc["cam"])
+    T = sc["Tcw_true"]
+    tt, qt = T[:3, 3].copy(), R.normalize_rotation(R.quat_from_R(T[:3, :3]))
+    x, y, z = R.quat_rotate(qt, E.Xw) + tt[:, None]
+    E.u, E.v = x / z * E.fx + E.cx, y / z * E.fy + E.cy
+    r = R.pose_optimization(sc["obs"], sc["cam"], sc["Tcw0"], edges=E)
+    assert r["ngood"] == 200 and r["rounds"] == 4
+    assert np.abs(r["t"] - tt).max() <= 1e-9 and np.abs(r["q"] - qt).max() <= 1e-9
+    assert np.abs(np.float64(sc["Tcw0"]) - T).max() > 1e-3     # and the start was somewhere else
+
+
+@pytest.mark.parametrize("name", ["all_mono", "all_stereo", "mixed300", "n256", "invalid", "outliers600"])
+def test_returned_pose_is_a_stationary_point(name):
+    """The gradient of the plain (non-robust) cost over the final inliers, at the returned pose: <= 1e-6 of what it is at the start -
+    for monocular, stereo and mixed scenes, so that every row of b is under the property.  The edges keep the stereo projection's
+    1 / z in double here (Edges(exact_invz=True)), as the noise-free test keeps the observations in double: with the reference's
+    float invz the cost is a staircase with steps of ~4e-5 px, whose gradient has a noise floor of its own (1e-8 .. 2e-6 of the
+    start on these scenes) that says nothing about the optimiser."""
+    sc = S.case(name)
+    E = R.Edges(sc["obs"], sc["cam"], exact_invz=True)
+    r = R.pose_optimization(sc["obs"], sc["cam"], sc["Tcw0"], edges=E)
+    inl = ~r["trace"][-1]["flags"]
+    assert r["rounds"] == 4 and 0 < (~inl).sum() < len(inl)
+    _, g0, _, _ = E.linearize(*R.se3_from_T(sc["Tcw0"]), inl, False)
+    _, g1, _, _ = E.linearize(r["t"], r["q"], inl, False)
+    print("gradient norm: start %.3e, returned pose %.3e" % (np.linalg.norm(g0), np.linalg.norm(g1)))
+    assert np.linalg.norm(g1) <= 1e-6 * np.linalg.norm(g0)
+
+
+@pytest.mark.parametrize("name", ["n64", "n257", "mixed300", "outliers600", "all_mono", "all_stereo", "invalid", "far"])
+def test_flags_are_a_chi2_test_at_the_returned_pose(name):
+    sc = S.case(name)
+    r = R.pose_optimization(sc["obs"], sc["cam"], sc["Tcw0"])
+    E = R.Edges(sc["obs"], sc["cam"])
+    e, _ = E.error(r["t"], r["q"])
+    chi2 = E.chi2(e)
+    outside = np.abs(chi2 / E.thr.astype(np.float64) - 1.0) > 1e-5
+    direct = chi2.astype(np.float32) > E.thr
+    assert (direct == r["outlier"][E.idx].astype(bool))[outside].all()
+    assert r["ngood"] == r["correspondences"] - r["bad"] and r["bad"] == int(r["outlier"][E.idx].sum())
+    # entries without a map point keep the caller's flag
+    inv = sc["obs"]["valid"] == 0
+    mark = np.where(inv, 7, 1).astype(np.uint8)
+    r2 = R.pose_optimization(sc["obs"], sc["cam"], sc["Tcw0"], outlier=mark)
+    assert (r2["outlier"][inv] == 7).all() and (r2["outlier"][~inv] == r["outlier"][~inv]).all()
+
+
+def test_scenes_reach_the_branches():
+    far = S.case("far")
+    assert np.abs(np.float64(far["Tcw0"]) - far["Tcw_true"])[:3, 3].max() > 0.3
+    r = R.pose_optimization(far["obs"], far["cam"], far["Tcw0"])
+    assert any(False in t["accepted"] for t in r["trace"]) and all(True in t["accepted"] for t in r["trace"])     # a rejected trial
+    assert np.abs(r["Tcw"] - far["Tcw_true"]).max() < 0.02                                                        # and it still gets there
+    sc = S.case("n257")
+    r = R.pose_optimization(sc["obs"], sc["cam"], sc["Tcw0"])
+    first = r["trace"][0]["flags"]
+    assert any((first & ~t["flags"]).any() for t in r["trace"][1:])        # flagged in round 0, an inlier again later
+    sc = S.case("n9")
+    r = R.pose_optimization(sc["obs"], sc["cam"], sc["Tcw0"])
+    assert r["rounds"] == 1 and len(r["trace"]) == 1 and r["iterations"][1:] == [0, 0, 0] and r["ngood"] > 0       # n < 10: one round
+    assert R.pose_optimization(S.case("n10")["obs"], S.CAM, S.case("n10")["Tcw0"])["rounds"] == 4
+    sc = S.case("n2")
+    r = R.pose_optimization(sc["obs"], sc["cam"], sc["Tcw0"], outlier=np.ones(2, np.uint8))
+    assert r["ngood"] == 0 and r["rounds"] == 0 and (r["Tcw"] == sc["Tcw0"]).all() and (r["outlier"] == 0).all()  # < 3: returns 0
+    assert R.pose_optimization(np.zeros(0, R.OBS_DTYPE), S.CAM, np.eye(4))["ngood"] == 0
+
+
+def test_summation_order_moves_the_pose_by_rounding_only():
+    sc = S.case("mixed300")
+    a = R.pose_optimization(sc["obs"], sc["cam"], sc["Tcw0"])
+    b = R.pose_optimization(sc["obs"], sc["cam"], sc["Tcw0"], order=np.arange(300)[::-1])
+    assert np.abs(a["t"] - b["t"]).max() < 1e-12 and np.abs(a["q"] - b["q"]).max() < 1e-13
+    assert (a["outlier"] == b["outlier"]).all() and (a["Tcw"] == b["Tcw"]).all()
+
+
+@pytest.fixture(scope="module")
+def lockstep(tmp_path_factory):
+    """tests/cpp/poseopt_lockstep.cc: the kernel's text compiled for the host as one thread (no GPU, no HIP runtime)"""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path_factory.mktemp("bin") / "poseopt_lockstep")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I" + os.path.join(root, "include"),
+                           "-I" + os.path.join(root, "orb_slam2v2-1_amd", "csrc"), "-o", exe, os.path.join(root, "tests", "cpp", "poseopt_lockstep.cc")])
+    return exe
+
+
+@pytest.mark.parametrize("name", list(S.CASES))
+def test_kernel_text_as_one_host_thread_equals_the_restatement(pkg, lockstep, tmp_path, name):
+    """One thread sums its edges in ascending order, which is the restatement's order: every output byte must agree, the double pose
+    and the LM counts included.  (The 256-thread order, the barriers and the device's sin / cos are the GPU tests'.)"""
+    import subprocess
+    sc = S.case(name)
+    n = len(sc["obs"])
+    mark = np.where(sc["obs"]["valid"] == 0, 5, 1).astype(np.uint8)
+    (tmp_path / "in.bin").write_bytes(np.int32(n).tobytes() + np.array(sc["cam"], np.float32).tobytes() + sc["Tcw0"].tobytes() +
+                                      sc["obs"].tobytes() + mark.tobytes())
+    subprocess.run([lockstep, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], check=True, timeout=60)
+    b = (tmp_path / "out.bin").read_bytes()
+    assert len(b) == 64 + 4 + 104 + n
+    T, ng = np.frombuffer(b[:64], np.float32).reshape(4, 4), int(np.frombuffer(b[64:68], np.int32)[0])
+    info, out = np.frombuffer(b[68:172], pkg.POSE_INFO_DTYPE)[0], np.frombuffer(b[172:], np.uint8)
+    r = R.pose_optimization(sc["obs"], sc["cam"], sc["Tcw0"], outlier=mark)
+    assert T.tobytes() == r["Tcw"].tobytes() and ng == r["ngood"] and (out == r["outlier"]).all()
+    assert (info["correspondences"], info["bad"], info["rounds"]) == (r["correspondences"], r["bad"], r["rounds"])
+    assert list(info["iterations"]) == r["iterations"] and list(info["trials"]) == r["trials"]
+    assert info["t"].tobytes() == r["t"].tobytes() and info["q"].tobytes() == r["q"].tobytes()
+
+
+def test_library_exports_the_declared_entry_points(pkg):
+    import re
+    txt = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "orbx.h")).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    names = sorted(set(re.findall(r"\b(orbo_[a-z0-9_]+)\s*\(", txt)))
+    assert names == sorted(pkg.POSE_EXPORTS) and len(names) == 3
+    for L in (pkg.lib(), pkg.lib(developer=True)):
+        assert all(hasattr(L, n) for n in names)
+
+
+def test_record_layouts(pkg):
+    assert pkg.POSE_OBS_DTYPE.itemsize == 32 and pkg.POSE_OBS_DTYPE == R.OBS_DTYPE and pkg.POSE_WORLDPOS_DTYPE.itemsize == 16
+    d = pkg.POSE_INFO_DTYPE
+    assert d.itemsize == 104 and d.fields["rounds"][1] == 40 and d.fields["t"][1] == 48 and d.fields["q"][1] == 72
+
+
+def test_argument_errors_before_a_device(pkg):
+    L = pkg.lib()
+    p = lambda a: a.ctypes.data   # noqa: E731
+    obs = np.zeros(4, pkg.POSE_OBS_DTYPE); T = np.eye(4, dtype=np.float32); To = np.zeros((2, 4, 4), np.float32)
+    out = np.zeros(4, np.uint8); ng = C.c_int(0); cam = pkg.Camera(*S.CAM); ngs = np.zeros(2, np.int32)
+    f = L.orbo_pose_optimization
+    assert f(None, 4, C.byref(cam), p(T), p(To), p(out), C.byref(ng), None, 0) == pkg.ORBX_ERR_ARG
+    assert f(p(obs), -1, C.byref(cam), p(T), p(To), p(out), C.byref(ng), None, 0) == pkg.ORBX_ERR_ARG
+    assert f(p(obs), 4, None, p(T), p(To), p(out), C.byref(ng), None, 0) == pkg.ORBX_ERR_ARG
+    assert f(p(obs), 4, C.byref(cam), None, p(To), p(out), C.byref(ng), None, 0) == pkg.ORBX_ERR_ARG
+    assert f(p(obs), 4, C.byref(cam), p(T), None, p(out), C.byref(ng), None, 0) == pkg.ORBX_ERR_ARG
+    assert f(p(obs), 4, C.byref(cam), p(T), p(To), None, C.byref(ng), None, 0) == pkg.ORBX_ERR_ARG
+    assert f(p(obs), 4, C.byref(cam), p(T), p(To), p(out), None, None, 0) == pkg.ORBX_ERR_ARG
+    g = L.orbo_pose_optimization_batch
+    cams = (pkg.Camera * 2)(cam, cam); T2 = np.stack([T, T])
+    off = np.array([0, 2, 4], np.int32)
+    assert g(p(obs), p(off), -1, C.addressof(cams), p(T2), p(To), p(out), p(ngs), None, 0) == pkg.ORBX_ERR_ARG
+    assert g(p(obs), None, 2, C.addressof(cams), p(T2), p(To), p(out), p(ngs), None, 0) == pkg.ORBX_ERR_ARG
+    assert g(p(obs), p(off), 2, None, p(T2), p(To), p(out), p(ngs), None, 0) == pkg.ORBX_ERR_ARG
+    assert g(None, p(off), 2, C.addressof(cams), p(T2), p(To), p(out), p(ngs), None, 0) == pkg.ORBX_ERR_ARG
+    for bad in ([0, 3, 2], [-1, 2, 4], [2, 1, 4]):
+        assert g(p(obs), p(np.array(bad, np.int32)), 2, C.addressof(cams), p(T2), p(To), p(out), p(ngs), None, 0) == pkg.ORBX_ERR_ARG
+    assert b"monotone" in L.orbx_last_error()
+    assert g(None, p(np.zeros(1, np.int32)), 0, None, None, None, None, None, None, 0) == pkg.ORBX_OK      # B = 0: nothing to do
+    h = L.orbo_pose_optimization_device
+    is2 = S.INV_SIGMA2; pts = np.zeros(4, pkg.POSE_WORLDPOS_DTYPE)
+    assert h(None, None, 4, p(is2), 8, p(pts), C.byref(cam), p(T), p(To), p(out), C.byref(ng), None, 0, None) == pkg.ORBX_ERR_ARG
+    assert h(None, None, 0, None, 8, p(pts), C.byref(cam), p(T), p(To), p(out), C.byref(ng), None, 0, None) == pkg.ORBX_ERR_ARG
+    assert h(None, None, 0, p(is2), 17, p(pts), C.byref(cam), p(T), p(To), p(out), C.byref(ng), None, 0, None) == pkg.ORBX_ERR_ARG
+    assert h(None, None, -1, p(is2), 8, p(pts), C.byref(cam), p(T), p(To), p(out), C.byref(ng), None, 0, None) == pkg.ORBX_ERR_ARG
+
+
+def test_pose_optimization_needs_a_gpu(pkg):
+    """no CPU fallback: without a device the calls fail with ORBX_ERR_NO_DEVICE; with one they work"""
+    sc = S.case("n9")
+    if pkg.device_count() == 0:
+        for call in (lambda: pkg.pose_optimization(sc["obs"], sc["cam"], sc["Tcw0"]),
+                     lambda: pkg.pose_optimization(sc["obs"][:0], sc["cam"], sc["Tcw0"]),
+                     lambda: pkg.pose_optimization_batch(sc["obs"], [0, 4, 9], [sc["cam"]] * 2, [sc["Tcw0"]] * 2),
+                     lambda: pkg.pose_optimization_device(1 << 20, 1 << 20, 9, S.INV_SIGMA2, np.zeros(9, pkg.POSE_WORLDPOS_DTYPE),
+                                                          sc["cam"], sc["Tcw0"])):
+            with pytest.raises(pkg.OrbxError) as e:
+                call()
+            assert e.value.status == pkg.ORBX_ERR_NO_DEVICE
+        assert pkg.lib().orbx_thread_release_scratch() == pkg.ORBX_OK
+    else:
+        assert pkg.pose_optimization(sc["obs"], sc["cam"], sc["Tcw0"])[2] == R.pose_optimization(sc["obs"], sc["cam"], sc["Tcw0"])["ngood"]
