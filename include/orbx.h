@@ -851,6 +851,46 @@ int orbo_pose_optimization_device(const orbx_keypoint_t *d_kun, const float *d_u
                                   int nlevels, const orbo_worldpos_t *pts, const orbm_camera_t *cam, const float *Tcw_in16,
                                   float *Tcw_out16, uint8_t *outlier, int *ngood, orbo_pose_info_t *info, int device, void *stream);
 
+/* ---- Initializer::Initialize (src/Initializer.cc:44-929): the monocular map initialisation Tracking runs on the matches of
+ * ORBmatcher::SearchForInitialization (src/Tracking.cc:723, :757), on flat arrays.  2 x iterations RANSAC hypotheses (a
+ * homography and a fundamental matrix from the 8 matches each set names), scored over all N matches; the choice RH > 0.40;
+ * the decomposition into 8 (H) or 4 (F) motions, each checked by triangulating every inlier; the reference's acceptance rule.
+ * A chain of four launches on one stream, every branch taken on the device, one synchronisation.  A
+ * restatement in float with the reference's double promotions; the SVDs are this library's own Jacobi (csrc/orbx_jacobi_svd.h),
+ * not OpenCV's.  Score sums run in match order: two calls give the same bytes, and a hypothesis' score depends on its model only.
+ *
+ * keys1 / keys2: x y pairs of ALL undistorted keypoints of the two frames (Normalize reads them all); matches [N][2]: indices
+ * into keys1 / keys2 (mvMatches12); sets [iterations][8]: indices into matches (mvSets).  K4 = fx fy cx cy.
+ * Returns ORBX_OK and *result = 1 / 0 (Initialize's bool).  On 0: R21, t21, P3D and triangulated are zero.  P3D [N][3] and
+ * triangulated [N] are in MATCH order.  N < 8, iterations <= 0, an index out of range, NULL pointers, sigma that is not > 0:
+ * ORBX_ERR_ARG, checked before the device is touched.  No usable GPU: ORBX_ERR_NO_DEVICE; there is no CPU path.  Scratch,
+ * pinned mirror and stream are per host thread (orbx_thread_release_scratch). */
+typedef struct {
+    float SH, SF, RH;
+    int32_t model;                     /* 0: homography, 1: fundamental (RH > 0.40 chooses 0) */
+    int32_t best_iteration[2];         /* H, F: the first iteration whose score exceeds all before it; -1: none scored above 0 */
+    int32_t inliers[2];                /* H, F */
+    int32_t best_good, second_good;    /* the acceptance rule's counts (F: maxGood and the runner-up) */
+    float parallax;                    /* of the best motion, degrees */
+    int32_t ncand;                     /* motions checked: 8, 4, or 0 when the decomposition returned early */
+    int32_t ngood[8];
+    float cand_parallax[8];
+    float H21[9], F21[9];              /* zero when best_iteration is -1 */
+} orbi_init_info_t;
+int orbi_initialize(const float *keys1, int n1, const float *keys2, int n2, const int32_t *matches, int N, const int32_t *sets,
+                    int iterations, const float *K4, float sigma, float min_parallax, int min_triangulated, int *result,
+                    float *R21, float *t21, float *P3D, uint8_t *triangulated, orbi_init_info_t *info /* may be NULL */, int device);
+/* The two frames left in HBM by extraction: d_keys1 / d_keys2 are device arrays of n1 / n2 keypoint records (mvKeysUn); matches
+ * and sets are on the host.  Runs on `stream`; returns when the results are on the host.  Same results as orbi_initialize. */
+int orbi_initialize_device(const orbx_keypoint_t *d_keys1, int n1, const orbx_keypoint_t *d_keys2, int n2, const int32_t *matches,
+                           int N, const int32_t *sets, int iterations, const float *K4, float sigma, float min_parallax,
+                           int min_triangulated, int *result, float *R21, float *t21, float *P3D, uint8_t *triangulated,
+                           orbi_init_info_t *info, int device, void *stream);
+/* FindHomography and FindFundamental only: scores [2][iterations] (H first), inliersH / inliersF [N] of the best hypotheses (all
+ * zero when none scored above 0); info->SH .. inliers, H21 and F21 are filled, the rest of info is zero. */
+int orbi_search(const float *keys1, int n1, const float *keys2, int n2, const int32_t *matches, int N, const int32_t *sets,
+                int iterations, float sigma, float *scores, uint8_t *inliersH, uint8_t *inliersF, orbi_init_info_t *info, int device);
+
 /* The host-array matcher entry points keep grow-only device scratch, a pinned mirror and one non-blocking stream
  * PER HOST THREAD (re-entrant without locks: the reference calls matchers from Tracking, LocalMapping and LoopClosing
  * threads at once, src/LocalMapping.cc:223, src/LoopClosing.cc:249).  Nothing is freed implicitly; a thread calls

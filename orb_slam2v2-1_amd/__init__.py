@@ -48,6 +48,10 @@ POSE_WORLDPOS_DTYPE = np.dtype([("valid", "<i4"), ("wx", "<f4"), ("wy", "<f4"), 
 POSE_INFO_DTYPE = np.dtype({"names": ["correspondences", "bad", "iterations", "trials", "rounds", "t", "q"],
                             "formats": ["<i4", "<i4", ("<i4", 4), ("<i4", 4), "<i4", ("<f8", 3), ("<f8", 4)],
                             "offsets": [0, 4, 8, 24, 40, 48, 72], "itemsize": 104})
+# orbi_init_info_t (Initializer, initialize_device)
+INIT_INFO_DTYPE = np.dtype([("SH", "<f4"), ("SF", "<f4"), ("RH", "<f4"), ("model", "<i4"), ("best_iteration", "<i4", (2,)),
+                            ("inliers", "<i4", (2,)), ("best_good", "<i4"), ("second_good", "<i4"), ("parallax", "<f4"), ("ncand", "<i4"),
+                            ("ngood", "<i4", (8,)), ("cand_parallax", "<f4", (8,)), ("H21", "<f4", (9,)), ("F21", "<f4", (9,))])
 DB_HIT_DTYPE = np.dtype([("kf_id", "<i4"), ("words", "<i4"), ("flags", "<u4"), ("score", "<f4"), ("acc_score", "<f4"), ("best_kf", "<i4")])
 DB_MAX_KF_ID, DB_MAX_QUERY, DB_MAX_COVISIBLE = (1 << 20) - 1, 8192, 10
 
@@ -79,6 +83,8 @@ EXPORTS = [
 ]
 # the optimiser section of include/orbx.h (prefix orbo_), listed apart: EXPORTS is compared with the header's orbx_ / orbm_ / orbv_ names
 POSE_EXPORTS = ["orbo_pose_optimization", "orbo_pose_optimization_batch", "orbo_pose_optimization_device"]
+# the initialiser section (prefix orbi_), apart for the same reason
+INIT_EXPORTS = ["orbi_initialize", "orbi_initialize_device", "orbi_search"]
 # what include/orbx_dev.h declares on top: exported by the developer build only
 DEV_EXPORTS = ["orbx_debug_level_points", "orbx_debug_sincosf", "orbx_debug_blur_patches", "orbm_debug_features_in_area",
                "orbx_debug_blurred_level", "orbx_debug_octree_fallbacks", "orbm_debug_match_path", "orbm_debug_resolve_plan",
@@ -360,6 +366,9 @@ def _load(path, dev):
     L.orbo_pose_optimization_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, i32]
     L.orbo_pose_optimization_device.argtypes = [vp, vp, i32, vp, i32, vp, C.POINTER(Camera), vp, vp, vp, C.POINTER(i32), vp, i32, vp]
     L.orbm_best_in_windows.argtypes = [vp, vp, vp, i32, C.POINTER(GridGeom), C.POINTER(GridGeom), vp, vp, i32, vp, i32, vp, vp, i32]
+    L.orbi_initialize.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, vp, f32, f32, i32, C.POINTER(i32), vp, vp, vp, vp, vp, i32]
+    L.orbi_initialize_device.argtypes = L.orbi_initialize.argtypes + [vp]
+    L.orbi_search.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, f32, vp, vp, vp, vp, i32]
     if dev:
         L.orbx_debug_level_points.argtypes = [vp, i32, i32, i32, vp, i32, C.POINTER(i32)]
         L.orbx_debug_sincosf.argtypes = [vp, i32, vp, vp, i32]
@@ -1198,6 +1207,87 @@ def pose_optimization_device(d_kun, d_uright, n, inv_level_sigma2, pts, cam, Tcw
     _check(matcher_lib().orbo_pose_optimization_device(d_kun, d_uright, int(n), _p(is2), len(is2), _p(pts), C.byref(cam), _p(T), _p(To),
                                                        _p(out), C.byref(ng), _p(info), int(device), stream or None))
     return To, out, ng.value, _pose_info(info[0])
+
+
+def draw_sets(n, iterations, rng):
+    """mvSets (src/Initializer.cc:78-97): per iteration 8 distinct indices < n, drawn without replacement - the drawn slot is
+    overwritten by the last available index, which is dropped - from a numpy Generator instead of rand()."""
+    if n < 8:
+        raise ValueError("draw_sets: %d matches, 8 are needed" % n)
+    sets = np.zeros((int(iterations), 8), np.int32)
+    for it in range(int(iterations)):
+        avail = list(range(n))
+        for j in range(8):
+            k = int(rng.integers(0, len(avail)))
+            sets[it, j] = avail[k]
+            avail[k] = avail[-1]
+            avail.pop()
+    return sets
+
+
+def _init_info(rec):
+    d = {k: (rec[k].copy() if rec[k].ndim else rec[k].item()) for k in INIT_INFO_DTYPE.names}
+    d["H21"], d["F21"] = d["H21"].reshape(3, 3), d["F21"].reshape(3, 3)
+    d["ngood"], d["cand_parallax"] = d["ngood"][:d["ncand"]], d["cand_parallax"][:d["ncand"]]
+    return d
+
+
+def _init_args(matches12, sets, iterations, rng):
+    m = np.ascontiguousarray(matches12, np.int32).reshape(-1, 2)
+    if sets is None:
+        sets = draw_sets(len(m), iterations, rng)
+    s = np.ascontiguousarray(sets, np.int32).reshape(-1, 8)
+    return m, s
+
+
+class Initializer:
+    """ORB_SLAM2::Initializer (src/Initializer.cc) on the GPU: keys1 [n1, 2] the reference frame's undistorted keypoint positions,
+    K (fx, fy, cx, cy).  matches12 [N, 2]: index pairs into keys1 / keys2 (mvMatches12); sets [iterations, 8]: indices into
+    matches12 (mvSets), drawn by draw_sets from a generator seeded with 0 when None."""
+
+    def __init__(self, keys1, K, sigma=1.0, iterations=200, device=0):
+        self.keys1 = np.ascontiguousarray(keys1, np.float32).reshape(-1, 2)
+        self.K = np.ascontiguousarray([float(k) for k in K], np.float32)
+        assert len(self.K) == 4
+        self.sigma, self.iterations, self.device = float(sigma), int(iterations), int(device)
+        self.rng = np.random.default_rng(0)
+
+    def initialize(self, keys2, matches12, sets=None, min_parallax=1.0, min_triangulated=50):
+        """-> (ok, R21 [3, 3], t21 [3], P3D [N, 3], triangulated [N] uint8, info dict), P3D / triangulated in match order"""
+        k2 = np.ascontiguousarray(keys2, np.float32).reshape(-1, 2)
+        m, s = _init_args(matches12, sets, self.iterations, self.rng)
+        N = len(m)
+        R, t, P, tri = np.zeros((3, 3), np.float32), np.zeros(3, np.float32), np.zeros((max(N, 1), 3), np.float32), np.zeros(max(N, 1), np.uint8)
+        info, ok = np.zeros(1, INIT_INFO_DTYPE), C.c_int(0)
+        _check(matcher_lib().orbi_initialize(_p(self.keys1), len(self.keys1), _p(k2), len(k2), _p(m), N, _p(s), len(s), _p(self.K), self.sigma,
+                                             float(min_parallax), int(min_triangulated), C.byref(ok), _p(R), _p(t), _p(P), _p(tri), _p(info),
+                                             self.device))
+        return bool(ok.value), R, t, P[:N], tri[:N], _init_info(info[0])
+
+    def search(self, keys2, matches12, sets=None):
+        """FindHomography + FindFundamental only -> (scores [2, iterations] (H, F), inliersH [N], inliersF [N], info dict)"""
+        k2 = np.ascontiguousarray(keys2, np.float32).reshape(-1, 2)
+        m, s = _init_args(matches12, sets, self.iterations, self.rng)
+        N = len(m)
+        sc, iH, iF = np.zeros((2, max(len(s), 1)), np.float32), np.zeros(max(N, 1), np.uint8), np.zeros(max(N, 1), np.uint8)
+        info = np.zeros(1, INIT_INFO_DTYPE)
+        _check(matcher_lib().orbi_search(_p(self.keys1), len(self.keys1), _p(k2), len(k2), _p(m), N, _p(s), len(s), self.sigma, _p(sc), _p(iH),
+                                         _p(iF), _p(info), self.device))
+        return sc, iH[:N], iF[:N], _init_info(info[0])
+
+
+def initialize_device(d_keys1, n1, d_keys2, n2, matches12, sets, K, sigma=1.0, min_parallax=1.0, min_triangulated=50, device=0, stream=None):
+    """orbi_initialize_device: d_keys1 / d_keys2 are raw device pointers to the two frames' keypoint records (mvKeysUn in HBM)
+    -> as Initializer.initialize"""
+    m, s = _init_args(matches12, sets, 0, None)
+    N = len(m)
+    K = np.ascontiguousarray([float(k) for k in K], np.float32)
+    R, t, P, tri = np.zeros((3, 3), np.float32), np.zeros(3, np.float32), np.zeros((max(N, 1), 3), np.float32), np.zeros(max(N, 1), np.uint8)
+    info, ok = np.zeros(1, INIT_INFO_DTYPE), C.c_int(0)
+    _check(matcher_lib().orbi_initialize_device(d_keys1, int(n1), d_keys2, int(n2), _p(m), N, _p(s), len(s), _p(K), float(sigma),
+                                                float(min_parallax), int(min_triangulated), C.byref(ok), _p(R), _p(t), _p(P), _p(tri),
+                                                _p(info), int(device), stream or None))
+    return bool(ok.value), R, t, P[:N], tri[:N], _init_info(info[0])
 
 
 def match_windows(kun, desc, uright, geom, queries, query_desc, holder, ext_blocks=None, max_dist=100,
