@@ -891,6 +891,41 @@ int orbi_initialize_device(const orbx_keypoint_t *d_keys1, int n1, const orbx_ke
 int orbi_search(const float *keys1, int n1, const float *keys2, int n2, const int32_t *matches, int N, const int32_t *sets,
                 int iterations, float sigma, float *scores, uint8_t *inliersH, uint8_t *inliersF, orbi_init_info_t *info, int device);
 
+/* ---- Sim3Solver (src/Sim3Solver.cc:37-423): the similarity transform LoopClosing::ComputeSim3 (src/LoopClosing.cc:248-339) looks
+ * for between the current keyframe and each loop candidate, on flat arrays.  Per problem (candidate): up to `iterations` RANSAC
+ * hypotheses, each Horn's closed form on the 3 pairs its set names followed by the two-way reprojection test over all pairs;
+ * then the replay of the reference's sequential loop over the inlier counts.  A chain of three launches on one stream for ALL
+ * problems of a call, one synchronisation.  A restatement in float with the reference's double promotions;
+ * cv::eigen and cv::Rodrigues are this library's own (csrc/orbx_jacobi_eig.h), not OpenCV's.  Counts are integer: two calls give
+ * the same bytes.
+ *
+ * pairs [n]: the world positions of the two matched map points and mvLevelSigma2[octave] of their keypoints.  A pair's
+ * thresholds are (size_t)(9.210 * sigma2), TRUNCATED to an integer as the reference's std::vector<size_t> does.
+ * sets [iterations][3]: indices into pairs, three different ones per set.  counts [iterations]; models [iterations][13]: s, R
+ * row-major, t (may be NULL); flags [iterations][n] (may be NULL); hit_inliers [n]: the flags of the hit iteration, zero
+ * without a hit.  hit_iteration: the first iteration whose count is > min_inliers, or -1; best_iteration: the LAST iteration
+ * of the maximal count among those run (up to and including the hit, or all), -1 when iterations is 0; s, R, t, T12: its model.
+ * iterations == 0 (what orbs_sim3_iterations answers for n < min_inliers) launches nothing and answers "no hit".
+ * NULL pointers, iterations < 0, n < 0, n < 3 with iterations > 0, a set index out of range or a set naming a pair twice,
+ * decreasing or negative offsets, a sigma2 that is negative or not finite: ORBX_ERR_ARG, checked before the device is touched.
+ * No usable GPU: ORBX_ERR_NO_DEVICE; there is no CPU path.  Scratch, pinned mirror and stream are per host thread
+ * (orbx_thread_release_scratch). */
+typedef struct { float w1[3], w2[3]; float sigma2_1, sigma2_2; } orbs_pair_t;                         /* 32 B */
+typedef struct { float Tcw1[16], Tcw2[16]; float K1[4], K2[4]; int32_t fix_scale, min_inliers; } orbs_problem_t;   /* K: fx fy cx cy */
+typedef struct { int32_t n, iterations, hit_iteration, best_iteration, best_inliers; float s, R[9], t[3], T12[16]; } orbs_sim3_info_t;
+/* Host code, no device: what SetRansacParameters (:114-138) leaves in mRansacMaxIts; 0 when n < min_inliers (iterate answers
+ * bNoMore without looking, :146-150). */
+int orbs_sim3_iterations(int n, double probability, int min_inliers, int max_iterations);
+int orbs_sim3_ransac(const orbs_pair_t *pairs, int n, const orbs_problem_t *problem, const int32_t *sets, int iterations,
+                     int32_t *counts, float *models, uint8_t *flags, uint8_t *hit_inliers, orbs_sim3_info_t *info, int device);
+/* B problems in one chain of launches: problem b owns pairs offsets[b] .. offsets[b+1]-1 and sets set_offsets[b] ..
+ * set_offsets[b+1]-1 (its sets index ITS pairs from 0).  counts [set_offsets[B]], models [set_offsets[B]][13], flags: problem
+ * b's [iterations_b][n_b] block after those of the problems before it, hit_inliers [offsets[B]], infos [B].  Each problem's
+ * results are those of its single call.  An empty problem is allowed and answers "no hit". */
+int orbs_sim3_ransac_batch(const orbs_pair_t *pairs, const int32_t *offsets, int B, const orbs_problem_t *problems,
+                           const int32_t *sets, const int32_t *set_offsets, int32_t *counts, float *models, uint8_t *flags,
+                           uint8_t *hit_inliers, orbs_sim3_info_t *infos, int device);
+
 /* The host-array matcher entry points keep grow-only device scratch, a pinned mirror and one non-blocking stream
  * PER HOST THREAD (re-entrant without locks: the reference calls matchers from Tracking, LocalMapping and LoopClosing
  * threads at once, src/LocalMapping.cc:223, src/LoopClosing.cc:249).  Nothing is freed implicitly; a thread calls

@@ -52,6 +52,12 @@ POSE_INFO_DTYPE = np.dtype({"names": ["correspondences", "bad", "iterations", "t
 INIT_INFO_DTYPE = np.dtype([("SH", "<f4"), ("SF", "<f4"), ("RH", "<f4"), ("model", "<i4"), ("best_iteration", "<i4", (2,)),
                             ("inliers", "<i4", (2,)), ("best_good", "<i4"), ("second_good", "<i4"), ("parallax", "<f4"), ("ncand", "<i4"),
                             ("ngood", "<i4", (8,)), ("cand_parallax", "<f4", (8,)), ("H21", "<f4", (9,)), ("F21", "<f4", (9,))])
+# orbs_pair_t / orbs_problem_t / orbs_sim3_info_t (Sim3Solver, sim3_ransac_batch)
+SIM3_PAIR_DTYPE = np.dtype([("w1", "<f4", (3,)), ("w2", "<f4", (3,)), ("sigma2_1", "<f4"), ("sigma2_2", "<f4")])
+SIM3_PROBLEM_DTYPE = np.dtype([("Tcw1", "<f4", (16,)), ("Tcw2", "<f4", (16,)), ("K1", "<f4", (4,)), ("K2", "<f4", (4,)),
+                               ("fix_scale", "<i4"), ("min_inliers", "<i4")])
+SIM3_INFO_DTYPE = np.dtype([("n", "<i4"), ("iterations", "<i4"), ("hit_iteration", "<i4"), ("best_iteration", "<i4"),
+                            ("best_inliers", "<i4"), ("s", "<f4"), ("R", "<f4", (9,)), ("t", "<f4", (3,)), ("T12", "<f4", (16,))])
 DB_HIT_DTYPE = np.dtype([("kf_id", "<i4"), ("words", "<i4"), ("flags", "<u4"), ("score", "<f4"), ("acc_score", "<f4"), ("best_kf", "<i4")])
 DB_MAX_KF_ID, DB_MAX_QUERY, DB_MAX_COVISIBLE = (1 << 20) - 1, 8192, 10
 
@@ -85,6 +91,8 @@ EXPORTS = [
 POSE_EXPORTS = ["orbo_pose_optimization", "orbo_pose_optimization_batch", "orbo_pose_optimization_device"]
 # the initialiser section (prefix orbi_), apart for the same reason
 INIT_EXPORTS = ["orbi_initialize", "orbi_initialize_device", "orbi_search"]
+# the Sim3Solver section (prefix orbs_), apart for the same reason
+SIM3_EXPORTS = ["orbs_sim3_iterations", "orbs_sim3_ransac", "orbs_sim3_ransac_batch"]
 # what include/orbx_dev.h declares on top: exported by the developer build only
 DEV_EXPORTS = ["orbx_debug_level_points", "orbx_debug_sincosf", "orbx_debug_blur_patches", "orbm_debug_features_in_area",
                "orbx_debug_blurred_level", "orbx_debug_octree_fallbacks", "orbm_debug_match_path", "orbm_debug_resolve_plan",
@@ -369,6 +377,9 @@ def _load(path, dev):
     L.orbi_initialize.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, vp, f32, f32, i32, C.POINTER(i32), vp, vp, vp, vp, vp, i32]
     L.orbi_initialize_device.argtypes = L.orbi_initialize.argtypes + [vp]
     L.orbi_search.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, f32, vp, vp, vp, vp, i32]
+    L.orbs_sim3_iterations.argtypes = [i32, C.c_double, i32, i32]
+    L.orbs_sim3_ransac.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32]
+    L.orbs_sim3_ransac_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32]
     if dev:
         L.orbx_debug_level_points.argtypes = [vp, i32, i32, i32, vp, i32, C.POINTER(i32)]
         L.orbx_debug_sincosf.argtypes = [vp, i32, vp, vp, i32]
@@ -1288,6 +1299,164 @@ def initialize_device(d_keys1, n1, d_keys2, n2, matches12, sets, K, sigma=1.0, m
                                                 float(min_parallax), int(min_triangulated), C.byref(ok), _p(R), _p(t), _p(P), _p(tri),
                                                 _p(info), int(device), stream or None))
     return bool(ok.value), R, t, P[:N], tri[:N], _init_info(info[0])
+
+
+def sim3_iterations(n, probability=0.99, min_inliers=6, max_iterations=300):
+    """orbs_sim3_iterations: what Sim3Solver::SetRansacParameters (src/Sim3Solver.cc:114-138) leaves in mRansacMaxIts for n
+    correspondences; 0 when n < min_inliers (iterate answers bNoMore without looking).  Host code, no device."""
+    return int(matcher_lib().orbs_sim3_iterations(int(n), float(probability), int(min_inliers), int(max_iterations)))
+
+
+def sim3_draw_sets(n, iterations, rng):
+    """the minimal sets of Sim3Solver::iterate (:163-177): per iteration 3 distinct indices < n, drawn without replacement - the
+    drawn slot is overwritten by the last available index, which is dropped - from a numpy Generator instead of rand()."""
+    if n < 3 and iterations > 0:
+        raise ValueError("sim3_draw_sets: %d pairs, 3 are needed" % n)
+    sets = np.zeros((int(iterations), 3), np.int32)
+    for it in range(int(iterations)):
+        avail = list(range(n))
+        for j in range(3):
+            k = int(rng.integers(0, len(avail)))
+            sets[it, j] = avail[k]
+            avail[k] = avail[-1]
+            avail.pop()
+    return sets
+
+
+def sim3_problem(Tcw1, Tcw2, K1, K2, fix_scale, min_inliers):
+    p = np.zeros(1, SIM3_PROBLEM_DTYPE)
+    p["Tcw1"], p["Tcw2"] = np.asarray(Tcw1, np.float32).reshape(16), np.asarray(Tcw2, np.float32).reshape(16)
+    p["K1"], p["K2"] = [float(k) for k in K1], [float(k) for k in K2]
+    p["fix_scale"], p["min_inliers"] = int(bool(fix_scale)), int(min_inliers)
+    return p
+
+
+def _sim3_info(rec):
+    d = {k: (rec[k].copy() if rec[k].ndim else rec[k].item()) for k in SIM3_INFO_DTYPE.names}
+    d["R"], d["T12"] = d["R"].reshape(3, 3), d["T12"].reshape(4, 4)
+    return d
+
+
+def sim3_ransac_batch(pairs, offsets, problems, sets, set_offsets, device=0):
+    """orbs_sim3_ransac_batch: B problems (loop candidates) in one chain of launches.  pairs [offsets[B]] SIM3_PAIR_DTYPE, problems
+    [B] SIM3_PROBLEM_DTYPE (sim3_problem), sets [set_offsets[B], 3] indices into each problem's own pairs
+    -> a list of B dicts: the fields of orbs_sim3_info_t, counts [its], models [its, 13] (s, R, t), flags [its, n], hit_inliers [n]"""
+    pairs = np.ascontiguousarray(pairs, SIM3_PAIR_DTYPE)
+    problems = np.ascontiguousarray(problems, SIM3_PROBLEM_DTYPE)
+    off, soff = np.ascontiguousarray(offsets, np.int32), np.ascontiguousarray(set_offsets, np.int32)
+    B = len(problems)
+    if len(off) != B + 1 or len(soff) != B + 1:
+        raise ValueError("sim3_ransac_batch: %d problems need %d offsets" % (B, B + 1))
+    sets = np.ascontiguousarray(sets, np.int32).reshape(-1, 3)
+    np_, nh = int(off[-1]), int(soff[-1])
+    if len(pairs) < np_ or len(sets) < nh:
+        raise ValueError("sim3_ransac_batch: the offsets reach beyond the pairs or the sets")
+    nfl = sum(max(int(soff[b + 1] - soff[b]), 0) * max(int(off[b + 1] - off[b]), 0) for b in range(B))
+    counts, models = np.zeros(max(nh, 1), np.int32), np.zeros((max(nh, 1), 13), np.float32)
+    flags, hit, infos = np.zeros(max(nfl, 1), np.uint8), np.zeros(max(np_, 1), np.uint8), np.zeros(max(B, 1), SIM3_INFO_DTYPE)
+    pp = pairs if len(pairs) else np.zeros(1, SIM3_PAIR_DTYPE)
+    ss = sets if len(sets) else np.zeros((1, 3), np.int32)
+    _check(matcher_lib().orbs_sim3_ransac_batch(_p(pp), _p(off), B, _p(problems), _p(ss), _p(soff), _p(counts), _p(models), _p(flags),
+                                                _p(hit), _p(infos), int(device)))
+    out, fb = [], 0
+    for b in range(B):
+        n, its = int(off[b + 1] - off[b]), int(soff[b + 1] - soff[b])
+        d = _sim3_info(infos[b])
+        d.update(counts=counts[soff[b]:soff[b + 1]].copy(), models=models[soff[b]:soff[b + 1]].copy(),
+                 flags=flags[fb:fb + its * n].reshape(its, n).copy(), hit_inliers=hit[off[b]:off[b + 1]].copy())
+        fb += its * n
+        out.append(d)
+    return out
+
+
+class Sim3Solver:
+    """ORB_SLAM2::Sim3Solver (src/Sim3Solver.cc) on the GPU, on flat arrays: pairs [n] SIM3_PAIR_DTYPE (the world positions of the two
+    matched map points, mvLevelSigma2[octave] of their keypoints), Tcw1 / Tcw2 the two keyframes' poses, K1 / K2 (fx, fy, cx, cy).
+    The first iterate / find after set_ransac_parameters runs ONE device call over all mRansacMaxIts sets (drawn by sim3_draw_sets
+    from a generator seeded with 0 when sets is None); every iterate(k) then advances over the stored counts with the
+    reference's semantics."""
+
+    def __init__(self, pairs, Tcw1, Tcw2, K1, K2, fix_scale, device=0):
+        self.pairs = np.ascontiguousarray(pairs, SIM3_PAIR_DTYPE)
+        self.Tcw1, self.Tcw2 = np.asarray(Tcw1, np.float32).reshape(4, 4), np.asarray(Tcw2, np.float32).reshape(4, 4)
+        self.K1, self.K2, self.fix_scale, self.device = tuple(K1), tuple(K2), bool(fix_scale), int(device)
+        self.rng = np.random.default_rng(0)
+        self.set_ransac_parameters()
+
+    def set_ransac_parameters(self, probability=0.99, min_inliers=6, max_iterations=300):
+        self.min_inliers = int(min_inliers)
+        self.max_iterations = sim3_iterations(len(self.pairs), probability, min_inliers, max_iterations)
+        self.iterations, self.best_inliers, self.best_iteration, self._trace = 0, 0, -1, None
+
+    def problem(self):
+        return sim3_problem(self.Tcw1, self.Tcw2, self.K1, self.K2, self.fix_scale, self.min_inliers)
+
+    def draw(self, sets=None):
+        """the sets of the one device call: the first max_iterations rows of `sets`, or drawn"""
+        if sets is None:
+            return sim3_draw_sets(len(self.pairs), self.max_iterations, self.rng)
+        s = np.ascontiguousarray(sets, np.int32).reshape(-1, 3)
+        if len(s) < self.max_iterations:
+            raise ValueError("Sim3Solver: %d sets, %d iterations" % (len(s), self.max_iterations))
+        return s[:self.max_iterations]
+
+    def prime(self, trace):
+        self._trace = trace
+
+    def trace(self, sets=None):
+        """-> dict: the device call's answer (counts [its], models [its, 13], flags [its, n], hit_iteration, best_iteration, ...)"""
+        if self._trace is None:
+            s = self.draw(sets)
+            self._trace = sim3_ransac_batch(self.pairs, [0, len(self.pairs)], self.problem(), s, [0, len(s)], self.device)[0]
+        return self._trace
+
+    def iterate(self, k, sets=None):
+        """-> (T12 [4, 4] or None, no_more, inliers [n] uint8, n_inliers): Sim3Solver::iterate (:140-207)"""
+        n = len(self.pairs)
+        inl = np.zeros(n, np.uint8)
+        if n < self.min_inliers:
+            return None, True, inl, 0
+        tr = self.trace(sets)
+        cur = 0
+        while self.iterations < self.max_iterations and cur < k:
+            cur += 1
+            i = self.iterations
+            self.iterations += 1
+            c = int(tr["counts"][i])
+            if c >= self.best_inliers:
+                self.best_inliers, self.best_iteration = c, i
+                if c > self.min_inliers:
+                    return self.estimated_T12(), False, tr["flags"][i].copy(), c
+        return None, self.iterations >= self.max_iterations, inl, 0
+
+    def find(self, sets=None):
+        return self.iterate(self.max_iterations, sets)
+
+    def estimated(self):
+        """-> (s, R [3, 3], t [3]) of the best iteration so far (GetEstimatedScale / Rotation / Translation)"""
+        m = self._trace["models"][self.best_iteration]
+        return float(m[0]), m[1:10].reshape(3, 3).copy(), m[10:13].copy()
+
+    def estimated_T12(self):
+        s, R, t = self.estimated()
+        T = np.eye(4, dtype=np.float32)
+        T[:3, :3] = (R.astype(np.float64) * np.float64(np.float32(s))).astype(np.float32)
+        T[:3, 3] = t
+        return T
+
+    @staticmethod
+    def iterate_all(solvers, sets=None):
+        """prime several solvers (loop candidates) with ONE batched device call; sets: a list with one array (or None) per solver"""
+        todo = [(i, s) for i, s in enumerate(solvers) if s._trace is None and len(s.pairs) >= s.min_inliers]
+        if not todo:
+            return
+        drawn = [s.draw(None if sets is None else sets[i]) for i, s in todo]
+        off = np.cumsum([0] + [len(s.pairs) for _, s in todo])
+        soff = np.cumsum([0] + [len(d) for d in drawn])
+        res = sim3_ransac_batch(np.concatenate([s.pairs for _, s in todo]), off, np.concatenate([s.problem() for _, s in todo]),
+                                np.concatenate(drawn), soff, todo[0][1].device)
+        for (_, s), r in zip(todo, res):
+            s.prime(r)
 
 
 def match_windows(kun, desc, uright, geom, queries, query_desc, holder, ext_blocks=None, max_dist=100,

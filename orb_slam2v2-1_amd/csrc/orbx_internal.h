@@ -167,6 +167,7 @@ void orbx_internal_release_arena();                          // orbx_match_fast.
 void orbx_internal_release_bow_scratch();                    // orbx_bow.hip        (thread-local scratch)
 void orbx_internal_release_pose_scratch();                   // orbx_poseopt.hip    (thread-local scratch, mirror and stream)
 void orbx_internal_release_init_scratch();                   // orbx_initializer.hip (thread-local scratch, mirror and stream)
+void orbx_internal_release_sim3_scratch();                   // orbx_sim3.hip       (thread-local scratch, mirror and stream)
 #ifdef ORBX_DEVELOPER
 // what the calling thread holds of each of the three, for orbm_debug_thread_scratch (include/orbx_dev.h): no HIP call, nothing allocated
 void orbx_internal_arena_info(int64_t *out5);                // capacity, device, call counter, has a stream, has a completion word

@@ -3,21 +3,12 @@
 #include <cstdlib>
 #include <stdexcept>
 #include <string>
+#include "dutils_random.h"
 #include "orbx.h"
 
 namespace ORB_SLAM2 {
 
 int Initializer::device = std::getenv("ORBX_DEVICE") ? std::atoi(std::getenv("ORBX_DEVICE")) : 0;
-
-// Thirdparty/DBoW2/DUtils/Random.cpp: SeedRandOnce(0) seeds rand() once per process, RandomInt scales it (:47-50)
-static void SeedRandOnce(int seed) {
-    static bool seeded = false;
-    if (!seeded) { std::srand(seed); seeded = true; }
-}
-static int RandomInt(int min, int max) {
-    int d = max - min + 1;
-    return int(((double)std::rand() / ((double)RAND_MAX + 1.0)) * d) + min;
-}
 
 Initializer::Initializer(const Frame &ReferenceFrame, float sigma, int iterations) {
     mK = ReferenceFrame.mK.clone();
@@ -49,11 +40,11 @@ bool Initializer::Initialize(const Frame &CurrentFrame, const std::vector<int> &
     vAllIndices.reserve(N);
     for (int i = 0; i < N; i++) vAllIndices.push_back(i);
     mvSets = std::vector<std::vector<size_t> >(mMaxIterations, std::vector<size_t>(8, 0));
-    SeedRandOnce(0);
+    DUtils::Random::SeedRandOnce(0);
     for (int it = 0; it < mMaxIterations; it++) {
         vAvailableIndices = vAllIndices;
         for (size_t j = 0; j < 8; j++) {
-            int randi = RandomInt(0, (int)vAvailableIndices.size() - 1);
+            int randi = DUtils::Random::RandomInt(0, (int)vAvailableIndices.size() - 1);
             int idx = (int)vAvailableIndices[randi];
             mvSets[it][j] = idx;
             vAvailableIndices[randi] = vAvailableIndices.back();

@@ -1,7 +1,7 @@
 // Initializer.h — ORB_SLAM2::Initializer (include/Initializer.h, src/Initializer.cc) executed on an MI355X through include/orbx.h
 // (orbi_initialize): the monocular map initialisation Tracking runs on the matches of ORBmatcher::SearchForInitialization
 // (src/Tracking.cc:723, :757).  The class keeps the reference's bookkeeping - mvMatches12, mvbMatched1, the RANSAC sets drawn with
-// rand() - and hands the arithmetic to the library.  PnPsolver and Sim3Solver are not part of this library.
+// rand() (dutils_random.h, shared with Sim3Solver.h) - and hands the arithmetic to the library.  PnPsolver is not part of this library.
 #ifndef ORBX_INITIALIZER_H
 #define ORBX_INITIALIZER_H
 #include <utility>

@@ -1,0 +1,89 @@
+// sim3_lockstep.cc — the text of k_sim3_prepare / k_sim3_ransac / k_sim3_select (orb_slam2v2-1_amd/csrc/orbx_sim3.hip) compiled for
+// the host and run as ONE thread per workgroup, the workgroups one after the other, for tests/test_sim3_cpu.py: every output byte
+// must equal tests/sim3_ref.py's.  That pins the kernels' arithmetic and control flow without a GPU; what it cannot show - the
+// sharing of pairs among lanes, the ballot, the device's atan2, sin and cos - is tests/test_sim3_gpu.py's.  Build with
+// -ffp-contract=off, as the library is.
+//   sim3_lockstep IN OUT
+//       IN:  int32 B | int32 offsets[B+1] | int32 set_offsets[B+1] | orbs_problem_t problems[B] | orbs_pair_t pairs[offsets[B]] |
+//            int32 sets[set_offsets[B]][3]
+//       OUT: orbs_sim3_info_t infos[B] | int32 counts[set_offsets[B]] | uint8 hit_inliers[offsets[B]] | float models[set_offsets[B]][13] |
+//            uint8 flags[sum of iterations x pairs]
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <vector>
+#include "orbx.h"
+
+// the HIP keywords and built-ins the kernels use, for workgroups of one thread
+#define ORBX_SIM3_HOST
+#define __global__
+#define __device__
+#define __forceinline__ inline
+#define __shared__
+#define __launch_bounds__(x)
+#define __restrict__
+struct Idx3 { int x; };
+static const Idx3 threadIdx = {0};
+static Idx3 blockIdx = {0};
+static const Idx3 gridDim = {1};
+static inline void __syncthreads() {}
+static inline unsigned long long __ballot(int p) { return p ? 1ull : 0ull; }
+static inline int __popcll(unsigned long long v) { return __builtin_popcountll(v); }
+
+#include "orbx_sim3.hip"
+
+template <typename T> static bool rd(FILE *f, std::vector<T> &v, size_t n) { v.resize(n + 1); return n == 0 || fread(v.data(), sizeof(T), n, f) == n; }
+
+int main(int argc, char **argv) {
+    if (argc < 3) { fprintf(stderr, "usage: sim3_lockstep IN OUT\n"); return 2; }
+    FILE *f = fopen(argv[1], "rb");
+    int32_t B;
+    if (!f || fread(&B, 4, 1, f) != 1 || B < 1 || B > 1024) return 1;
+    std::vector<int32_t> off, soff, sets, pprob, hprob;
+    std::vector<orbs_problem_t> prob;
+    std::vector<orbs_pair_t> pairs;
+    if (!rd(f, off, (size_t)B + 1) || !rd(f, soff, (size_t)B + 1) || !rd(f, prob, (size_t)B)) return 1;
+    if (off[0] != 0 || soff[0] != 0) return 1;
+    for (int b = 0; b < B; b++)
+        if (off[b + 1] < off[b] || soff[b + 1] < soff[b] || off[b + 1] > (1 << 20) || soff[b + 1] > (1 << 20) ||
+            (soff[b + 1] > soff[b] && off[b + 1] - off[b] < 3)) return 1;
+    const int np = off[B], nh = soff[B];
+    if (!rd(f, pairs, (size_t)np) || !rd(f, sets, (size_t)nh * 3)) return 1;
+    fclose(f);
+    std::vector<int64_t> fbase(B + 1);
+    pprob.resize(np + 1); hprob.resize(nh + 1);
+    int64_t fb = 0;
+    for (int b = 0; b < B; b++) {
+        fbase[b] = fb;
+        for (int i = off[b]; i < off[b + 1]; i++) pprob[i] = b;
+        for (int h = soff[b]; h < soff[b + 1]; h++) {
+            hprob[h] = b;
+            for (int c = 0; c < 3; c++)
+                if (sets[h * 3 + c] < 0 || sets[h * 3 + c] >= off[b + 1] - off[b]) return 1;
+        }
+        fb += (int64_t)(soff[b + 1] - soff[b]) * (off[b + 1] - off[b]);
+    }
+    Sim3In in;
+    in.pairs = pairs.data(); in.prob = prob.data(); in.off = off.data(); in.soff = soff.data(); in.sets = sets.data();
+    in.pprob = pprob.data(); in.hprob = hprob.data(); in.fbase = fbase.data(); in.B = B; in.npairs = np; in.nhyp = nh;
+    std::vector<Sim3Rec> recs(np + 1);
+    std::vector<float> models((size_t)nh * 13 + 1);
+    std::vector<int32_t> counts(nh + 1);
+    std::vector<uint8_t> flags((size_t)fb + 1), hit(np + 1);
+    std::vector<orbs_sim3_info_t> infos(B);
+    memset(infos.data(), 0, B * sizeof(orbs_sim3_info_t));
+    blockIdx.x = 0;
+    if (np > 0 && nh > 0) {
+        k_sim3_prepare(in, recs.data());
+        for (blockIdx.x = 0; blockIdx.x < nh; blockIdx.x++) k_sim3_ransac(in, recs.data(), models.data(), counts.data(), flags.data());
+    }
+    for (blockIdx.x = 0; blockIdx.x < B; blockIdx.x++) k_sim3_select(in, models.data(), counts.data(), flags.data(), hit.data(), infos.data());
+    f = fopen(argv[2], "wb");
+    if (!f) return 1;
+    fwrite(infos.data(), sizeof(orbs_sim3_info_t), B, f); fwrite(counts.data(), 4, nh, f); fwrite(hit.data(), 1, np, f);
+    fwrite(models.data(), 4, (size_t)nh * 13, f); fwrite(flags.data(), 1, (size_t)fb, f);
+    fclose(f);
+    return 0;
+}
