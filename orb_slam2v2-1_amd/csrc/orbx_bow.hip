@@ -8,6 +8,7 @@
 //                   the candidates live in one 64-bit register per lane (candidate p -> lane p%64, bit p/64)
 //   k_bow_orient    rotation histogram + three maxima, one workgroup
 #include "orbx_match_dev.h"
+#include "orbx_stage.h"   // stage_align
 #include <math.h>
 #include <stdlib.h>
 #include <string>
@@ -166,17 +167,16 @@ void orbx_internal_release_bow_scratch() {
 #ifdef ORBX_DEVELOPER
 void orbx_internal_bow_scratch_info(int64_t *out2) { out2[0] = (int64_t)g_bs.cap; out2[1] = g_bs.device; }
 #endif
-#define ALN(x) (((x) + 255) & ~(size_t)255)
 
 extern "C" int orbv_transform(const orbv_vocabulary_t *v, const uint8_t *desc, int n, int levelsup, int32_t *word_id,
                               int32_t *node_id, double *weight) {
     if (!v || n < 0 || (n > 0 && (!desc || !word_id))) { orbx_set_error("orbv_transform: bad arguments"); return ORBX_ERR_ARG; }
     if (n == 0) return ORBX_OK;
     uint8_t *base;
-    int rc = scratch(v->device, ALN((size_t)n * 32) + 2 * ALN((size_t)n * 4), &base);
+    int rc = scratch(v->device, stage_align((size_t)n * 32) + 2 * stage_align((size_t)n * 4), &base);
     if (rc) return rc;
     uint8_t *dfeat = base;
-    int32_t *dleaf = (int32_t *)(base + ALN((size_t)n * 32)), *dnid = (int32_t *)((uint8_t *)dleaf + ALN((size_t)n * 4));
+    int32_t *dleaf = (int32_t *)(base + stage_align((size_t)n * 32)), *dnid = (int32_t *)((uint8_t *)dleaf + stage_align((size_t)n * 4));
     ORBX_HIP(hipMemcpy(dfeat, desc, (size_t)n * 32, hipMemcpyHostToDevice));
     (void)hipGetLastError();
     const int groups_per_block = 256 / VOC_GROUP;
@@ -303,7 +303,7 @@ extern "C" int orbm_search_by_bow(const uint8_t *q_desc, const float *q_angle, c
     std::vector<uint8_t> seen;
     if (check_items("orbm_search_by_bow", "q_items", q_items, tq, nq, seen) || check_items("orbm_search_by_bow", "c_items", c_items, tc, nc, seen)) return ORBX_ERR_ARG;
     size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += ALN(bytes); return o; };
+    auto take = [&](size_t bytes) { const size_t o = off; off += stage_align(bytes); return o; };
     const size_t o_qd = take((size_t)nq * 32), o_qa = take((size_t)nq * 4), o_qv = take(nq), o_cd = take((size_t)nc * 32),
                  o_ca = take((size_t)nc * 4), o_cv = take(nc), o_nqs = take((size_t)(nnodes + 1) * 4), o_ncs = take((size_t)(nnodes + 1) * 4),
                  o_qi = take((size_t)(tq > 0 ? tq : 1) * 4), o_ci = take((size_t)(tc > 0 ? tc : 1) * 4), o_m = take((size_t)nq * 4), o_out = take(16);
@@ -421,7 +421,7 @@ extern "C" int orbm_search_for_triangulation(const orbx_keypoint_t *kp1, const u
     std::vector<uint8_t> seen;
     if (check_items("orbm_search_for_triangulation", "q_items", q_items, tq, nq, seen) || check_items("orbm_search_for_triangulation", "c_items", c_items, tc, nc, seen)) return ORBX_ERR_ARG;
     size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += ALN(bytes); return o; };
+    auto take = [&](size_t bytes) { const size_t o = off; off += stage_align(bytes); return o; };
     const size_t o_k1 = take((size_t)nq * sizeof(orbx_keypoint_t)), o_qd = take((size_t)nq * 32), o_qf = take(nq), o_qa = take((size_t)nq * 4),
                  o_k2 = take((size_t)nc * sizeof(orbx_keypoint_t)), o_cd = take((size_t)nc * 32), o_cf = take(nc), o_ca = take((size_t)nc * 4),
                  o_nqs = take((size_t)(nnodes + 1) * 4), o_ncs = take((size_t)(nnodes + 1) * 4), o_qi = take((size_t)(tq > 0 ? tq : 1) * 4),

@@ -6,22 +6,23 @@
 //   k_init_reconstruct  ReconstructH / ReconstructF, CheckRT for every motion over every inlier, acceptance        1 workgroup
 //                       (:470-732, :798-929)
 // Float where the reference is CV_32F, double where it writes a double literal into a float expression, cv::gemm / cv::invert /
-// cv::norm / cv::determinant with double accumulation; the SVDs are csrc/orbx_jacobi_svd.h.  DESIGN.md section 6 has the list;
+// cv::norm / cv::determinant are csrc/orbx_cvmath.h; the SVDs are csrc/orbx_jacobi_svd.h.  DESIGN.md section 6 has the list;
 // tests/init_ref.py is the same arithmetic in numpy.  Sums whose order matters (the Normalize means, a hypothesis' score) are
 // accumulated by ONE thread in the reference's order from terms the others computed in parallel: the bytes do not depend on
 // the launch shape.  Every loop has a bound that is a constant or an argument.
 #ifdef ORBX_INIT_HOST
-// tests/cpp/initializer_lockstep.cc compiles the kernels' text for the host as ONE thread per workgroup (its own definitions of the
-// HIP keywords come first) and runs the workgroups one after the other.  Nothing below the kernels is compiled there.
+// tests/cpp/initializer_lockstep.cc compiles the kernels' text for the host as ONE thread per workgroup (tests/cpp/hip_lockstep.h
+// comes first) and runs the workgroups one after the other.  Nothing below the kernels is compiled there.
 #define INI_RT 1
 #define INI_BT 1
 #else
-#include "orbx_internal.h"
+#include "orbx_stage.h"
 #define INI_RT 64     // k_init_ransac: one wave
 #define INI_BT 256
 #endif
 #include <float.h>
 #include <math.h>
+#include "orbx_cvmath.h"
 #include "orbx_jacobi_svd.h"
 
 #define INI_CHUNK 512          // matches (k_init_ransac) or keys (k_init_normalize, x 2) whose terms are staged in LDS per ordered pass
@@ -35,41 +36,6 @@ struct InitIn {
     float sigma, fx, fy, cx, cy, minParallax; int minTri;
 };
 struct InitOut { int32_t result; float R[9], t[3]; };
-
-// cv::gemm on 3x3 CV_32F: double accumulation left to right, x alpha, narrowed
-__device__ __forceinline__ void gemm33(const float *a, const float *b, float *d, double alpha = 1.0) {
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++)
-            d[i * 3 + j] = (float)((((double)a[i * 3] * (double)b[j] + (double)a[i * 3 + 1] * (double)b[3 + j]) + (double)a[i * 3 + 2] * (double)b[6 + j]) * alpha);
-}
-__device__ __forceinline__ void gemv3(const float *a, const float *x, float *d, double alpha = 1.0) {
-    for (int i = 0; i < 3; i++)
-        d[i] = (float)((((double)a[i * 3] * (double)x[0] + (double)a[i * 3 + 1] * (double)x[1]) + (double)a[i * 3 + 2] * (double)x[2]) * alpha);
-}
-__device__ __forceinline__ double det3(const float *m) {
-#define M_(i, j) (double)m[3 * (i) + (j)]
-    return M_(0, 0) * (M_(1, 1) * M_(2, 2) - M_(1, 2) * M_(2, 1)) - M_(0, 1) * (M_(1, 0) * M_(2, 2) - M_(1, 2) * M_(2, 0)) +
-           M_(0, 2) * (M_(1, 0) * M_(2, 1) - M_(1, 1) * M_(2, 0));
-}
-// cv::invert(DECOMP_LU) on 3x3 CV_32F: det3 in double, d = 1./d, adjugate x d narrowed; singular: the zero matrix
-__device__ __forceinline__ void invert33(const float *m, float *t) {
-    double d = det3(m);
-    if (d == 0.0) { for (int k = 0; k < 9; k++) t[k] = 0.f; return; }
-    d = 1. / d;
-    t[0] = (float)((M_(1, 1) * M_(2, 2) - M_(1, 2) * M_(2, 1)) * d);
-    t[1] = (float)((M_(0, 2) * M_(2, 1) - M_(0, 1) * M_(2, 2)) * d);
-    t[2] = (float)((M_(0, 1) * M_(1, 2) - M_(0, 2) * M_(1, 1)) * d);
-    t[3] = (float)((M_(1, 2) * M_(2, 0) - M_(1, 0) * M_(2, 2)) * d);
-    t[4] = (float)((M_(0, 0) * M_(2, 2) - M_(0, 2) * M_(2, 0)) * d);
-    t[5] = (float)((M_(0, 2) * M_(1, 0) - M_(0, 0) * M_(1, 2)) * d);
-    t[6] = (float)((M_(1, 0) * M_(2, 1) - M_(1, 1) * M_(2, 0)) * d);
-    t[7] = (float)((M_(0, 1) * M_(2, 0) - M_(0, 0) * M_(2, 1)) * d);
-    t[8] = (float)((M_(0, 0) * M_(1, 1) - M_(0, 1) * M_(1, 0)) * d);
-#undef M_
-}
-__device__ __forceinline__ double norm3(const float *v) {   // cv::norm(NORM_L2) on CV_32F: double sum, double sqrt
-    return sqrt(((double)v[0] * (double)v[0] + (double)v[1] * (double)v[1]) + (double)v[2] * (double)v[2]);
-}
 
 // ---- Normalize (:749-795): workgroup 0 the reference frame, 1 the current one.  The four float sums are accumulated by thread 0
 // in ascending key order from LDS; the others only stage the keys.
@@ -335,8 +301,10 @@ __global__ __launch_bounds__(INI_BT) void k_init_reconstruct(InitIn in, const ui
     for (int c = 0; c < ncand; c++) {   // CheckRT (:798-907)
         const float *R = Rc[c], *t = tc[c];
         float P2[12], O2[3], Rt[9];
+        // P2 = K*[R|t] and R*p3dC1+t below are cv::gemm as in orbx_cvmath.h (the latter with its addend, + t in double), inline: a call of
+        // N = 2000 matches is 12 us slower with them in helpers (profiles/README.md, the per-call figures of the shared staging pair)
         for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 4; j++) {   // P2 = K*[R|t]
+            for (int j = 0; j < 4; j++) {
                 const float b0 = j < 3 ? R[j] : t[0], b1 = j < 3 ? R[3 + j] : t[1], b2 = j < 3 ? R[6 + j] : t[2];
                 P2[i * 4 + j] = (float)(((double)K[i * 3] * (double)b0 + (double)K[i * 3 + 1] * (double)b1) + (double)K[i * 3 + 2] * (double)b2);
             }
@@ -457,38 +425,9 @@ __global__ __launch_bounds__(INI_BT) void k_init_reconstruct(InitIn in, const ui
 
 #ifndef ORBX_INIT_HOST
 // ------------------------------------------------------------------------------------
-// host side: per-host-thread grow-only scratch, pinned mirror and stream
-struct InitScratch { uint8_t *d = nullptr, *h = nullptr; size_t cap = 0; int device = -1; hipStream_t stream = nullptr; };
-static thread_local InitScratch g_is;
-void orbx_internal_release_init_scratch() {
-    if (g_is.device >= 0) {
-        hipSetDevice(g_is.device);
-        if (g_is.d) hipFree(g_is.d);
-        if (g_is.h) hipHostFree(g_is.h);
-        if (g_is.stream) hipStreamDestroy(g_is.stream);
-    }
-    g_is = InitScratch();
-}
-static int init_scratch(int device, size_t need) {
-    ORBX_HIP(hipSetDevice(device));
-    if (g_is.device != device) orbx_internal_release_init_scratch();
-    if (g_is.device < 0) {
-        ORBX_HIP(hipSetDevice(device));
-        ORBX_HIP(hipStreamCreateWithFlags(&g_is.stream, hipStreamNonBlocking));
-        g_is.device = device;
-    }
-    if (g_is.cap < need) {
-        if (g_is.d) { hipFree(g_is.d); g_is.d = nullptr; }
-        if (g_is.h) { hipHostFree(g_is.h); g_is.h = nullptr; }
-        g_is.cap = 0;
-        const size_t cap = need * 2 > ((size_t)1 << 20) ? need * 2 : ((size_t)1 << 20);
-        ORBX_HIP(hipMalloc(&g_is.d, cap));
-        ORBX_HIP(hipHostMalloc(&g_is.h, cap, hipHostMallocDefault));
-        g_is.cap = cap;
-    }
-    return ORBX_OK;
-}
-#define INI_ALN(x) (((size_t)(x) + 255) & ~(size_t)255)
+// host side: this thread's staging pair (orbx_stage.h)
+static thread_local StagePair g_is;
+void orbx_internal_release_init_scratch() { g_is.release(); }
 
 static int init_check(const char *fn, const void *k1, int n1, const void *k2, int n2, const int32_t *matches, int N, const int32_t *sets,
                       int iterations, float sigma) {
@@ -511,15 +450,15 @@ static int init_run(const float *hk1, const float *hk2, const orbx_keypoint_t *d
                     int minTri, bool full, int *result, float *R21, float *t21, float *P3D, uint8_t *tri, float *scores,
                     uint8_t *inlH, uint8_t *inlF, orbi_init_info_t *info, int device, hipStream_t user, bool useUser) {
     const size_t nh = 2 * (size_t)iters;
+    StagePlan pl;
     // upload block: keys1 | keys2 | matches | sets;  download block: info | out | scores | inlBest | P3D | tri;  device only: the rest
-    const size_t oK1 = 0, oK2 = INI_ALN(oK1 + (hk1 ? (size_t)n1 * 8 : 0)), oM = INI_ALN(oK2 + (hk2 ? (size_t)n2 * 8 : 0));
-    const size_t oS = INI_ALN(oM + (size_t)N * 8), oUpEnd = INI_ALN(oS + (size_t)iters * 32);
-    const size_t oInfo = oUpEnd, oOut = INI_ALN(oInfo + sizeof(orbi_init_info_t)), oSc = INI_ALN(oOut + sizeof(InitOut));
-    const size_t oIb = INI_ALN(oSc + nh * 4), oP = INI_ALN(oIb + 2 * (size_t)N), oTri = INI_ALN(oP + (size_t)N * 12), oDnEnd = INI_ALN(oTri + N);
-    const size_t oNorm = oDnEnd, oMod = INI_ALN(oNorm + sizeof(InitNorm)), oInl = INI_ALN(oMod + nh * 36);
-    const size_t oCP = INI_ALN(oInl + nh * N), oCF = INI_ALN(oCP + 8 * (size_t)N * 12), oCC = INI_ALN(oCF + 8 * (size_t)N);
-    const size_t need = INI_ALN(oCC + 8 * (size_t)N * 4);
-    int rc = init_scratch(device, need);
+    const size_t oK1 = pl.take(hk1 ? (size_t)n1 * 8 : 0), oK2 = pl.take(hk2 ? (size_t)n2 * 8 : 0), oM = pl.take((size_t)N * 8), oS = pl.take((size_t)iters * 32);
+    pl.mark_inputs();
+    const size_t oInfo = pl.take(sizeof(orbi_init_info_t)), oOut = pl.take(sizeof(InitOut)), oSc = pl.take(nh * 4), oIb = pl.take(2 * (size_t)N);
+    const size_t oP = pl.take((size_t)N * 12), oTri = pl.take(N), oDnEnd = pl.off;
+    const size_t oNorm = pl.take(sizeof(InitNorm)), oMod = pl.take(nh * 36), oInl = pl.take(nh * N);
+    const size_t oCP = pl.take(8 * (size_t)N * 12), oCF = pl.take(8 * (size_t)N), oCC = pl.take(8 * (size_t)N * 4);
+    int rc = g_is.reserve(device, pl.off, (size_t)1 << 20);
     if (rc) return rc;
     uint8_t *d = g_is.d, *h = g_is.h;
     const hipStream_t st = useUser ? user : g_is.stream;
@@ -527,7 +466,7 @@ static int init_run(const float *hk1, const float *hk2, const orbx_keypoint_t *d
     if (hk2) memcpy(h + oK2, hk2, (size_t)n2 * 8);
     memcpy(h + oM, matches, (size_t)N * 8);
     memcpy(h + oS, sets, (size_t)iters * 32);
-    ORBX_HIP(hipMemcpyAsync(d, h, oUpEnd, hipMemcpyHostToDevice, st));
+    ORBX_HIP(hipMemcpyAsync(d, h, pl.in_end, hipMemcpyHostToDevice, st));
     InitIn in;
     in.k1 = hk1 ? (const float *)(d + oK1) : (const float *)dk1; in.s1 = hk1 ? 2 : (int)(sizeof(orbx_keypoint_t) / 4);
     in.k2 = hk2 ? (const float *)(d + oK2) : (const float *)dk2; in.s2 = hk2 ? 2 : (int)(sizeof(orbx_keypoint_t) / 4);

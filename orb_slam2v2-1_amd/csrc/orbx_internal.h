@@ -162,12 +162,12 @@ int orbx_internal_stereo_frame_device(orbx_extractor *h, const uint8_t *d_pair, 
 // ComputeStereoMatches of the frame in image slots 0 / 1 of h with the record layout of orbx_stereo_frame_view (orbx_match.hip)
 int orbx_internal_stereo_frame_record(orbx_extractor *h, uint8_t *d_rec, uint8_t *rec_hostdev, int cap, float mbf, float mb, hipStream_t st, bool recordsOnHost,
                                       int32_t *doneFlag, int doneSeq, int *flagArmed);
-void orbx_internal_release_match_scratch();                  // orbx_match.hip      (thread-local staging pair)
-void orbx_internal_release_arena();                          // orbx_match_fast.hip (thread-local arena)
-void orbx_internal_release_bow_scratch();                    // orbx_bow.hip        (thread-local scratch)
-void orbx_internal_release_pose_scratch();                   // orbx_poseopt.hip    (thread-local scratch, mirror and stream)
-void orbx_internal_release_init_scratch();                   // orbx_initializer.hip (thread-local scratch, mirror and stream)
-void orbx_internal_release_sim3_scratch();                   // orbx_sim3.hip       (thread-local scratch, mirror and stream)
+void orbx_internal_release_match_scratch();                  // orbx_match.hip       (thread-local StagePair, orbx_stage.h)
+void orbx_internal_release_arena();                          // orbx_match_fast.hip  (thread-local arena)
+void orbx_internal_release_bow_scratch();                    // orbx_bow.hip         (thread-local scratch)
+void orbx_internal_release_pose_scratch();                   // orbx_poseopt.hip     (thread-local StagePair)
+void orbx_internal_release_init_scratch();                   // orbx_initializer.hip (thread-local StagePair)
+void orbx_internal_release_sim3_scratch();                   // orbx_sim3.hip        (thread-local StagePair)
 #ifdef ORBX_DEVELOPER
 // what the calling thread holds of each of the three, for orbm_debug_thread_scratch (include/orbx_dev.h): no HIP call, nothing allocated
 void orbx_internal_arena_info(int64_t *out5);                // capacity, device, call counter, has a stream, has a completion word

@@ -11,6 +11,7 @@
 // 64-bit keys (distance | scan-order | index) with wavefront shuffles, so the result is the
 // same element the reference's sequential "first strictly smaller wins" scan selects.
 #include "orbx_match_dev.h"
+#include "orbx_stage.h"
 #define ORBX_FAST_FALLBACK_RC 1   // what the fast_* entry points return when the exact kernels must run
 #include <math.h>
 #include <algorithm>
@@ -644,42 +645,12 @@ extern "C" int orbm_stereo_batch_device_prev(orbx_extractor_t *hl, orbx_extracto
                              d_nmatch, stream, true);
 }
 
-// thread-local device scratch with a pinned host mirror of the same layout and a non-blocking stream of its own: the
-// host-array entry points below move their inputs with ONE upload and their results with ONE download + ONE
-// synchronisation of THAT stream (no hipMalloc per call, no device-wide synchronisation: other threads' extractors and
-// matchers keep running, as the reference's Tracking / LocalMapping / LoopClosing threads call matchers concurrently,
-// src/LocalMapping.cc:223, src/LoopClosing.cc:249)
-struct StagePair { uint8_t *d = nullptr, *h = nullptr; size_t cap = 0; int device = -1; hipStream_t st = nullptr; };
+// this thread's staging pair for the host-array entry points below (orbx_stage.h)
 static thread_local StagePair g_sp;
-static void stage_release() {
-    if (g_sp.device < 0) return;
-    hipSetDevice(g_sp.device);
-    if (g_sp.st) { hipStreamSynchronize(g_sp.st); hipStreamDestroy(g_sp.st); g_sp.st = nullptr; }
-    if (g_sp.d) hipFree(g_sp.d);
-    if (g_sp.h) hipHostFree(g_sp.h);
-    g_sp.d = nullptr; g_sp.h = nullptr; g_sp.cap = 0; g_sp.device = -1;
-}
-static int stage_reserve(int device, size_t need) {
-    if (g_sp.device == device && g_sp.cap >= need) return ORBX_OK;
-    stage_release();
-    ORBX_HIP(hipSetDevice(device));
-    const size_t cap = std::max(need * 2, (size_t)1 << 20);
-    ORBX_HIP(hipMalloc(&g_sp.d, cap));
-    ORBX_HIP(hipHostMalloc((void **)&g_sp.h, cap, hipHostMallocDefault));
-    ORBX_HIP(hipStreamCreateWithFlags(&g_sp.st, hipStreamNonBlocking));
-    g_sp.cap = cap; g_sp.device = device;
-    return ORBX_OK;
-}
-// layout of one call inside the StagePair: take() hands out 256-B aligned offsets; everything taken before mark_inputs()
-// is uploaded in one copy
-struct StagePlan {
-    size_t off = 0, in_end = 0;
-    size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
-    void mark_inputs() { in_end = off; }
-};
+static int stage_reserve(int device, size_t need) { return g_sp.reserve(device, need, (size_t)1 << 20); }
 template <typename T> static inline T *stage_dev(size_t o) { return (T *)(g_sp.d + o); }
 static inline void stage_put(size_t o, const void *src, size_t bytes) { if (bytes) memcpy(g_sp.h + o, src, bytes); }
-void orbx_internal_release_match_scratch() { stage_release(); }
+void orbx_internal_release_match_scratch() { g_sp.release(); }
 #ifdef ORBX_DEVELOPER
 void orbx_internal_match_scratch_info(int64_t *out2) { out2[0] = (int64_t)g_sp.cap; out2[1] = g_sp.device; }
 #endif
@@ -693,12 +664,10 @@ extern "C" int orbm_stereo(orbx_extractor_t *hl, orbx_extractor_t *hr, const orb
     }
     if (nmatch) *nmatch = 0;
     if (nl == 0) return ORBX_OK;
-    ORBX_HIP(hipSetDevice(hl->device));
     const int cap = std::max(std::max(nl, nr), 1);
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_kl = 0, o_dl = o_kl + al(sizeof(orbx_keypoint_t) * cap), o_kr = o_dl + al((size_t)32 * cap),
-                 o_dr = o_kr + al(sizeof(orbx_keypoint_t) * cap), o_n = o_dr + al((size_t)32 * cap), o_in_end = o_n + 256,
-                 o_u = o_in_end, o_d = o_u + al(sizeof(float) * cap), o_end = o_d + al(sizeof(float) * cap);
+    const size_t o_kl = 0, o_dl = o_kl + stage_align(sizeof(orbx_keypoint_t) * cap), o_kr = o_dl + stage_align((size_t)32 * cap),
+                 o_dr = o_kr + stage_align(sizeof(orbx_keypoint_t) * cap), o_n = o_dr + stage_align((size_t)32 * cap), o_in_end = o_n + 256,
+                 o_u = o_in_end, o_d = o_u + stage_align(sizeof(float) * cap), o_end = o_d + stage_align(sizeof(float) * cap);
     int rc = stage_reserve(hl->device, o_end);
     if (rc) return rc;
     memcpy(g_sp.h + o_kl, kl, sizeof(orbx_keypoint_t) * nl); memcpy(g_sp.h + o_dl, dl, (size_t)32 * nl);
@@ -789,8 +758,7 @@ extern "C" int orbm_debug_features_in_area(const orbx_keypoint_t *kun, int n, co
     const size_t o_keys = pl.take(8 * (size_t)n);
     int rc = stage_reserve(device, pl.off);
     if (rc) return rc;
-    ORBX_HIP(hipSetDevice(device));
-    hipStream_t st = g_sp.st;
+    hipStream_t st = g_sp.stream;
     stage_put(o_k, kun, sizeof(orbx_keypoint_t) * n);
     ORBX_HIP(hipMemcpyAsync(g_sp.d, g_sp.h, pl.in_end, hipMemcpyHostToDevice, st));
     (void)hipGetLastError();
@@ -921,8 +889,7 @@ extern "C" int orbm_search_for_initialization(const orbx_keypoint_t *k1, const u
                  o_code = pl.take(2 * (size_t)n2), o_bin = pl.take(4 * (size_t)n1);
     int rc = stage_reserve(device, pl.off);
     if (rc) return rc;
-    ORBX_HIP(hipSetDevice(device));
-    hipStream_t st = g_sp.st;
+    hipStream_t st = g_sp.stream;
     stage_put(o_k1, k1, sizeof(orbx_keypoint_t) * n1); stage_put(o_d1, d1, (size_t)32 * n1);
     stage_put(o_k2, k2, sizeof(orbx_keypoint_t) * n2); stage_put(o_d2, d2, (size_t)32 * n2);
     stage_put(o_prev, prev_matched, sizeof(float) * 2 * n1);
@@ -1133,8 +1100,7 @@ static int exact_search_by_projection_mp(const orbx_keypoint_t *kun, const uint8
     const size_t o_nm = pl.take(4), o_code = pl.take(2 * (size_t)n);
     int rc = stage_reserve(device, pl.off);
     if (rc) return rc;
-    ORBX_HIP(hipSetDevice(device));
-    hipStream_t st = dev ? dev->stream : g_sp.st;
+    hipStream_t st = dev ? dev->stream : g_sp.stream;
     if (!dev) { stage_put(o_k, kun, sizeof(orbx_keypoint_t) * n); stage_put(o_d, desc, (size_t)32 * n); stage_put(o_u, uright, 4 * (size_t)n); }
     stage_put(o_sf, scale_factors, 4 * (size_t)nlevels); stage_put(o_mp, mps, sizeof(orbm_mappoint_t) * m);
     stage_put(o_md, mp_desc, (size_t)32 * m); stage_put(o_fm, frame_mp, 4 * (size_t)n);
@@ -1302,8 +1268,7 @@ static int search_by_projection_frame_impl(const orbx_keypoint_t *kun, const uin
     const size_t o_nm = pl.take(4), o_code = pl.take(2 * (size_t)n), o_hi = pl.take(4 * (size_t)nlast), o_hb = pl.take(4 * (size_t)nlast);
     int rc = stage_reserve(device, pl.off);
     if (rc) return rc;
-    ORBX_HIP(hipSetDevice(device));
-    hipStream_t st = dev ? dev->stream : g_sp.st;
+    hipStream_t st = dev ? dev->stream : g_sp.stream;
     if (!dev) {
         stage_put(o_k, kun, sizeof(orbx_keypoint_t) * n); stage_put(o_d, desc, (size_t)32 * n); stage_put(o_u, uright, 4 * (size_t)n);
         stage_put(o_ld, last_desc, (size_t)32 * nlast);
@@ -1480,8 +1445,7 @@ extern "C" int orbm_match_windows(const orbx_keypoint_t *kun, const uint8_t *des
     const size_t o_nm = pl.take(4), o_code = pl.take(2 * (size_t)n), o_hi = pl.take(4 * (size_t)m), o_hb = pl.take(4 * (size_t)m);
     int rc = stage_reserve(device, pl.off);
     if (rc) return rc;
-    ORBX_HIP(hipSetDevice(device));
-    hipStream_t st = g_sp.st;
+    hipStream_t st = g_sp.stream;
     stage_put(o_k, kun, sizeof(orbx_keypoint_t) * n); stage_put(o_d, desc, (size_t)32 * n);
     stage_put(o_q, queries, sizeof(orbm_window_query_t) * m); stage_put(o_qd, query_desc, (size_t)32 * m);
     stage_put(o_h, holder, 4 * (size_t)n);

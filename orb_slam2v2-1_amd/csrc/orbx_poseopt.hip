@@ -10,13 +10,13 @@
 // the same bits.  After a sum every thread holds the same doubles and runs the solve and the LM control flow redundantly: all
 // branches are uniform without a broadcast, and every loop has a compile-time bound (4 rounds, 10 iterations, 10 trials).
 #ifdef ORBX_POSEOPT_HOST
-// tests/cpp/poseopt_lockstep.cc compiles the kernel's text for the host as ONE thread (its own definitions of the HIP keywords come
-// first): the thread's edges in ascending order are then the whole sum, which is tests/pose_ref.py's order - the two must agree
+// tests/cpp/poseopt_lockstep.cc compiles the kernel's text for the host as ONE thread (tests/cpp/hip_lockstep.h comes first): the
+// thread's edges in ascending order are then the whole sum, which is tests/pose_ref.py's order - the two must agree
 // bit for bit (tests/test_poseopt_cpu.py).  Nothing below the kernel is compiled there.
 #define PO_THREADS 1
 #define PO_LANES 1
 #else
-#include "orbx_internal.h"
+#include "orbx_stage.h"
 #define PO_THREADS 256
 #define PO_LANES 64
 #endif
@@ -435,51 +435,22 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(const PoseProblem *__re
 
 #ifndef ORBX_POSEOPT_HOST
 // ------------------------------------------------------------------------------------
-// host side: per-host-thread grow-only scratch, pinned mirror and stream
-struct PoseScratch { uint8_t *d = nullptr, *h = nullptr; size_t cap = 0; int device = -1; hipStream_t stream = nullptr; };
-static thread_local PoseScratch g_ps;
-void orbx_internal_release_pose_scratch() {
-    if (g_ps.device >= 0) {
-        hipSetDevice(g_ps.device);
-        if (g_ps.d) hipFree(g_ps.d);
-        if (g_ps.h) hipHostFree(g_ps.h);
-        if (g_ps.stream) hipStreamDestroy(g_ps.stream);
-    }
-    g_ps = PoseScratch();
-}
-static int pose_scratch(int device, size_t need) {
-    ORBX_HIP(hipSetDevice(device));
-    if (g_ps.device != device) orbx_internal_release_pose_scratch();
-    if (g_ps.device < 0) {
-        ORBX_HIP(hipSetDevice(device));
-        ORBX_HIP(hipStreamCreateWithFlags(&g_ps.stream, hipStreamNonBlocking));
-        g_ps.device = device;
-    }
-    if (g_ps.cap < need) {
-        if (g_ps.d) { hipFree(g_ps.d); g_ps.d = nullptr; }
-        if (g_ps.h) { hipHostFree(g_ps.h); g_ps.h = nullptr; }
-        g_ps.cap = 0;
-        const size_t cap = need * 2 > ((size_t)1 << 18) ? need * 2 : ((size_t)1 << 18);
-        ORBX_HIP(hipMalloc(&g_ps.d, cap));
-        ORBX_HIP(hipHostMalloc(&g_ps.h, cap, hipHostMallocDefault));
-        g_ps.cap = cap;
-    }
-    return ORBX_OK;
-}
-#define PO_ALN(x) (((size_t)(x) + 255) & ~(size_t)255)
+// host side: this thread's staging pair (orbx_stage.h)
+static thread_local StagePair g_ps;
+void orbx_internal_release_pose_scratch() { g_ps.release(); }
 
 // obs == NULL: the device form (src holds the HBM arrays, pts the host records of the one problem)
 static int pose_run(const orbo_observation_t *obs, const int32_t *offsets, int B, const orbm_camera_t *cams, const float *Tin,
                     float *Tout, uint8_t *outlier, int32_t *ngood, orbo_pose_info_t *infos, int device, PoseDevSrc src,
                     const orbo_worldpos_t *pts, hipStream_t user, bool useUser) {
     const size_t total = (size_t)offsets[B], nmax = total > 0 ? total : 1;
-    // upload block: problems | observations (or world positions) | flags;  on the device only: chi2;  download block: flags | poses | ngood | infos
-    const size_t oProb = 0, oObs = PO_ALN(oProb + (size_t)B * sizeof(PoseProblem));
-    const size_t oFl = PO_ALN(oObs + nmax * (obs ? sizeof(orbo_observation_t) : sizeof(orbo_worldpos_t)));
-    const size_t oT = PO_ALN(oFl + nmax), oNg = PO_ALN(oT + (size_t)B * 64), oInf = PO_ALN(oNg + (size_t)B * 4);
-    const size_t oChi = PO_ALN(oInf + (size_t)B * sizeof(orbo_pose_info_t)), need = PO_ALN(oChi + nmax * 4);
+    StagePlan pl;
+    // upload block: problems | observations (or world positions) | flags;  download block: flags | poses | ngood | infos;  device only: chi2
+    const size_t oProb = pl.take((size_t)B * sizeof(PoseProblem)), oObs = pl.take(nmax * (obs ? sizeof(orbo_observation_t) : sizeof(orbo_worldpos_t)));
+    const size_t oFl = pl.take(nmax), oT = pl.take((size_t)B * 64), oNg = pl.take((size_t)B * 4), oInf = pl.take((size_t)B * sizeof(orbo_pose_info_t));
+    const size_t oChi = pl.take(nmax * 4);
     src.dMono = (float)sqrt(5.991); src.dStereo = (float)sqrt(7.815);
-    int rc = pose_scratch(device, need);
+    int rc = g_ps.reserve(device, pl.off, (size_t)1 << 18);
     if (rc) return rc;
     uint8_t *d = g_ps.d, *h = g_ps.h;
     const hipStream_t st = useUser ? user : g_ps.stream;

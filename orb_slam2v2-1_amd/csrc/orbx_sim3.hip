@@ -3,22 +3,23 @@
 //   k_sim3_prepare   the per-pair part of the constructor (:54-109): X1c, X2c, their images, the two thresholds     pairs / 256 workgroups
 //   k_sim3_ransac    one hypothesis per workgroup of one wave: ComputeSim3 (:226-337), CheckInliers (:340-364)      sum of iterations
 //   k_sim3_select    the replay of iterate's sequential loop (:158-201) over the stored counts                      B workgroups
-// Float where the reference is CV_32F, double where it says double, cv::gemm with double accumulation; cv::eigen is
+// Float where the reference is CV_32F, double where it says double, cv::gemm and cv::norm are csrc/orbx_cvmath.h; cv::eigen is
 // csrc/orbx_jacobi_eig.h and cv::Rodrigues is written out below.  DESIGN.md section 6 has the list; tests/sim3_ref.py is the same
 // arithmetic in numpy.  No floating-point value crosses lanes: the inlier count is a ballot and a popcount, so the bytes do not
 // depend on the launch shape.  Every loop has a bound that is a constant or an argument.
 #ifdef ORBX_SIM3_HOST
-// tests/cpp/sim3_lockstep.cc compiles the kernels' text for the host as ONE thread per workgroup (its own definitions of the HIP
-// keywords come first) and runs the workgroups one after the other.  Nothing below the kernels is compiled there.
+// tests/cpp/sim3_lockstep.cc compiles the kernels' text for the host as ONE thread per workgroup (tests/cpp/hip_lockstep.h comes
+// first) and runs the workgroups one after the other.  Nothing below the kernels is compiled there.
 #define S3_RT 1
 #define S3_BT 1
 #else
-#include "orbx_internal.h"
+#include "orbx_stage.h"
 #define S3_RT 64      // k_sim3_ransac: one wave
 #define S3_BT 256
 #endif
 #include <float.h>
 #include <math.h>
+#include "orbx_cvmath.h"
 #include "orbx_jacobi_eig.h"
 
 struct Sim3Rec { float X1c[3], X2c[3], p1[2], p2[2], thr1, thr2; };   // 48 B per pair
@@ -29,18 +30,11 @@ struct Sim3In {
     int B, npairs, nhyp;
 };
 
-// Rcw*X+tcw as one cv::gemm on CV_32F: double accumulation left to right, + t in double, narrowed once.  T: the top three rows of a
+// Rcw*X+tcw as one cv::gemm with its addend: the sum of gemv3 (orbx_cvmath.h), + t in double, narrowed once.  T: the top three rows of a
 // row-major 4x4 (stride 4)
 __device__ __forceinline__ void s3_transform(const float *T, const float *X, float *d) {
     for (int k = 0; k < 3; k++)
         d[k] = (float)((((double)T[k * 4] * (double)X[0] + (double)T[k * 4 + 1] * (double)X[1]) + (double)T[k * 4 + 2] * (double)X[2]) + (double)T[k * 4 + 3]);
-}
-// FromCameraToImage / the tail of Project (:397-401, :417-421): no guard on z
-__device__ __forceinline__ void s3_image(const float *P, const float *K, float *uv) {
-    const float invz = 1 / P[2];
-    const float x = P[0] * invz, y = P[1] * invz;
-    uv[0] = K[0] * x + K[2];
-    uv[1] = K[1] * y + K[3];
 }
 // mvnMaxError (:87-88) is a std::vector<size_t>: 9.210*sigmaSquare in double, truncated; the comparison converts it to float.
 // At or above 2^64 (no pyramid has such a level) the conversion is pinned to 2^64.
@@ -56,8 +50,8 @@ __global__ __launch_bounds__(S3_BT) void k_sim3_prepare(Sim3In in, Sim3Rec *__re
         Sim3Rec r;
         s3_transform(pb->Tcw1, pr.w1, r.X1c);
         s3_transform(pb->Tcw2, pr.w2, r.X2c);
-        s3_image(r.X1c, pb->K1, r.p1);
-        s3_image(r.X2c, pb->K2, r.p2);
+        pinhole_image(r.X1c, pb->K1, r.p1);
+        pinhole_image(r.X2c, pb->K2, r.p2);
         r.thr1 = s3_threshold(pr.sigma2_1);
         r.thr2 = s3_threshold(pr.sigma2_2);
         recs[i] = r;
@@ -88,10 +82,8 @@ __global__ __launch_bounds__(S3_RT) void k_sim3_ransac(Sim3In in, const Sim3Rec 
     }
     s3_centroid(P1, Pr1, O1);
     s3_centroid(P2, Pr2, O2);
-    float M[9];                     // M = Pr2*Pr1.t()
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++)
-            M[i * 3 + j] = (float)(((double)Pr2[i * 3] * (double)Pr1[j * 3] + (double)Pr2[i * 3 + 1] * (double)Pr1[j * 3 + 1]) + (double)Pr2[i * 3 + 2] * (double)Pr1[j * 3 + 2]);
+    float M[9];
+    gemm33<true>(Pr2, Pr1, M);      // M = Pr2*Pr1.t()
     // the N entries are float expressions (M.at<float>() + M.at<float>() is float arithmetic) held in doubles and narrowed back (:251-265)
     const float N11 = M[0] + M[4] + M[8], N12 = M[5] - M[7], N13 = M[6] - M[2], N14 = M[1] - M[3];
     const float N22 = M[0] - M[4] - M[8], N23 = M[1] + M[3], N24 = M[6] + M[2];
@@ -100,7 +92,7 @@ __global__ __launch_bounds__(S3_RT) void k_sim3_ransac(Sim3In in, const Sim3Rec 
     float eval[4], evec[16];
     jacobi_eig4(Nm, eval, evec);    // evec row 0: the quaternion of the rotation
     float vec[3] = {evec[1], evec[2], evec[3]};
-    const double nv = sqrt(((double)vec[0] * (double)vec[0] + (double)vec[1] * (double)vec[1]) + (double)vec[2] * (double)vec[2]);
+    const double nv = norm3(vec);
     const double ang = atan2(nv, (double)evec[0]);
     const double alpha = (2 * ang) * (1. / nv);       // vec = 2*ang*vec/norm(vec): 0/0 for a zero imaginary part, unguarded
     for (int k = 0; k < 3; k++) vec[k] = (float)((double)vec[k] * alpha);
@@ -120,10 +112,8 @@ __global__ __launch_bounds__(S3_RT) void k_sim3_ransac(Sim3In in, const Sim3Rec 
     }
     float ms = 1.0f;
     if (!pb.fix_scale) {            // :292-309
-        float P3[9];                // P3 = mR12i*Pr2
-        for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 3; j++)
-                P3[i * 3 + j] = (float)(((double)R[i * 3] * (double)Pr2[j] + (double)R[i * 3 + 1] * (double)Pr2[3 + j]) + (double)R[i * 3 + 2] * (double)Pr2[6 + j]);
+        float P3[9];
+        gemm33(R, Pr2, P3);         // P3 = mR12i*Pr2
         double nom = 0.0, den = 0.0;
         for (int k = 0; k < 9; k++) nom += (double)Pr1[k] * (double)P3[k];
         for (int k = 0; k < 9; k++) den += (double)(P3[k] * P3[k]);   // cv::pow(P3, 2) squares in float
@@ -142,8 +132,7 @@ __global__ __launch_bounds__(S3_RT) void k_sim3_ransac(Sim3In in, const Sim3Rec 
         }
         T12[i * 4 + 3] = t[i];
     }
-    for (int i = 0; i < 3; i++)     // tinv = -sRinv*mt12i
-        T21[i * 4 + 3] = (float)((((double)T21[i * 4] * (double)t[0] + (double)T21[i * 4 + 1] * (double)t[1]) + (double)T21[i * 4 + 2] * (double)t[2]) * -1.0);
+    gemv3(T21, t, T21 + 3, -1.0, 4, 4);   // tinv = -sRinv*mt12i
     for (int j = 0; j < 4; j++) { T12[12 + j] = T21[12 + j] = (j == 3) ? 1.f : 0.f; }
     if (tid == 0) {
         float *m = models + (size_t)hyp * 13;
@@ -161,8 +150,8 @@ __global__ __launch_bounds__(S3_RT) void k_sim3_ransac(Sim3In in, const Sim3Rec 
         if (i < n) {
             const Sim3Rec r = rec[i];
             float q[3], P2im1[2], P1im2[2];
-            s3_transform(T12, r.X2c, q); s3_image(q, pb.K1, P2im1);
-            s3_transform(T21, r.X1c, q); s3_image(q, pb.K2, P1im2);
+            s3_transform(T12, r.X2c, q); pinhole_image(q, pb.K1, P2im1);
+            s3_transform(T21, r.X1c, q); pinhole_image(q, pb.K2, P1im2);
             const float d1x = r.p1[0] - P2im1[0], d1y = r.p1[1] - P2im1[1];
             const float d2x = P1im2[0] - r.p2[0], d2y = P1im2[1] - r.p2[1];
             const float err1 = (float)((double)d1x * (double)d1x + (double)d1y * (double)d1y);
@@ -220,38 +209,9 @@ __global__ __launch_bounds__(S3_BT) void k_sim3_select(Sim3In in, const float *_
 
 #ifndef ORBX_SIM3_HOST
 // ------------------------------------------------------------------------------------
-// host side: per-host-thread grow-only scratch, pinned mirror and stream
-struct Sim3Scratch { uint8_t *d = nullptr, *h = nullptr; size_t cap = 0; int device = -1; hipStream_t stream = nullptr; };
-static thread_local Sim3Scratch g_ss;
-void orbx_internal_release_sim3_scratch() {
-    if (g_ss.device >= 0) {
-        hipSetDevice(g_ss.device);
-        if (g_ss.d) hipFree(g_ss.d);
-        if (g_ss.h) hipHostFree(g_ss.h);
-        if (g_ss.stream) hipStreamDestroy(g_ss.stream);
-    }
-    g_ss = Sim3Scratch();
-}
-static int sim3_scratch(int device, size_t need) {
-    ORBX_HIP(hipSetDevice(device));
-    if (g_ss.device != device) orbx_internal_release_sim3_scratch();
-    if (g_ss.device < 0) {
-        ORBX_HIP(hipSetDevice(device));
-        ORBX_HIP(hipStreamCreateWithFlags(&g_ss.stream, hipStreamNonBlocking));
-        g_ss.device = device;
-    }
-    if (g_ss.cap < need) {
-        if (g_ss.d) { hipFree(g_ss.d); g_ss.d = nullptr; }
-        if (g_ss.h) { hipHostFree(g_ss.h); g_ss.h = nullptr; }
-        g_ss.cap = 0;
-        const size_t cap = need * 2 > ((size_t)1 << 20) ? need * 2 : ((size_t)1 << 20);
-        ORBX_HIP(hipMalloc(&g_ss.d, cap));
-        ORBX_HIP(hipHostMalloc(&g_ss.h, cap, hipHostMallocDefault));
-        g_ss.cap = cap;
-    }
-    return ORBX_OK;
-}
-#define S3_ALN(x) (((size_t)(x) + 255) & ~(size_t)255)
+// host side: this thread's staging pair (orbx_stage.h)
+static thread_local StagePair g_ss;
+void orbx_internal_release_sim3_scratch() { g_ss.release(); }
 #define S3_MAX_TOTAL (1 << 24)      // pairs, and hypotheses, of one call
 
 extern "C" int orbs_sim3_iterations(int n, double probability, int min_inliers, int max_iterations) {
@@ -301,15 +261,17 @@ extern "C" int orbs_sim3_ransac_batch(const orbs_pair_t *pairs, const int32_t *o
     }
     if (nflags > ((size_t)1 << 31)) { orbx_set_error("%s: %zu flag bytes", fn, nflags); return ORBX_ERR_ARG; }
     const int p0 = offsets[0], h0 = set_offsets[0], np = offsets[B] - p0, nh = set_offsets[B] - h0;   // the arrays' used ranges start at offsets[0]
+    StagePlan pl;
     // upload block: pairs | problems | off | soff | sets | pprob | hprob | fbase;  download block: infos | counts | hit | models | flags;
     // device only: the records
-    const size_t oPa = 0, oPr = S3_ALN(oPa + (size_t)np * sizeof(orbs_pair_t)), oOf = S3_ALN(oPr + (size_t)B * sizeof(orbs_problem_t));
-    const size_t oSo = S3_ALN(oOf + ((size_t)B + 1) * 4), oSe = S3_ALN(oSo + ((size_t)B + 1) * 4), oPp = S3_ALN(oSe + (size_t)nh * 12);
-    const size_t oHp = S3_ALN(oPp + (size_t)np * 4), oFb = S3_ALN(oHp + (size_t)nh * 4), oUpEnd = S3_ALN(oFb + (size_t)B * 8);
-    const size_t oInfo = oUpEnd, oCnt = S3_ALN(oInfo + (size_t)B * sizeof(orbs_sim3_info_t)), oHit = S3_ALN(oCnt + (size_t)nh * 4);
-    const size_t oMod = S3_ALN(oHit + (size_t)np), oFl = S3_ALN(oMod + (size_t)nh * 52), oDnEnd = S3_ALN(oFl + nflags);
-    const size_t oRec = oDnEnd, need = S3_ALN(oRec + (size_t)np * sizeof(Sim3Rec));
-    int rc = sim3_scratch(device, need);
+    const size_t oPa = pl.take((size_t)np * sizeof(orbs_pair_t)), oPr = pl.take((size_t)B * sizeof(orbs_problem_t));
+    const size_t oOf = pl.take(((size_t)B + 1) * 4), oSo = pl.take(((size_t)B + 1) * 4), oSe = pl.take((size_t)nh * 12);
+    const size_t oPp = pl.take((size_t)np * 4), oHp = pl.take((size_t)nh * 4), oFb = pl.take((size_t)B * 8);
+    pl.mark_inputs();
+    const size_t oInfo = pl.take((size_t)B * sizeof(orbs_sim3_info_t)), oCnt = pl.take((size_t)nh * 4), oHit = pl.take((size_t)np);
+    const size_t oMod = pl.take((size_t)nh * 52), oFl = pl.take(nflags), oDnEnd = pl.off;
+    const size_t oRec = pl.take((size_t)np * sizeof(Sim3Rec));
+    int rc = g_ss.reserve(device, pl.off, (size_t)1 << 20);
     if (rc) return rc;
     uint8_t *d = g_ss.d, *h = g_ss.h;
     const hipStream_t st = g_ss.stream;
@@ -326,7 +288,7 @@ extern "C" int orbs_sim3_ransac_batch(const orbs_pair_t *pairs, const int32_t *o
         fb += (int64_t)(set_offsets[b + 1] - set_offsets[b]) * (offsets[b + 1] - offsets[b]);
     }
     hOf[B] = np; hSo[B] = nh;
-    ORBX_HIP(hipMemcpyAsync(d, h, oUpEnd, hipMemcpyHostToDevice, st));
+    ORBX_HIP(hipMemcpyAsync(d, h, pl.in_end, hipMemcpyHostToDevice, st));
     Sim3In in;
     in.pairs = (const orbs_pair_t *)(d + oPa); in.prob = (const orbs_problem_t *)(d + oPr); in.off = (const int32_t *)(d + oOf);
     in.soff = (const int32_t *)(d + oSo); in.sets = (const int32_t *)(d + oSe); in.pprob = (const int32_t *)(d + oPp);

@@ -18,21 +18,8 @@
 #include <vector>
 #include "orbx.h"
 
-// the HIP keywords and built-ins the kernels use, for workgroups of one thread
 #define ORBX_INIT_HOST
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __shared__
-#define __launch_bounds__(x)
-#define __restrict__
-struct Idx3 { int x; };
-static const Idx3 threadIdx = {0};
-static Idx3 blockIdx = {0};
-static inline void __syncthreads() {}
-static inline int atomicAdd(int *p, int v) { const int old = *p; *p += v; return old; }
-static inline uint32_t __float_as_uint(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
-static inline float __uint_as_float(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
+#include "hip_lockstep.h"
 
 #include "orbx_initializer.hip"
 

@@ -14,21 +14,9 @@
 #include <vector>
 #include "orbx.h"
 
-// the HIP keywords and built-ins the kernel uses, for a grid of one block of one thread
 #define ORBX_POSEOPT_HOST
 #define ORBX_MAX_LEVELS 16
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __shared__
-#define __launch_bounds__(x)
-#define __restrict__
-#define __align__(x)
-struct Idx3 { int x; };
-static const Idx3 threadIdx = {0}, blockIdx = {0};
-static inline void __syncthreads() {}
-static inline int atomicAdd(int *p, int v) { const int old = *p; *p += v; return old; }
-static inline double __shfl_xor(double v, int, int) { return v; }   // never reached: a wave of one lane has no butterfly steps
+#include "hip_lockstep.h"
 uint8_t po_lds[1536 * sizeof(orbo_observation_t)];                  // the kernel's dynamic LDS (extern __shared__)
 
 #include "orbx_poseopt.hip"

@@ -16,21 +16,8 @@
 #include <vector>
 #include "orbx.h"
 
-// the HIP keywords and built-ins the kernels use, for workgroups of one thread
 #define ORBX_SIM3_HOST
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __shared__
-#define __launch_bounds__(x)
-#define __restrict__
-struct Idx3 { int x; };
-static const Idx3 threadIdx = {0};
-static Idx3 blockIdx = {0};
-static const Idx3 gridDim = {1};
-static inline void __syncthreads() {}
-static inline unsigned long long __ballot(int p) { return p ? 1ull : 0ull; }
-static inline int __popcll(unsigned long long v) { return __builtin_popcountll(v); }
+#include "hip_lockstep.h"
 
 #include "orbx_sim3.hip"
 

@@ -160,3 +160,28 @@ def test_second_host_thread_after_release(pkg):
     t.start()
     t.join()
     assert got["rc"] == pkg.ORBX_OK and same_bytes(got["r"], first) and same_bytes(call(), first) and same_bytes(first, run(pkg, "wave_65"))
+
+
+def test_scratch_regrows_inside_one_thread(pkg):
+    """a fresh host thread: a small scene reserves the staging pair at its 1 MiB floor, a batch of K copies of n_257 whose flag
+    bytes alone exceed that floor makes it regrow, the small scene runs in the regrown pair; every output equals the single calls'"""
+    big = S.case("n_257")
+    n, its = len(big["pairs"]), len(big["sets"])
+    K = (1 << 20) // (its * n) + 1                                  # the smallest K with K * iterations * pairs > 1 MiB
+    assert (K - 1) * its * n <= 1 << 20 < K * its * n
+    small = S.case("wave_65")
+    call_small = lambda: pkg.sim3_ransac_batch(small["pairs"], [0, 65], S.problem(small), small["sets"], [0, len(small["sets"])])[0]   # noqa: E731
+    got = {}
+
+    def worker():
+        got["first"] = call_small()
+        got["big"] = pkg.sim3_ransac_batch(np.tile(big["pairs"], K), np.arange(K + 1) * n, np.tile(S.problem(big), K),
+                                           np.tile(big["sets"], (K, 1)), np.arange(K + 1) * its)
+        got["again"] = call_small()
+        got["rc"] = pkg.matcher_lib().orbx_thread_release_scratch()
+    t = threading.Thread(target=worker)
+    t.start()
+    t.join()
+    assert len(got["big"]) == K and all(same_bytes(o, run(pkg, "n_257")) for o in got["big"])
+    assert same_bytes(got["first"], run(pkg, "wave_65")) and same_bytes(got["again"], run(pkg, "wave_65"))
+    assert got["rc"] == pkg.ORBX_OK
