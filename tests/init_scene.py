@@ -77,6 +77,16 @@ def degenerate(seed):
 # one seed in six does for a homography scene, whose wrong motions put many points at the 0.99998 test of CheckRT - and, for the
 # first two, recovers the motion within the bounds of tests/test_initializer_cpu.py.  wg_257 / wg_257_mt: the same scene with sets
 # from two generators (PCG64, MT19937).
+# Past the LDS stages of csrc/orbx_initializer.hip (INI_CHUNK = 512 matches per pass of k_init_ransac, 2 x INI_CHUNK keys per pass
+# of k_init_normalize) and past the 1 MiB floor of the staging pair - general scenes only: of planar scenes of 260, 300 and 513
+# matches none of 400 seeds each met margin_rt.  Each seed is the first from 200 up at which the four conditions hold, whatever
+# Initialize answers (seeds tried: 4, 3, 15, 1, 1, 6):
+#   chunk_512        one full pass, cnt == INI_CHUNK                                               answers true
+#   chunk_513        a second pass of one match; k_init_reconstruct strides 256 three times        answers true
+#   chunk_1025       three passes (512 + 512 + 1); 1025 keys: two Normalize passes in both frames  answers true
+#   keys_1024_1025   frame 1 exactly one Normalize pass, frame 2 one key more; 100 matches         answers false (23 points)
+#   keys_2049_3000   three Normalize passes with different counts in the two frames                answers false (73 of 86 inliers)
+#   regrow_513       2 x 1100 x 513 flag bytes > 1 MiB: the staging pair regrows; 2200 hypotheses  answers false (382 of 438 inliers)
 CASES = {
     "general_150": (lambda: make(251, 150, outliers=30, iterations=200), (1, 1)),
     "planar_120": (lambda: make(1614, 120, kind="planar", outliers=20, iterations=200, plane=(2.5, 0.0, 1.0)), (1, 0)),
@@ -90,6 +100,12 @@ CASES = {
     "unmatched_keys": (lambda: make(200, 100, extra1=200, extra2=180, outliers=10), (None, None)),
     "iter_1": (lambda: make(201, 80, iterations=1), (None, None)),
     "degenerate": (lambda: degenerate(213), (0, None)),
+    "chunk_512": (lambda: make(203, 512, outliers=60, iterations=64), (1, 1)),
+    "chunk_513": (lambda: make(202, 513, outliers=60, iterations=64), (1, 1)),
+    "chunk_1025": (lambda: make(214, 1025, outliers=150, iterations=64), (1, 1)),
+    "keys_1024_1025": (lambda: make(200, 100, extra1=924, extra2=925, outliers=10), (0, 1)),
+    "keys_2049_3000": (lambda: make(200, 100, extra1=1949, extra2=2900, outliers=10), (0, 1)),
+    "regrow_513": (lambda: make(205, 513, outliers=60, iterations=1100), (0, 1)),
 }
 
 

@@ -54,7 +54,8 @@ def make(seed, n, mono=0.0, outliers=0.0, invalid=0.0, noise=0.7, rot=0.01, tran
 
 # The shapes the GPU tests run (tests/test_poseopt_gpu.py), smallest where the kernel can go wrong: name -> make() arguments.
 # 0 / 2: fewer than 3 correspondences; 3: the minimum; 9 / 10: the `< 10` break; 63-65: a wave's edge; 255-257: the workgroup's edge and
-# the strided loop; then the mixes, each edge kind alone, invalid entries in between, and a start far enough off for a rejected trial.
+# the strided loop; then the mixes, each edge kind alone, invalid entries in between, and a start far enough off for a rejected trial;
+# 1536 / 1537: the last edge the kernel stages in LDS (PO_LDS_EDGES) and the first it reads from memory; 2000: well past the stage.
 CASES = {
     "n0": dict(seed=100, n=0), "n2": dict(seed=102, n=2), "n3": dict(seed=103, n=3), "n9": dict(seed=109, n=9), "n10": dict(seed=110, n=10),
     "n63": dict(seed=163, n=63, mono=0.3, outliers=0.2), "n64": dict(seed=164, n=64, mono=0.3, outliers=0.2),
@@ -64,6 +65,8 @@ CASES = {
     "all_mono": dict(seed=120, n=120, mono=1.0, outliers=0.1), "all_stereo": dict(seed=121, n=120, mono=0.0, outliers=0.1),
     "invalid": dict(seed=150, n=150, mono=0.3, outliers=0.2, invalid=0.3),
     "far": dict(seed=200, n=200, mono=0.3, outliers=0.2, rot=0.2, trans=2.0),
+    "n1536": dict(seed=1536, n=1536, mono=0.3, outliers=0.2, invalid=0.05), "n1537": dict(seed=1537, n=1537, mono=0.3, outliers=0.2, invalid=0.05),
+    "n2000": dict(seed=2000, n=2000, mono=0.3, outliers=0.2, invalid=0.05),
 }
 
 

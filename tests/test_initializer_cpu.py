@@ -105,6 +105,37 @@ def test_scenes_reach_the_shapes():
     assert (n["wave_65"], n["wg_257"], n["min_8"], n["exact_64"]) == (65, 257, 8, 64) and S.case("iter_1")["iterations"] == 1
     assert S.case("wg_257")["iterations"] == 200 and (S.case("wg_257")["sets"] != S.case("wg_257_mt")["sets"]).any()
     assert {S.reference(k)["model"] for k in S.CASES} == {0, 1} and {S.reference(k)["result"] for k in S.CASES} == {0, 1}
+    # past the LDS stages, from the kernels' own constant: k_init_ransac stages CHUNK matches, k_init_normalize 2 x CHUNK keys per pass
+    CHUNK = kernel_constant("INI_CHUNK")
+    assert CHUNK >= 256
+    keys = {k: (len(S.case(k)["keys1"]), len(S.case(k)["keys2"])) for k in S.CASES}
+    assert (n["chunk_512"], n["chunk_513"], n["chunk_1025"]) == (CHUNK, CHUNK + 1, 2 * CHUNK + 1)
+    assert keys["chunk_1025"] == (2 * CHUNK + 1, 2 * CHUNK + 1)                       # two Normalize passes in both frames
+    assert keys["keys_1024_1025"] == (2 * CHUNK, 2 * CHUNK + 1) and n["keys_1024_1025"] < CHUNK
+    k1, k2 = keys["keys_2049_3000"]
+    assert k1 == 4 * CHUNK + 1 and -(-k1 // (2 * CHUNK)) == -(-k2 // (2 * CHUNK)) == 3 and k1 % (2 * CHUNK) != k2 % (2 * CHUNK)
+    big = S.case("regrow_513")
+    assert n["regrow_513"] == CHUNK + 1 and 2 * big["iterations"] * n["regrow_513"] > 1 << 20      # the flag bytes alone pass the floor
+    new = ("chunk_512", "chunk_513", "chunk_1025", "keys_1024_1025", "keys_2049_3000", "regrow_513")
+    assert {S.reference(k)["result"] for k in new} == {0, 1}
+
+
+def kernel_constant(name):
+    txt = open(os.path.join(ROOT, "orb_slam2v2-1_amd", "csrc", "orbx_initializer.hip")).read()
+    return int(re.search(r"^#define\s+%s\s+(\d+)\b" % name, txt, flags=re.M).group(1))
+
+
+def test_normalize_past_one_stage():
+    """keys_2049_3000: three passes of k_init_normalize per frame.  The restatement's T1 / T2 are those of all keys, and differ from
+    those of the first pass' keys and from those of the matched keys: a dropped pass cannot hide in this scene."""
+    sc = S.case("keys_2049_3000")
+    stage = 2 * kernel_constant("INI_CHUNK")
+    s = S.reference("keys_2049_3000")["search"]
+    for T, keys, col in ((s["T1"], sc["keys1"], 0), (s["T2"], sc["keys2"], 1)):
+        assert len(keys) > 2 * stage
+        assert (T == R.normalize(keys)[2]).all()
+        for part in (keys[:stage], keys[:2 * stage], keys[stage:], keys[sc["matches"][:, col]]):
+            assert (T != R.normalize(part)[2]).any()
 
 
 @pytest.fixture(scope="module")

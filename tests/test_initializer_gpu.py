@@ -3,7 +3,8 @@ restatement tests/init_ref.py on every scene of tests/init_scene.py: CASES.  The
 on the restatement's own trace.  Discrete outputs equal; the float outputs - the scores of all 2 x iterations hypotheses, H21,
 F21, R21, t21, the points - BYTE-equal: the sums are ordered, nothing is contracted, and float / and sqrt are correctly rounded;
 only the parallax goes through the device's math library (acosf): within 4 ulp.  Two runs byte-identical; the device form equal
-to the host form; a second host thread after orbx_thread_release_scratch equal to the first."""
+to the host form, also past the LDS chunks; a second host thread after orbx_thread_release_scratch equal to the first; a thread
+whose staging pair regrows in between equal to the single calls."""
 import os
 import sys
 import threading
@@ -135,6 +136,51 @@ def test_device_form_and_second_thread_equal_host_form(pkg):
     th.start(); th.join()
     assert "error" not in got, got.get("error")
     assert got["a"] == got["b"] == got["c"] == as_bytes(host)
+
+
+def test_scratch_regrows_inside_one_thread(pkg):
+    """a fresh host thread: wave_65 reserves the staging pair at its 1 MiB floor, regrow_513 - whose 2 x 1100 x 513 flag bytes alone
+    exceed that floor - makes it regrow, wave_65 runs in the regrown pair; every output equals the same call from this thread
+    (and regrow_513's equals its restatement: test_kernels_against_restatement)"""
+    big, small = S.case("regrow_513"), S.case("wave_65")
+    assert 2 * big["iterations"] * len(big["matches"]) > 1 << 20 > 64 * 2 * small["iterations"] * len(small["matches"])
+    got = {}
+
+    def worker():
+        try:
+            got["first"] = as_bytes(*run(pkg, small))
+            got["big"] = as_bytes(*run(pkg, big))
+            got["again"] = as_bytes(*run(pkg, small))
+            got["rc"] = pkg.matcher_lib().orbx_thread_release_scratch()
+        except Exception as e:      # noqa: BLE001
+            got["error"] = e
+
+    th = threading.Thread(target=worker)
+    th.start(); th.join()
+    assert "error" not in got, got.get("error")
+    assert got["big"] == as_bytes(*run(pkg, big))
+    assert got["first"] == got["again"] == as_bytes(*run(pkg, small))
+    assert got["rc"] == pkg.ORBX_OK == 0
+
+
+def test_device_form_past_the_chunks(pkg):
+    """chunk_1025 with keypoint records (stride 7) in HBM: three passes of k_init_ransac, two of k_init_normalize per frame, and the
+    strided loop of k_init_reconstruct read their keys through the record stride; equal to the host form bit for bit"""
+    import torch
+    sc = S.case("chunk_1025")
+    host = pkg.Initializer(sc["keys1"], sc["K4"], iterations=sc["iterations"]).initialize(sc["keys2"], sc["matches"], sc["sets"])
+    recs = []
+    for k in (sc["keys1"], sc["keys2"]):
+        kp = np.zeros(len(k), pkg.KP_DTYPE)
+        kp["x"], kp["y"], kp["size"], kp["angle"], kp["octave"], kp["class_id"] = k[:, 0], k[:, 1], 31.0, 45.0, 1, -1
+        recs.append(torch.from_numpy(kp.view(np.uint8).copy()).cuda())
+    assert pkg.KP_DTYPE.itemsize == 7 * 4 and len(sc["matches"]) == len(sc["keys1"]) == len(sc["keys2"]) == 1025
+    stream = torch.cuda.current_stream().cuda_stream
+    torch.cuda.synchronize()
+    dev = pkg.initialize_device(recs[0].data_ptr(), len(sc["keys1"]), recs[1].data_ptr(), len(sc["keys2"]), sc["matches"], sc["sets"],
+                                sc["K4"], stream=stream)
+    assert as_bytes(dev) == as_bytes(host) and host[0]
+    assert host[0] == bool(S.reference("chunk_1025")["result"]) and tuple(host[5]["best_iteration"]) == tuple(S.reference("chunk_1025")["best"])
 
 
 def test_default_sets_are_drawn_when_none_are_given(pkg):

@@ -2,8 +2,10 @@
 tests/pose_scene.py: CASES.  Flags and counts equal; the float pose within 1 ulp; the double pose within 64 x the deviation the
 restatement itself shows when its edges are summed in 16 random orders (the kernel differs from it by its summation order and by
 the device's sqrt / sin / cos / division); two runs byte-identical; a batch equal to its single calls; the device form equal to the
-host form, also from a second host thread after orbx_thread_release_scratch."""
+host form, also from a second host thread after orbx_thread_release_scratch, and also past the LDS stage with octaves outside the
+level table; a batch that outgrows the staging pair's floor equal to its single calls."""
 import os
+import re
 import sys
 import threading
 
@@ -94,15 +96,107 @@ def test_rejected_trial_and_break_are_reached(pkg):
     assert pkg.pose_optimization(S.case("n10")["obs"], S.CAM, S.case("n10")["Tcw0"])[3]["rounds"] == 4
 
 
+def lds_edges():
+    """PO_LDS_EDGES of csrc/orbx_poseopt.hip: the edges the kernel stages in LDS"""
+    txt = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "orb_slam2v2-1_amd", "csrc", "orbx_poseopt.hip")).read()
+    return int(re.search(r"^#define\s+PO_LDS_EDGES\s+(\d+)\b", txt, flags=re.M).group(1))
+
+
 def test_edges_behind_the_lds_stage(pkg):
     """more edges than the kernel stages in LDS (1536): the rest is read from memory, same arithmetic"""
-    sc = S.make(2000, 2000, mono=0.3, outliers=0.2, invalid=0.05)
+    assert (S.CASES["n1536"]["n"], S.CASES["n1537"]["n"]) == (lds_edges(), lds_edges() + 1) and S.CASES["n2000"]["n"] == 2000 > lds_edges()
+    sc = S.case("n2000")
     ref = R.pose_optimization(sc["obs"], sc["cam"], sc["Tcw0"])
     T, out, ng, info = pkg.pose_optimization(sc["obs"], sc["cam"], sc["Tcw0"])
     assert min(t["min_margin"] for t in ref["trace"]) > MARGIN
     assert ng == ref["ngood"] and (out == ref["outlier"]).all() and info["rounds"] == 4
     ulp = np.spacing(np.maximum(np.float32(1), np.abs(ref["Tcw"])).astype(np.float32))
     assert (np.abs(T.astype(np.float64) - ref["Tcw"].astype(np.float64)) <= ulp).all()
+    # and the full comparison: the double pose, the iteration and trial counts, the markers of the invalid entries
+    check_against_reference("n2000", pkg.pose_optimization(sc["obs"], sc["cam"], sc["Tcw0"], outlier=reference("n2000")[1]))
+
+
+def device_arrays(pkg, name, low, high):
+    """the Frame arrays of a scene as the device form reads them - keypoint records, uright, world positions - with octave -1 at
+    `low` and octave nlevels at `high`, and the host-form observations of the same call: inv_sigma2 of level 0 and of level
+    nlevels - 1 there, which is the kernel's clamp as written (Frame produces neither octave)"""
+    sc = S.case(name)
+    obs, n = sc["obs"].copy(), len(sc["obs"])
+    octave = sc["octave"].astype(np.int32)
+    assert (obs["inv_sigma2"] == S.INV_SIGMA2[octave]).all()
+    octave[low], octave[high] = -1, S.NLEVELS
+    obs["inv_sigma2"] = S.INV_SIGMA2[np.clip(octave, 0, S.NLEVELS - 1)]
+    kp = np.zeros(n, pkg.KP_DTYPE)
+    kp["x"], kp["y"], kp["size"], kp["angle"], kp["response"], kp["octave"], kp["class_id"] = obs["u"], obs["v"], 31.0, 45.0, 20.0, octave, -1
+    pts = np.zeros(n, pkg.POSE_WORLDPOS_DTYPE)
+    for a in ("valid", "wx", "wy", "wz"):
+        pts[a] = obs[a]
+    return sc, obs, kp, np.ascontiguousarray(obs["ur"], np.float32), pts
+
+
+@pytest.mark.parametrize("name", ["n1537", "n2000"])
+def test_device_form_past_the_lds_stage(pkg, name):
+    """The device form's fetch - keypoint record, uright, world position, the clamped octave - on both sides of the LDS stage: equal
+    to the host form on the same observations, bit for bit.  n1537 has ONE edge past the stage, which takes octave nlevels (the
+    clamp that would otherwise read past the level table); n2000 has half of each handful past it."""
+    import torch
+    E = lds_edges()
+    valid = np.nonzero(S.case(name)["obs"]["valid"])[0]
+    below, past = valid[valid < E], valid[valid >= E]
+    if name == "n1537":
+        assert list(past) == [E]                                           # the one edge read from memory is a correspondence
+        low, high = below[[3, 700, 1400]], np.concatenate([below[[5, 900]], past])
+    else:
+        low, high = np.concatenate([below[[3, 1400]], past[[0, 200]]]), np.concatenate([below[[5, 900]], past[[1, -1]]])
+    assert (low >= E).sum() * 2 in (0, len(low)) and (high >= E).any() and not set(low) & set(high)
+    sc, obs, kp, ur, pts = device_arrays(pkg, name, low, high)
+    assert len({float(obs["inv_sigma2"][i]) for i in high}) == 1 and obs["inv_sigma2"][low[0]] == 1.0
+    assert (obs["inv_sigma2"] != sc["obs"]["inv_sigma2"]).sum() >= 2       # the clamped levels are not the scene's own
+    mark = np.where(obs["valid"] == 0, 5, 1).astype(np.uint8)
+    host = pkg.pose_optimization(obs, sc["cam"], sc["Tcw0"], outlier=mark)
+    d_kp, d_ur = torch.from_numpy(kp.view(np.uint8).copy()).cuda(), torch.from_numpy(ur.copy()).cuda()
+    stream = torch.cuda.current_stream().cuda_stream
+    torch.cuda.synchronize()
+    dev = pkg.pose_optimization_device(d_kp.data_ptr(), d_ur.data_ptr(), len(obs), S.INV_SIGMA2, pts, sc["cam"], sc["Tcw0"], outlier=mark,
+                                       stream=stream)
+    assert as_bytes(dev) == as_bytes(host)
+    inv = obs["valid"] == 0
+    assert inv.any() and (host[1][inv] == 5).all() and (host[1][~inv] <= 1).all() and host[3]["rounds"] == 4
+    assert host[2] > 0.6 * (~inv).sum()                                    # and the pose is one that explains the inliers
+
+
+def test_batch_past_the_stage_and_the_floor(pkg):
+    """[n65, n1537 x K, n2, n1536] in one launch from a fresh host thread, after n65 alone reserved the staging pair at its 256 KiB
+    floor: the observations alone exceed the floor, so the pair regrows; the LDS is sized for the largest problem while the small
+    ones stage only their own edges; flags and chi2 sit at offsets up to K x 1537.  Every problem equals its single call."""
+    n_big = S.CASES["n1537"]["n"]
+    K = (1 << 18) // (32 * n_big) + 1                               # the smallest K with K x 1537 observations > 256 KiB
+    assert pkg.POSE_OBS_DTYPE.itemsize == 32 and (K - 1) * 32 * n_big <= 1 << 18 < K * 32 * n_big
+    names = ["n65"] + ["n1537"] * K + ["n2", "n1536"]
+    scs = {n: (S.case(n), np.where(S.case(n)["obs"]["valid"] == 0, 5, 1).astype(np.uint8)) for n in set(names)}
+    obs = np.concatenate([scs[n][0]["obs"] for n in names])
+    mark = np.concatenate([scs[n][1] for n in names])
+    off = np.cumsum([0] + [len(scs[n][0]["obs"]) for n in names])
+    single = lambda n: pkg.pose_optimization(scs[n][0]["obs"], S.CAM, scs[n][0]["Tcw0"], outlier=scs[n][1])      # noqa: E731
+    got = {}
+
+    def worker():
+        try:
+            got["first"] = as_bytes(single("n65"))
+            got["batch"] = pkg.pose_optimization_batch(obs, off, [S.CAM] * len(names), [scs[n][0]["Tcw0"] for n in names], outlier=mark)
+            got["again"] = as_bytes(single("n65"))
+            got["rc"] = pkg.matcher_lib().orbx_thread_release_scratch()
+        except Exception as e:      # noqa: BLE001
+            got["error"] = e
+
+    th = threading.Thread(target=worker)
+    th.start(); th.join()
+    assert "error" not in got, got.get("error")
+    one = {n: as_bytes(single(n)) for n in scs}
+    Ts, out, ng, infos = got["batch"]
+    for b, n in enumerate(names):
+        assert as_bytes((Ts[b], out[off[b]:off[b + 1]], int(ng[b]), infos[b])) == one[n], (b, n)
+    assert got["first"] == got["again"] == one["n65"] and got["rc"] == pkg.ORBX_OK
 
 
 def test_batch_equals_single_calls(pkg):
