@@ -926,6 +926,56 @@ int orbs_sim3_ransac_batch(const orbs_pair_t *pairs, const int32_t *offsets, int
                            const int32_t *sets, const int32_t *set_offsets, int32_t *counts, float *models, uint8_t *flags,
                            uint8_t *hit_inliers, orbs_sim3_info_t *infos, int device);
 
+/* ---- PnPsolver (src/PnPsolver.cc:67-950): the EPnP RANSAC Tracking::Relocalization (src/Tracking.cc:1530-1556) runs for every
+ * candidate keyframe, on flat arrays.  One call covers the iterations ONE PnPsolver::iterate call may run, for B problems
+ * (candidates): per set EPnP on the 4 correspondences it names and the reprojection test over all n (k_pnp_ransac); EPnP again on
+ * the inlier set of every iteration that becomes the best one, and on the prior best set the caller carries (k_pnp_refine); then
+ * the replay of the reference's sequential loop (k_pnp_select).  Three launches on one stream for ALL problems, one
+ * synchronisation.  EPnP is in double as in the reference; the five OpenCV calls it makes are this
+ * library's own Jacobi routines (csrc/orbx_jacobi_eig.h, csrc/orbx_jacobi_svd.h), not OpenCV's.  Counts are integer: two calls
+ * give the same bytes.
+ *
+ * corrs [n]: the world position of the map point, the undistorted keypoint, mvLevelSigma2[octave]; a correspondence's threshold
+ * is sigma2 * th2 in float.  problem: K = fx fy cx cy; min_inliers and max_iterations as orbp_pnp_parameters adjusts them;
+ * iterations_done = mnIterations before the call; prior_best_inliers = mnBestInliers, and prior_best_flags [n] = mvbBestInliers
+ * (NULL when the prior count is 0).  sets [iterations][4]: indices into corrs, four different ones per set.
+ * Per iteration: counts; models [iterations][12] double (R row-major, t; may be NULL); tcws [iterations][16] float (may be NULL);
+ * choices [iterations]: which beta approximation (1-3) gave the least reprojection error (may be NULL); flags [iterations][n]
+ * (may be NULL).  Per refinement slot (slot i < iterations: iteration i's own flags; slot `iterations`: the prior best set):
+ * refined_counts [iterations + 1], -1 where the slot is no record and nothing was computed (may be NULL).
+ * inliers [n]: the flags that go with the returned pose; best_flags [n]: mvbBestInliers after the call, to be passed back.
+ * info: hit_iteration (the iteration at which a refinement counted > min_inliers) or -1; iterations_run; best_iteration or -1
+ * when the prior best still stands; best_inliers; refined_inliers (at a hit); no_more; pose: ORBP_POSE_NONE, ORBP_POSE_REFINED
+ * (Tcw = mRefinedTcw), ORBP_POSE_BEST (exhausted, Tcw = this call's best iteration's) or ORBP_POSE_PRIOR_BEST (exhausted and the
+ * prior best stands: the caller returns the mBestTcw it kept); best_Tcw: this call's best iteration's pose (zero without one).
+ * A problem with n < min_inliers or without sets launches nothing and answers no_more (:173-177).
+ * NULL pointers, negative sizes, sets for a problem with n < 4 or n < min_inliers, a set index out of range or a set naming a
+ * correspondence twice, decreasing or negative offsets, a sigma2 that is negative or not finite, a prior count that is not
+ * the number of prior flags set: ORBX_ERR_ARG, checked before the device is touched.  No usable GPU: ORBX_ERR_NO_DEVICE; there is
+ * no CPU path.  Scratch, pinned mirror and stream are per host thread (orbx_thread_release_scratch). */
+typedef struct { float w[3]; float u, v; float sigma2; } orbp_corr_t;                                   /* 24 B */
+typedef struct { float K[4]; float th2; int32_t min_inliers, max_iterations, iterations_done, prior_best_inliers; } orbp_problem_t;   /* 36 B */
+#define ORBP_POSE_NONE 0
+#define ORBP_POSE_REFINED 1
+#define ORBP_POSE_BEST 2
+#define ORBP_POSE_PRIOR_BEST 3
+typedef struct { int32_t n, iterations, hit_iteration, iterations_run, best_iteration, best_inliers, refined_inliers, no_more, pose;
+                 float Tcw[16], best_Tcw[16]; } orbp_pnp_info_t;                                       /* 164 B */
+/* Host code, no device: SetRansacParameters (:121-157).  adj_min_inliers = max(int(n * epsilon), min_inliers, min_set);
+ * adj_max_iterations = max(1, min(nIterations, max_iterations)).  min_set != 4, n < 0 or a NULL result: ORBX_ERR_ARG. */
+int orbp_pnp_parameters(int n, double probability, int min_inliers, int max_iterations, int min_set, float epsilon,
+                        int *adj_min_inliers, int *adj_max_iterations);
+int orbp_pnp_ransac(const orbp_corr_t *corrs, int n, const orbp_problem_t *problem, const int32_t *sets, int iterations,
+                    const uint8_t *prior_best_flags, int32_t *counts, double *models, float *tcws, int32_t *choices, uint8_t *flags,
+                    int32_t *refined_counts, uint8_t *inliers, uint8_t *best_flags, orbp_pnp_info_t *info, int device);
+/* B problems in one chain of launches, laid out as orbs_sim3_ransac_batch lays them out: corrs, prior_best_flags, inliers and
+ * best_flags [offsets[B]]; counts, models, tcws, choices [set_offsets[B]]; refined_counts: problem b's iterations_b + 1 slots
+ * start at set_offsets[b] + b; flags: problem b's [iterations_b][n_b] block after those of the problems before it. */
+int orbp_pnp_ransac_batch(const orbp_corr_t *corrs, const int32_t *offsets, int B, const orbp_problem_t *problems,
+                          const int32_t *sets, const int32_t *set_offsets, const uint8_t *prior_best_flags, int32_t *counts,
+                          double *models, float *tcws, int32_t *choices, uint8_t *flags, int32_t *refined_counts, uint8_t *inliers,
+                          uint8_t *best_flags, orbp_pnp_info_t *infos, int device);
+
 /* The host-array matcher entry points keep grow-only device scratch, a pinned mirror and one non-blocking stream
  * PER HOST THREAD (re-entrant without locks: the reference calls matchers from Tracking, LocalMapping and LoopClosing
  * threads at once, src/LocalMapping.cc:223, src/LoopClosing.cc:249).  Nothing is freed implicitly; a thread calls

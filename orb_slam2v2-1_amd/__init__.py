@@ -58,6 +58,14 @@ SIM3_PROBLEM_DTYPE = np.dtype([("Tcw1", "<f4", (16,)), ("Tcw2", "<f4", (16,)), (
                                ("fix_scale", "<i4"), ("min_inliers", "<i4")])
 SIM3_INFO_DTYPE = np.dtype([("n", "<i4"), ("iterations", "<i4"), ("hit_iteration", "<i4"), ("best_iteration", "<i4"),
                             ("best_inliers", "<i4"), ("s", "<f4"), ("R", "<f4", (9,)), ("t", "<f4", (3,)), ("T12", "<f4", (16,))])
+# orbp_corr_t / orbp_problem_t / orbp_pnp_info_t (PnPsolver, pnp_ransac_batch)
+PNP_CORR_DTYPE = np.dtype([("w", "<f4", (3,)), ("u", "<f4"), ("v", "<f4"), ("sigma2", "<f4")])
+PNP_PROBLEM_DTYPE = np.dtype([("K", "<f4", (4,)), ("th2", "<f4"), ("min_inliers", "<i4"), ("max_iterations", "<i4"),
+                              ("iterations_done", "<i4"), ("prior_best_inliers", "<i4")])
+PNP_INFO_DTYPE = np.dtype([("n", "<i4"), ("iterations", "<i4"), ("hit_iteration", "<i4"), ("iterations_run", "<i4"),
+                           ("best_iteration", "<i4"), ("best_inliers", "<i4"), ("refined_inliers", "<i4"), ("no_more", "<i4"),
+                           ("pose", "<i4"), ("Tcw", "<f4", (16,)), ("best_Tcw", "<f4", (16,))])
+PNP_POSE_NONE, PNP_POSE_REFINED, PNP_POSE_BEST, PNP_POSE_PRIOR_BEST = 0, 1, 2, 3
 DB_HIT_DTYPE = np.dtype([("kf_id", "<i4"), ("words", "<i4"), ("flags", "<u4"), ("score", "<f4"), ("acc_score", "<f4"), ("best_kf", "<i4")])
 DB_MAX_KF_ID, DB_MAX_QUERY, DB_MAX_COVISIBLE = (1 << 20) - 1, 8192, 10
 
@@ -93,6 +101,8 @@ POSE_EXPORTS = ["orbo_pose_optimization", "orbo_pose_optimization_batch", "orbo_
 INIT_EXPORTS = ["orbi_initialize", "orbi_initialize_device", "orbi_search"]
 # the Sim3Solver section (prefix orbs_), apart for the same reason
 SIM3_EXPORTS = ["orbs_sim3_iterations", "orbs_sim3_ransac", "orbs_sim3_ransac_batch"]
+# the PnPsolver section (prefix orbp_), apart for the same reason
+PNP_EXPORTS = ["orbp_pnp_parameters", "orbp_pnp_ransac", "orbp_pnp_ransac_batch"]
 # what include/orbx_dev.h declares on top: exported by the developer build only
 DEV_EXPORTS = ["orbx_debug_level_points", "orbx_debug_sincosf", "orbx_debug_blur_patches", "orbm_debug_features_in_area",
                "orbx_debug_blurred_level", "orbx_debug_octree_fallbacks", "orbm_debug_match_path", "orbm_debug_resolve_plan",
@@ -380,6 +390,9 @@ def _load(path, dev):
     L.orbs_sim3_iterations.argtypes = [i32, C.c_double, i32, i32]
     L.orbs_sim3_ransac.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32]
     L.orbs_sim3_ransac_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32]
+    L.orbp_pnp_parameters.argtypes = [i32, C.c_double, i32, i32, i32, f32, C.POINTER(i32), C.POINTER(i32)]
+    L.orbp_pnp_ransac.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
+    L.orbp_pnp_ransac_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
     if dev:
         L.orbx_debug_level_points.argtypes = [vp, i32, i32, i32, vp, i32, C.POINTER(i32)]
         L.orbx_debug_sincosf.argtypes = [vp, i32, vp, vp, i32]
@@ -1457,6 +1470,167 @@ class Sim3Solver:
                                 np.concatenate(drawn), soff, todo[0][1].device)
         for (_, s), r in zip(todo, res):
             s.prime(r)
+
+
+def pnp_parameters(n, probability=0.99, min_inliers=8, max_iterations=300, min_set=4, epsilon=0.4):
+    """orbp_pnp_parameters: PnPsolver::SetRansacParameters (src/PnPsolver.cc:121-157) -> (adjusted min_inliers, adjusted
+    max_iterations).  Host code, no device.  min_set != 4 raises (ORBX_ERR_ARG)."""
+    a, b = C.c_int(0), C.c_int(0)
+    _check(matcher_lib().orbp_pnp_parameters(int(n), float(probability), int(min_inliers), int(max_iterations), int(min_set),
+                                             float(epsilon), C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def pnp_draw_sets(n, iterations, rng):
+    """the minimal sets of PnPsolver::iterate (:188-201): per iteration 4 distinct indices < n, drawn without replacement - the
+    drawn slot is overwritten by the last available index, which is dropped - from a numpy Generator instead of rand()."""
+    if n < 4 and iterations > 0:
+        raise ValueError("pnp_draw_sets: %d correspondences, 4 are needed" % n)
+    sets = np.zeros((int(iterations), 4), np.int32)
+    for it in range(int(iterations)):
+        avail = list(range(n))
+        for j in range(4):
+            k = int(rng.integers(0, len(avail)))
+            sets[it, j] = avail[k]
+            avail[k] = avail[-1]
+            avail.pop()
+    return sets
+
+
+def pnp_problem(K, th2, min_inliers, max_iterations, iterations_done=0, prior_best_inliers=0):
+    p = np.zeros(1, PNP_PROBLEM_DTYPE)
+    p["K"], p["th2"] = [float(k) for k in K], float(th2)
+    p["min_inliers"], p["max_iterations"] = int(min_inliers), int(max_iterations)
+    p["iterations_done"], p["prior_best_inliers"] = int(iterations_done), int(prior_best_inliers)
+    return p
+
+
+def pnp_ransac_batch(corrs, offsets, problems, sets, set_offsets, prior_best_flags=None, device=0):
+    """orbp_pnp_ransac_batch: B problems (relocalisation candidates), one PnPsolver::iterate call each, in one chain of launches.
+    corrs [offsets[B]] PNP_CORR_DTYPE, problems [B] PNP_PROBLEM_DTYPE (pnp_problem), sets [set_offsets[B], 4] indices into each
+    problem's own correspondences, prior_best_flags [offsets[B]] or None
+    -> a list of B dicts: the fields of orbp_pnp_info_t (Tcw, best_Tcw as [4, 4]), counts [its], models [its, 12] float64 (R, t),
+    tcws [its, 4, 4], choices [its], flags [its, n], refined_counts [its + 1], inliers [n], best_flags [n]"""
+    corrs = np.ascontiguousarray(corrs, PNP_CORR_DTYPE)
+    problems = np.ascontiguousarray(problems, PNP_PROBLEM_DTYPE)
+    off, soff = np.ascontiguousarray(offsets, np.int32), np.ascontiguousarray(set_offsets, np.int32)
+    B = len(problems)
+    if len(off) != B + 1 or len(soff) != B + 1:
+        raise ValueError("pnp_ransac_batch: %d problems need %d offsets" % (B, B + 1))
+    sets = np.ascontiguousarray(sets, np.int32).reshape(-1, 4)
+    np_, nh = int(off[-1]), int(soff[-1])
+    if len(corrs) < np_ or len(sets) < nh:
+        raise ValueError("pnp_ransac_batch: the offsets reach beyond the correspondences or the sets")
+    prior = None
+    if prior_best_flags is not None:
+        prior = np.ascontiguousarray(prior_best_flags, np.uint8)
+        if len(prior) < np_:
+            raise ValueError("pnp_ransac_batch: %d prior flags, %d correspondences" % (len(prior), np_))
+    nfl = sum(max(int(soff[b + 1] - soff[b]), 0) * max(int(off[b + 1] - off[b]), 0) for b in range(B))
+    counts, choices = np.zeros(max(nh, 1), np.int32), np.zeros(max(nh, 1), np.int32)
+    models, tcws = np.zeros((max(nh, 1), 12), np.float64), np.zeros((max(nh, 1), 4, 4), np.float32)
+    rcounts = np.full(max(nh, 0) + B + 1, -1, np.int32)
+    flags, inl, best = np.zeros(max(nfl, 1), np.uint8), np.zeros(max(np_, 1), np.uint8), np.zeros(max(np_, 1), np.uint8)
+    infos = np.zeros(max(B, 1), PNP_INFO_DTYPE)
+    cc = corrs if len(corrs) else np.zeros(1, PNP_CORR_DTYPE)
+    ss = sets if len(sets) else np.zeros((1, 4), np.int32)
+    _check(matcher_lib().orbp_pnp_ransac_batch(_p(cc), _p(off), B, _p(problems), _p(ss), _p(soff), None if prior is None else _p(prior),
+                                               _p(counts), _p(models), _p(tcws), _p(choices), _p(flags), _p(rcounts), _p(inl), _p(best),
+                                               _p(infos), int(device)))
+    out, fb = [], 0
+    for b in range(B):
+        n, its = int(off[b + 1] - off[b]), int(soff[b + 1] - soff[b])
+        d = {k: (infos[b][k].copy() if infos[b][k].ndim else infos[b][k].item()) for k in PNP_INFO_DTYPE.names}
+        d["Tcw"], d["best_Tcw"] = d["Tcw"].reshape(4, 4), d["best_Tcw"].reshape(4, 4)
+        h = slice(soff[b], soff[b + 1])
+        d.update(counts=counts[h].copy(), models=models[h].copy(), tcws=tcws[h].copy(), choices=choices[h].copy(),
+                 flags=flags[fb:fb + its * n].reshape(its, n).copy(), refined_counts=rcounts[soff[b] + b:soff[b + 1] + b + 1].copy(),
+                 inliers=inl[off[b]:off[b + 1]].copy(), best_flags=best[off[b]:off[b + 1]].copy())
+        fb += its * n
+        out.append(d)
+    return out
+
+
+class PnPsolver:
+    """ORB_SLAM2::PnPsolver (src/PnPsolver.cc) on the GPU, on flat arrays: corrs [n] PNP_CORR_DTYPE (the world position of the matched
+    map point, the undistorted keypoint, mvLevelSigma2[octave]), K (fx, fy, cx, cy).  Every iterate(k) is ONE device call over the
+    max(max_iterations - iterations, k) sets the reference's loop may run (drawn at the call by pnp_draw_sets from a generator
+    seeded with 0, or the first rows of `sets`); the best set, its count and pose and the iteration counter are carried from call
+    to call as the reference's members are."""
+
+    def __init__(self, corrs, K, device=0):
+        self.corrs = np.ascontiguousarray(corrs, PNP_CORR_DTYPE)
+        self.K, self.device = tuple(float(k) for k in K), int(device)
+        self.rng = np.random.default_rng(0)
+        self.iterations, self.best_inliers, self.best_flags, self.best_Tcw = 0, 0, None, None
+        self.set_ransac_parameters()
+
+    def set_ransac_parameters(self, probability=0.99, min_inliers=8, max_iterations=300, min_set=4, epsilon=0.4, th2=5.991):
+        self.min_inliers, self.max_iterations = pnp_parameters(len(self.corrs), probability, min_inliers, max_iterations, min_set, epsilon)
+        self.th2 = float(th2)
+
+    def problem(self):
+        return pnp_problem(self.K, self.th2, self.min_inliers, self.max_iterations, self.iterations, self.best_inliers)
+
+    def planned(self, k):
+        """how many iterations a call iterate(k) may run: the loop's condition is mnIterations < mRansacMaxIts || nCurrent < k"""
+        return 0 if len(self.corrs) < self.min_inliers else max(self.max_iterations - self.iterations, int(k))
+
+    def draw(self, k, sets=None):
+        its = self.planned(k)
+        if sets is None:
+            return pnp_draw_sets(len(self.corrs), its, self.rng)
+        s = np.ascontiguousarray(sets, np.int32).reshape(-1, 4)
+        if len(s) < its:
+            raise ValueError("PnPsolver: %d sets, %d iterations" % (len(s), its))
+        return s[:its]
+
+    def absorb(self, r):
+        """take one problem's answer of pnp_ransac_batch -> (Tcw [4, 4] or None, no_more, inliers [n] uint8, n_inliers)"""
+        self.last = r
+        self.iterations += r["iterations_run"]
+        if r["best_iteration"] >= 0:
+            self.best_Tcw = r["best_Tcw"].copy()
+        self.best_inliers, self.best_flags = r["best_inliers"], r["best_flags"].copy()
+        if r["pose"] == PNP_POSE_REFINED:
+            return r["Tcw"].copy(), False, r["inliers"].copy(), r["refined_inliers"]
+        if r["pose"] in (PNP_POSE_BEST, PNP_POSE_PRIOR_BEST):
+            return self.best_Tcw.copy(), True, r["inliers"].copy(), r["best_inliers"]
+        return None, bool(r["no_more"]), np.zeros(len(self.corrs), np.uint8), 0
+
+    def iterate(self, k, sets=None):
+        """-> (Tcw [4, 4] or None, no_more, inliers [n] uint8, n_inliers): PnPsolver::iterate (:165-258)"""
+        n = len(self.corrs)
+        if n < self.min_inliers:
+            return None, True, np.zeros(n, np.uint8), 0
+        s = self.draw(k, sets)
+        r = pnp_ransac_batch(self.corrs, [0, n], self.problem(), s, [0, len(s)], self.best_flags, self.device)[0]
+        return self.absorb(r)
+
+    def find(self, sets=None):
+        return self.iterate(self.max_iterations, sets)
+
+    @staticmethod
+    def iterate_all(solvers, k, sets=None):
+        """iterate(k) of several solvers (the live candidates of a Relocalization pass) as ONE batched device call; sets: a list
+        with one array (or None) per solver -> a list of iterate's tuples"""
+        out = [None] * len(solvers)
+        todo = []
+        for i, s in enumerate(solvers):
+            if len(s.corrs) < s.min_inliers:
+                out[i] = (None, True, np.zeros(len(s.corrs), np.uint8), 0)
+            else:
+                todo.append((i, s))
+        if todo:
+            drawn = [s.draw(k, None if sets is None else sets[i]) for i, s in todo]
+            off = np.cumsum([0] + [len(s.corrs) for _, s in todo])
+            soff = np.cumsum([0] + [len(d) for d in drawn])
+            prior = np.concatenate([np.zeros(len(s.corrs), np.uint8) if s.best_flags is None else s.best_flags for _, s in todo])
+            res = pnp_ransac_batch(np.concatenate([s.corrs for _, s in todo]), off, np.concatenate([s.problem() for _, s in todo]),
+                                   np.concatenate(drawn), soff, prior, todo[0][1].device)
+            for (i, s), r in zip(todo, res):
+                out[i] = s.absorb(r)
+        return out
 
 
 def match_windows(kun, desc, uright, geom, queries, query_desc, holder, ext_blocks=None, max_dist=100,

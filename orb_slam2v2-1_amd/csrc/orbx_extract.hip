@@ -43,6 +43,7 @@ extern "C" int orbx_thread_release_scratch(void) {
     orbx_internal_release_pose_scratch();
     orbx_internal_release_init_scratch();
     orbx_internal_release_sim3_scratch();
+    orbx_internal_release_pnp_scratch();
     return ORBX_OK;
 }
 #ifdef ORBX_DEVELOPER

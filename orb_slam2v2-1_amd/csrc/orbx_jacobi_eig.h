@@ -80,4 +80,66 @@ __device__ __forceinline__ void jacobi_eig4(const float *N, float *eval, float *
         }
     }
 }
+
+// jacobi_eig<N>: the same rotations on a symmetric double N x N held in memory (PnPsolver: the 12x12 MtM and the 3x3 PCA matrix;
+// DESIGN.md section 6, "k_pnp_*"; tests/pnp_ref.py).  A is overwritten (its diagonal ends as the eigenvalues), V [N][N] is set to
+// the identity and ends with the eigenvectors in its COLUMNS.  thr = JE_EPS sqrt(sum of all N N A[i][j]^2, row-major); pairs
+// (p, q) in the cyclic order; g, A[p][p] and A[q][q] are read before anything of the pair is written.  The 2 N row updates of a
+// pair - the N - 2 rows k of A, the two diagonal entries, the N rows of V - are independent, so with COOP the threads tid, tid + nth,
+// .. of a workgroup share them (A and V in LDS, two barriers per pair) and leave the bytes one thread leaves.
+template <int N, bool COOP>
+__device__ __forceinline__ void jacobi_eig(double *A, double *V, int tid, int nth) {
+    double ss = 0.0;
+    for (int k = 0; k < N * N; k++) ss += A[k] * A[k];
+    const double thr = JE_EPS * sqrt(ss);
+    for (int k = tid; k < N * N; k += nth) V[k] = (k % (N + 1) == 0) ? 1.0 : 0.0;
+    if (COOP) __syncthreads();
+    for (int sweep = 0; sweep < JE_MAX_SWEEPS; sweep++) {
+        bool changed = false;
+        for (int p = 0; p < N - 1; p++) {
+            for (int q = p + 1; q < N; q++) {
+                const double g = A[p * N + q], app = A[p * N + p], aqq = A[q * N + q];
+                if (COOP) __syncthreads();
+                if (fabs(g) > thr) {
+                    changed = true;
+                    const double theta = (aqq - app) / (2.0 * g);
+                    double t = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));
+                    if (theta < 0.0) t = -t;
+                    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+                    for (int k = tid; k < 2 * N; k += nth) {
+                        if (k == p) { A[p * N + p] = app - t * g; A[p * N + q] = 0.0; }
+                        else if (k == q) { A[q * N + q] = aqq + t * g; A[q * N + p] = 0.0; }
+                        else if (k < N) {
+                            const double x = A[k * N + p], y = A[k * N + q];
+                            A[k * N + p] = c * x - s * y; A[p * N + k] = A[k * N + p];
+                            A[k * N + q] = s * x + c * y; A[q * N + k] = A[k * N + q];
+                        } else {
+                            const int r = k - N;
+                            const double x = V[r * N + p], y = V[r * N + q];
+                            V[r * N + p] = c * x - s * y;
+                            V[r * N + q] = s * x + c * y;
+                        }
+                    }
+                }
+                if (COOP) __syncthreads();
+            }
+        }
+        if (!changed) break;
+    }
+}
+
+// the order cvSVD gives a symmetric positive semi-definite matrix: w[j] = |A[j][j]|, order[k] = the columns by descending w, a stable
+// selection (of equal values the lower column first; NaN compares false and stays where it is)
+template <int N>
+__device__ __forceinline__ void jacobi_eig_order(const double *A, double *w, int *order) {
+    for (int j = 0; j < N; j++) w[j] = fabs(A[j * N + j]);
+    unsigned used = 0;
+    for (int k = 0; k < N; k++) {
+        int best = -1;
+        for (int j = 0; j < N; j++)
+            if (!(used >> j & 1) && (best < 0 || w[j] > w[best])) best = j;
+        used |= 1u << best;
+        order[k] = best;
+    }
+}
 #endif

@@ -86,6 +86,7 @@ public:
     cv::Mat mTcw;
     void SetPose(cv::Mat Tcw) { mTcw = Tcw.clone(); }   // src/Frame.cc:262-266, without the derived Rcw / tcw / Ow the matchers do not read
     std::vector<float> mvScaleFactors, mvInvScaleFactors, mvInvLevelSigma2;
+    std::vector<float> mvLevelSigma2;   // include/Frame.h: read by PnPsolver
     static float mnMinX, mnMaxX, mnMinY, mnMaxY;
     int mnScaleLevels = 0;          // src/Frame.cc:69
     float mfScaleFactor = 0.f, mfLogScaleFactor = 0.f;  // :70-71
