@@ -921,7 +921,11 @@ int orbs_sim3_ransac(const orbs_pair_t *pairs, int n, const orbs_problem_t *prob
 /* B problems in one chain of launches: problem b owns pairs offsets[b] .. offsets[b+1]-1 and sets set_offsets[b] ..
  * set_offsets[b+1]-1 (its sets index ITS pairs from 0).  counts [set_offsets[B]], models [set_offsets[B]][13], flags: problem
  * b's [iterations_b][n_b] block after those of the problems before it, hit_inliers [offsets[B]], infos [B].  Each problem's
- * results are those of its single call.  An empty problem is allowed and answers "no hit". */
+ * results are those of its single call.  An empty problem is allowed and answers "no hit".
+ * offsets[0] and set_offsets[0] need not be 0 (a caller may pass offsets + k, set_offsets + k, problems + k, B - k to run the
+ * problems from k on, with the arrays' base pointers unchanged): whatever is indexed by a pair or by a set - pairs, sets,
+ * counts, models, hit_inliers - is read and written at the positions the offsets name, and nothing before offsets[0] /
+ * set_offsets[0] is touched; flags and infos are counted from the call's own first problem (flags[0], infos[0]). */
 int orbs_sim3_ransac_batch(const orbs_pair_t *pairs, const int32_t *offsets, int B, const orbs_problem_t *problems,
                            const int32_t *sets, const int32_t *set_offsets, int32_t *counts, float *models, uint8_t *flags,
                            uint8_t *hit_inliers, orbs_sim3_info_t *infos, int device);
@@ -970,7 +974,11 @@ int orbp_pnp_ransac(const orbp_corr_t *corrs, int n, const orbp_problem_t *probl
                     int32_t *refined_counts, uint8_t *inliers, uint8_t *best_flags, orbp_pnp_info_t *info, int device);
 /* B problems in one chain of launches, laid out as orbs_sim3_ransac_batch lays them out: corrs, prior_best_flags, inliers and
  * best_flags [offsets[B]]; counts, models, tcws, choices [set_offsets[B]]; refined_counts: problem b's iterations_b + 1 slots
- * start at set_offsets[b] + b; flags: problem b's [iterations_b][n_b] block after those of the problems before it. */
+ * start at set_offsets[b] + b; flags: problem b's [iterations_b][n_b] block after those of the problems before it.
+ * offsets[0] and set_offsets[0] need not be 0, as there: corrs, prior_best_flags, sets, counts, models, tcws, choices, inliers
+ * and best_flags are read and written at the positions the offsets name and nothing before them is touched; flags and infos
+ * start at flags[0] and infos[0]; and in refined_counts' set_offsets[b] + b the b is counted in THIS call, so the
+ * set_offsets[B] - set_offsets[0] + B slots written start at set_offsets[0]. */
 int orbp_pnp_ransac_batch(const orbp_corr_t *corrs, const int32_t *offsets, int B, const orbp_problem_t *problems,
                           const int32_t *sets, const int32_t *set_offsets, const uint8_t *prior_best_flags, int32_t *counts,
                           double *models, float *tcws, int32_t *choices, uint8_t *flags, int32_t *refined_counts, uint8_t *inliers,

@@ -167,6 +167,9 @@ class FrontEnd:
             self.side.wait_stream(self.side2)     # the matcher of the step before ran there and uses the same stereo scratch of the handle
         self._match(self.ex, j, self.side.cuda_stream)
         self._publish_side(j, step)
+        ev = torch.cuda.Event()
+        ev.record(self.side)
+        self._ev_side[j] = ev                     # whoever reads set j on another stream (fetch's download) waits for this matcher too
         main.wait_stream(self.side)
 
     def _publish_side(self, j, step, side=None):

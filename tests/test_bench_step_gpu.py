@@ -108,6 +108,19 @@ def test_bench_step_rotating_batches(mode, w, h, nf, B, steps):
 
 @pytest.mark.parametrize("mode", ["pipelined", "pipelined_late", "pyramid_ahead_only", "plain"])
 def test_host_streaming_rotating_batches(mode):
+    _host_streaming(mode)
+
+
+def test_host_streaming_last_fetch_waits_for_the_matcher_it_flushes():
+    """The last step's matcher is still owed when its results are fetched: fetch issues it on the side stream, behind everything on
+    the compute stream, and the download must wait for it, not only for the step's own kernels.  The compute stream is parked behind
+    other work between the last step and its fetch, so a download that left early carries the stereo results the buffer set held
+    three steps before.  TWO batches rotate through the THREE buffer sets here, so those are the other batch's (with three batches
+    a buffer set always meets the same batch again, and only a download torn by the running matcher would show)."""
+    _host_streaming("pipelined", park_before_last_fetch=True, nsets=2)
+
+
+def _host_streaming(mode, park_before_last_fetch=False, nsets=3):
     """End to end from host memory (FrontEnd.enable_host_streaming): THREE different batches in pinned host memory arrive by
     asynchronous copies on an upload stream into three image buffers while other batches compute, results leave on a download
     stream; eight steps without a host synchronisation until the last results are waited for.  Every result still in the pinned
@@ -115,7 +128,7 @@ def test_host_streaming_rotating_batches(mode):
     its buffer, a pyramid built ahead of its upload, or a download that left before the (lagged) matcher would show."""
     import torch
     pl, ref = _pipeline(), _ref()
-    w, h, nf, B, nsets, steps = 752, 480, 600, 6, 3, 8
+    w, h, nf, B, steps = 752, 480, 600, 6, 8
     fe = pl.FrontEnd(w, h, nf, True, B, prefetch=(mode != "plain"), lag_stereo=mode.startswith("pipelined"), stereo_late=(mode == "pipelined_late"))
     exps = [ref.run_pool(ref.stereo_frame, [(w, h, nf, 1700 + 50 * s + i, fe.mbf, fe.mb) for i in range(B)]) for s in range(nsets)]
     fe.upload(np.stack([e["left"] for e in exps[0]]), np.stack([e["right"] for e in exps[0]]))
@@ -133,6 +146,9 @@ def test_host_streaming_rotating_batches(mode):
             fe.fetch(i - 1)
         if i + 2 < steps:
             fe.submit(i + 2, *src[(i + 2) % nsets])
+    if park_before_last_fetch:
+        for _ in range(4):
+            x = (x @ x) * 1e-4
     fe.fetch(steps - 1)
     bad = []
     for i in range(steps - fe.ring.nbuf, steps):

@@ -69,6 +69,56 @@ def test_batch_equals_the_single_calls(pkg):
     assert outs[2]["iterations"] == 0 and outs[2]["n"] == 9 and outs[2]["no_more"] == 1          # n_9: correspondences but no iteration
 
 
+def sentinel(count, dtype):
+    """an output array whose every byte is 0xA5: what a call did not write still reads so"""
+    return np.full(count * np.dtype(dtype).itemsize, 0xA5, np.uint8).view(dtype)
+
+
+def untouched(a):
+    return bool((np.ascontiguousarray(a).view(np.uint8) == 0xA5).all())
+
+
+def test_batch_whose_first_offset_is_not_zero(pkg):
+    """the C ABI called on problems 1 .. of the four-problem batch: offsets + 1, set_offsets + 1, problems + 1, B - 1, the arrays'
+    base pointers as in the full call.  Then offsets[0] = 60 and set_offsets[0] = 35 (p0, h0 of csrc/orbx_pnp.hip).  Every output
+    indexed by a correspondence or a set lands where the full call puts it and equals the single call's; refined_counts, flags
+    and infos are counted from this call's first problem; no byte of problem 0's ranges and none behind the used ranges is written"""
+    b = S.batch(S.BATCH_3)
+    off, soff, B = b["offsets"], b["set_offsets"], len(b["problems"])
+    p0, h0, np_, nh = int(off[1]), int(soff[1]), int(off[B]), int(soff[B])
+    assert B == 4 and p0 == 60 and h0 == 35 and nh > h0
+    sets = np.ascontiguousarray(b["sets"], np.int32)
+    nfl = [int(soff[k + 1] - soff[k]) * int(off[k + 1] - off[k]) for k in range(B)]
+    counts, choices, rc = sentinel(nh, np.int32), sentinel(nh, np.int32), sentinel(nh + B, np.int32)
+    models, tcws = sentinel(nh * 12, np.float64).reshape(nh, 12), sentinel(nh * 16, np.float32).reshape(nh, 4, 4)
+    flags, inl, best, infos = sentinel(sum(nfl), np.uint8), sentinel(np_, np.uint8), sentinel(np_, np.uint8), sentinel(B, R.INFO_DTYPE)
+    p = lambda a: a.ctypes.data   # noqa: E731
+    assert pkg.matcher_lib().orbp_pnp_ransac_batch(p(b["corrs"]), p(off) + 4, B - 1, p(b["problems"]) + b["problems"].itemsize, p(sets), p(soff) + 4,
+                                                   p(b["prior"]), p(counts), p(models), p(tcws), p(choices), p(flags), p(rc), p(inl), p(best),
+                                                   p(infos), 0) == pkg.ORBX_OK
+    for a, first in ((counts, h0), (choices, h0), (models, h0), (tcws, h0), (rc, h0), (inl, p0), (best, p0)):
+        assert untouched(a[:first])                                # problem 0's ranges
+    singles = {1: None, 2: run(pkg, S.BATCH_3[1]), 3: run(pkg, S.BATCH_3[2])}
+    fb = 0
+    for k in range(1, B):
+        c = k - 1                                                  # the problem's number in this call
+        h, q = slice(soff[k], soff[k + 1]), slice(off[k], off[k + 1])
+        r = slice(soff[k] + c, soff[k + 1] + c + 1)                # refined_counts: set_offsets[b] + b, b counted in THIS call
+        o = singles[k]
+        if o is None:                                              # the empty problem
+            assert (infos[c]["n"], infos[c]["iterations"], infos[c]["no_more"], infos[c]["pose"]) == (0, 0, 1, 0) and list(rc[r]) == [-1]
+            continue
+        for name in R.INFO_DTYPE.names:
+            assert np.asarray(infos[c][name]).tobytes() == np.asarray(o[name], R.INFO_DTYPE[name].base).tobytes(), (k, name)
+        assert (inl[q] == o["inliers"]).all() and (best[q] == o["best_flags"]).all() and (rc[r] == o["refined_counts"]).all()
+        assert counts[h].tobytes() == o["counts"].tobytes() and choices[h].tobytes() == o["choices"].tobytes()
+        assert models[h].tobytes() == o["models"].tobytes() and tcws[h].tobytes() == o["tcws"].tobytes()
+        assert flags[fb:fb + nfl[k]].tobytes() == o["flags"].tobytes()                  # flags start at flags[0]
+        fb += nfl[k]
+    assert fb == sum(nfl[1:]) and untouched(flags[fb:]) and untouched(infos[B - 1:])
+    assert untouched(rc[h0 + (nh - h0) + B - 1:]) and not untouched(rc[h0:h0 + (nh - h0) + B - 1])
+
+
 def test_two_calls_through_the_c_abi(pkg):
     """the state carried by the caller: the first call's best flags, best count and iterations run go into the second call, in which
     a qualifying iteration that is no record returns the refinement of the PRIOR set"""

@@ -105,6 +105,42 @@ def test_batch_equals_the_single_calls(pkg):
     assert outs[2]["iterations"] == 0 and outs[2]["n"] == 19 and outs[2]["hit_iteration"] == -1      # n_19: pairs but no iteration
 
 
+def test_batch_whose_first_offset_is_not_zero(pkg):
+    """the C ABI called on problems 1 .. of the four-problem batch: offsets + 1, set_offsets + 1, problems + 1, B - 1, the arrays'
+    base pointers as in the full call.  Then offsets[0] = 60 and set_offsets[0] > 0 (p0, h0 of csrc/orbx_sim3.hip).  counts, models
+    and hit_inliers land where the full call puts them and equal the single calls'; flags and infos are counted from this call's
+    first problem; no byte of problem 0's ranges and none behind the used ranges is written"""
+    b = S.batch(S.BATCH_3)
+    off, soff, B = b["offsets"], b["set_offsets"], len(b["problems"])
+    p0, h0, np_, nh = int(off[1]), int(soff[1]), int(off[B]), int(soff[B])
+    assert B == 4 and p0 == 60 and h0 > 0 and nh > h0
+    sets = np.ascontiguousarray(b["sets"], np.int32)
+    nfl = [int(soff[k + 1] - soff[k]) * int(off[k + 1] - off[k]) for k in range(B)]
+    sentinel = lambda count, dtype: np.full(count * np.dtype(dtype).itemsize, 0xA5, np.uint8).view(dtype)   # noqa: E731
+    untouched = lambda a: bool((np.ascontiguousarray(a).view(np.uint8) == 0xA5).all())                        # noqa: E731
+    counts, models = sentinel(nh, np.int32), sentinel(nh * 13, np.float32).reshape(nh, 13)
+    flags, hit, infos = sentinel(sum(nfl), np.uint8), sentinel(np_, np.uint8), sentinel(B, S.INFO_DTYPE)
+    p = lambda a: a.ctypes.data   # noqa: E731
+    assert pkg.matcher_lib().orbs_sim3_ransac_batch(p(b["pairs"]), p(off) + 4, B - 1, p(b["problems"]) + b["problems"].itemsize, p(sets), p(soff) + 4,
+                                                    p(counts), p(models), p(flags), p(hit), p(infos), 0) == pkg.ORBX_OK
+    assert untouched(counts[:h0]) and untouched(models[:h0]) and untouched(hit[:p0])                        # problem 0's ranges
+    singles = {1: None, 2: run(pkg, S.BATCH_3[1]), 3: run(pkg, S.BATCH_3[2])}
+    fb = 0
+    for k in range(1, B):
+        c = k - 1                                                  # the problem's number in this call
+        h, q = slice(soff[k], soff[k + 1]), slice(off[k], off[k + 1])
+        o = singles[k]
+        if o is None:                                              # the empty problem
+            assert (infos[c]["n"], infos[c]["iterations"], infos[c]["hit_iteration"], infos[c]["best_iteration"]) == (0, 0, -1, -1)
+            continue
+        for name in S.INFO_DTYPE.names:
+            assert np.asarray(infos[c][name]).tobytes() == np.asarray(o[name], S.INFO_DTYPE[name].base).tobytes(), (k, name)
+        assert (hit[q] == o["hit_inliers"]).all() and counts[h].tobytes() == o["counts"].tobytes() and models[h].tobytes() == o["models"].tobytes()
+        assert flags[fb:fb + nfl[k]].tobytes() == o["flags"].tobytes()                  # flags start at flags[0]
+        fb += nfl[k]
+    assert fb == sum(nfl[1:]) and untouched(flags[fb:]) and untouched(infos[B - 1:])
+
+
 def test_python_solver_chunks_as_the_restatement(pkg):
     import sim3_ref as R
     for name in ("hit_60", "exhausted_60", "n_19"):
