@@ -152,6 +152,7 @@ def lib():
         L.oracle_search_by_sim3.restype = i32
         L.oracle_search_by_sim3.argtypes = [vp, vp, i32, vp, vp, i32, G, G, vp, i32, f32, K, vp, vp, f32, vp, vp, vp, vp, vp, vp,
                                             f32, vp]
+        L.oracle_sim3_pair_window_queries.argtypes = [i32, i32, G, vp, i32, f32, K, vp, vp, f32, vp, vp, vp, vp, f32, vp, vp]
         L.oracle_predict_scale_ratio.restype = i32
         L.oracle_predict_scale_ratio.argtypes = [f32, f32, i32]
         L.oracle_is_in_frustum.argtypes = [vp, vp, i32, vp, K, G, f32, f32, i32, vp]
@@ -530,6 +531,16 @@ def search_by_sim3(k1, d1, k2, d2, geom, sf, log_sf, cam, T1w, T2w, s12, R12, t1
                                     float(log_sf), C.byref(cam), _p(T1), _p(T2), float(s12), _p(R), _p(t), _p(pts1),
                                     _p(pd1), _p(pts2), _p(pd2), float(th), _p(m12))
     return n, m12
+
+
+def sim3_pair_window_queries(geom, sf, log_sf, cam, T1w, T2w, s12, R12, t12, pts1, pts2, th):
+    """the two window-query lists of SearchBySim3 -> (q1 [n1]: KF1's points in KF2's image, q2 [n2]: KF2's points in KF1's image)"""
+    pts1 = np.ascontiguousarray(pts1, MP3D_DTYPE); pts2 = np.ascontiguousarray(pts2, MP3D_DTYPE)
+    sf = _f32(sf); T1 = _f32(T1w); T2 = _f32(T2w); R = _f32(R12); t = _f32(t12)
+    q1 = np.zeros(len(pts1), WINDOW_DTYPE); q2 = np.zeros(len(pts2), WINDOW_DTYPE)
+    lib().oracle_sim3_pair_window_queries(len(pts1), len(pts2), C.byref(geom), _p(sf), len(sf), float(log_sf), C.byref(cam), _p(T1), _p(T2),
+                                          float(s12), _p(R), _p(t), _p(pts1), _p(pts2), float(th), _p(q1), _p(q2))
+    return q1, q2
 
 
 def distinctive_descriptor(desc):

@@ -220,6 +220,11 @@ int oracle_fuse_sim3(const oracle_kp_t *kun, const uint8_t *desc, int n, const o
                      int nlevels, float log_sf, const oracle_cam_t *cam, const float *Scw,
                      const oracle_mappoint3d_t *pts, const uint8_t *pdesc, int m, const int32_t *bad, int32_t *slot,
                      const int32_t *ext_bad, float th, int32_t *best_idx, int32_t *replace);
+/* the two projections of SearchBySim3 as window queries (q1[n1]: KF1's points in KF2's image, q2[n2]: the converse) */
+void oracle_sim3_pair_window_queries(int n1, int n2, const oracle_grid_geom_t *g, const float *sf, int nlevels, float log_sf,
+                                     const oracle_cam_t *cam, const float *T1w, const float *T2w, float s12, const float *R12,
+                                     const float *t12, const oracle_mappoint3d_t *pts1, const oracle_mappoint3d_t *pts2, float th,
+                                     oracle_window_query_t *q1, oracle_window_query_t *q2);
 int oracle_search_by_sim3(const oracle_kp_t *k1, const uint8_t *d1, int n1, const oracle_kp_t *k2, const uint8_t *d2,
                           int n2, const oracle_grid_geom_t *g, const oracle_grid_geom_t *ga, const float *sf, int nlevels,
                           float log_sf,

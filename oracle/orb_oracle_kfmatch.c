@@ -254,14 +254,12 @@ int oracle_fuse_sim3(const oracle_kp_t *kun, const uint8_t *desc, int n, const o
     return nFused;
 }
 
-/* SearchBySim3 :1104-1328.  pts1[i].valid = pMP && !vbAlreadyMatched1[i] && !isBad (same for 2).
- * T1w / T2w: keyframe poses (4x4); R12 3x3 row-major, t12[3].  match12[n1] out: index in KF2 or -1. */
-int oracle_search_by_sim3(const oracle_kp_t *k1, const uint8_t *d1, int n1, const oracle_kp_t *k2, const uint8_t *d2,
-                          int n2, const oracle_grid_geom_t *g, const oracle_grid_geom_t *ga, const float *sf, int nlevels,
-                          float log_sf,
-                          const oracle_cam_t *cam, const float *T1w, const float *T2w, float s12, const float *R12,
-                          const float *t12, const oracle_mappoint3d_t *pts1, const uint8_t *pd1,
-                          const oracle_mappoint3d_t *pts2, const uint8_t *pd2, float th, int32_t *match12) {
+/* the two projections of SearchBySim3 (:1150-1201, :1230-1281) as window queries: q1[n1] the points of KF1 in KF2's image,
+ * q2[n2] the points of KF2 in KF1's image */
+void oracle_sim3_pair_window_queries(int n1, int n2, const oracle_grid_geom_t *g, const float *sf, int nlevels, float log_sf,
+                                     const oracle_cam_t *cam, const float *T1w, const float *T2w, float s12, const float *R12,
+                                     const float *t12, const oracle_mappoint3d_t *pts1, const oracle_mappoint3d_t *pts2, float th,
+                                     oracle_window_query_t *q1, oracle_window_query_t *q2) {
     float sR12[9], sR21[9], t21[3];
     const float a12 = s12, a21 = (float)(1.0 / (double)s12);
     for (int r = 0; r < 3; r++)
@@ -274,8 +272,6 @@ int oracle_search_by_sim3(const oracle_kp_t *k1, const uint8_t *d1, int n1, cons
         for (int k = 0; k < 3; k++) s += (double)sR21[i * 3 + k] * (double)t12[k];
         t21[i] = (float)(s * -1.0);
     }
-    oracle_window_query_t *q1 = (oracle_window_query_t *)malloc(sizeof(*q1) * (n1 > 0 ? n1 : 1));
-    oracle_window_query_t *q2 = (oracle_window_query_t *)malloc(sizeof(*q2) * (n2 > 0 ? n2 : 1));
     for (int dir = 0; dir < 2; dir++) {
         const int np = dir ? n2 : n1;
         const oracle_mappoint3d_t *pts = dir ? pts2 : pts1;
@@ -304,6 +300,19 @@ int oracle_search_by_sim3(const oracle_kp_t *k1, const uint8_t *d1, int n1, cons
             q[i].min_level = lvl - 1; q[i].max_level = lvl;
         }
     }
+}
+
+/* SearchBySim3 :1104-1328.  pts1[i].valid = pMP && !vbAlreadyMatched1[i] && !isBad (same for 2).
+ * T1w / T2w: keyframe poses (4x4); R12 3x3 row-major, t12[3].  match12[n1] out: index in KF2 or -1. */
+int oracle_search_by_sim3(const oracle_kp_t *k1, const uint8_t *d1, int n1, const oracle_kp_t *k2, const uint8_t *d2,
+                          int n2, const oracle_grid_geom_t *g, const oracle_grid_geom_t *ga, const float *sf, int nlevels,
+                          float log_sf,
+                          const oracle_cam_t *cam, const float *T1w, const float *T2w, float s12, const float *R12,
+                          const float *t12, const oracle_mappoint3d_t *pts1, const uint8_t *pd1,
+                          const oracle_mappoint3d_t *pts2, const uint8_t *pd2, float th, int32_t *match12) {
+    oracle_window_query_t *q1 = (oracle_window_query_t *)malloc(sizeof(*q1) * (n1 > 0 ? n1 : 1));
+    oracle_window_query_t *q2 = (oracle_window_query_t *)malloc(sizeof(*q2) * (n2 > 0 ? n2 : 1));
+    oracle_sim3_pair_window_queries(n1, n2, g, sf, nlevels, log_sf, cam, T1w, T2w, s12, R12, t12, pts1, pts2, th, q1, q2);
     int32_t *m1 = (int32_t *)malloc(sizeof(int32_t) * (n1 > 0 ? n1 : 1)), *m2 = (int32_t *)malloc(sizeof(int32_t) * (n2 > 0 ? n2 : 1));
     int32_t *b1 = (int32_t *)malloc(sizeof(int32_t) * (n1 > 0 ? n1 : 1)), *b2 = (int32_t *)malloc(sizeof(int32_t) * (n2 > 0 ? n2 : 1));
     oracle_best_in_windows(k2, d2, NULL, n2, g, ga, q1, pd1, n1, NULL, nlevels, m1, b1);   /* KF1 points into KF2 */
