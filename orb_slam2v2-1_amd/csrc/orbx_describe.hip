@@ -324,6 +324,38 @@ __global__ __launch_bounds__(256) void k_blur_levels(const uint8_t *__restrict__
     }
 }
 
+// k_describe's horizontal pass for patch alignment SH (the patch origin's byte inside its dword; wave-uniform).  Output jj of an
+// item is the 7-tap sum over the bytes SH + jj .. SH + jj + 6 of the item's 16 source bytes: dword m of the window's weights is
+// word m of K7 << 8 (SH + jj), K7 = the seven taps as bytes.  With SH known at compile time the words that are zero for EVERY
+// taps are known too, and their products are left out: 10 v_dot4 per item for each SH (2+2+3+3, 2+3+3+2, 3+3+2+2, 3+2+2+3)
+// where weights shifted at run time paid for 13.  K7 is a literal for the flavours with literal taps (the weights are then
+// constants), the handle's for ORBX_GAUSS_FIXED_TAPS (scalar shifts by constants).
+__device__ __forceinline__ constexpr uint32_t desc_hweight(unsigned long long K7, int o, int m) {
+    const int s = 8 * o - 32 * m;
+    return s >= 64 || s <= -64 ? 0u : s >= 0 ? (uint32_t)(K7 << s) : (uint32_t)(K7 >> -s);
+}
+template <int SH>
+__device__ __forceinline__ void desc_hpass(const uint8_t *P, uint8_t *Tt, const uint32_t (&hitem)[DESC_H_ITERS], unsigned long long K7) {
+    // round `it`: this lane's item (row r, column group cg) of the list c_reach.hitem - only what lies inside the disc
+#pragma unroll
+    for (int it = 0; it < DESC_H_ITERS; it++) {
+        const uint32_t *pr = (const uint32_t *)(P + (hitem[it] & 0xFFFFu));   // row r, dwords cg .. cg+3 = bytes 4cg .. 4cg+15
+        const uint32_t d[4] = {pr[0], pr[1], pr[2], pr[3]};
+        uint32_t oo[4];
+#pragma unroll
+        for (int jj = 0; jj < 4; jj++) {   // window bytes SH+jj .. SH+jj+6 <= 12 (<= 65535 in total)
+            uint32_t acc = 0u;
+#pragma unroll
+            for (int m = 0; m < 4; m++)
+                if (4 * m + 3 >= SH + jj && 4 * m <= SH + jj + 6) acc = __builtin_amdgcn_udot4(d[m], desc_hweight(K7, SH + jj, m), acc, false);
+            oo[jj] = acc;
+        }
+        uint16_t *dst = (uint16_t *)(Tt + (hitem[it] >> 16));   // column 4cg + jj, row r: four 16-bit stores off one address
+#pragma unroll
+        for (int jj = 0; jj < 4; jj++) dst[jj * (TCS / 2)] = (uint16_t)oo[jj];
+    }
+}
+
 template <int GAUSS, bool SPLIT>
 __global__ __launch_bounds__(64 * DESC_WAVES) __attribute__((amdgpu_waves_per_eu(7, 7))) void k_describe(
     const uint8_t *__restrict__ pyr, size_t pyrImgBytes, const LevelGeom *__restrict__ geom, int nlevels,
@@ -334,52 +366,57 @@ __global__ __launch_bounds__(64 * DESC_WAVES) __attribute__((amdgpu_waves_per_eu
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     int bx, b;
     xcd_block_map(bx, b);   // all patches of an image are read through ONE L2
-    int o = bx * DESC_WAVES + wave;
     PHASE("locate");
-    // locate (level, k) of output ordinal o: level-major concatenation (:1076-1104)
-    int l = 0, base = 0, total = 0, obefore = 0;
-    {   // lane i < nlevels holds the count of level i: ONE load, a prefix sum inside the first DPP row (16 lanes >= ORBX_MAX_LEVELS:
-        // four row_shr additions, no LDS round trips), a ballot
-        static_assert(ORBX_MAX_LEVELS <= 16, "the level counts fit one DPP row");
-        const int c = lane < nlevels ? lvlCnt[b * nlevels + lane] : 0;
-        int inc = c;
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xf, 0xf, true);   // row_shr:1
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xf, 0xf, true);   // row_shr:2
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xf, 0xf, true);   // row_shr:4
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x118, 0xf, 0xf, true);   // row_shr:8
-        total = __builtin_amdgcn_readlane(inc, ORBX_MAX_LEVELS - 1);
-        if (SPLIT) {
-            if (grp.writeCounts && bx == 0 && threadIdx.x == 0) counts[b] = min(total, cap);
-            // keypoints in front of this launch's first level (0 for a launch that starts at level 0; the scratch arrays of the later
-            // levels are indexed from their own first keypoint)
-            const int before = grp.lvBegin > 0 ? __builtin_amdgcn_readlane(inc, max(grp.lvBegin - 1, 0)) : 0;
-            if (bx >= grp.copyBlock0) {
-                // move the records of the levels [lvEnd, nlevels) from the scratch arrays to their place behind this launch's levels
-                const int cA = __builtin_amdgcn_readlane(inc, grp.lvEnd - 1), cB = total - cA;
-                const int t = threadIdx.x, i = (bx - grp.copyBlock0) * DESC_COPY_PER_BLOCK + (t >> 4), part = t & 15;
-                if (i < cB && cA + i < cap && part < 15) {
-                    const size_t si = (size_t)b * cap + i, di = (size_t)b * cap + cA + i;
-                    if (part < 7) ((uint32_t *)(kps + di))[part] = ((const uint32_t *)(grp.kpsScratch + si))[part];
-                    else ((uint32_t *)(desc + di * 32))[part - 7] = ((const uint32_t *)(grp.descScratch + si * 32))[part - 7];
-                }
-                return;
-            }
-            o += before;   // ordinal over all levels
-            obefore = before;
-            const unsigned long long hit = __ballot(lane >= grp.lvBegin && lane < grp.lvEnd && o < inc);
-            if (!hit || o - before >= cap) return;  // wave-uniform
-            l = __builtin_ctzll(hit);
-        } else {   // the usual launch: every level, into the caller's arrays
-            if (bx == 0 && threadIdx.x == 0) counts[b] = min(total, cap);
-            const unsigned long long hit = __ballot(lane < nlevels && o < inc);
-            if (!hit || o >= cap) return;  // wave-uniform
-            l = __builtin_ctzll(hit);
-        }
-        base = __builtin_amdgcn_readlane(inc - c, l);
+    // A block belongs to ONE level (grp.blk0: its first block, by value - desc_level_blocks beside the launch), so the level is a
+    // handful of scalar compares, the level counts are one scalar load, and the keypoint's place in the level-major concatenation
+    // (:1076-1104) is scalar adds: nothing of this runs on the vector ALU.
+    static_assert(ORBX_MAX_LEVELS <= 16, "the level counts are one 16-dword scalar load");
+    // The array of level counts has ORBX_MAX_LEVELS ints per image of the plan's batch, so the 16 dwords from b * nlevels are inside
+    // it for any nlevels; those past nlevels belong to other images and are only ever added under i < nlevels / i < lvEnd.
+    int cnt[ORBX_MAX_LEVELS];
+#pragma unroll
+    for (int i = 0; i < ORBX_MAX_LEVELS; i++) cnt[i] = lvlCnt[b * nlevels + i];
+    // walk up the levels until the block is this level's (blk0[i] = 0 up to lvBegin, INT_MAX from lvEnd on): level 0 has the most
+    // keypoints, so the walk is short - a compare, a branch and an add per level passed
+    int first[ORBX_MAX_LEVELS];
+#pragma unroll
+    for (int i = 1; i < ORBX_MAX_LEVELS; i++) {   // the whole table in registers before the walk (wide argument loads; left to itself
+        first[i] = grp.blk0[i];                   // the compiler loads every entry behind the compare in front of it: a load latency per level)
+        asm volatile("" : "+s"(first[i]));
     }
-    l = __builtin_amdgcn_readfirstlane(l);
+    int l = 0, blk0 = 0, base = 0, lc = cnt[0];
+#pragma unroll
+    for (int i = 1; i < ORBX_MAX_LEVELS; i++) {
+        if (bx < first[i]) break;
+        base += lc;
+        lc = cnt[i]; blk0 = first[i]; l = i;
+    }
+    int total = 0, obefore = 0, cA = 0;   // (total: the first thread of an image and the copy blocks only)
+#pragma unroll
+    for (int i = 0; i < ORBX_MAX_LEVELS; i++) {
+        total += i < nlevels ? cnt[i] : 0;
+        if (SPLIT) { obefore += i < grp.lvBegin ? cnt[i] : 0; cA += i < grp.lvEnd ? cnt[i] : 0; }
+    }
+    if ((!SPLIT || grp.writeCounts) && bx == 0 && threadIdx.x == 0) counts[b] = min(total, cap);
+    if (SPLIT && bx >= grp.copyBlock0) {
+        // move the records of the levels [lvEnd, nlevels) from the scratch arrays to their place behind this launch's levels
+        const int cB = total - cA;
+        const int t = threadIdx.x, i = (bx - grp.copyBlock0) * DESC_COPY_PER_BLOCK + (t >> 4), part = t & 15;
+        if (i < cB && cA + i < cap && part < 15) {
+            const size_t si = (size_t)b * cap + i, di = (size_t)b * cap + cA + i;
+            if (part < 7) ((uint32_t *)(kps + di))[part] = ((const uint32_t *)(grp.kpsScratch + si))[part];
+            else ((uint32_t *)(desc + di * 32))[part - 7] = ((const uint32_t *)(grp.descScratch + si * 32))[part - 7];
+        }
+        return;
+    }
+    // keypoint k of level l = output ordinal o over all levels; a launch that starts behind level 0 fills the scratch arrays from
+    // their start (obefore = keypoints in front of its first level).  Wave-uniform returns, before the first vector load: no key
+    // is read past the level's count.
+    const int k = (bx - blk0) * DESC_WAVES + wave;
+    const int o = base + k;
+    if (k >= lc || o - obefore >= cap) return;
     const LevelGeom g = geom[l];
-    const uint32_t key = lvlKp[(size_t)b * lvlKpCap + g.lvlKpOff + (o - base)];
+    const uint32_t key = lvlKp[(size_t)b * lvlKpCap + g.lvlKpOff + k];
     const int cx = (int)(key & 0xFFF) + ORBX_MINB, cy = (int)((key >> 12) & 0xFFF) + ORBX_MINB;
     const int score = (int)(key >> 24);
 
@@ -462,29 +499,23 @@ __global__ __launch_bounds__(64 * DESC_WAVES) __attribute__((amdgpu_waves_per_eu
     {   // all (PROWS*12 + 63) / 64 loads of a lane are in flight before the first LDS write: one memory latency per keypoint
         constexpr int NI = (PROWS * 12 + 63) / 64;
         uint32_t v[NI];
-        // item i = lane + 64 * k is dword c = i % 12 of row r = i / 12: +64 items = 5 rows + 4 dwords with a carry into the
-        // row.  The patch origin is wave-uniform (scalar base), so a lane only keeps a 32-bit byte offset.
+        // A round is FIVE whole rows: lane j < 60 owns dword j % 12 of row j / 12 in every round, so round k is the same lane
+        // offset on a base 5 k rows further down - a scalar add - and the same LDS slot + 60 k dwords - an immediate (rounds of 64
+        // items carried from the dword into the row, an add3 / cndmask chain per load).  Lanes 60 .. 63 redo lane 59's dword.
+        static_assert(NI == 9 && PROWS == 43 && PSTRIDE == 48, "nine rounds of five rows; the last one has three");
         const uint8_t *sbase = (const uint8_t *)src;
-        int c = lane % 12;
-        uint32_t off = (uint32_t)((lane / 12) * pstr4 + c) * 4u;
-        const uint32_t step = (uint32_t)(5 * pstr4 + 4) * 4u, stepCarry = (uint32_t)(6 * pstr4 + 4 - 12) * 4u;
+        const uint32_t rowSkip = (uint32_t)(g.pstride - PSTRIDE);   // row r, dword c = item j = 12 r + c: byte r * pstride + 4 c = r * rowSkip + 4 j
+        const int j = min(lane, 59), j8 = min(lane, 3 * 12 - 1);    // last round: rows 40 .. 42, the lanes past them redo the last dword of the patch
+        const uint32_t off = (uint32_t)((j * 43) >> 9) * rowSkip + 4u * (uint32_t)j;   // j / 12 for j < 60
+        const uint32_t off8 = (uint32_t)((j8 * 43) >> 9) * rowSkip + 4u * (uint32_t)j8;
 #pragma unroll
-        for (int k = 0; k < NI - 1; k++) {           // items < 512 <= PROWS * 12: no clamping
-            v[k] = *(const uint32_t *)(sbase + off);
-            c += 4;
-            const bool carry = c >= 12;
-            c -= carry ? 12 : 0;
-            off += carry ? stepCarry : step;
-        }
-        {   // last step: items 512 .. 575, clamped to the last dword of the patch
-            static_assert(NI == 9 && PROWS * 12 == 516, "tail of the patch staging");
-            const int i = min(lane + 64 * (NI - 1), PROWS * 12 - 1), r = i / 12, cc = i - r * 12;
-            v[NI - 1] = *(const uint32_t *)(sbase + (uint32_t)(r * pstr4 + cc) * 4u);
-        }
-        // unconditional writes to the clamped slot (lanes past the end rewrite the last dword with its own value): a store
+        for (int k = 0; k < NI - 1; k++) v[k] = *(const uint32_t *)(sbase + (size_t)(5 * k) * g.pstride + off);
+        v[NI - 1] = *(const uint32_t *)(sbase + (size_t)(5 * (NI - 1)) * g.pstride + off8);
+        // unconditional writes to the clamped slot (the spare lanes rewrite a dword with its own value): a store
         // under a lane condition lets the compiler sink the last load behind a divergent branch = one more memory latency
 #pragma unroll
-        for (int k = 0; k < NI; k++) ((uint32_t *)P)[min(lane + 64 * k, PROWS * 12 - 1)] = v[k];
+        for (int k = 0; k < NI - 1; k++) ((uint32_t *)P)[60 * k + j] = v[k];
+        ((uint32_t *)P)[60 * (NI - 1) + j8] = v[NI - 1];
     }
     wave_sync();
     // pixel (cx-21+c, cy-21+r) is byte P[r*48 + sh + c], r,c in [0,43)
@@ -519,43 +550,27 @@ __global__ __launch_bounds__(64 * DESC_WAVES) __attribute__((amdgpu_waves_per_eu
     // ---- horizontal 7-tap pass: 4 outputs per lane-iteration from one aligned b128 read.  Output j of a group is the
     // 7-tap sum over bytes o .. o+6 of those 16 bytes, o = sh + j.  Instead of realigning the DATA (9 v_alignbyte per
     // group) the WEIGHTS are shifted: W[j] = taps << 8*o as a 128-bit constant, wave-uniform (scalar registers), and the
-    // sum is a v_dot4_u32_u8 per dword the window can touch - 13 dot products per group, no alignment instructions.
+    // sum is a v_dot4_u32_u8 per dword the window touches - 10 dot products per group, no alignment instructions.
     PHASE("horizontal");
     const uint8_t *Bl0 = Bl;           // blurred pixel (cx - 18 + c, cy - 18 + r) = Bl0[r * BSTRIDE + c]
     if (pre) Bl0 = (const uint8_t *)Tm + shB;
     else {
-    uint32_t Wt[4][4];
-    {
-        // ORBX_GAUSS_FIXED_TAPS: the taps are the handle's (grp.taps, wave-uniform); the other flavours keep their literals
-        const uint32_t tp = GAUSS == ORBX_GAUSS_FIXED_TAPS ? (uint32_t)__builtin_amdgcn_readfirstlane((int)grp.taps) : ORBX_GAUSS_TAPS_DEFAULT;
-        const unsigned long long T0 = tp & 0xFFu, T1 = (tp >> 8) & 0xFFu, T2 = (tp >> 16) & 0xFFu, T3 = tp >> 24;
-        const unsigned __int128 K7 = (unsigned __int128)(T0 | (T1 << 8) | (T2 << 16) | (T3 << 24) | (T2 << 32) | (T1 << 40) | (T0 << 48));
-#pragma unroll
-        for (int jj = 0; jj < 4; jj++) {
-            const unsigned __int128 v = K7 << (8 * (sh + jj));
-#pragma unroll
-            for (int m = 0; m < 4; m++) Wt[jj][m] = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> (32 * m)));
-        }
-    }
-    // round `it`: this lane's item (row r, column group cg) of the list c_reach.hitem - only what lies inside the disc
+    // ORBX_GAUSS_FIXED_TAPS: the taps are the handle's (grp.taps, wave-uniform); the other flavours keep their literals
+    const uint32_t tp = GAUSS == ORBX_GAUSS_FIXED_TAPS ? (uint32_t)__builtin_amdgcn_readfirstlane((int)grp.taps) : ORBX_GAUSS_TAPS_DEFAULT;
+    const unsigned long long T0 = tp & 0xFFu, T1 = (tp >> 8) & 0xFFu, T2 = (tp >> 16) & 0xFFu, T3 = tp >> 24;
+    const unsigned long long K7 = T0 | (T1 << 8) | (T2 << 16) | (T3 << 24) | (T2 << 32) | (T1 << 40) | (T0 << 48);
     uint8_t *Tt = (uint8_t *)Tm;
-#pragma unroll
-    for (int it = 0; it < DESC_H_ITERS; it++) {
-        const uint32_t *pr = (const uint32_t *)(P + (hitem[it] & 0xFFFFu));   // row r, dwords cg .. cg+3 = bytes 4cg .. 4cg+15
-        const uint32_t d0 = pr[0], d1 = pr[1], d2 = pr[2], d3 = pr[3];
-        uint32_t oo[4];
-#pragma unroll
-        for (int jj = 0; jj < 4; jj++) {   // window bytes sh+jj .. sh+jj+6 <= 12: dword 3 only for jj = 3 (<= 65535 in total)
-            uint32_t acc = __builtin_amdgcn_udot4(d0, Wt[jj][0], 0u, false);
-            acc = __builtin_amdgcn_udot4(d1, Wt[jj][1], acc, false);
-            acc = __builtin_amdgcn_udot4(d2, Wt[jj][2], acc, false);
-            if (jj == 3) acc = __builtin_amdgcn_udot4(d3, Wt[jj][3], acc, false);
-            oo[jj] = acc;
-        }
-        uint16_t *dst = (uint16_t *)(Tt + (hitem[it] >> 16));   // column 4cg + jj, row r: four 16-bit stores off one address
-#pragma unroll
-        for (int jj = 0; jj < 4; jj++) dst[jj * (TCS / 2)] = (uint16_t)oo[jj];
+    // sh is wave-uniform: one branch into the copy of the pass that knows which dwords every window touches (desc_hpass)
+#ifdef ORBX_PHASE_MARKERS   // the counted build keeps ONE of the four copies (they have the same instruction mix): the count is static
+    desc_hpass<0>(P, Tt, hitem, K7);
+#else
+    switch (sh) {
+    case 0: desc_hpass<0>(P, Tt, hitem, K7); break;
+    case 1: desc_hpass<1>(P, Tt, hitem, K7); break;
+    case 2: desc_hpass<2>(P, Tt, hitem, K7); break;
+    default: desc_hpass<3>(P, Tt, hitem, K7); break;
     }
+#endif
     wave_sync();
     PHASE("vertical");
 
@@ -642,9 +657,18 @@ __global__ __launch_bounds__(64 * DESC_WAVES) __attribute__((amdgpu_waves_per_eu
     }
     PHASE("store");
     const size_t oi = (size_t)b * cap + (o - obefore);   // a launch that starts behind level 0 fills the scratch arrays from their start
-    if (lane < 4) ((unsigned long long *)(desc + oi * 32))[lane] = bits[lane];
-    if (grp.hostDelta && lane < 4) ((unsigned long long *)(desc + oi * 32 + grp.hostDelta))[lane] = bits[lane];   // (wave-uniform condition)
     if (lane == 0) {
+        // the descriptor words are ballots and every field of the record is wave-uniform: lane 0 stores all of it with wide stores
+        // (two of 16 bytes for the descriptor, 16 + 12 for the 28-byte record) - no selecting bits[lane] per lane
+        typedef uint32_t desc4 __attribute__((ext_vector_type(4), aligned(8)));
+        const desc4 dlo = {(uint32_t)bits[0], (uint32_t)(bits[0] >> 32), (uint32_t)bits[1], (uint32_t)(bits[1] >> 32)};
+        const desc4 dhi = {(uint32_t)bits[2], (uint32_t)(bits[2] >> 32), (uint32_t)bits[3], (uint32_t)(bits[3] >> 32)};
+        desc4 *dp = (desc4 *)(desc + oi * 32);
+        dp[0] = dlo; dp[1] = dhi;
+        if (grp.hostDelta) {   // (wave-uniform condition)
+            desc4 *dt = (desc4 *)(desc + oi * 32 + grp.hostDelta);
+            dt[0] = dlo; dt[1] = dhi;
+        }
         orbx_keypoint_t kp;
         kp.x = (float)cx;
         kp.y = (float)cy;

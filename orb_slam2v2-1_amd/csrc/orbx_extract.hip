@@ -644,30 +644,32 @@ static int launch_chunk(orbx_extractor *h, const ChunkView &v, int B, int stride
         const auto kDesc = p.aSplit > 0 ? (ftaps ? k_describe<ORBX_GAUSS_FIXED_TAPS, true> : sse2 ? k_describe<ORBX_GAUSS_ROUND_SSE2, true> : k_describe<ORBX_GAUSS_ROUND_HALF_UP, true>)
                                         : (ftaps ? k_describe<ORBX_GAUSS_FIXED_TAPS, false> : sse2 ? k_describe<ORBX_GAUSS_ROUND_SSE2, false> : k_describe<ORBX_GAUSS_ROUND_HALF_UP, false>);
         const uint8_t *blurp = h->blurMaskLast ? h->d_blur + (size_t)v.b0 * h->sp.pyrImgBytes : nullptr;
+        // a describing block belongs to one level: blocks for the most keypoints every level can return (desc_level_blocks)
+        const auto bound = [&](int l) { return std::max(h->sp.geom[l].N + 2, 4 * h->sp.geom[l].nIni); };
         if (p.aSplit > 0) {
-            int boundA = 0, boundB = 0;
-            for (int l = 0; l < nl; l++) (l < p.aSplit ? boundA : boundB) += std::max(h->sp.geom[l].N + 2, 4 * h->sp.geom[l].nIni);
-            const int maxoA = std::min(cap, boundA), maxoB = std::min(cap, boundB);
+            int boundB = 0;
+            for (int l = p.aSplit; l < nl; l++) boundB += bound(l);
+            const int maxoB = std::min(cap, boundB);
             orbx_keypoint_t *kB = h->d_kpsB + (size_t)v.b0 * cap;
             uint8_t *dB = h->d_descB + (size_t)v.b0 * cap * 32;
-            const int nbB = (maxoB + DESC_WAVES - 1) / DESC_WAVES, nbA = (maxoA + DESC_WAVES - 1) / DESC_WAVES;
-            DescGroup gB = {p.aSplit, nl, 0, nbB, nullptr, nullptr};
+            DescGroup gB = {p.aSplit, nl, 0, 0, nullptr, nullptr};
+            const int nbB = gB.copyBlock0 = desc_level_blocks(p.aSplit, nl, bound, gB.blk0);
             gB.taps = taps;
             hipLaunchKernelGGL(kDesc, dim3(nbB, B), dim3(64 * DESC_WAVES), descPad, st, v.pyr, h->sp.pyrImgBytes, h->d_geom, nl,
                                v.lvlKp, h->sp.lvlKpCap, v.lvlCnt, kB, dB, d_counts, cap, (uint8_t *)nullptr, blurp, h->blurMaskLast, gB);
             ORBX_HIP(hipStreamWaitEvent(st, h->evOctA, 0));
-            DescGroup gA = {0, p.aSplit, 1, nbA, kB, dB};
+            DescGroup gA = {0, p.aSplit, 1, 0, kB, dB};
+            const int nbA = gA.copyBlock0 = desc_level_blocks(0, p.aSplit, bound, gA.blk0);
             gA.taps = taps;
             hipLaunchKernelGGL(kDesc, dim3(nbA + (maxoB + DESC_COPY_PER_BLOCK - 1) / DESC_COPY_PER_BLOCK, B), dim3(64 * DESC_WAVES), descPad, st,
                                v.pyr, h->sp.pyrImgBytes, h->d_geom, nl, v.lvlKp, h->sp.lvlKpCap, v.lvlCnt, d_kps, d_desc, d_counts, cap,
                                (uint8_t *)nullptr, blurp, h->blurMaskLast, gA);
         } else {
-            const int maxo = std::min(cap, h->sp.max_kp);
-            dim3 grid((maxo + DESC_WAVES - 1) / DESC_WAVES, B);
-            DescGroup gAll = {0, nl, 1, (int)grid.x, nullptr, nullptr};
+            DescGroup gAll = {0, nl, 1, 0, nullptr, nullptr};
+            const int nb = gAll.copyBlock0 = desc_level_blocks(0, nl, bound, gAll.blk0);
             gAll.taps = taps;
             gAll.hostDelta = h->descHostDelta;   // latency form: records also stored into their pinned host twin
-            hipLaunchKernelGGL(kDesc, grid, dim3(64 * DESC_WAVES), descPad, st, v.pyr, h->sp.pyrImgBytes, h->d_geom, nl,
+            hipLaunchKernelGGL(kDesc, dim3(nb, B), dim3(64 * DESC_WAVES), descPad, st, v.pyr, h->sp.pyrImgBytes, h->d_geom, nl,
                                v.lvlKp, h->sp.lvlKpCap, v.lvlCnt, d_kps, d_desc, d_counts, cap, h->d_dbgBlur, blurp, h->blurMaskLast, gAll);
         }
     }

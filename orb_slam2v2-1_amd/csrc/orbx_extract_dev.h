@@ -63,7 +63,22 @@ struct DescGroup {
     uint32_t taps;                       // k_describe<ORBX_GAUSS_FIXED_TAPS, .>: the Gaussian's Q8 taps k3 | k2 << 8 | k1 << 16 | k0 << 24 (k0 = centre)
     long long hostDelta;                 // != 0 (latency form): every keypoint / descriptor / count store is repeated at address + hostDelta - the
                                          // frame record's twin in pinned host memory - so that the last kernel only has mvuRight / mvDepth left to move
+    // A describing block belongs to ONE level: level l of [lvBegin, lvEnd) owns the blocks [blk0[l], blk0[l + 1]) (the last one up
+    // to copyBlock0), enough for the most keypoints the level can return (desc_level_blocks).  So that the level of block bx is
+    // the number of i >= 1 with bx >= blk0[i], the entries up to lvBegin are 0 and those from lvEnd on INT_MAX.
+    int blk0[ORBX_MAX_LEVELS];
 };
+// The table above for the levels [lvBegin, lvEnd) of a plan; returns the number of describing blocks.  bound(l) = the most keypoints
+// level l returns (max(N + 2, 4 nIni)).
+template <class Bound>
+static inline int desc_level_blocks(int lvBegin, int lvEnd, Bound bound, int *blk0) {
+    int nb = 0;
+    for (int l = 0; l < ORBX_MAX_LEVELS; l++) {
+        blk0[l] = l <= lvBegin ? 0 : l < lvEnd ? nb : 0x7fffffff;
+        if (l >= lvBegin && l < lvEnd) nb += (bound(l) + DESC_WAVES - 1) / DESC_WAVES;
+    }
+    return nb;
+}
 #define DESC_COPY_PER_BLOCK 16
 #define BLUR_R 16                // output rows per wave of k_blur_levels
 #define BLUR_SRC (BLUR_R + 6)    // source rows a tile reads
