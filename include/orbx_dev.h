@@ -118,6 +118,20 @@ int orbx_debug_size_plan(int nfeatures, float scale_factor, int nlevels, int w, 
 #define ORBM_DEBUG_THREAD_SCRATCH_INTS 9
 int orbm_debug_thread_scratch(int64_t *out, int n_out);
 
+/* Fill fresh scratch.  Every scratch block of the library - device (hipMalloc) and pinned (hipHostMalloc): the extractor's plan buffers,
+ * staging and frame records, the matchers' arena and its mirror, the staging pairs, the BoW scratch, the keyframe database, the cloud /
+ * octree / rgbd / rectify / stereo scratch - is allocated through one wrapper pair (csrc/orbx_internal.h).  With enable != 0 the wrapper
+ * fills a NEW block with the 32-bit `word` before anything else happens to it: a device block by a 32-bit memset that has completed when
+ * the wrapper returns, a pinned block by a host loop (bytes behind the last whole word repeat the word's bytes, little endian).  The
+ * explicit initialisations (the zeroed plan buffers, the completion words, the frame records' memset) follow the fill as they follow
+ * the allocation.  No result may depend on the word: a recycled block holds whatever its last owner left, a first block usually zero
+ * pages, and tests/test_scratch_fill_gpu.py runs every module on blocks filled with 1 and with 3.  Scratch is made fresh by
+ * orbx_thread_release_scratch() or a new handle; there is no hook that refills memory between calls.
+ * The state is process-wide and atomic, off by default; a set (either value of enable) restarts the statistics.
+ * orbx_debug_alloc_fill_stats: out[0] = blocks filled, out[1] = bytes filled since the last set.  Neither makes a HIP call. */
+int orbx_debug_set_alloc_fill(int enable, uint32_t word);
+int orbx_debug_alloc_fill_stats(int64_t out[2]);
+
 #ifdef __cplusplus
 }
 #endif

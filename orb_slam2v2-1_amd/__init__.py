@@ -107,7 +107,7 @@ PNP_EXPORTS = ["orbp_pnp_parameters", "orbp_pnp_ransac", "orbp_pnp_ransac_batch"
 DEV_EXPORTS = ["orbx_debug_level_points", "orbx_debug_sincosf", "orbx_debug_blur_patches", "orbm_debug_features_in_area",
                "orbx_debug_blurred_level", "orbx_debug_octree_fallbacks", "orbm_debug_match_path", "orbm_debug_resolve_plan",
                "orbm_debug_stereo_path", "orbx_debug_plan_chunk", "orbx_debug_last_plan", "orbm_debug_thread_scratch",
-               "orbx_debug_size_plan"]
+               "orbx_debug_size_plan", "orbx_debug_set_alloc_fill", "orbx_debug_alloc_fill_stats"]
 # include/orbx_dev.h: the int64 record of orbx_debug_size_plan, field order
 SIZE_PLAN_FIELDS = ["max_kp", "totalCells", "maxNodeCap", "lvlKpCap", "pyrImgBytes", "slotsPerImg", "keysPerImg", "fastTileStride", "fastScoreStride",
                     "fastTileRows", "fastLdsPerWave", "totalStrips", "stripLevels", "octLdsBytes", "octPyrLdsBytes", "octPyrWords", "octBigMask",
@@ -420,6 +420,8 @@ def _load(path, dev):
         L.orbx_debug_last_plan.argtypes = [vp, vp, i32]
         L.orbm_debug_thread_scratch.argtypes = [vp, i32]
         L.orbx_debug_size_plan.argtypes = [i32, f32, i32, i32, i32, i32, vp, vp, vp, i32, vp, i32, vp, i32]
+        L.orbx_debug_set_alloc_fill.argtypes = [i32, C.c_uint32]
+        L.orbx_debug_alloc_fill_stats.argtypes = [vp]
     L.orbx_last_error.restype = C.c_char_p
     L.orbx_version.restype = C.c_char_p
     L._orbx_developer = bool(dev)
@@ -895,6 +897,19 @@ def debug_thread_scratch():
     out = np.zeros(len(THREAD_SCRATCH_FIELDS), np.int64)
     _check(lib(True).orbm_debug_thread_scratch(_p(out), len(out)), lib(True))
     return {k: int(v) for k, v in zip(THREAD_SCRATCH_FIELDS, out)}
+
+
+def debug_set_alloc_fill(enable, word=0):
+    """Test hook, no HIP call by itself: from now on every scratch block the developer build allocates (device and pinned) is filled with the
+    32-bit `word` before anything else happens to it; enable = 0 switches that off.  Process-wide; either call restarts the statistics."""
+    _check(lib(True).orbx_debug_set_alloc_fill(int(bool(enable)), int(word) & 0xFFFFFFFF), lib(True))
+
+
+def debug_alloc_fill_stats():
+    """Test hook: (blocks filled, bytes filled) since the last debug_set_alloc_fill."""
+    out = np.zeros(2, np.int64)
+    _check(lib(True).orbx_debug_alloc_fill_stats(_p(out)), lib(True))
+    return int(out[0]), int(out[1])
 
 
 def debug_stereo_path():

@@ -92,9 +92,9 @@ extern "C" int orbv_create(int k, int L, int scoring, int weighting, int nnodes,
     for (int i = 1; i < nnodes; i++) children[cnt[parent[i]] + fill[parent[i]]++] = i;   // children in id order
     v->child_start = cnt;
     hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipMalloc(&v->d_desc, (size_t)nnodes * 32);
-    if (e == hipSuccess) e = hipMalloc(&v->d_child_start, sizeof(int32_t) * (nnodes + 1));
-    if (e == hipSuccess) e = hipMalloc(&v->d_children, sizeof(int32_t) * (nnodes - 1));
+    if (e == hipSuccess) e = scratch_malloc(&v->d_desc, (size_t)nnodes * 32);
+    if (e == hipSuccess) e = scratch_malloc(&v->d_child_start, sizeof(int32_t) * (nnodes + 1));
+    if (e == hipSuccess) e = scratch_malloc(&v->d_children, sizeof(int32_t) * (nnodes - 1));
     if (e == hipSuccess) e = hipMemcpy(v->d_desc, desc, (size_t)nnodes * 32, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(v->d_child_start, cnt.data(), sizeof(int32_t) * (nnodes + 1), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(v->d_children, children.data(), sizeof(int32_t) * (nnodes - 1), hipMemcpyHostToDevice);
@@ -154,7 +154,7 @@ static int scratch(int device, size_t need, uint8_t **p) {
     if (g_bs.device != device || g_bs.cap < need) {
         if (g_bs.d) { hipSetDevice(g_bs.device); hipFree(g_bs.d); hipSetDevice(device); g_bs.d = nullptr; g_bs.cap = 0; }
         const size_t cap = need * 2 > ((size_t)1 << 20) ? need * 2 : ((size_t)1 << 20);
-        ORBX_HIP(hipMalloc(&g_bs.d, cap));
+        ORBX_HIP(scratch_malloc(&g_bs.d, cap));
         g_bs.cap = cap; g_bs.device = device;
     }
     *p = g_bs.d;

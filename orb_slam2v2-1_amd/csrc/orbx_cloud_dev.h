@@ -198,7 +198,7 @@ static inline int reserve(uint8_t **p, size_t *have, size_t need) {
     need = ((need + 255) & ~(size_t)255) + 256;
     if (*have >= need) return ORBX_OK;
     hipFree(*p); *p = nullptr; *have = 0;   // (hipFree waits for the device: no kernel still reads the old block)
-    ORBX_HIP(hipMalloc(p, need));
+    ORBX_HIP(scratch_malloc(p, need));
     *have = need;
     return ORBX_OK;
 }

@@ -708,7 +708,7 @@ extern "C" int orbx_debug_sincosf(const float *angles, int n, float *sin_out, fl
     if (!angles || !sin_out || !cos_out || n < 1) { orbx_set_error("orbx_debug_sincosf: bad arguments"); return ORBX_ERR_ARG; }
     ORBX_HIP(hipSetDevice(device));
     float *d = nullptr;
-    ORBX_HIP(hipMalloc(&d, sizeof(float) * 3 * (size_t)n));
+    ORBX_HIP(scratch_malloc(&d, sizeof(float) * 3 * (size_t)n));
     hipError_t e = hipMemcpy(d, angles, sizeof(float) * (size_t)n, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         (void)hipGetLastError();

@@ -55,6 +55,43 @@ extern "C" int orbm_debug_thread_scratch(int64_t *out, int n_out) {
     orbx_internal_bow_scratch_info(out + 7);
     return ORBX_OK;
 }
+
+// include/orbx_dev.h: fill every new scratch block (scratch_malloc / scratch_host_malloc, orbx_internal.h).  Process-wide, atomic, off by default
+static int g_fillOn = 0;
+static uint32_t g_fillWord = 0;
+static long long g_fillBlocks = 0, g_fillBytes = 0;
+extern "C" int orbx_debug_set_alloc_fill(int enable, uint32_t word) {
+    __atomic_store_n(&g_fillOn, 0, __ATOMIC_SEQ_CST);
+    __atomic_store_n(&g_fillWord, word, __ATOMIC_SEQ_CST);
+    __atomic_store_n(&g_fillBlocks, 0, __ATOMIC_SEQ_CST);
+    __atomic_store_n(&g_fillBytes, 0, __ATOMIC_SEQ_CST);
+    __atomic_store_n(&g_fillOn, enable ? 1 : 0, __ATOMIC_SEQ_CST);
+    return ORBX_OK;
+}
+extern "C" int orbx_debug_alloc_fill_stats(int64_t out[2]) {
+    if (!out) { orbx_set_error("orbx_debug_alloc_fill_stats: bad arguments"); return ORBX_ERR_ARG; }
+    out[0] = __atomic_load_n(&g_fillBlocks, __ATOMIC_SEQ_CST);
+    out[1] = __atomic_load_n(&g_fillBytes, __ATOMIC_SEQ_CST);
+    return ORBX_OK;
+}
+// a block's bytes are the word's, little endian, repeated: whole words by a 32-bit memset, the up to three bytes behind them one by one
+hipError_t orbx_internal_scratch_filled(void *p, size_t bytes, bool pinned) {
+    if (!__atomic_load_n(&g_fillOn, __ATOMIC_SEQ_CST) || !p || bytes == 0) return hipSuccess;
+    const uint32_t word = __atomic_load_n(&g_fillWord, __ATOMIC_SEQ_CST);
+    const size_t nw = bytes / 4;
+    if (pinned) {
+        for (size_t i = 0; i < nw; i++) ((volatile uint32_t *)p)[i] = word;
+        for (size_t i = nw * 4; i < bytes; i++) ((volatile uint8_t *)p)[i] = (uint8_t)(word >> (8 * (i & 3)));
+    } else {
+        hipError_t e = nw ? hipMemsetD32((hipDeviceptr_t)p, (int)word, nw) : hipSuccess;
+        for (size_t i = nw * 4; i < bytes && e == hipSuccess; i++) e = hipMemset((uint8_t *)p + i, (int)((word >> (8 * (i & 3))) & 255u), 1);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) return e;
+    }
+    __atomic_fetch_add(&g_fillBlocks, 1, __ATOMIC_SEQ_CST);
+    __atomic_fetch_add(&g_fillBytes, (long long)bytes, __ATOMIC_SEQ_CST);
+    return hipSuccess;
+}
 #endif
 
 // Per-handle options (include/orbx.h): which of several kernels / launch arrangements with identical results the handle uses.
@@ -130,7 +167,7 @@ extern "C" int orbx_create_flavoured(int nfeatures, float scale_factor, int nlev
     extractor_tables(nfeatures, h->scale_factor, nlevels, &h->tb);
     ORBX_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     // host-mapped word the quad-tree kernels store a call's sequence number into when they flag a corner-sparse level (launch_chunk)
-    ORBX_HIP(hipHostMalloc((void **)&h->h_sparseSeen, sizeof(int32_t), hipHostMallocMapped | hipHostMallocCoherent));
+    ORBX_HIP(scratch_host_malloc((void **)&h->h_sparseSeen, sizeof(int32_t), hipHostMallocMapped | hipHostMallocCoherent));
     *h->h_sparseSeen = (int32_t)0xC0000000u;   // far behind call 0 in unsigned distance
     ORBX_HIP(hipHostGetDevicePointer((void **)&h->d_sparseSeen, h->h_sparseSeen, 0));
     for (int i = 0; i < ORBX_SIDE_STREAMS; i++) {
@@ -261,7 +298,7 @@ static int ensure_plan(orbx_extractor *h, int w, int hgt, int B) {
     free_plan(h);
     h->sp = std::move(sp);
     for (const PlanBuffer &b : plan_buffers(h, h->sp, B)) {
-        ORBX_HIP(hipMalloc(b.ptr, b.bytes));
+        ORBX_HIP(scratch_malloc(b.ptr, b.bytes));
         if (b.zero) ORBX_HIP(hipMemset(*b.ptr, 0, b.bytes));
     }
     ORBX_HIP(hipMemcpy(h->d_geom, h->sp.geom, sizeof(LevelGeom) * ORBX_MAX_LEVELS, hipMemcpyHostToDevice));
@@ -340,7 +377,7 @@ static int ensure_blur(orbx_extractor *h, uint8_t **buf, size_t *bytes) {
     if (h->last_valid) ORBX_HIP(hipStreamSynchronize(h->last_stream));
     for (int i = 0; i < ORBX_SIDE_STREAMS; i++) ORBX_HIP(hipStreamSynchronize(h->side[i]));
     hipFree(*buf); *buf = nullptr; *bytes = 0;
-    ORBX_HIP(hipMalloc(buf, need));
+    ORBX_HIP(scratch_malloc(buf, need));
     *bytes = need;
     return ORBX_OK;
 }
@@ -565,8 +602,8 @@ static int launch_chunk(orbx_extractor *h, const ChunkView &v, int B, int stride
                 ORBX_HIP(hipStreamSynchronize(st));
                 ORBX_HIP(hipStreamSynchronize(s2));
                 hipFree(h->d_kpsB); hipFree(h->d_descB); h->d_kpsB = nullptr; h->d_descB = nullptr; h->splitBytes = 0;
-                ORBX_HIP(hipMalloc(&h->d_kpsB, (size_t)h->pB * cap * sizeof(orbx_keypoint_t)));
-                ORBX_HIP(hipMalloc(&h->d_descB, (size_t)h->pB * cap * 32));
+                ORBX_HIP(scratch_malloc(&h->d_kpsB, (size_t)h->pB * cap * sizeof(orbx_keypoint_t)));
+                ORBX_HIP(scratch_malloc(&h->d_descB, (size_t)h->pB * cap * 32));
                 h->splitBytes = need;
             }
         }
@@ -752,7 +789,7 @@ extern "C" int orbx_extract_batch_device(orbx_extractor_t *h, const uint8_t *d_i
             if (h->pyrAltBytes < h->sp.pyrImgBytes * (size_t)h->pB) {   // first rotation: the "previous" buffer does not exist yet
                 ORBX_HIP(hipStreamSynchronize(h->side[0]));
                 hipFree(h->d_pyrAlt); h->d_pyrAlt = nullptr;
-                ORBX_HIP(hipMalloc(&h->d_pyrAlt, h->sp.pyrImgBytes * (size_t)h->pB));
+                ORBX_HIP(scratch_malloc(&h->d_pyrAlt, h->sp.pyrImgBytes * (size_t)h->pB));
                 h->pyrAltBytes = h->sp.pyrImgBytes * (size_t)h->pB;
             }
             uint8_t *oldPrev = h->d_pyrAlt;
@@ -781,7 +818,7 @@ extern "C" int orbx_extract_batch_device_prefetch(orbx_extractor_t *h, const uin
     if (*tgtBytes < need) {
         ORBX_HIP(hipStreamSynchronize(h->side[0]));
         hipFree(*tgt); *tgt = nullptr; *tgtBytes = 0;
-        ORBX_HIP(hipMalloc(tgt, need));
+        ORBX_HIP(scratch_malloc(tgt, need));
         *tgtBytes = need;
     }
     hipStream_t sd = side_stream ? (hipStream_t)side_stream : h->side[0];   // the caller's side stream (work it queued there comes first) or the handle's own
@@ -889,21 +926,21 @@ extern "C" void *orbx_side_stream_for(orbx_extractor_t *h, void *main_stream) {
 static int ensure_staging(orbx_extractor *h, size_t in_bytes, int B, int cap) {
     if (h->d_in_bytes < in_bytes) {
         hipFree(h->d_in); h->d_in = nullptr; h->d_in_bytes = 0;
-        ORBX_HIP(hipMalloc(&h->d_in, in_bytes));
+        ORBX_HIP(scratch_malloc(&h->d_in, in_bytes));
         h->d_in_bytes = in_bytes;
     }
     if (h->out_cap < cap || h->out_B < B) {
         hipFree(h->d_kps); hipFree(h->d_desc); hipFree(h->d_counts);
         h->d_kps = nullptr; h->d_desc = nullptr; h->d_counts = nullptr;
         const int nb = std::max(B, h->out_B), nc = std::max(cap, h->out_cap);
-        ORBX_HIP(hipMalloc(&h->d_kps, sizeof(orbx_keypoint_t) * (size_t)nb * nc));
-        ORBX_HIP(hipMalloc(&h->d_desc, (size_t)32 * nb * nc));
-        ORBX_HIP(hipMalloc(&h->d_counts, sizeof(int32_t) * nb));
+        ORBX_HIP(scratch_malloc(&h->d_kps, sizeof(orbx_keypoint_t) * (size_t)nb * nc));
+        ORBX_HIP(scratch_malloc(&h->d_desc, (size_t)32 * nb * nc));
+        ORBX_HIP(scratch_malloc(&h->d_counts, sizeof(int32_t) * nb));
         // pinned mirrors: the results of a host-API call come down in three copies and ONE synchronisation
         if (h->h_kps) { hipHostFree(h->h_kps); hipHostFree(h->h_desc); hipHostFree(h->h_counts); h->h_kps = nullptr; h->h_desc = nullptr; h->h_counts = nullptr; }
-        ORBX_HIP(hipHostMalloc((void **)&h->h_kps, sizeof(orbx_keypoint_t) * (size_t)nb * nc, hipHostMallocDefault));
-        ORBX_HIP(hipHostMalloc((void **)&h->h_desc, (size_t)32 * nb * nc, hipHostMallocDefault));
-        ORBX_HIP(hipHostMalloc((void **)&h->h_counts, sizeof(int32_t) * nb, hipHostMallocDefault));
+        ORBX_HIP(scratch_host_malloc((void **)&h->h_kps, sizeof(orbx_keypoint_t) * (size_t)nb * nc, hipHostMallocDefault));
+        ORBX_HIP(scratch_host_malloc((void **)&h->h_desc, (size_t)32 * nb * nc, hipHostMallocDefault));
+        ORBX_HIP(scratch_host_malloc((void **)&h->h_counts, sizeof(int32_t) * nb, hipHostMallocDefault));
         h->out_cap = nc; h->out_B = nb;
     }
     return ORBX_OK;
@@ -973,8 +1010,8 @@ static int stereo_frame_run(orbx_extractor *h, const uint8_t *left, const uint8_
         hipFree(h->d_sfr); h->d_sfr = nullptr;
         if (h->h_sfr) { hipHostFree(h->h_sfr); h->h_sfr = nullptr; }
         h->sfr_cap = 0;
-        ORBX_HIP(hipMalloc(&h->d_sfr, sizeof(float) * (2 * (size_t)dcap + 4)));
-        ORBX_HIP(hipHostMalloc((void **)&h->h_sfr, sizeof(float) * (2 * (size_t)dcap + 4), hipHostMallocDefault));
+        ORBX_HIP(scratch_malloc(&h->d_sfr, sizeof(float) * (2 * (size_t)dcap + 4)));
+        ORBX_HIP(scratch_host_malloc((void **)&h->h_sfr, sizeof(float) * (2 * (size_t)dcap + 4), hipHostMallocDefault));
         h->sfr_cap = dcap;
     }
     hipStream_t st = h->stream;
@@ -1074,9 +1111,12 @@ extern "C" int orbx_stereo_frame_view(orbx_extractor_t *h, const uint8_t *left, 
         }
         h->fv_cap = 0;
         for (int i = 0; i < 2; i++) {
-            ORBX_HIP(hipMalloc(&h->fv_d[i], recBytes));
-            ORBX_HIP(hipMemset(h->fv_d[i], 0, recBytes));
-            ORBX_HIP(hipHostMalloc((void **)&h->fv_h[i], recBytes, hipHostMallocDefault));
+            ORBX_HIP(scratch_malloc(&h->fv_d[i], recBytes));
+            // on the handle's stream, in front of the call's kernels.  (hipMemset runs on the NULL stream and may return before it has run; the
+            // handle's stream is non-blocking, so nothing ordered that memset against k_describe / k_stereo_finish: on a busy GPU it could zero a
+            // record in HBM after they had written it - the pinned twin stayed right, the guided search on the HBM record found nothing.)
+            ORBX_HIP(hipMemsetAsync(h->fv_d[i], 0, recBytes, h->stream));
+            ORBX_HIP(scratch_host_malloc((void **)&h->fv_h[i], recBytes, hipHostMallocDefault));
             ORBX_HIP(hipHostGetDevicePointer((void **)&h->fv_hdev[i], h->fv_h[i], 0));
         }
         h->fv_cap = cap;
@@ -1087,7 +1127,7 @@ extern "C" int orbx_stereo_frame_view(orbx_extractor_t *h, const uint8_t *left, 
         if (h->fv_stage_bytes < 2 * img_bytes) {
             ORBX_HIP(hipStreamSynchronize(h->stream));
             if (h->fv_stage) { hipHostFree(h->fv_stage); h->fv_stage = nullptr; h->fv_stage_bytes = 0; }
-            ORBX_HIP(hipHostMalloc((void **)&h->fv_stage, 2 * img_bytes, hipHostMallocDefault));
+            ORBX_HIP(scratch_host_malloc((void **)&h->fv_stage, 2 * img_bytes, hipHostMallocDefault));
             ORBX_HIP(hipHostGetDevicePointer((void **)&h->fv_stage_dev, h->fv_stage, 0));
             h->fv_stage_bytes = 2 * img_bytes;
         }
@@ -1107,7 +1147,7 @@ extern "C" int orbx_stereo_frame_view(orbx_extractor_t *h, const uint8_t *left, 
     h->descHostDelta = 0;
     if (rc) return rc;
     if (!h->fv_flag) {
-        ORBX_HIP(hipHostMalloc((void **)&h->fv_flag, 64, hipHostMallocMapped | hipHostMallocCoherent));
+        ORBX_HIP(scratch_host_malloc((void **)&h->fv_flag, 64, hipHostMallocMapped | hipHostMallocCoherent));
         *h->fv_flag = 0;
         ORBX_HIP(hipHostGetDevicePointer((void **)&h->fv_flag_dev, h->fv_flag, 0));
     }
@@ -1358,7 +1398,7 @@ extern "C" int orbx_debug_blur_patches(orbx_extractor_t *h, int enable, uint8_t 
     hipFree(h->d_dbgBlur); h->d_dbgBlur = nullptr; h->dbgBlurCap = 0;
     if (enable) {
         h->dbgBlurCap = h->sp.max_kp > 0 ? h->sp.max_kp + 300 : h->nfeatures + 3 * h->nlevels + 300;
-        ORBX_HIP(hipMalloc(&h->d_dbgBlur, (size_t)h->dbgBlurCap * 37 * 37));
+        ORBX_HIP(scratch_malloc(&h->d_dbgBlur, (size_t)h->dbgBlurCap * 37 * 37));
     }
     return ORBX_OK;
 }

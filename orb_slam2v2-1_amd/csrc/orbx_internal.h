@@ -31,6 +31,25 @@
         }                                                                                   \
     } while (0)
 
+// Every scratch allocation of the library (device and pinned) goes through this pair.  The product build's is the plain call.  The
+// developer build's can fill a new block with one 32-bit word before anyone else sees it (orbx_debug_set_alloc_fill, include/orbx_dev.h;
+// off by default), so that a test runs every call on scratch that holds neither zero pages nor its own earlier results
+// (tests/test_scratch_fill_gpu.py).  A device block's fill has completed when the wrapper returns.
+#ifdef ORBX_DEVELOPER
+hipError_t orbx_internal_scratch_filled(void *p, size_t bytes, bool pinned);   // orbx_extract.hip
+template <class T> static inline hipError_t scratch_malloc(T **p, size_t bytes) {
+    const hipError_t e = hipMalloc((void **)p, bytes);
+    return e != hipSuccess ? e : orbx_internal_scratch_filled((void *)*p, bytes, false);
+}
+template <class T> static inline hipError_t scratch_host_malloc(T **p, size_t bytes, unsigned flags) {
+    const hipError_t e = hipHostMalloc((void **)p, bytes, flags);
+    return e != hipSuccess ? e : orbx_internal_scratch_filled((void *)*p, bytes, true);
+}
+#else
+template <class T> static inline hipError_t scratch_malloc(T **p, size_t bytes) { return hipMalloc((void **)p, bytes); }
+template <class T> static inline hipError_t scratch_host_malloc(T **p, size_t bytes, unsigned flags) { return hipHostMalloc((void **)p, bytes, flags); }
+#endif
+
 struct orbx_extractor {
     int nfeatures, nlevels, ini_th, min_th, device;
     double scale_factor;

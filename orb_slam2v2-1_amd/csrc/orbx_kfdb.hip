@@ -240,7 +240,7 @@ static int db_grow(orbv_db *db, void **p, size_t *cap, size_t need, size_t elem,
     size_t nc = *cap ? *cap : 64;
     while (nc < need) nc *= 2;
     void *q = nullptr;
-    ORBX_HIP(hipMalloc(&q, nc * elem));
+    ORBX_HIP(scratch_malloc(&q, nc * elem));
     db->devBytes += nc * elem;
     hipError_t e = hipSuccess;
     if (keep) e = hipMemcpyAsync(q, *p, keep * elem, hipMemcpyDeviceToDevice, db->stream);
@@ -256,7 +256,7 @@ static int db_pin(orbv_db *db, size_t need) {
     size_t nc = db->pinCap ? db->pinCap : ((size_t)1 << 16);
     while (nc < need) nc *= 2;
     if (db->h_pin) { ORBX_HIP(hipHostFree(db->h_pin)); db->h_pin = nullptr; db->pinCap = 0; }
-    ORBX_HIP(hipHostMalloc((void **)&db->h_pin, nc, hipHostMallocDefault));
+    ORBX_HIP(scratch_host_malloc((void **)&db->h_pin, nc, hipHostMallocDefault));
     db->pinCap = nc;
     return ORBX_OK;
 }
@@ -284,8 +284,8 @@ static int db_init(orbv_db *db, int initial_entries) {
     ORBX_HIP(hipSetDevice(db->device));
     ORBX_HIP(hipStreamCreateWithFlags(&db->stream, hipStreamNonBlocking));
     const size_t n0 = initial_entries > 0 ? (size_t)initial_entries : ((size_t)1 << 20);
-    ORBX_HIP(hipMalloc((void **)&db->d_pw, n0 * 4)); db->devBytes += n0 * 4;
-    ORBX_HIP(hipMalloc((void **)&db->d_pv, n0 * 8)); db->devBytes += n0 * 8;
+    ORBX_HIP(scratch_malloc((void **)&db->d_pw, n0 * 4)); db->devBytes += n0 * 4;
+    ORBX_HIP(scratch_malloc((void **)&db->d_pv, n0 * 8)); db->devBytes += n0 * 8;
     db->poolCap = n0;
     return db_pin(db, (size_t)1 << 16);
 }
@@ -451,7 +451,7 @@ static int db_scratch(orbv_db *db, size_t n, DbLayout *L) {
         int rc = db_free(db, db->d_q, db->qCap);
         db->d_q = nullptr; db->qCap = 0;
         if (rc) return rc;
-        ORBX_HIP(hipMalloc((void **)&db->d_q, L2.total));
+        ORBX_HIP(scratch_malloc((void **)&db->d_q, L2.total));
         db->qCap = L2.total; db->devBytes += L2.total;
     }
     return ORBX_OK;

@@ -508,7 +508,11 @@ __global__ __launch_bounds__(SF_T) void k_stereo_finish(uint4 *rec, uint4 *__res
     if (doneFlag && gridDim.x == 1) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // my stores to the (uncached) host record have been acknowledged; ONE wave fences and signals
         __syncthreads();
-        if (tid == 0) { __threadfence_system(); __hip_atomic_store(doneFlag, doneSeq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
+        if (tid == 0) {   // the fence releases and its write-back is waited for; the word's store is relaxed (k_resolve_par, orbx_match_fast.hip, says why)
+            __threadfence_system();
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __hip_atomic_store(doneFlag, doneSeq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
     }
 }
 
@@ -540,10 +544,10 @@ static int stereo_scratch_reserve(orbx_extractor *hl, int B, int cap) {
     if (hl->st_stream) ORBX_HIP(hipStreamSynchronize(hl->st_stream));
     hipFree(hl->st_sad); hipFree(hl->st_rc); hipFree(hl->st_binStart); hipFree(hl->st_items);
     hl->st_sad = nullptr; hl->st_rc = nullptr; hl->st_binStart = nullptr; hl->st_items = nullptr; hl->st_n = 0; hl->st_nB = 0;
-    ORBX_HIP(hipMalloc(&hl->st_sad, sizeof(int32_t) * need));
-    ORBX_HIP(hipMalloc(&hl->st_rc, sizeof(uint2) * need));
-    ORBX_HIP(hipMalloc(&hl->st_items, sizeof(uint4) * ST_MAX_SPAN * need));
-    ORBX_HIP(hipMalloc(&hl->st_binStart, sizeof(int32_t) * (ST_MAX_BINS + 1) * (size_t)B));
+    ORBX_HIP(scratch_malloc(&hl->st_sad, sizeof(int32_t) * need));
+    ORBX_HIP(scratch_malloc(&hl->st_rc, sizeof(uint2) * need));
+    ORBX_HIP(scratch_malloc(&hl->st_items, sizeof(uint4) * ST_MAX_SPAN * need));
+    ORBX_HIP(scratch_malloc(&hl->st_binStart, sizeof(int32_t) * (ST_MAX_BINS + 1) * (size_t)B));
     hl->st_n = need; hl->st_nB = B;
     return ORBX_OK;
 }

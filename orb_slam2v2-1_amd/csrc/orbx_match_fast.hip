@@ -753,16 +753,25 @@ __global__ __launch_bounds__(RP_T) void k_resolve_par(const u64 *__restrict__ ke
     if (tid == 0) {
         out[0] = sh_nm; out[1] = sh_ov; out[2] = rounds;     // [2]: rounds the iteration took (diagnostics)
         if (out_host) { out_host[0] = sh_nm; out_host[1] = sh_ov; out_host[2] = rounds; }
-        // ... and the call's sequence number behind everything: the host polls this word instead of waiting for the stream (a stream
-        // synchronisation costs 10-15 us of wake-up latency on top of the kernel - a third of a 45-us matcher call)
-        if (doneFlag) { __threadfence_system(); __hip_atomic_store(doneFlag, doneSeq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
 #ifdef ORBX_DEVELOPER
-        // developer build: [3] = time stamps in 0.1-us units (100-MHz counter): loads << 20 | rounds << 10 | epilogue
+        // developer build: [3] = time stamps in 0.1-us units (100-MHz counter): loads << 20 | rounds << 10 | epilogue (up to here).  In
+        // FRONT of the completion word like every other store: once the word is out the host goes on, and the next call lays its inputs
+        // out in the same mirror.  The product build never writes [3] and nothing reads it there (the trace line is the developer build's)
         const unsigned long long dvT3 = wall_clock64();
         const int stamp = ((int)min((dvT1 - dvT0) / 10ull, 1023ull) << 20) | ((int)min((dvT2 - dvT1) / 10ull, 1023ull) << 10) | (int)min((dvT3 - dvT2) / 10ull, 1023ull);
         out[3] = stamp;
         if (out_host) out_host[3] = stamp;
 #endif
+        // ... and the call's sequence number behind everything: the host polls this word instead of waiting for the stream (a stream
+        // synchronisation costs 10-15 us of wake-up latency on top of the kernel - a third of a 45-us matcher call)
+        // The fence is the release: its write-back is waited for (s_waitcnt vmcnt(0)) before the word goes out.  The store itself is relaxed: as
+        // a release store it repeated the write-back, and the compiler - this wave's vmcnt being provably empty behind the fence - put NO wait
+        // between that second write-back and the word.  The explicit wait keeps the first one's from being dropped the same way by a later edit.
+        if (doneFlag) {
+            __threadfence_system();
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __hip_atomic_store(doneFlag, doneSeq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
     }
 }
 
@@ -980,11 +989,11 @@ static int arena_begin(int device, size_t need) {
         }
         g_ar.base = nullptr; g_ar.cap = 0;
         const size_t cap = std::max(need * 2, (size_t)4 << 20);
-        ORBX_HIP(hipMalloc(&g_ar.base, cap));
-        ORBX_HIP(hipHostMalloc((void **)&g_ar.hbase, cap, hipHostMallocDefault));
+        ORBX_HIP(scratch_malloc(&g_ar.base, cap));
+        ORBX_HIP(scratch_host_malloc((void **)&g_ar.hbase, cap, hipHostMallocDefault));
         ORBX_HIP(hipHostGetDevicePointer((void **)&g_ar.hdev, g_ar.hbase, 0));   // the mirror as the kernels see it (small inputs are read, results written, in place)
         if (!g_ar.hflag) {
-            ORBX_HIP(hipHostMalloc((void **)&g_ar.hflag, 64, hipHostMallocMapped | hipHostMallocCoherent));
+            ORBX_HIP(scratch_host_malloc((void **)&g_ar.hflag, 64, hipHostMallocMapped | hipHostMallocCoherent));
             *g_ar.hflag = 0;
             ORBX_HIP(hipHostGetDevicePointer((void **)&g_ar.dflag, g_ar.hflag, 0));
         }
@@ -1059,6 +1068,20 @@ static int arena_wait(hipStream_t st, int seq) {
     }
     ORBX_HIP(hipStreamSynchronize(st));
     return ORBX_OK;
+}
+// developer aid (ORBX_TRACE_RESOLVE, read once): what k_resolve_par left in out[] on stderr.  out[3], the kernel's time stamps, exists in the
+// developer build only: the product build's kernel never writes that word and its line does not print it
+static bool trace_resolve() {
+    static const bool on = getenv("ORBX_TRACE_RESOLVE") != nullptr;
+    return on;
+}
+static void trace_resolve_line(const char *mode, int m, int n, const int32_t *out) {
+#ifdef ORBX_DEVELOPER
+    fprintf(stderr, "k_resolve_par<%s>: %d queries, %d keypoints, %d rounds; loads %.1f us, rounds %.1f us, epilogue %.1f us\n", mode, m, n, out[2],
+            (out[3] >> 20) / 10.0, ((out[3] >> 10) & 1023) / 10.0, (out[3] & 1023) / 10.0);
+#else
+    fprintf(stderr, "k_resolve_par<%s>: %d queries, %d keypoints, %d rounds\n", mode, m, n, out[2]);
+#endif
 }
 static inline int resolve_par_q(int m) { return m <= 2 * RP_T ? 2 : 4; }
 static inline size_t resolve_par_lds(int m, int n) { return sizeof(uint32_t) * ((size_t)QK * RP_T * resolve_par_q(m) + 2 * (size_t)n + (size_t)(n + 31) / 32); }
@@ -1265,7 +1288,7 @@ int fast_search_by_projection_mp(const orbx_keypoint_t *kun, const uint8_t *desc
     if (rc) return rc;
     if (world && proj_out) memcpy(proj_out, arena_host(dmp), sizeof(orbm_mappoint_t) * (size_t)m);
     const int32_t *out = arena_host(dout);
-    if (getenv("ORBX_TRACE_RESOLVE")) fprintf(stderr, "k_resolve_par<mp>: %d queries, %d keypoints, %d rounds; developer build: loads %.1f us, rounds %.1f us, epilogue %.1f us\n", m, n, out[2], (out[3] >> 20) / 10.0, ((out[3] >> 10) & 1023) / 10.0, (out[3] & 1023) / 10.0);
+    if (trace_resolve()) trace_resolve_line("mp", m, n, out);
     if (out[1]) return path_fallback(resolve_fallback(out[1]));
     memcpy(frame_mp, arena_host(dfm), sizeof(int32_t) * (size_t)n);
     *nmatches = out[0];
@@ -1339,7 +1362,7 @@ int fast_search_by_projection_frame(const orbx_keypoint_t *kun, const uint8_t *d
         fprintf(stderr, "search_by_projection_frame host: stage inputs %.1f us, enqueue %.1f us, wait %.1f us\n", us(ts0, ts1), us(ts1, ts2), us(ts2, ts3));
     }
     const int32_t *out = arena_host(dout);
-    if (getenv("ORBX_TRACE_RESOLVE")) fprintf(stderr, "k_resolve_par<frame>: %d queries, %d keypoints, %d rounds; developer build: loads %.1f us, rounds %.1f us, epilogue %.1f us\n", nlast, n, out[2], (out[3] >> 20) / 10.0, ((out[3] >> 10) & 1023) / 10.0, (out[3] & 1023) / 10.0);
+    if (trace_resolve()) trace_resolve_line("frame", nlast, n, out);
     if (out[1]) return path_fallback(resolve_fallback(out[1]));
     memcpy(cur_mp, arena_host(dcm), sizeof(int32_t) * (size_t)n);
     *nmatches = out[0];

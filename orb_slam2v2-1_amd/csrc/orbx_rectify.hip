@@ -269,8 +269,8 @@ extern "C" int orbx_rectifier_create(const double K[9], const double *D, int nD,
         rc = ORBX_ERR_HIP;
     };
     hipError_t e;
-    if ((e = hipMalloc(&r->d_mapx, npx * 4)) || (e = hipMalloc(&r->d_mapy, npx * 4)) || (e = hipMalloc(&r->d_fix, npx * 8)) ||
-        (e = hipMalloc(&r->d_tiles, sizeof(RectTile) * r->ntiles)) || (e = hipMalloc(&d_box, box.size() * 4)))
+    if ((e = scratch_malloc(&r->d_mapx, npx * 4)) || (e = scratch_malloc(&r->d_mapy, npx * 4)) || (e = scratch_malloc(&r->d_fix, npx * 8)) ||
+        (e = scratch_malloc(&r->d_tiles, sizeof(RectTile) * r->ntiles)) || (e = scratch_malloc(&d_box, box.size() * 4)))
         fail(e, "hipMalloc");
     else if ((e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking)))
         fail(e, "hipStreamCreate");
@@ -393,7 +393,7 @@ void orbx_internal_free_rect_scratch(orbx_extractor *h) {
 static int grow_dev(uint8_t **p, size_t *have, size_t need) {
     if (*have >= need) return ORBX_OK;
     hipFree(*p); *p = nullptr; *have = 0;
-    ORBX_HIP(hipMalloc(p, need));
+    ORBX_HIP(scratch_malloc(p, need));
     *have = need;
     return ORBX_OK;
 }
@@ -471,7 +471,7 @@ extern "C" int orbx_stereo_frame_view_rectified(orbx_extractor_t *h, const orbx_
         if (s->stageBytes < 2 * img) {
             ORBX_HIP(hipStreamSynchronize(h->stream));
             if (s->h_stage) { hipHostFree(s->h_stage); s->h_stage = nullptr; s->stageBytes = 0; }
-            ORBX_HIP(hipHostMalloc((void **)&s->h_stage, 2 * img, hipHostMallocDefault));
+            ORBX_HIP(scratch_host_malloc((void **)&s->h_stage, 2 * img, hipHostMallocDefault));
             ORBX_HIP(hipHostGetDevicePointer((void **)&s->h_stage_dev, s->h_stage, 0));
             s->stageBytes = 2 * img;
         }

@@ -264,7 +264,7 @@ static int grow(uint8_t **p, size_t *have, size_t need) {
     need = ((need + 255) & ~(size_t)255) + 256;   // (as the host API's staging: whole 256-byte blocks and one more)
     if (*have >= need) return ORBX_OK;
     hipFree(*p); *p = nullptr; *have = 0;
-    ORBX_HIP(hipMalloc(p, need));
+    ORBX_HIP(scratch_malloc(p, need));
     *have = need;
     return ORBX_OK;
 }
@@ -297,8 +297,8 @@ extern "C" int orbx_rgbd_frame(orbx_extractor_t *h, const uint8_t *img, int chan
         hipFree(s->d_out); s->d_out = nullptr;
         if (s->h_out) { hipHostFree(s->h_out); s->h_out = nullptr; }
         s->cap = 0;
-        ORBX_HIP(hipMalloc(&s->d_out, L.bytes));
-        ORBX_HIP(hipHostMalloc((void **)&s->h_out, L.bytes, hipHostMallocDefault));
+        ORBX_HIP(scratch_malloc(&s->d_out, L.bytes));
+        ORBX_HIP(scratch_host_malloc((void **)&s->h_out, L.bytes, hipHostMallocDefault));
         s->cap = dcap;
     }
     hipStream_t st = h->stream;

@@ -35,8 +35,8 @@ struct StagePair {
         if (h) { hipHostFree(h); h = nullptr; }
         cap = 0;
         const size_t c = need * 2 > min_cap ? need * 2 : min_cap;
-        ORBX_HIP(hipMalloc(&d, c));
-        ORBX_HIP(hipHostMalloc((void **)&h, c, hipHostMallocDefault));
+        ORBX_HIP(scratch_malloc(&d, c));
+        ORBX_HIP(scratch_host_malloc((void **)&h, c, hipHostMallocDefault));
         cap = c;
         return ORBX_OK;
     }

@@ -330,8 +330,17 @@ def big_local_points_case(pkg, oracle, synth):
     m = 1
     while arena_need_local_points(n, m) <= ARENA_MIN:
         m += 1
+    big = local_points_case(pkg, oracle, synth, m, "search_local_points_big")
+    assert big.n == n
+    big.need, big.before = arena_need_local_points(n, m), ARENA_MIN
+    return big
+
+
+def local_points_case(pkg, oracle, synth, m, name):
+    """Tracking::SearchLocalPoints on that frame with a local map of m world points (m picks the resolver: k_resolve_par with 2 queries
+    per thread up to 2048, 4 up to 4096, the single-wave resolver beyond)."""
     ks_, w, h, rng, k, d, sf, cam, log_sf, T, pts3, wp, pd, obs = local_map(pkg, oracle, synth, 7, m=m)
-    assert len(k) == n
+    n = len(k)
     uright = np.where(rng.random(n) < 0.5, k["x"] - rng.uniform(1, 40, n), -1).astype(np.float32)
     frame_mp = np.full(n, -1, np.int32)
     held = rng.choice(n, 150, replace=False)
@@ -347,6 +356,6 @@ def big_local_points_case(pkg, oracle, synth):
     def run(pkg, shared):
         gn, gfm, gproj = pkg.search_local_points(k, d, uright, pkg.grid_geom(w, h), sf, wp, pd, T, pcam, 0.5, thr, frame_mp, ext_obs, 1.0, 0.8)
         return {"nmatches": gn, "frame_mp": gfm, "projections": np.frombuffer(gproj.tobytes(), np.uint8)}
-    big = Case("search_local_points_big", run, {"nmatches": on, "frame_mp": ofm, "projections": np.frombuffer(proj.tobytes(), np.uint8)}, guided=True)
-    big.need, big.before = arena_need_local_points(n, m), ARENA_MIN
-    return big
+    case = Case(name, run, {"nmatches": on, "frame_mp": ofm, "projections": np.frombuffer(proj.tobytes(), np.uint8)}, guided=True)
+    case.n = n
+    return case

@@ -21,6 +21,9 @@ more iteration - the scratch is re-created with the arena's call counter already
 NEW threads, `--iters2` iterations, the roles rotated by one thread.  Every case's expected results are computed by the oracle,
 single-threaded, before the first GPU call.  Prints one JSON line.
 
+--alloc-fill WORD switches the developer build's scratch fill on (orbx_debug_set_alloc_fill) before the first GPU call: every arena,
+mirror, staging pair, plan buffer and frame record of both waves starts out holding WORD instead of whatever the allocator returned.
+
 --options role=fast_wave,role=exact sets orbm_set_thread_option(3, 1) / (2, 1) in the threads of that role; every thread records
 what orbm_debug_match_path reports after each guided search it made."""
 import argparse
@@ -81,10 +84,32 @@ def check_results(thread, iteration, call, got, want, bad):
             bad.append({"thread": thread, "iteration": iteration, "call": call, "field": field, "first_index": i})
 
 
-def check_chain(thread, iteration, diff, bad):
-    """diff: tracking_chain.first_difference(oracle log, this log)."""
+def chain_detail(want_snap, got_snap, field):
+    """What differed in one field of a chain snapshot.  A number: the values got and wanted.  An array (the log keeps its bytes): both lengths
+    in bytes and the first eight differing indices, counted in 32-bit words - every array of the log is made of 4-byte fields but the
+    descriptors, whose index / 8 is the row - with the words got and wanted there (hex)."""
+    got, want = (got_snap or {}).get(field), (want_snap or {}).get(field)
+    if not isinstance(got, (bytes, bytearray)) or not isinstance(want, (bytes, bytearray)):
+        plain = lambda v: v if isinstance(v, (int, float, str, type(None))) else repr(v)[:80]
+        return {"got": plain(got), "want": plain(want)}
+    n = min(len(got), len(want)) // 4
+    a, b = np.frombuffer(got, np.uint32, n), np.frombuffer(want, np.uint32, n)
+    idx = np.flatnonzero(a != b)[:8]
+    return {"got_bytes": len(got), "want_bytes": len(want), "indices": [int(i) for i in idx], "got": ["%08x" % a[i] for i in idx],
+            "want": ["%08x" % b[i] for i in idx]}
+
+
+def check_chain(thread, iteration, diff, bad, want_log=None, got_log=None):
+    """diff: tracking_chain.first_difference(oracle log, this log); with both logs, the entry also says what differed (chain_detail)."""
     if diff is not None:
-        bad.append({"thread": thread, "iteration": iteration, "call": "chain", "field": diff[1], "first_index": int(diff[0])})
+        entry = {"thread": thread, "iteration": iteration, "call": "chain", "field": diff[1], "first_index": int(diff[0])}
+        if want_log is not None and got_log is not None:
+            t = int(diff[0])
+            if diff[1] == "length":
+                entry.update(got=len(got_log), want=len(want_log))
+            elif t < len(want_log) and t < len(got_log):
+                entry.update(chain_detail(want_log[t], got_log[t], diff[1]))
+        bad.append(entry)
 
 
 def scratch_is_released(s):
@@ -177,7 +202,8 @@ def role_thread(ctx, wave, name, role, iters, regrow_at, option, out):
                     c = state["chain"] = tc.Chain(state["backend"], W, H, NF)
                 for _ in range(FRAMES_PER_ITER):
                     c.step(ctx["frames"][c.t][0], ctx["frames"][c.t][1], ctx["poses"][c.t])
-                check_chain(name, it, tc.first_difference(ctx["oracle_log"][:len(c.log)], c.log), bad)
+                want = ctx["oracle_log"][:len(c.log)]
+                check_chain(name, it, tc.first_difference(want, c.log), bad, want, c.log)
             else:
                 for case in ctx["cases"][role]:
                     check_results(name, it, case.name, rec.call(case.name, case.guided, case.run, pkg, ctx["shared"]), case.want, bad)
@@ -305,6 +331,7 @@ def main():
     ap.add_argument("--iters2", type=int, default=10)
     ap.add_argument("--options", default="")
     ap.add_argument("--cache", default=None)
+    ap.add_argument("--alloc-fill", type=int, default=None, metavar="WORD")
     a = ap.parse_args()
     options = dict(x.split("=") for x in a.options.split(",") if x)
     # every call of this process - the bag-of-words entry points too - goes to the developer build, where the hook lives
@@ -320,6 +347,8 @@ def main():
     # b. both libraries and the shared read-only handles, in the main thread
     L, ML = pkg.lib(), pkg.matcher_lib()
     assert L._orbx_developer and ML._orbx_developer
+    if a.alloc_fill is not None:   # before the first GPU call: every scratch block of this process is born filled with the word
+        pkg.debug_set_alloc_fill(1, a.alloc_fill)
     voc = mc.vocabulary()
     ctx["shared"]["voc"] = pkg.Vocabulary(10, 3, 0, 0, voc["parent"], voc["is_leaf"], voc["desc"], voc["weight"])
     report = {"options": options, "cases_s": t_cases, "waves": []}
@@ -328,6 +357,7 @@ def main():
     if not any(t.get("error") for t in report["waves"][0]["threads"].values()):
         report["waves"].append(run_wave(ctx, ROLES[-1:] + ROLES[:-1], a.iters2, min(10, a.iters2 // 2), options))
     report["main_thread_scratch"] = pkg.debug_thread_scratch()
+    report["alloc_fill"] = None if a.alloc_fill is None else {"word": a.alloc_fill, "stats": list(pkg.debug_alloc_fill_stats())}
     report["total_s"] = time.perf_counter() - t0
     print(json.dumps(report), flush=True)
 

@@ -131,6 +131,19 @@ def test_matchers_from_three_threads(pkg, cache):
         assert any(p[0] in (pkg.RES_PAR_Q2, pkg.RES_PAR_Q4) for ps in tr.values() for p in ps), tr
 
 
+def test_matchers_from_three_threads_on_filled_scratch(pkg, cache):
+    """--alloc-fill 1: every scratch block of the child (arenas and their mirrors, staging pairs, BoW scratch, the extractors' plan buffers
+    and frame records, the completion words before their initialisation) is born holding the word 1 - wave 1 then runs under wave 2's
+    conditions (blocks that are no zero pages), on every run.  6 and 3 iterations; everything check_report asks, and the fill reached the
+    threads' scratch: at least the three arenas + mirrors of each wave, more than 2 * 3 * 2 blocks of 4 MiB."""
+    rep = run_worker(cache, "--alloc-fill", "1", "--iters1", "6", "--iters2", "3")
+    print("cases built in %.1f s, the run took %.1f s; filled %s" % (rep["cases_s"], rep["total_s"], rep["alloc_fill"]))
+    check_report(rep, (6, 3))
+    assert rep["alloc_fill"]["word"] == 1
+    blocks, nbytes = rep["alloc_fill"]["stats"]
+    assert blocks >= 12 and nbytes >= 12 * MIN["arena_cap"], rep["alloc_fill"]
+
+
 def _data_fallback(pkg, p):
     """The exact kernels for a reason of the call's data or size, not of an option."""
     return p[0] == pkg.RES_EXACT and p[1] in (pkg.FB_CAND_CAP, pkg.FB_QK, pkg.FB_INIT_SIZE, pkg.FB_N)

@@ -13,6 +13,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import match_cases as mc                 # noqa: E402
 import match_threads_worker as worker    # noqa: E402
+import tracking_chain as tc              # noqa: E402
 
 NOTHING = {"arena_cap": 0, "arena_device": -1, "arena_stream": 0, "arena_word": 0, "stage_cap": 0, "stage_device": -1, "bow_cap": 0,
            "bow_device": -1}
@@ -100,6 +101,46 @@ def test_worker_comparison_names_thread_iteration_call_and_field():
     assert bad == [{"thread": "2", "iteration": 7, "call": "chain", "field": "local", "first_index": 5}]
     worker.check_scratch("2", 10, "search_local_points_big", False, bad)
     assert bad[-1] == {"thread": "2", "iteration": 10, "call": "search_local_points_big", "field": "scratch", "first_index": -1}
+
+
+def test_worker_chain_report_says_what_differed():
+    """A wrong tracking chain: besides frame and field, the report holds the values got and wanted of a count, and of an array the first
+    eight differing 32-bit word indices with the words on both sides - one occurrence of a rare failure then says what differed."""
+    rng = np.random.default_rng(5)
+    proj = rng.integers(-1, 900, 40).astype(np.int32)
+    want = [{"n": 300, "proj_n": 0, "proj": b""}, {"n": 301, "proj_n": 212, "proj": proj.tobytes()}]
+    same = [dict(x) for x in want]
+    bad = []
+    worker.check_chain("0", 1, tc.first_difference(want, same), bad, want, same)
+    assert bad == []
+    # a count
+    got = [dict(x) for x in want]
+    got[1]["proj_n"] = 211
+    worker.check_chain("0", 2, tc.first_difference(want, got), bad, want, got)
+    assert bad == [{"thread": "0", "iteration": 2, "call": "chain", "field": "proj_n", "first_index": 1, "got": 211, "want": 212}]
+    # an array: ten wrong elements, the first eight are named, in order, with both words
+    wrong = proj.copy()
+    where = [3, 5, 8, 13, 21, 22, 30, 31, 38, 39]
+    wrong[where] += 1
+    got = [dict(x) for x in want]
+    got[1]["proj"] = wrong.tobytes()
+    bad = []
+    worker.check_chain("1", 3, tc.first_difference(want, got), bad, want, got)
+    assert len(bad) == 1 and (bad[0]["field"], bad[0]["first_index"]) == ("proj", 1)
+    assert bad[0]["indices"] == where[:8] and bad[0]["got_bytes"] == bad[0]["want_bytes"] == 160
+    assert bad[0]["got"] == ["%08x" % (int(v) & 0xFFFFFFFF) for v in wrong[where[:8]]]
+    assert bad[0]["want"] == ["%08x" % (int(v) & 0xFFFFFFFF) for v in proj[where[:8]]]
+    # another length: both lengths, and the differing words of the common part
+    got[1]["proj"] = wrong.tobytes()[:-8]
+    bad = []
+    worker.check_chain("1", 4, tc.first_difference(want, got), bad, want, got)
+    assert (bad[0]["got_bytes"], bad[0]["want_bytes"], bad[0]["indices"]) == (152, 160, where[:8])
+    # a shorter log
+    bad = []
+    worker.check_chain("2", 5, (1, "length"), bad, want, want[:1])
+    assert bad == [{"thread": "2", "iteration": 5, "call": "chain", "field": "length", "first_index": 1, "got": 1, "want": 2}]
+    import json
+    json.dumps(bad)          # the report travels as JSON
 
 
 def test_worker_overlap_matrix_is_ordered():
