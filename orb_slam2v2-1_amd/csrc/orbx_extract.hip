@@ -421,9 +421,15 @@ static void launch_pyramid(orbx_extractor *h, const uint8_t *d_imgs, uint8_t *py
     if ((h->opt[24] == 2 || (h->opt[24] == 0 && B <= ORBX_HIST_IMAGES)) && padLds <= 60 * 1024)
         hipLaunchKernelGGL(k_pyr_pad_rows, dim3((g0.h + PAD_ROWS_PER_BLOCK - 1) / PAD_ROWS_PER_BLOCK, B), dim3(256), padLds, st, d_imgs, stride, img_stride, pyr,
                            h->sp.pyrImgBytes, h->d_geom);
-    else
-        hipLaunchKernelGGL(k_pyr_pad<true>, dim3(((g0.pstride >> 4) * g0.prows + 255) / 256, 1, B), dim3(256), 0, st, d_imgs, stride,
-                           img_stride, pyr, h->sp.pyrImgBytes, h->d_geom, 0);
+    else {
+        // the interior 16-byte chunks of PAD_FULL_ROWS padded rows per blockIdx.y (whole waves, at most 256 threads), then the rows of
+        // blocks that share out the chunks touching the frame (the kernel derives the same nI / nE / rowBlocks from the level's geometry)
+        const int pc = g0.pstride >> 4, cI0 = (ORBX_EDGE + 15) >> 4, cI1 = std::max((g0.w + ORBX_EDGE) >> 4, cI0), nI = cI1 - cI0, nE = pc - nI;
+        const int threads = std::min(256, std::max(64, (nI + 63) & ~63)), gx = std::max(1, (nI + threads - 1) / threads);
+        const int rowBlocks = (g0.prows + PAD_FULL_ROWS - 1) / PAD_FULL_ROWS, edgeRows = (nE * g0.prows + gx * threads - 1) / (gx * threads);
+        hipLaunchKernelGGL(k_pyr_pad<true>, dim3(gx, rowBlocks + edgeRows, B), dim3(threads), 0, st, d_imgs, stride, img_stride, pyr,
+                           h->sp.pyrImgBytes, h->d_geom, 0);
+    }
     // ORBX_OPT_PYRAMID_FORM = 4 (and small batches by default, ORBX_OPT_PYR_CHAINS): the levels in chains, one launch per chain
     const int cv = h->opt[25] == 3 ? 1 : 0;   // ORBX_OPT_PYR_CHAINS: 2 / 3 = chains of up to 4 / 7 levels (0: the default, 1: never)
     if (h->sp.nChains[cv] > 0 && !hybrid && (h->opt[5] == 4 || (h->opt[5] == 0 && h->opt[25] != 1 && B <= ORBX_HIST_IMAGES))) {

@@ -114,6 +114,7 @@ __global__ void k_pyr_pad(const uint8_t *img, int sstride, size_t simg, uint8_t 
 __global__ void k_pyr_chain(uint8_t *pyr, size_t pyrImgBytes, const LevelGeom *geom, const int32_t *tab, ChainPlan cp);   // orbx_pyramid.hip
 __global__ void k_pyr_pad_rows(const uint8_t *img, int sstride, size_t simg, uint8_t *pyr, size_t pyrImgBytes, const LevelGeom *geom);   // orbx_pyramid.hip
 #define PAD_ROWS_PER_BLOCK 4
+#define PAD_FULL_ROWS 4        // k_pyr_pad<true>: padded rows whose interior chunks one blockIdx.y copies
 struct StripBases { int v[ORBX_MAX_LEVELS + 1]; };   // first strip of every level (levels with cells wider than 32 px own none)
 __global__ void k_fast_strips(const uint8_t *pyr, size_t pyrImgBytes, const LevelGeom *geom, int nlevels, int totalStrips, int totalCells,
                               uint32_t *cellCnt, uint32_t *cellRaw, uint32_t *slots, size_t slotsPerImg, int iniTh, int minTh,

@@ -1,6 +1,7 @@
 // orbx_fast.hip — per-cell cv::FAST with threshold fallback (src/ORBextractor.cc:789-829): k_fast_strips, k_fast_cells, k_gather
 // (part of the ORB extractor, see orbx_extract.hip for the pipeline and the C ABI)
 #include "orbx_extract_dev.h"
+#include "orbx_bufaddr.h"
 // ------------------------------------------------------------------------------------
 // K2: one wave per 30-px cell (:789-829).  The cell window (cell + 6 px) is staged in LDS
 // as one dword per pixel holding the pixel PAIR (p, p+1) in two 16-bit halves, so that the
@@ -449,12 +450,13 @@ __global__ __launch_bounds__(64 * FAST_WAVES) void k_fast_strips(
     const int chS = __builtin_amdgcn_readfirstlane(ch), thS = __builtin_amdgcn_readfirstlane(th), pstrideS = __builtin_amdgcn_readfirstlane(g.pstride);
     // everything that depends on the row number alone is kept on the scalar unit (readfirstlane): the loop counter, the ring
     // slot, the row's byte offset (a padded level is far smaller than 4 GiB) - the vector ALU is the kernel's bottleneck
+    // The window through a buffer descriptor (orbx_bufaddr.h): base = the aligned window origin, range = the rest of the padded level
+    // (a window row's 8-byte items end inside their padded row), lane offset = the item, scalar offset = the row: no address
+    // arithmetic on the vector ALU (as a pointer sum the compiler folds the scalar row offset into a 64-bit VECTOR add per load).
+    const orbx_buf_t rowBuf = buf_make(src, (uint32_t)g.pstride * (uint32_t)g.prows - (uint32_t)(a - sh));
     auto load_row = [&](int r) -> uint2 {
         const uint32_t ro = (uint32_t)(min(r, thS - 1) * pstrideS);
-        const uint32_t *p = (const uint32_t *)(src + ro + loff);   // scalar row base + 32-bit lane offset
-        uint2 d;
-        d.x = p[0]; d.y = p[1];
-        return d;
+        return buf_load_b64(rowBuf, loff, ro);   // descriptor + 32-bit lane offset + scalar row offset
     };
     uint32_t *Ew = E + 4 * qi;
     auto write_row = [&](int slot, uint2 d) {   // slot = row & 7, a compile-time constant at every call site
@@ -479,18 +481,20 @@ __global__ __launch_bounds__(64 * FAST_WAVES) void k_fast_strips(
     const int i0 = c * g.wCell + 3 + 2 * j;                   // strip column of my pair's first pixel
     const uint32_t *q0 = E + sh + i0;
     const uint32_t vmask = (2 * j < cw ? 0xFFFFu : 0u) | (2 * j + 1 < cw ? 0xFFFF0000u : 0u);
-    // the lanes of my cell below me / up to me
-    const uint32_t ltc = (1u << j) - 1u;
+    // the lanes of my cell below me in a row's 16 ballot bits; the same for the second row of a pair (all of the first row + those)
+    const uint32_t ltc = (1u << j) - 1u, ltcB = 0xFFFFu | (ltc << 16);
     const int cs = 16 * c;   // my cell's 16 lanes inside a ballot
     const half2v tl2 = __builtin_bit_cast(half2v, (uint32_t)tlo * 0x00010001u);
     const uint32_t x0 = (uint32_t)(cj * g.wCell + 3 + 2 * j), ybase = (uint32_t)(ci * g.hCell + 3);
-    // slot list of my cell: scalar base of the level's slots + 32-bit lane offset
-    uint32_t *lvlSlots = slots + (size_t)b * slotsPerImg + g.slotOff;
-    const uint32_t cellOff = (uint32_t)((ci * g.nCols + cj) * g.capc);
+    // slot list of my cell: descriptor of the level's slot block (ncells * capc words) + 32-bit lane offset.  slot4 = byte offset of
+    // my cell's next free slot (the same in its 16 lanes); the survivors >= min(iniTh, minTh) so far are (slot4 - cellOff4) / 4.
+    const orbx_buf_t slotBuf = buf_make(slots + (size_t)b * slotsPerImg + g.slotOff, (uint32_t)g.keyCap * 4u);
+    const uint32_t cellOff4 = (uint32_t)((ci * g.nCols + cj) * g.capc) * 4u;
+    uint32_t slot4 = cellOff4;
     // NMS state: S1 = scores (+1) of row y-1, H1 / H2 = 3-wide horizontal maxima of rows y-1 / y-2, LR1 = max(left, right) of row y-1
     uint32_t S1 = 0, H1 = 0, H2 = 0, LR1 = 0;
-    uint32_t nRaw = 0, nHi = 0;   // survivors >= min(iniTh, minTh) so far in my cell (same in its 16 lanes) / MY survivors >= max(iniTh, minTh)
-    // one evaluated row: scores of row y, suppression verdict for row y-1 (sign flags of its two pixels, its scores), ring update
+    uint32_t nHi = 0;   // MY survivors >= max(iniTh, minTh)
+    // one evaluated row: scores of row y, suppression verdict for row y-1 (per pixel: S1 - neighbours clamped at 0, its scores), ring update
     // R = y & 7 is a compile-time constant at every call site (the loop below advances by 8 rows): window row y + k sits in ring
     // slot (R + k) & 7, an immediate offset from ONE base register - no mirror of the ring's first rows, no per-row address
     auto rowstep = [&](const int R, int y, uint32_t &kpOut, uint32_t &sOut) {
@@ -539,10 +543,11 @@ __global__ __launch_bounds__(64 * FAST_WAVES) void k_fast_strips(
         const uint32_t H0 = __builtin_bit_cast(uint32_t, pk_max3(Lh, Sh, Rh));
         // max(left, right, tlo): the threshold min(iniTh, minTh) rides along as a third "neighbour" (score + 1 > tlo <=> score >= tlo)
         const uint32_t LR0 = __builtin_bit_cast(uint32_t, pk_max3(Lh, Rh, tl2));
-        // strict 3x3 maximum of row y-1 (rows y-2 and y through their horizontal maxima) and score >= tlo: ONE sign test per
-        // pixel (exact on these values; a negative f16 is a negative int16)
+        // strict 3x3 maximum of row y-1 (rows y-2 and y through their horizontal maxima) and score >= tlo: a strict maximum is the
+        // only POSITIVE S1 - nb (exact on these values), so with the difference clamped at 0 the dword is non-zero exactly when
+        // one of the lane's two pixels survives: ONE compare per row
         const half2v nb = pk_max3(__builtin_bit_cast(half2v, H2), __builtin_bit_cast(half2v, H0), __builtin_bit_cast(half2v, LR1));
-        kpOut = __builtin_bit_cast(uint32_t, __builtin_bit_cast(half2v, S1) - nb);
+        kpOut = __builtin_bit_cast(uint32_t, __builtin_elementwise_maximum(__builtin_bit_cast(half2v, S1) - nb, (half2v){(_Float16)0, (_Float16)0}));
         sOut = S1;
         S1 = S; H2 = H1; H1 = H0; LR1 = LR0;
         // stream: window row y+7 (loaded during this iteration) replaces row y-1 in the ring; row y+8 goes in flight
@@ -559,21 +564,22 @@ __global__ __launch_bounds__(64 * FAST_WAVES) void k_fast_strips(
         rowstep(R, y, kpA, sA);          // verdict for row y-1
         rowstep(R + 1, y + 1, kpB, sB);  // verdict for row y   (y + 1 > chS: an all-zero row, nothing survives)
         FPHASE("emission");
-        const short2v fa = __builtin_bit_cast(short2v, kpA), fb = __builtin_bit_cast(short2v, kpB);
-        const bool inA = fa.x > 0 || fa.y > 0, inB = fb.x > 0 || fb.y > 0;
-        const unsigned long long mA = __ballot(inA), mB = __ballot(inB);
+        const bool inB = kpB != 0u;
+        const unsigned long long mA = __ballot(kpA != 0u), mB = __ballot(inB);
         if (mA | mB) {   // wave-uniform
-            const uint32_t aA = (uint32_t)(mA >> cs) & 0xFFFFu, aB = (uint32_t)(mB >> cs) & 0xFFFFu;   // my cell's 16 lanes of the ballots
-            const bool second = inB ? fb.y > 0 : fa.y > 0;                       // my survivor is the pair's second pixel
+            // my cell's 16 lanes of the two ballots as ONE word in row-major order: row y-1 in the low half, row y in the high half
+            const uint32_t T = __builtin_amdgcn_perm((uint32_t)(mB >> cs), (uint32_t)(mA >> cs), 0x05040100u);
+            const uint32_t k = kpA | kpB;                                        // at most ONE of its four halves is non-zero: my survivor's
+            const bool second = k > 0xFFFFu;                                     // my survivor is the pair's second pixel
             const uint32_t sv = inB ? sB : sA;
             const uint32_t sc = second ? sv >> 16 : sv & 0xFFFFu;                // its score + 1
             // row-major order: row y-1 before row y, inside a row the survivors of my cell's lower lanes first
-            const uint32_t pos = cellOff + nRaw + (inB ? __popc(aA) + __popc(aB & ltc) : __popc(aA & ltc));
+            const uint32_t pos4 = slot4 + 4u * __popc(T & (inB ? ltcB : ltc));
+            const uint32_t yrow = ((ybase + (uint32_t)(y - 1)) << 12) - (1u << 24);   // scalar
             // (a cell cannot hold more than capc = ceil(w/2) * ceil(h/2) strict 3x3 maxima: no two of them are neighbours)
-            if (inA || inB)
-                lvlSlots[pos] = (sc << 24) + (second ? x0 + 1u : x0) + ((ybase + (uint32_t)(y - 1) + (inB ? 1u : 0u)) << 12) - (1u << 24);
-            nHi += (inA || inB) && sc > (uint32_t)thi ? 1u : 0u;
-            nRaw += __popc(aA) + __popc(aB);
+            if (k != 0u) buf_store_b32(slotBuf, pos4, 0u, (sc << 24) + (x0 + (second ? 1u : 0u)) + (inB ? yrow + (1u << 12) : yrow));
+            nHi += k != 0u && sc > (uint32_t)thi ? 1u : 0u;
+            slot4 += 4u * __popc(T);
         }
     };
     FPHASE("loop");
@@ -590,6 +596,7 @@ __global__ __launch_bounds__(64 * FAST_WAVES) void k_fast_strips(
 #pragma unroll
     for (int o = 8; o > 0; o >>= 1) nHi += __shfl_xor(nHi, o);
     if (j == 0 && exists) {
+        const uint32_t nRaw = (slot4 - cellOff4) >> 2;   // survivors >= min(iniTh, minTh) of my cell
         // {>= iniTh} if non-empty else {>= minTh} (:809-816): one of the two sets is the whole list, the other the nHi entries
         const uint32_t nA = iniTh >= minTh ? nHi : nRaw, nB = iniTh >= minTh ? nRaw : nHi;
         cellCnt[cellIdx] = min(nA ? nA : nB, (uint32_t)g.capc);

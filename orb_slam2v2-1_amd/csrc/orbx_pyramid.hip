@@ -1,6 +1,7 @@
 // orbx_pyramid.hip — ORBextractor::ComputePyramid (src/ORBextractor.cc:1107-1132): k_pyr_pad, k_pyr_level, k_pyramid_fused
 // (part of the ORB extractor, see orbx_extract.hip for the pipeline and the C ABI)
 #include "orbx_extract_dev.h"
+#include "orbx_bufaddr.h"
 // ------------------------------------------------------------------------------------
 // K1: ComputePyramid (:1107-1132) in ONE launch.  A workgroup owns a tile of the coarsest
 // level and, through the resize source offsets, the corresponding rectangles of every finer
@@ -200,16 +201,20 @@ __global__ __launch_bounds__(256) void k_pyr_level(uint8_t *__restrict__ pyr, si
         if (RW == 16) m |= __shfl_xor(m, 8);
         const uint32_t mask = __builtin_amdgcn_readfirstlane(m);
         const int lastk = 31 - __builtin_clz(mask | 1u);   // source rows past the last output row's second one are neither fetched nor filtered
-        uint2 q[SR];
+        // Both levels through buffer descriptors (orbx_bufaddr.h), one per (image, level): the source from its padded row of source
+        // row 0 to the level's end, the destination the whole padded level.  The lane's part of an address is its 32-bit column
+        // offset, the row is a SCALAR byte offset: no per-lane address arithmetic, no 64-bit pointer per row in vector registers.
+        const orbx_buf_t srcBuf = buf_make(srow0, (uint32_t)sps * (uint32_t)(geom[l - 1].prows - ORBX_EDGE));
+        const orbx_buf_t dstBuf = buf_make(base + G.poff, (uint32_t)G.pstride * (uint32_t)G.prows);
+        uint2 q[SR];   // rows past lastk stay unset: the load and its use sit under the same wave-uniform guard
 #pragma unroll
-        for (int k = 0; k < SR; k++) {   // scalar row pointer + the lane's 32-bit column offset: no per-lane address arithmetic
-            const uint8_t *rowp = srow0 + (uint32_t)(min(rf + k, sh - 1) * sps);   // 32-bit scalar product (a padded level is far smaller than 4 GiB)
-            q[k] = make_uint2(0u, 0u);
-            if (k <= lastk) q[k] = *(const uint2 *)(rowp + (uint32_t)A);   // wave-uniform
+        for (int k = 0; k < SR; k++) {
+            if (k > lastk) continue;   // wave-uniform
+            q[k] = buf_load_b64(srcBuf, (uint32_t)A, (uint32_t)(min(rf + k, sh - 1) * sps));   // 32-bit scalar product (a padded level is far smaller than 4 GiB)
         }
         uint32_t tpa = 0, tpb = 0;
         int cnt = 0;
-        uint8_t *drow = drow0 + (size_t)y0 * G.pstride - 1;   // scalar; the lane's column x0 = xoff - 1 with xoff >= 0
+        uint32_t drow = (uint32_t)((ORBX_EDGE + y0) * G.pstride + ORBX_EDGE - 1);   // scalar; the lane's column x0 = xoff - 1 with xoff >= 0
         const uint32_t xoff = (uint32_t)(x0 + 1);
 #pragma unroll
         for (int k = 0; k < SR; k++) {
@@ -221,8 +226,8 @@ __global__ __launch_bounds__(256) void k_pyr_level(uint8_t *__restrict__ pyr, si
                 const uint32_t b0 = (bb & 0xFFFu) << 12, b1 = ((bb >> 16) & 0xFFFu) << 12;   // scalar; beta <= 2048
                 const uint32_t pa = (vmulhi24(b0, tpa) + vmulhi24(b1, tca) + 2) >> 2;
                 const uint32_t pb = (vmulhi24(b0, tpb) + vmulhi24(b1, tcb) + 2) >> 2;
-                if (vst) *(uint16_t *)(drow + xoff) = (uint16_t)(pa | (pb << 8));
-                drow += G.pstride;
+                if (vst) buf_store_b16(dstBuf, xoff, drow, (uint16_t)(pa | (pb << 8)));
+                drow += (uint32_t)G.pstride;
                 cnt++;
             }
             tpa = tca; tpb = tcb;
@@ -265,7 +270,7 @@ template <bool FULL>
 __global__ __launch_bounds__(256) void k_pyr_pad(const uint8_t *__restrict__ img, int sstride, size_t simg,
                                                  uint8_t *__restrict__ pyr, size_t pyrImgBytes,
                                                  const LevelGeom *__restrict__ geom, int l0) {
-    const int l = l0 + blockIdx.y;
+    const int l = FULL ? l0 : l0 + blockIdx.y;   // (FULL: blockIdx.y counts blocks of padded rows)
     const LevelGeom G = geom[l];
     uint8_t *lvl = pyr + (size_t)blockIdx.z * pyrImgBytes + G.poff;
     const uint8_t *src = FULL ? img + (size_t)blockIdx.z * simg : lvl + (size_t)ORBX_EDGE * G.pstride + ORBX_EDGE;
@@ -273,37 +278,47 @@ __global__ __launch_bounds__(256) void k_pyr_pad(const uint8_t *__restrict__ img
     const int pw4 = (G.w + 2 * ORBX_EDGE + 3) >> 2, rows = G.h + 2 * ORBX_EDGE;
     const int LW = (ORBX_EDGE >> 2) + 1, R0 = (ORBX_EDGE + G.w) >> 2, side = LW + (pw4 - R0);
     if (FULL) {   // 16-byte chunks of the padded rows; interior chunks are one (unaligned) 16-byte load
-        // Chunk order: first every chunk that lies inside the image row (one 16-byte load), then the few per row that touch
-        // the frame (byte gathers) - in row-major order each of those sat in a different wave and made nearly EVERY wave run
-        // both paths (213 VALU instructions per wave for a copy).
-        const int pc = G.pstride >> 4, totalc = pc * rows;
+        // Grid (launch_pyramid): blockIdx.y < rowBlocks is the interior chunks - the chunks that lie inside the image row - of
+        // PAD_FULL_ROWS consecutive padded rows.  The reflected source rows and all row bases are scalar, a thread's part of every
+        // address is its 32-bit chunk offset, and a chunk is a straight 16-byte copy: no division, no border test, no 64-bit row
+        // product per thread; the rows' loads are all in flight before the first store (one row per block made 64 % more waves
+        // than a chunk per thread, each waiting on one load: the launch took 5 % longer for a quarter of the instructions).  The
+        // few chunks per row that touch the frame (byte gathers) are packed into the blocks blockIdx.y >= rowBlocks, so that only
+        // those waves run the gather (in row-major order each of them sat in a different wave and made nearly EVERY wave run both paths).
+        const int pc = G.pstride >> 4;
         const int cI0 = (ORBX_EDGE + 15) >> 4, cI1 = max((G.w + ORBX_EDGE) >> 4, cI0);   // interior chunks: cI0 <= c < cI1
-        const int nI = cI1 - cI0, nE = pc - nI, totalI = nI * rows;
-        for (int i = blockIdx.x * 256 + threadIdx.x; i < totalc; i += gridDim.x * 256) {
-            int py, c;
-            if (i < totalI) {
-                py = i / nI;
-                c = cI0 + (i - py * nI);
-            } else {
-                const int j = i - totalI;
-                py = j / nE;
-                const int k = j - py * nE;
-                c = k < cI0 ? k : cI1 + (k - cI0);
-            }
-            const uint8_t *srow = src + (size_t)reflect101c(py - ORBX_EDGE, G.h) * ss;
-            const int px = c * 16 - ORBX_EDGE;
-            uint4 v;
-            if (px >= 0 && px + 15 < G.w) __builtin_memcpy(&v, srow + px, 16);
-            else {
-                uint32_t t[4];
+        const int nI = cI1 - cI0, nE = pc - nI;
+        const int rowBlocks = (rows + PAD_FULL_ROWS - 1) / PAD_FULL_ROWS;
+        if ((int)blockIdx.y < rowBlocks) {
+            const int i = blockIdx.x * blockDim.x + threadIdx.x;
+            if (i >= nI) return;
+            const uint32_t off = (uint32_t)i * 16u;
+            uint4 v[PAD_FULL_ROWS];
 #pragma unroll
-                for (int u = 0; u < 4; u++)
-                    t[u] = (uint32_t)srow[reflect101c(px + 4 * u, G.w)] | ((uint32_t)srow[reflect101c(px + 4 * u + 1, G.w)] << 8) |
-                           ((uint32_t)srow[reflect101c(px + 4 * u + 2, G.w)] << 16) | ((uint32_t)srow[reflect101c(px + 4 * u + 3, G.w)] << 24);
-                v = make_uint4(t[0], t[1], t[2], t[3]);
+            for (int r = 0; r < PAD_FULL_ROWS; r++) {   // (rows past the last one repeat it: the same bytes to the same place)
+                const int py = min((int)blockIdx.y * PAD_FULL_ROWS + r, rows - 1);
+                const uint8_t *srow = src + (size_t)reflect101c(py - ORBX_EDGE, G.h) * ss + (cI0 * 16 - ORBX_EDGE);   // scalar
+                __builtin_memcpy(&v[r], srow + off, 16);
             }
-            *(uint4 *)(lvl + (size_t)py * G.pstride + c * 16) = v;
+#pragma unroll
+            for (int r = 0; r < PAD_FULL_ROWS; r++) {
+                const int py = min((int)blockIdx.y * PAD_FULL_ROWS + r, rows - 1);
+                *(uint4 *)(lvl + (size_t)py * G.pstride + cI0 * 16 + off) = v[r];                                      // scalar row base
+            }
+            return;
         }
+        const int j = (((int)blockIdx.y - rowBlocks) * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x;
+        if (j >= nE * rows) return;
+        const int py = j / nE, k = j - py * nE;
+        const int c = k < cI0 ? k : cI1 + (k - cI0);
+        const uint8_t *srow = src + (size_t)reflect101c(py - ORBX_EDGE, G.h) * ss;
+        const int px = c * 16 - ORBX_EDGE;
+        uint32_t t[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++)
+            t[u] = (uint32_t)srow[reflect101c(px + 4 * u, G.w)] | ((uint32_t)srow[reflect101c(px + 4 * u + 1, G.w)] << 8) |
+                   ((uint32_t)srow[reflect101c(px + 4 * u + 2, G.w)] << 16) | ((uint32_t)srow[reflect101c(px + 4 * u + 3, G.w)] << 24);
+        *(uint4 *)(lvl + (size_t)py * G.pstride + c * 16) = make_uint4(t[0], t[1], t[2], t[3]);
         return;
     }
     const int total = 2 * ORBX_EDGE * pw4 + G.h * side;
