@@ -854,6 +854,40 @@ int orbo_pose_optimization_device(const orbx_keypoint_t *d_kun, const float *d_u
                                   int nlevels, const orbo_worldpos_t *pts, const orbm_camera_t *cam, const float *Tcw_in16,
                                   float *Tcw_out16, uint8_t *outlier, int *ngood, orbo_pose_info_t *info, int device, void *stream);
 
+/* ---- Optimizer::OptimizeSim3 (src/Optimizer.cc:1051-1246): the refinement of a loop candidate's Sim3 between SearchBySim3 and
+ * the projection search of LoopClosing::ComputeSim3 (src/LoopClosing.cc:336), on flat arrays.  One free 7-DoF vertex
+ * (VertexSim3Expmap), per match the two edges EdgeSim3ProjectXYZ (point 2 through S12 into camera 1) and
+ * EdgeInverseSim3ProjectXYZ (point 1 through S12^-1 into camera 2) with every map-point vertex fixed, the dense solver: a 7x7
+ * Levenberg-Marquardt with the Huber kernel (delta = (float)sqrt(th2)) and g2o's NUMERIC Jacobian (central differences, 1e-9:
+ * base_binary_edge.hpp:131-205; the analytic one is commented out in types_seven_dof_expmap).  optimize(5), the matches whose
+ * last evaluation exceeded th2 on either edge dropped, optimize(10 if any was dropped, else 5) continuing from the first, the
+ * same test again.  A restatement in double with the reference's float narrowings; the whole schedule is
+ * ONE kernel launch, one workgroup per problem; two calls on the same input give the same bytes.  A singular normal matrix is
+ * not pinned to the reference: the call terminates, returns ORBX_OK and its output is finite or unchanged.
+ *
+ * A row is one match the caller's filter accepted (:1106-1141: both map points present and not bad, the second observed in
+ * keyframe 2): the two WORLD positions, the two undistorted keypoints (u1 v1 in keyframe 1, u2 v2 in keyframe 2) and
+ * mvInvLevelSigma2[octave] of each.  The kernel moves the points into their camera frames in float as the reference's cv::Mat
+ * product does (Tcw1, Tcw2: row-major float 4x4).  K = fx fy cx cy.  s, R, t: Sim3Solver's float estimate, from which the start
+ * is g2o::Sim3(Matrix3d R, t, s) - Quaterniond(R) of the widened floats, not normalised.
+ * dropped[i] = 1 for a match nulled in either round.  *ninliers = the reference's return value.  When fewer than 10 matches
+ * survive the first round (or n < 10) the reference returns 0 with the first round's drops applied and the Sim3 as it came in:
+ * then *ninliers = 0, info->rounds < 2 and the outputs hold the INPUT Sim3.  S12_out16 = Converter::toCvMat(Sim3): s*R | t as a
+ * row-major float 4x4; info (may be NULL): the same estimate in double (q = x y z w), iterations[r] / trials[r] the LM
+ * iterations and linear solves of round r.
+ * NULL pointers, n < 0, B < 0, offsets that start below 0 or decrease, an inv_sigma2 or th2 that is negative or not finite:
+ * ORBX_ERR_ARG, checked before the device is touched.  No usable GPU: ORBX_ERR_NO_DEVICE; there is no CPU path.  Scratch, pinned
+ * mirror and stream are per host thread (orbx_thread_release_scratch).  (Prefix orbz_: orbo_ is PoseOptimization's section.) */
+typedef struct { float w1[3], w2[3]; float u1, v1, u2, v2; float inv_sigma2_1, inv_sigma2_2; } orbz_sim3_match_t;   /* 48 B */
+typedef struct { float Tcw1[16], Tcw2[16]; float K1[4], K2[4]; float s, R[9], t[3]; float th2; int32_t fix_scale; } orbz_sim3_problem_t; /* 220 B */
+typedef struct { int32_t correspondences, bad, rounds, iterations[2], trials[2], reserved; double q[4], t[3], s; } orbz_sim3_info_t; /* 96 B */
+int orbz_optimize_sim3(const orbz_sim3_match_t *m, int n, const orbz_sim3_problem_t *p, float *S12_out16, uint8_t *dropped,
+                       int *ninliers, orbz_sim3_info_t *info /* may be NULL */, int device);
+/* B independent problems (loop candidates) in one launch: offsets[B+1] into m / dropped (offsets[0] need not be 0), ps[B],
+ * S12_out16 [B][16], ninliers[B], infos[B] (may be NULL).  Each problem's results are those of its single call, byte for byte. */
+int orbz_optimize_sim3_batch(const orbz_sim3_match_t *m, const int32_t *offsets, int B, const orbz_sim3_problem_t *ps,
+                             float *S12_out16, uint8_t *dropped, int32_t *ninliers, orbz_sim3_info_t *infos, int device);
+
 /* ---- Initializer::Initialize (src/Initializer.cc:44-929): the monocular map initialisation Tracking runs on the matches of
  * ORBmatcher::SearchForInitialization (src/Tracking.cc:723, :757), on flat arrays.  2 x iterations RANSAC hypotheses (a
  * homography and a fundamental matrix from the 8 matches each set names), scored over all N matches; the choice RH > 0.40;

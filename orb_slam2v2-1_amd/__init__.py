@@ -58,6 +58,13 @@ SIM3_PROBLEM_DTYPE = np.dtype([("Tcw1", "<f4", (16,)), ("Tcw2", "<f4", (16,)), (
                                ("fix_scale", "<i4"), ("min_inliers", "<i4")])
 SIM3_INFO_DTYPE = np.dtype([("n", "<i4"), ("iterations", "<i4"), ("hit_iteration", "<i4"), ("best_iteration", "<i4"),
                             ("best_inliers", "<i4"), ("s", "<f4"), ("R", "<f4", (9,)), ("t", "<f4", (3,)), ("T12", "<f4", (16,))])
+# orbz_sim3_match_t / orbz_sim3_problem_t / orbz_sim3_info_t (Optimizer::OptimizeSim3, optimize_sim3*)
+SIM3OPT_MATCH_DTYPE = np.dtype([("w1", "<f4", (3,)), ("w2", "<f4", (3,)), ("u1", "<f4"), ("v1", "<f4"), ("u2", "<f4"), ("v2", "<f4"),
+                                ("inv_sigma2_1", "<f4"), ("inv_sigma2_2", "<f4")])
+SIM3OPT_PROBLEM_DTYPE = np.dtype([("Tcw1", "<f4", (16,)), ("Tcw2", "<f4", (16,)), ("K1", "<f4", (4,)), ("K2", "<f4", (4,)), ("s", "<f4"),
+                                  ("R", "<f4", (9,)), ("t", "<f4", (3,)), ("th2", "<f4"), ("fix_scale", "<i4")])
+SIM3OPT_INFO_DTYPE = np.dtype([("correspondences", "<i4"), ("bad", "<i4"), ("rounds", "<i4"), ("iterations", "<i4", (2,)),
+                               ("trials", "<i4", (2,)), ("reserved", "<i4"), ("q", "<f8", (4,)), ("t", "<f8", (3,)), ("s", "<f8")])
 # orbp_corr_t / orbp_problem_t / orbp_pnp_info_t (PnPsolver, pnp_ransac_batch)
 PNP_CORR_DTYPE = np.dtype([("w", "<f4", (3,)), ("u", "<f4"), ("v", "<f4"), ("sigma2", "<f4")])
 PNP_PROBLEM_DTYPE = np.dtype([("K", "<f4", (4,)), ("th2", "<f4"), ("min_inliers", "<i4"), ("max_iterations", "<i4"),
@@ -103,6 +110,8 @@ INIT_EXPORTS = ["orbi_initialize", "orbi_initialize_device", "orbi_search"]
 SIM3_EXPORTS = ["orbs_sim3_iterations", "orbs_sim3_ransac", "orbs_sim3_ransac_batch"]
 # the PnPsolver section (prefix orbp_), apart for the same reason
 PNP_EXPORTS = ["orbp_pnp_parameters", "orbp_pnp_ransac", "orbp_pnp_ransac_batch"]
+# the Sim3 optimiser section (prefix orbz_; orbo_ is PoseOptimization's), apart for the same reason
+SIM3OPT_EXPORTS = ["orbz_optimize_sim3", "orbz_optimize_sim3_batch"]
 # what include/orbx_dev.h declares on top: exported by the developer build only
 DEV_EXPORTS = ["orbx_debug_level_points", "orbx_debug_sincosf", "orbx_debug_blur_patches", "orbm_debug_features_in_area",
                "orbx_debug_blurred_level", "orbx_debug_octree_fallbacks", "orbm_debug_match_path", "orbm_debug_resolve_plan",
@@ -403,6 +412,8 @@ def _load(path, dev):
     L.orbs_sim3_iterations.argtypes = [i32, C.c_double, i32, i32]
     L.orbs_sim3_ransac.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32]
     L.orbs_sim3_ransac_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32]
+    L.orbz_optimize_sim3.argtypes = [vp, i32, vp, vp, vp, C.POINTER(i32), vp, i32]
+    L.orbz_optimize_sim3_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, i32]
     L.orbp_pnp_parameters.argtypes = [i32, C.c_double, i32, i32, i32, f32, C.POINTER(i32), C.POINTER(i32)]
     L.orbp_pnp_ransac.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
     L.orbp_pnp_ransac_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
@@ -1283,6 +1294,56 @@ def pose_optimization_device(d_kun, d_uright, n, inv_level_sigma2, pts, cam, Tcw
     _check(matcher_lib().orbo_pose_optimization_device(d_kun, d_uright, int(n), _p(is2), len(is2), _p(pts), C.byref(cam), _p(T), _p(To),
                                                        _p(out), C.byref(ng), _p(info), int(device), stream or None))
     return To, out, ng.value, _pose_info(info[0])
+
+
+def sim3opt_problem(Tcw1, Tcw2, K1, K2, R, t, s, th2, fix_scale):
+    """one SIM3OPT_PROBLEM_DTYPE record: the keyframes' float 4x4 poses, K = (fx, fy, cx, cy) of each, Sim3Solver's R / t / s, the
+    chi2 threshold and bFixScale"""
+    p = np.zeros(1, SIM3OPT_PROBLEM_DTYPE)
+    p["Tcw1"], p["Tcw2"] = np.asarray(Tcw1, np.float32).reshape(16), np.asarray(Tcw2, np.float32).reshape(16)
+    p["K1"], p["K2"] = np.asarray(K1, np.float32)[:4], np.asarray(K2, np.float32)[:4]
+    p["R"], p["t"], p["s"] = np.asarray(R, np.float32).reshape(9), np.asarray(t, np.float32).reshape(3), s
+    p["th2"], p["fix_scale"] = th2, int(bool(fix_scale))
+    return p[0]
+
+
+def _sim3opt_info(rec):
+    return {"correspondences": int(rec["correspondences"]), "bad": int(rec["bad"]), "rounds": int(rec["rounds"]),
+            "iterations": [int(x) for x in rec["iterations"]], "trials": [int(x) for x in rec["trials"]],
+            "q": np.array(rec["q"], np.float64), "t": np.array(rec["t"], np.float64), "s": float(rec["s"])}
+
+
+def optimize_sim3(matches, problem, device=0):
+    """Optimizer::OptimizeSim3 (orbz_optimize_sim3): matches [n] SIM3OPT_MATCH_DTYPE (the rows the reference's filter accepts), problem
+    one SIM3OPT_PROBLEM_DTYPE record (sim3opt_problem) -> (S12 [4, 4] float32 = s*R | t, dropped [n] uint8, ninliers, info dict:
+    correspondences, bad, rounds, iterations, trials, q (x y z w), t, s in double).  rounds < 2: the reference's early `return 0` -
+    the first round's drops, the Sim3 as it came in."""
+    m = np.ascontiguousarray(matches, SIM3OPT_MATCH_DTYPE)
+    n = len(m)
+    pr = np.ascontiguousarray(np.asarray(problem, SIM3OPT_PROBLEM_DTYPE).reshape(1))
+    So = np.zeros((4, 4), np.float32)
+    dropped = np.zeros(n, np.uint8)
+    info = np.zeros(1, SIM3OPT_INFO_DTYPE)
+    ni = C.c_int(0)
+    _check(matcher_lib().orbz_optimize_sim3(_p(m), n, _p(pr), _p(So), _p(dropped), C.byref(ni), _p(info), int(device)))
+    return So, dropped, ni.value, _sim3opt_info(info[0])
+
+
+def optimize_sim3_batch(matches, offsets, problems, device=0):
+    """orbz_optimize_sim3_batch: B problems (loop candidates) in one launch.  matches are the problems' rows back to back, offsets
+    [B + 1] into them (offsets[0] need not be 0), problems [B] SIM3OPT_PROBLEM_DTYPE
+    -> (S12 [B, 4, 4], dropped [len(matches)], ninliers [B], infos: list of B dicts)"""
+    m = np.ascontiguousarray(matches, SIM3OPT_MATCH_DTYPE)
+    off = np.ascontiguousarray(offsets, np.int32)
+    B = len(off) - 1
+    pr = np.ascontiguousarray(np.asarray(problems, SIM3OPT_PROBLEM_DTYPE).reshape(-1))
+    assert len(pr) == B and (B == 0 or off[B] <= len(m))
+    So = np.zeros((max(B, 1), 4, 4), np.float32)
+    dropped = np.zeros(len(m), np.uint8)
+    infos = np.zeros(max(B, 1), SIM3OPT_INFO_DTYPE)
+    ni = np.zeros(max(B, 1), np.int32)
+    _check(matcher_lib().orbz_optimize_sim3_batch(_p(m), _p(off), B, _p(pr), _p(So), _p(dropped), _p(ni), _p(infos), int(device)))
+    return So[:B], dropped, ni[:B], [_sim3opt_info(infos[b]) for b in range(B)]
 
 
 def draw_sets(n, iterations, rng):

@@ -135,6 +135,7 @@ void orbx_internal_release_pose_scratch();                   // orbx_poseopt.hip
 void orbx_internal_release_init_scratch();                   // orbx_initializer.hip (thread-local StagePair)
 void orbx_internal_release_sim3_scratch();                   // orbx_sim3.hip        (thread-local StagePair)
 void orbx_internal_release_pnp_scratch();                    // orbx_pnp.hip         (thread-local StagePair)
+void orbx_internal_release_sim3opt_scratch();                // orbx_sim3opt.hip     (thread-local StagePair)
 #ifdef ORBX_DEVELOPER
 // what the calling thread holds of each of the three, for orbm_debug_thread_scratch (include/orbx_dev.h): no HIP call, nothing allocated
 void orbx_internal_arena_info(int64_t *out5);                // capacity, device, call counter, has a stream, has a completion word

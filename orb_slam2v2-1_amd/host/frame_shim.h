@@ -149,6 +149,7 @@ public:
     }
     bool IsInImage(const float &x, const float &y) const { return (x >= mnMinX && x < mnMaxX && y >= mnMinY && y < mnMaxY); }
     float fx = 0, fy = 0, cx = 0, cy = 0, mbf = 0;
+    cv::Mat mK;   // include/KeyFrame.h: the 3x3 CV_32F calibration, read by Optimizer::OptimizeSim3
     int N = 0;
     std::vector<cv::KeyPoint> mvKeysUn;
     std::vector<float> mvuRight;

@@ -1,0 +1,127 @@
+"""Seeded Optimizer::OptimizeSim3 scenes: two keyframes in two maps that differ by a similarity, matched map points in front of both
+cameras (z between 4 and 30 in camera 1, and - the relative motion being small - well above 0 in camera 2), their keypoints with
+pixel noise scaled by the level sigma, a stated fraction of gross outliers, and a start estimate next to the true Sim3: the
+Sim3Solver's leftover error of 1-2 degrees, 1-2 % and a few centimetres, from which the first round is already accepting steps."""
+import os
+import re
+
+import numpy as np
+
+import sim3opt_ref as R
+
+NLEVELS, SCALE = 8, 1.2
+SF = (np.float32(SCALE) ** np.arange(NLEVELS)).astype(np.float32)
+INV_SIGMA2 = (np.float32(1.0) / (SF * SF)).astype(np.float32)
+K_A = (718.856, 718.856, 607.19, 185.2)         # fx fy cx cy: KITTI-00
+K_B = (517.3, 516.5, 318.6, 255.3)              # TUM freiburg1
+TH2 = 10.0                                      # LoopClosing::ComputeSim3's argument (src/LoopClosing.cc:336)
+
+
+def lds_rows():
+    """S3O_LDS_ROWS of csrc/orbx_sim3opt.hip: the matches the kernel stages in LDS"""
+    txt = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "orb_slam2v2-1_amd", "csrc", "orbx_sim3opt.hip")).read()
+    return int(re.search(r"^#define\s+S3O_LDS_ROWS\s+(\d+)\b", txt, flags=re.M).group(1))
+
+
+def rodrigues(rvec):
+    rvec = np.asarray(rvec, np.float64)
+    th = np.linalg.norm(rvec)
+    K = np.array([[0, -rvec[2], rvec[1]], [rvec[2], 0, -rvec[0]], [-rvec[1], rvec[0], 0]])
+    return np.eye(3) if th == 0 else np.eye(3) + np.sin(th) / th * K + (1 - np.cos(th)) / th ** 2 * (K @ K)
+
+
+def pose(rvec, t):
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = rodrigues(rvec), t
+    return T
+
+
+def project(K, X):
+    return np.stack([X[0] / X[2] * K[0] + K[2], X[1] / X[2] * K[1] + K[3]])
+
+
+def make(seed, n, outliers=0.0, gross_first=None, noise=0.7, rot=0.025, trans=0.04, dscale=0.015, scale=1.12, fix_scale=False, K1=K_A,
+         K2=K_A, th2=TH2):
+    """-> dict(matches [n] MATCH_DTYPE, prob [1] PROBLEM_DTYPE record, true (the true Sim3 S12), gross [n] bool, octave [n, 2]).
+    gross_first = g: exactly the first g matches are gross outliers (instead of the fraction `outliers`)."""
+    rng = np.random.default_rng(seed)
+    s_true = 1.0 if fix_scale else scale * float(np.exp(rng.normal(0, 0.03)))
+    St = R.Sim3(R.quat_from_R(rodrigues(rng.normal(0, 0.06, 3))), rng.normal(0, 0.25, 3), s_true)
+    Tcw1 = pose(rng.normal(0, 0.3, 3), rng.normal(0, 2.0, 3)).astype(np.float32)
+    Tcw2 = pose(rng.normal(0, 0.3, 3), rng.normal(0, 2.0, 3)).astype(np.float32)
+    z = rng.uniform(4.0, 30.0, n)
+    X1 = np.stack([rng.uniform(-0.4, 0.4, n) * z, rng.uniform(-0.25, 0.25, n) * z, z])                # camera 1
+    X2 = St.inverse().map(X1)                                                                         # camera 2
+    inv = lambda T: np.linalg.inv(T.astype(np.float64))       # noqa: E731
+    w1 = (inv(Tcw1) @ np.vstack([X1, np.ones(n)]))[:3].T.astype(np.float32)
+    w2 = (inv(Tcw2) @ np.vstack([X2, np.ones(n)]))[:3].T.astype(np.float32)
+    # the keypoints are those of the points the optimiser will see: the float world positions through the float poses
+    P1 = R.transform(Tcw1, w1).astype(np.float64)
+    P2 = R.transform(Tcw2, w2).astype(np.float64)
+    octave = rng.integers(0, NLEVELS, (n, 2))
+    sig = SF[octave].astype(np.float64) * noise
+    uv1 = project(K1, St.map(P2)) + rng.normal(0, 1, (2, n)) * sig[:, 0]
+    uv2 = project(K2, St.inverse().map(P1)) + rng.normal(0, 1, (2, n)) * sig[:, 1]
+    gross = rng.random(n) < outliers
+    if gross_first is not None:
+        gross = np.arange(n) < gross_first
+    jump = rng.choice([-1, 1], (2, n)) * rng.uniform(15, 80, (2, n))
+    side = rng.random(n) < 0.5
+    uv1 = np.where(gross & side, uv1 + jump, uv1)
+    uv2 = np.where(gross & ~side, uv2 + jump, uv2)
+    m = np.zeros(n, R.MATCH_DTYPE)
+    m["w1"], m["w2"] = w1, w2
+    m["u1"], m["v1"], m["u2"], m["v2"] = uv1[0], uv1[1], uv2[0], uv2[1]
+    m["inv_sigma2_1"], m["inv_sigma2_2"] = INV_SIGMA2[octave[:, 0]], INV_SIGMA2[octave[:, 1]]
+    # the start: the truth moved by rot rad, trans m and dscale (relative)
+    d = rng.normal(0, 1, 7)
+    R0 = rodrigues(d[:3] / np.linalg.norm(d[:3]) * rot) @ R.quat_to_R(St.q)
+    t0 = St.t + d[3:6] / np.linalg.norm(d[3:6]) * trans
+    s0 = 1.0 if fix_scale else St.s * (1.0 + np.sign(d[6]) * dscale)
+    prob = np.zeros(1, R.PROBLEM_DTYPE)
+    prob["Tcw1"], prob["Tcw2"], prob["K1"], prob["K2"] = Tcw1.reshape(-1), Tcw2.reshape(-1), K1, K2
+    prob["s"], prob["R"], prob["t"], prob["th2"], prob["fix_scale"] = s0, R0.reshape(-1), t0, th2, int(fix_scale)
+    return dict(matches=m, prob=prob[0], true=St, gross=gross, octave=octave)
+
+
+L = lds_rows()
+# The shapes the tests run, smallest where the kernel can go wrong: name -> make() arguments.  0: nothing to optimise; 9: one round,
+# then the `< 10` return; 10: the smallest that runs both rounds; clean64: no drop, so the second round has 5 iterations; out65: drops,
+# so it has 10, and one match past a wave; fix_scale65: update[6] = 0; drop_below10: 14 matches of which 6 are gross - 8 < 10 survive
+# round one; far: a start far enough off that a trial is rejected; L, L + 1, 1.3 L: the last match staged in LDS, the first read from
+# memory, and more than a workgroup's worth past it; mixed300: two different cameras.
+CASES = {
+    "n0": dict(seed=400, n=0), "n9": dict(seed=409, n=9), "n10": dict(seed=410, n=10),
+    "clean64": dict(seed=464, n=64), "out65": dict(seed=465, n=65, outliers=0.2),
+    "fix_scale65": dict(seed=466, n=65, outliers=0.2, fix_scale=True),
+    "drop_below10": dict(seed=414, n=14, gross_first=6),
+    "far": dict(seed=425, n=120, outliers=0.15, rot=0.5, trans=2.0, dscale=0.4),
+    "nL": dict(seed=3024, n=L, outliers=0.2), "nL+1": dict(seed=1025, n=L + 1, outliers=0.2),
+    "n1.3L": dict(seed=4331, n=L + L * 3 // 10, outliers=0.2),
+    "mixed300": dict(seed=300, n=300, outliers=0.25, K1=K_A, K2=K_B),
+}
+_cache = {}
+
+
+def case(name):
+    if name not in _cache:
+        _cache[name] = make(**CASES[name])
+    return _cache[name]
+
+
+MARGIN = 1e-5       # |chi2 / th2 - 1| below which a flag may differ; the value tests/test_poseopt_gpu.py uses
+DRAWS = 16
+_refs = {}
+
+
+def reference(name):
+    """-> (scene, the restatement's result, its DRAWS results with the matches summed in a random order and every exp / sin / cos moved
+    by up to +-ULPS ulp, S: its largest deviation in q / t / s over those).  Computed once, shared by the CPU and the GPU tests."""
+    if name not in _refs:
+        sc = case(name)
+        ref = R.optimize_sim3(sc["matches"], sc["prob"])
+        rng = np.random.default_rng(4321)
+        draws = [R.optimize_sim3(sc["matches"], sc["prob"], order=rng.permutation(len(sc["matches"])), perturb=rng) for _ in range(DRAWS)]
+        dev = max([0.0] + [float(np.abs(d["sim3"].vec() - ref["sim3"].vec()).max()) for d in draws])
+        _refs[name] = (sc, ref, draws, dev)
+    return _refs[name]
