@@ -132,6 +132,16 @@ int orbm_debug_thread_scratch(int64_t *out, int n_out);
 int orbx_debug_set_alloc_fill(int enable, uint32_t word);
 int orbx_debug_alloc_fill_stats(int64_t out[2]);
 
+/* Stream order under injected stalls (tests/stream_stall.py, tests/test_stream_order_gpu.py).
+ * orbx_debug_stall_stream: one wave of k_spin on `stream` (NULL = the default stream) of `device` - the bounded loop on the 100 MHz wall
+ * clock orbx_side_stream_for probes queues with - for `microseconds` in [1, 50000] (anything else: ORBX_ERR_ARG).  It launches nothing
+ * else and waits for nothing: what is queued on the stream afterwards starts that much later, and a consumer on another stream that
+ * lacks its wait reads what the buffers held before.
+ * orbx_debug_streams: out[0..2] = the handle's own stream, side[0], side[1] (NULL when h is NULL), out[3] = the calling thread's matcher
+ * arena stream, out[4] = its matcher staging-pair stream (NULL: the thread holds none).  n_out must be exactly 5.  Read only, no HIP call. */
+int orbx_debug_stall_stream(void *stream, int microseconds, int device);
+int orbx_debug_streams(orbx_extractor_t *h, void **out, int n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -116,7 +116,8 @@ SIM3OPT_EXPORTS = ["orbz_optimize_sim3", "orbz_optimize_sim3_batch"]
 DEV_EXPORTS = ["orbx_debug_level_points", "orbx_debug_sincosf", "orbx_debug_blur_patches", "orbm_debug_features_in_area",
                "orbx_debug_blurred_level", "orbx_debug_octree_fallbacks", "orbm_debug_match_path", "orbm_debug_resolve_plan",
                "orbm_debug_stereo_path", "orbx_debug_plan_chunk", "orbx_debug_last_plan", "orbm_debug_thread_scratch",
-               "orbx_debug_size_plan", "orbx_debug_set_alloc_fill", "orbx_debug_alloc_fill_stats"]
+               "orbx_debug_size_plan", "orbx_debug_set_alloc_fill", "orbx_debug_alloc_fill_stats", "orbx_debug_stall_stream",
+               "orbx_debug_streams"]
 # include/orbx_dev.h: the int64 record of orbx_debug_size_plan, field order
 SIZE_PLAN_FIELDS = ["max_kp", "totalCells", "maxNodeCap", "lvlKpCap", "pyrImgBytes", "slotsPerImg", "keysPerImg", "fastTileStride", "fastScoreStride",
                     "fastTileRows", "fastLdsPerWave", "totalStrips", "stripLevels", "octLdsBytes", "octPyrLdsBytes", "octPyrWords", "octBigMask",
@@ -433,6 +434,8 @@ def _load(path, dev):
         L.orbx_debug_size_plan.argtypes = [i32, f32, i32, i32, i32, i32, vp, vp, vp, i32, vp, i32, vp, i32]
         L.orbx_debug_set_alloc_fill.argtypes = [i32, C.c_uint32]
         L.orbx_debug_alloc_fill_stats.argtypes = [vp]
+        L.orbx_debug_stall_stream.argtypes = [vp, i32, i32]
+        L.orbx_debug_streams.argtypes = [vp, vp, i32]
     L.orbx_last_error.restype = C.c_char_p
     L.orbx_version.restype = C.c_char_p
     L._orbx_developer = bool(dev)
@@ -921,6 +924,25 @@ def debug_alloc_fill_stats():
     out = np.zeros(2, np.int64)
     _check(lib(True).orbx_debug_alloc_fill_stats(_p(out)), lib(True))
     return int(out[0]), int(out[1])
+
+
+def debug_stall_stream(stream, microseconds, device=0):
+    """Test hook: hold `stream` (a raw hipStream_t, 0 = the default stream) back by a one-wave spin of 1 .. 50000 microseconds; launches
+    nothing else and waits for nothing."""
+    _check(lib(True).orbx_debug_stall_stream(int(stream) if stream else None, int(microseconds), int(device)), lib(True))
+
+
+DEBUG_STREAM_FIELDS = ("main", "side0", "side1", "arena", "staging")
+
+
+def debug_streams(extractor=None):
+    """Test hook, no HIP call: raw hipStream_t values (0 = none) as a dict of DEBUG_STREAM_FIELDS - the own stream and the two side streams
+    of `extractor` (a developer-build ORBextractor, or None), then the calling thread's matcher arena and staging-pair streams."""
+    if extractor is not None:
+        extractor._hooks()
+    out = (C.c_void_p * 5)()
+    _check(lib(True).orbx_debug_streams(extractor._h if extractor is not None else None, out, 5), lib(True))
+    return {k: int(v or 0) for k, v in zip(DEBUG_STREAM_FIELDS, out)}
 
 
 def debug_stereo_path():

@@ -929,6 +929,26 @@ extern "C" void *orbx_side_stream_for(orbx_extractor_t *h, void *main_stream) {
     (void)hipGetLastError();
     return (void *)h->side[0];
 }
+#ifdef ORBX_DEVELOPER
+// include/orbx_dev.h: hold `stream` back by one k_spin (tests/test_stream_order_gpu.py).  Launches nothing else and waits for nothing.
+extern "C" int orbx_debug_stall_stream(void *stream, int microseconds, int device) {
+    if (microseconds < 1 || microseconds > 50000 || device < 0) { orbx_set_error("orbx_debug_stall_stream: 1 .. 50000 microseconds"); return ORBX_ERR_ARG; }
+    ORBX_HIP(hipSetDevice(device));
+    hipLaunchKernelGGL(k_spin, dim3(1), dim3(64), 0, (hipStream_t)stream, 100ll * microseconds);   // 100 ticks of the wall clock per microsecond
+    ORBX_HIP(hipGetLastError());
+    return ORBX_OK;
+}
+// include/orbx_dev.h: the streams a call on h (and a matcher call of this thread) issues work on, read only, no HIP call
+extern "C" int orbx_debug_streams(orbx_extractor_t *h, void **out, int n_out) {
+    if (!out || n_out != 5) { orbx_set_error("orbx_debug_streams: bad arguments"); return ORBX_ERR_ARG; }
+    out[0] = h ? (void *)h->stream : nullptr;
+    out[1] = h ? (void *)h->side[0] : nullptr;
+    out[2] = h ? (void *)h->side[1] : nullptr;
+    out[3] = orbx_internal_arena_stream();
+    out[4] = orbx_internal_match_scratch_stream();
+    return ORBX_OK;
+}
+#endif
 
 static int ensure_staging(orbx_extractor *h, size_t in_bytes, int B, int cap) {
     if (h->d_in_bytes < in_bytes) {

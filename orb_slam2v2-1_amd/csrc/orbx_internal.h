@@ -141,6 +141,9 @@ void orbx_internal_release_sim3opt_scratch();                // orbx_sim3opt.hip
 void orbx_internal_arena_info(int64_t *out5);                // capacity, device, call counter, has a stream, has a completion word
 void orbx_internal_match_scratch_info(int64_t *out2);        // capacity, device
 void orbx_internal_bow_scratch_info(int64_t *out2);          // capacity, device
+// the calling thread's arena stream / staging-pair stream (NULL: it holds none), for orbx_debug_streams
+void *orbx_internal_arena_stream();                          // orbx_match_fast.hip
+void *orbx_internal_match_scratch_stream();                  // orbx_match.hip
 #endif
 // the address a kernel reads an image at (device, pinned or managed memory), or NULL for ordinary pageable host memory (orbx_extract.hip)
 const uint8_t *orbx_internal_device_visible(const uint8_t *p);

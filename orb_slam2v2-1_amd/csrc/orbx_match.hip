@@ -657,6 +657,7 @@ static inline void stage_put(size_t o, const void *src, size_t bytes) { if (byte
 void orbx_internal_release_match_scratch() { g_sp.release(); }
 #ifdef ORBX_DEVELOPER
 void orbx_internal_match_scratch_info(int64_t *out2) { out2[0] = (int64_t)g_sp.cap; out2[1] = g_sp.device; }
+void *orbx_internal_match_scratch_stream() { return (void *)g_sp.stream; }
 #endif
 
 extern "C" int orbm_stereo(orbx_extractor_t *hl, orbx_extractor_t *hr, const orbx_keypoint_t *kl,

@@ -1017,6 +1017,7 @@ void orbx_internal_release_arena() {
 void orbx_internal_arena_info(int64_t *out5) {
     out5[0] = (int64_t)g_ar.cap; out5[1] = g_ar.device; out5[2] = g_ar.seq; out5[3] = g_ar.st ? 1 : 0; out5[4] = g_ar.hflag ? 1 : 0;
 }
+void *orbx_internal_arena_stream() { return (void *)g_ar.st; }
 #endif
 template <typename T> static T *arena_get(size_t count) {
     const size_t bytes = (count * sizeof(T) + 255) & ~(size_t)255;

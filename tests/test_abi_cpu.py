@@ -26,6 +26,8 @@ PATH_HOOKS = ["orbm_debug_match_path", "orbm_debug_resolve_plan", "orbm_debug_st
 SCRATCH_HOOKS = ["orbm_debug_thread_scratch"]
 # fill every fresh scratch block with a word (tests/test_scratch_fill_gpu.py)
 FILL_HOOKS = ["orbx_debug_set_alloc_fill", "orbx_debug_alloc_fill_stats"]
+# hold one stream back, name the streams a call uses (tests/stream_stall.py, tests/test_stream_order_gpu.py)
+STALL_HOOKS = ["orbx_debug_stall_stream", "orbx_debug_streams"]
 
 
 def test_library_exports_every_declared_symbol_and_hook(pkg):
@@ -44,7 +46,7 @@ def test_library_exports_every_declared_symbol_and_hook(pkg):
     assert "debug" not in nm, [l for l in nm.splitlines() if "debug" in l]
     D = pkg.lib(developer=True)
     dev = sorted(set(_declared("orbx_dev.h")) - set(names))
-    assert dev == sorted(pkg.DEV_EXPORTS) == sorted(STAGE_HOOKS + PATH_HOOKS + SCRATCH_HOOKS + FILL_HOOKS) and len(dev) == 15
+    assert dev == sorted(pkg.DEV_EXPORTS) == sorted(STAGE_HOOKS + PATH_HOOKS + SCRATCH_HOOKS + FILL_HOOKS + STALL_HOOKS) and len(dev) == 17
     for n in names + dev:
         assert hasattr(D, n), "developer build: missing export %s" % n
 
