@@ -1025,6 +1025,64 @@ int orbp_pnp_ransac_batch(const orbp_corr_t *corrs, const int32_t *offsets, int 
                           double *models, float *tcws, int32_t *choices, uint8_t *flags, int32_t *refined_counts, uint8_t *inliers,
                           uint8_t *best_flags, orbp_pnp_info_t *infos, int device);
 
+/* ---- LocalMapping::CreateNewMapPoints (reference: src/LocalMapping.cc:215-460; prefix orbl_) ------------------------------------
+ * What happens to the pairs ORBmatcher::SearchForTriangulation returns: per matched pair the ray-parallax test, a 4x4 SVD
+ * (orbi_initialize's Jacobi SVD, not pinned to OpenCV's) or KeyFrame::UnprojectStereo, two depth tests, two chi-square reprojection
+ * tests and the scale-consistency test, one thread per match, :299-439 statement by statement ("k_new_points").
+ * A keyframe is its view, its undistorted keypoints mvKeysUn (orbx_keypoint_t, as the matchers take them), an optional stereo array
+ * (NULL: a monocular keyframe; ur < 0: a monocular feature; raw_u / raw_v: mvKeys, which UnprojectStereo reads) and its level
+ * tables mvScaleFactors / mvLevelSigma2 [view.nlevels].
+ * Status of a row, in the reference's order: 0 accepted (triangulated), 1 accepted from UnprojectStereo of keyframe 1, 2 of keyframe
+ * 2, -1 low parallax, -2 w == 0, -3 z1 <= 0, -4 z2 <= 0, -5 reprojection in keyframe 1, -6 in keyframe 2, -7 a zero distance,
+ * -8 scale ratio, -9 the pair of keyframes was skipped by the baseline rule, -10 no match (orbl_create_new_map_points only).
+ * x y z hold x3D whenever it was formed (0, 1, 2, -3 .. -8) and are zero otherwise; cos_stereo = min(cosParallaxStereo1, 2); rows
+ * of status -9 / -10 are all zero but the status.
+ * ORBX_ERR_ARG, checked before the device is touched, with every output zeroed: a NULL pointer, a NaN in a view, nlevels outside
+ * 1..ORBL_MAX_LEVELS, a level sigma2 or scale factor that is not positive, a keypoint that is NaN or whose octave is outside
+ * [0, nlevels), a stereo feature (ur >= 0) whose depth is not positive (the reference dereferences an empty matrix there) or whose
+ * raw position is NaN, a match index outside [0, n).  No usable GPU: ORBX_ERR_NO_DEVICE; there is no CPU path.  Scratch, pinned
+ * mirror and stream are per host thread (orbx_thread_release_scratch). */
+#define ORBL_MAX_LEVELS 16
+#define ORBL_MAX_NEIGHBOURS 32
+typedef struct { float Tcw[16]; float Ow[3]; float fx, fy, cx, cy, invfx, invfy, mb, mbf, scale_factor; int32_t nlevels; } orbl_view_t;   /* 116 B; Tcw row-major, Ow as KeyFrame::SetPose stores it (-Rwc*tcw) */
+typedef struct { float ur, depth, raw_u, raw_v; } orbl_stereo_t;                                                                          /* 16 B */
+typedef struct { float x, y, z; int32_t status; float cos_rays, cos_stereo; int32_t reserved[2]; } orbl_point_t;                          /* 32 B */
+typedef struct { const orbl_view_t *view; const orbx_keypoint_t *kp; const orbl_stereo_t *st /* may be NULL */; int32_t n;
+                 const float *scale_factors, *level_sigma2; } orbl_keyframe_t;
+/* One pair of keyframes, one launch: pairs [nm][2] = (idx1, idx2), points [nm], *nnew = rows with status >= 0.  nm == 0: ORBX_OK,
+ * no launch. */
+int orbl_triangulate(const orbl_view_t *view1, const orbx_keypoint_t *kp1, const orbl_stereo_t *st1, int n1, const float *scale_factors1,
+                     const float *level_sigma2_1, const orbl_view_t *view2, const orbx_keypoint_t *kp2, const orbl_stereo_t *st2, int n2,
+                     const float *scale_factors2, const float *level_sigma2_2, const int32_t *pairs, int nm, orbl_point_t *points,
+                     int *nnew, int device);
+/* npairs pairs of keyframes (kf1[p], kf2[p]) in one launch: pair p's matches are pairs[match_off[p] .. match_off[p + 1]) and its rows
+ * points[the same]; match_off[0] == 0, an empty pair is legal; nnew [npairs]. */
+int orbl_triangulate_batch(const orbl_keyframe_t *kf1, const orbl_keyframe_t *kf2, int npairs, const int32_t *match_off,
+                           const int32_t *pairs, orbl_point_t *points, int32_t *nnew, int device);
+/* The baseline rule of :252-269, host code: 1 = go on, 0 = skip the neighbour.  baseline = (float)norm(Ow2 - Ow1); stereo / RGB-D:
+ * skip when baseline < view2->mb; monocular: skip when (double)(baseline / median_depth2) < 0.01.  NULL view: ORBX_ERR_ARG. */
+int orbl_baseline_ok(const orbl_view_t *view1, const orbl_view_t *view2, int monocular, float median_depth2);
+/* LocalMapping::ComputeF12 with SkewSymmetricMatrix (:544-561, :706-711), host code: every cv::Mat product materialised to float in
+ * the order written (csrc/orbx_cvmath.h).  K = fx fy cx cy.  Not pinned to an OpenCV build. */
+int orbl_compute_f12(const float *Tcw1_16, const float *K1_4, const float *Tcw2_16, const float *K2_4, float *F12_9);
+/* CreateNewMapPoints' loop over the covisible neighbours (:245-459) as ONE stream-ordered submission.  cur: the current keyframe, nq =
+ * cur->n features with descriptors q_desc [nq][32] and q_flags [nq] as orbm_search_for_triangulation takes them (bit 0: a query, i.e. no
+ * map point yet; bit 1: stereo).  A neighbour is the candidate side of orbm_search_for_triangulation (kf.kp = kp2, kf.n = nc, c_desc,
+ * c_flags, the four node lists, F12, the epipole ex / ey; the matcher reads the NEIGHBOUR's level tables) with its view, stereo array
+ * and, for the monocular rule, ComputeSceneMedianDepth(2).  Everything is staged once.  Then, for every neighbour that passes
+ * orbl_baseline_ok, in order: the matcher's kernels on the device-resident flags, and k_new_points over all nq queries, which reads
+ * match_q on the device, writes status -10 where there is no match and clears bit 0 of the device q_flags[idx1] for every accepted
+ * row - the next neighbour's matcher no longer takes that feature as a query (src/ORBmatcher.cc:703-704).  One synchronisation at the end.
+ * Outputs, neighbour i at [i * nq]: match_q [nn][nq], points [nn][nq]; nmatches, nnew, skipped [nn] (skipped: 1 = the baseline rule, its
+ * rows have status -9 and match_q -1); q_flags_out [nq]: the flags after the last neighbour.  nn > ORBL_MAX_NEIGHBOURS, or more than
+ * 4096 candidates in one vocabulary node of some neighbour: ORBX_ERR_UNSUPPORTED; on any error match_q is all -1, points, nmatches,
+ * nnew and skipped are zero and q_flags_out is q_flags. */
+typedef struct { orbl_keyframe_t kf; const uint8_t *c_desc, *c_flags; const int32_t *node_qstart, *q_items, *node_cstart, *c_items; int32_t nnodes;
+                 float F12[9]; float ex, ey; float median_depth2; } orbl_neighbour_t;
+int orbl_create_new_map_points(const orbl_keyframe_t *cur, const uint8_t *q_desc, const uint8_t *q_flags, const orbl_neighbour_t *neighbours, int nn,
+                               int monocular, int max_dist, int check_orientation, int32_t *match_q, orbl_point_t *points, int32_t *nmatches,
+                               int32_t *nnew, uint8_t *skipped, uint8_t *q_flags_out, int device);
+
 /* The host-array matcher entry points keep grow-only device scratch, a pinned mirror and one non-blocking stream
  * PER HOST THREAD (re-entrant without locks: the reference calls matchers from Tracking, LocalMapping and LoopClosing
  * threads at once, src/LocalMapping.cc:223, src/LoopClosing.cc:249).  Nothing is freed implicitly; a thread calls

@@ -65,6 +65,14 @@ SIM3OPT_PROBLEM_DTYPE = np.dtype([("Tcw1", "<f4", (16,)), ("Tcw2", "<f4", (16,))
                                   ("R", "<f4", (9,)), ("t", "<f4", (3,)), ("th2", "<f4"), ("fix_scale", "<i4")])
 SIM3OPT_INFO_DTYPE = np.dtype([("correspondences", "<i4"), ("bad", "<i4"), ("rounds", "<i4"), ("iterations", "<i4", (2,)),
                                ("trials", "<i4", (2,)), ("reserved", "<i4"), ("q", "<f8", (4,)), ("t", "<f8", (3,)), ("s", "<f8")])
+# orbl_view_t / orbl_stereo_t / orbl_point_t (LocalMapping::CreateNewMapPoints, triangulate_new_points*)
+NEWPOINT_VIEW_DTYPE = np.dtype([("Tcw", "<f4", (16,)), ("Ow", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"),
+                                ("invfx", "<f4"), ("invfy", "<f4"), ("mb", "<f4"), ("mbf", "<f4"), ("scale_factor", "<f4"), ("nlevels", "<i4")])
+NEWPOINT_STEREO_DTYPE = np.dtype([("ur", "<f4"), ("depth", "<f4"), ("raw_u", "<f4"), ("raw_v", "<f4")])
+NEWPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("status", "<i4"), ("cos_rays", "<f4"), ("cos_stereo", "<f4"),
+                           ("reserved", "<i4", (2,))])
+NEWPOINT_TRIANGULATED, NEWPOINT_STEREO1, NEWPOINT_STEREO2 = 0, 1, 2      # status >= 0: accepted; the negative ones: include/orbx.h
+NEWPOINT_MAX_LEVELS = 16
 # orbp_corr_t / orbp_problem_t / orbp_pnp_info_t (PnPsolver, pnp_ransac_batch)
 PNP_CORR_DTYPE = np.dtype([("w", "<f4", (3,)), ("u", "<f4"), ("v", "<f4"), ("sigma2", "<f4")])
 PNP_PROBLEM_DTYPE = np.dtype([("K", "<f4", (4,)), ("th2", "<f4"), ("min_inliers", "<i4"), ("max_iterations", "<i4"),
@@ -112,6 +120,8 @@ SIM3_EXPORTS = ["orbs_sim3_iterations", "orbs_sim3_ransac", "orbs_sim3_ransac_ba
 PNP_EXPORTS = ["orbp_pnp_parameters", "orbp_pnp_ransac", "orbp_pnp_ransac_batch"]
 # the Sim3 optimiser section (prefix orbz_; orbo_ is PoseOptimization's), apart for the same reason
 SIM3OPT_EXPORTS = ["orbz_optimize_sim3", "orbz_optimize_sim3_batch"]
+# the LocalMapping section (prefix orbl_), apart for the same reason
+NEWPOINTS_EXPORTS = ["orbl_triangulate", "orbl_triangulate_batch", "orbl_baseline_ok", "orbl_compute_f12", "orbl_create_new_map_points"]
 # what include/orbx_dev.h declares on top: exported by the developer build only
 DEV_EXPORTS = ["orbx_debug_level_points", "orbx_debug_sincosf", "orbx_debug_blur_patches", "orbm_debug_features_in_area",
                "orbx_debug_blurred_level", "orbx_debug_octree_fallbacks", "orbm_debug_match_path", "orbm_debug_resolve_plan",
@@ -415,6 +425,11 @@ def _load(path, dev):
     L.orbs_sim3_ransac_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32]
     L.orbz_optimize_sim3.argtypes = [vp, i32, vp, vp, vp, C.POINTER(i32), vp, i32]
     L.orbz_optimize_sim3_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, i32]
+    L.orbl_triangulate.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, C.POINTER(i32), i32]
+    L.orbl_triangulate_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32]
+    L.orbl_baseline_ok.argtypes = [vp, vp, i32, f32]
+    L.orbl_compute_f12.argtypes = [vp, vp, vp, vp, vp]
+    L.orbl_create_new_map_points.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32]
     L.orbp_pnp_parameters.argtypes = [i32, C.c_double, i32, i32, i32, f32, C.POINTER(i32), C.POINTER(i32)]
     L.orbp_pnp_ransac.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
     L.orbp_pnp_ransac_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
@@ -1366,6 +1381,130 @@ def optimize_sim3_batch(matches, offsets, problems, device=0):
     ni = np.zeros(max(B, 1), np.int32)
     _check(matcher_lib().orbz_optimize_sim3_batch(_p(m), _p(off), B, _p(pr), _p(So), _p(dropped), _p(ni), _p(infos), int(device)))
     return So[:B], dropped, ni[:B], [_sim3opt_info(infos[b]) for b in range(B)]
+
+
+class NewPointsKeyframe(C.Structure):
+    """orbl_keyframe_t"""
+    _fields_ = [("view", C.c_void_p), ("kp", C.c_void_p), ("st", C.c_void_p), ("n", C.c_int32), ("scale_factors", C.c_void_p),
+                ("level_sigma2", C.c_void_p)]
+
+
+class NewPointsNeighbour(C.Structure):
+    """orbl_neighbour_t"""
+    _fields_ = [("kf", NewPointsKeyframe), ("c_desc", C.c_void_p), ("c_flags", C.c_void_p), ("node_qstart", C.c_void_p), ("q_items", C.c_void_p),
+                ("node_cstart", C.c_void_p), ("c_items", C.c_void_p), ("nnodes", C.c_int32), ("F12", C.c_float * 9), ("ex", C.c_float),
+                ("ey", C.c_float), ("median_depth2", C.c_float)]
+
+
+NEWPOINT_MAX_NEIGHBOURS = 32
+
+
+def newpoints_view(Tcw, K, mb, mbf, scale_factor, nlevels):
+    """one NEWPOINT_VIEW_DTYPE record of a keyframe: its float 4x4 pose, K = (fx, fy, cx, cy), mb, mbf, mfScaleFactor and the number
+    of levels; invfx = 1.0f / fx and Ow = -Rwc*tcw as KeyFrame::SetPose forms it (the product in double, negated, narrowed once)"""
+    v = np.zeros(1, NEWPOINT_VIEW_DTYPE)
+    T = np.asarray(Tcw, np.float32).reshape(4, 4)
+    v["Tcw"] = T.reshape(16)
+    R, t = T[:3, :3].astype(np.float64), T[:3, 3].astype(np.float64)
+    v["Ow"] = (((R[0] * t[0] + R[1] * t[1]) + R[2] * t[2]) * -1.0).astype(np.float32)
+    fx, fy, cx, cy = [np.float32(k) for k in np.asarray(K, np.float32)[:4]]
+    v["fx"], v["fy"], v["cx"], v["cy"], v["invfx"], v["invfy"] = fx, fy, cx, cy, np.float32(1.0) / fx, np.float32(1.0) / fy
+    v["mb"], v["mbf"], v["scale_factor"], v["nlevels"] = mb, mbf, scale_factor, nlevels
+    return v[0]
+
+
+def newpoints_keyframe(view, kp, st, scale_factors, level_sigma2):
+    """one side of a triangulation: the view (newpoints_view), mvKeysUn as KP_DTYPE, the stereo array (NEWPOINT_STEREO_DTYPE: mvuRight,
+    mvDepth and the raw mvKeys position; None for a monocular keyframe; ur < 0 marks a monocular feature) and the level tables
+    mvScaleFactors / mvLevelSigma2 -> a dict that keeps the contiguous arrays alive and holds the orbl_keyframe_t"""
+    k = {"view": np.ascontiguousarray(np.asarray(view, NEWPOINT_VIEW_DTYPE).reshape(1)), "kp": np.ascontiguousarray(kp, KP_DTYPE),
+         "st": None if st is None else np.ascontiguousarray(st, NEWPOINT_STEREO_DTYPE),
+         "sf": np.ascontiguousarray(scale_factors, np.float32), "sig2": np.ascontiguousarray(level_sigma2, np.float32)}
+    nl = int(k["view"]["nlevels"][0])
+    assert k["st"] is None or len(k["st"]) == len(k["kp"])
+    assert len(k["sf"]) >= min(max(nl, 0), NEWPOINT_MAX_LEVELS) and len(k["sig2"]) >= min(max(nl, 0), NEWPOINT_MAX_LEVELS)
+    k["c"] = NewPointsKeyframe(_p(k["view"]), _p(k["kp"]), _p(k["st"]), len(k["kp"]), _p(k["sf"]), _p(k["sig2"]))
+    return k
+
+
+def triangulate_new_points(kf1, kf2, pairs, device=0):
+    """The body of LocalMapping::CreateNewMapPoints for one pair of keyframes (orbl_triangulate): kf1 the current keyframe, kf2 the
+    neighbour (newpoints_keyframe), pairs [nm, 2] the (idx1, idx2) SearchForTriangulation returned
+    -> (points [nm] NEWPOINT_DTYPE, nnew).  status >= 0: a new map point at x y z."""
+    pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    pts = np.zeros(len(pr), NEWPOINT_DTYPE)
+    nn = C.c_int(0)
+    a, b = kf1, kf2
+    _check(matcher_lib().orbl_triangulate(_p(a["view"]), _p(a["kp"]), _p(a["st"]), len(a["kp"]), _p(a["sf"]), _p(a["sig2"]), _p(b["view"]),
+                                          _p(b["kp"]), _p(b["st"]), len(b["kp"]), _p(b["sf"]), _p(b["sig2"]), _p(pr), len(pr), _p(pts),
+                                          C.byref(nn), int(device)))
+    return pts, nn.value
+
+
+def triangulate_new_points_batch(kf1s, kf2s, match_off, pairs, device=0):
+    """orbl_triangulate_batch: len(kf1s) pairs of keyframes in one launch; pair p's matches are pairs[match_off[p]:match_off[p + 1]]
+    -> (points [len(pairs)], nnew [npairs])"""
+    off = np.ascontiguousarray(match_off, np.int32)
+    npairs = len(off) - 1
+    pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    assert len(kf1s) == npairs and len(kf2s) == npairs and (npairs == 0 or off[npairs] <= len(pr))
+    A = (NewPointsKeyframe * max(npairs, 1))(*[k["c"] for k in kf1s])
+    B = (NewPointsKeyframe * max(npairs, 1))(*[k["c"] for k in kf2s])
+    pts = np.zeros(len(pr), NEWPOINT_DTYPE)
+    nn = np.zeros(max(npairs, 1), np.int32)
+    _check(matcher_lib().orbl_triangulate_batch(C.addressof(A), C.addressof(B), npairs, _p(off), _p(pr), _p(pts), _p(nn), int(device)))
+    return pts, nn[:npairs]
+
+
+def newpoints_neighbour(kf, c_desc, c_flags, node_qstart, q_items, node_cstart, c_items, F12, ex, ey, median_depth2=0.0):
+    """a covisible neighbour of create_new_map_points: its keyframe (newpoints_keyframe) and what search_for_triangulation takes for its
+    candidate side - descriptors, flags, the four node lists of the two keyframes' common vocabulary nodes, F12 (compute_f12) and the
+    epipole - plus ComputeSceneMedianDepth(2) for the monocular baseline rule"""
+    n = {"kf": kf, "cd": np.ascontiguousarray(c_desc, np.uint8), "cf": np.ascontiguousarray(c_flags, np.uint8),
+         "nqs": np.ascontiguousarray(node_qstart, np.int32), "qi": np.ascontiguousarray(q_items, np.int32),
+         "ncs": np.ascontiguousarray(node_cstart, np.int32), "ci": np.ascontiguousarray(c_items, np.int32)}
+    assert len(n["cd"]) == len(kf["kp"]) and len(n["cf"]) == len(kf["kp"]) and len(n["nqs"]) == len(n["ncs"])
+    F = np.ascontiguousarray(F12, np.float32).reshape(9)
+    n["c"] = NewPointsNeighbour(kf["c"], _p(n["cd"]), _p(n["cf"]), _p(n["nqs"]), _p(n["qi"]), _p(n["ncs"]), _p(n["ci"]), len(n["nqs"]) - 1,
+                                (C.c_float * 9)(*[float(x) for x in F]), float(ex), float(ey), float(median_depth2))
+    return n
+
+
+def create_new_map_points(cur, q_desc, q_flags, neighbours, monocular, max_dist=50, check_orientation=False, device=0):
+    """LocalMapping::CreateNewMapPoints' loop over the neighbours in one stream-ordered submission (orbl_create_new_map_points): cur the
+    current keyframe (newpoints_keyframe), q_desc [nq, 32], q_flags [nq] (bit 0: no map point yet, bit 1: stereo), neighbours a list of
+    newpoints_neighbour in covisibility order.  Defaults: ORBmatcher(0.6, false) and TH_LOW, as the reference calls it.
+    -> dict: match_q [nn, nq], points [nn, nq] NEWPOINT_DTYPE, nmatches, nnew [nn], skipped [nn] bool, q_flags [nq] after the last neighbour"""
+    qd, qf = np.ascontiguousarray(q_desc, np.uint8), np.ascontiguousarray(q_flags, np.uint8)
+    nq, nn = len(cur["kp"]), len(neighbours)
+    assert len(qd) == nq and len(qf) == nq
+    N = (NewPointsNeighbour * max(nn, 1))(*[n["c"] for n in neighbours])
+    mq = np.zeros((nn, nq), np.int32)
+    pts = np.zeros((nn, nq), NEWPOINT_DTYPE)
+    nm, nw, sk, fo = np.zeros(max(nn, 1), np.int32), np.zeros(max(nn, 1), np.int32), np.zeros(max(nn, 1), np.uint8), np.zeros(max(nq, 1), np.uint8)
+    _check(matcher_lib().orbl_create_new_map_points(C.addressof(cur["c"]), _p(qd), _p(qf), C.addressof(N), nn, int(bool(monocular)), int(max_dist),
+                                                    int(bool(check_orientation)), _p(mq), _p(pts), _p(nm), _p(nw), _p(sk), _p(fo), int(device)))
+    return {"match_q": mq, "points": pts, "nmatches": nm[:nn], "nnew": nw[:nn], "skipped": sk[:nn].astype(bool), "q_flags": fo[:nq]}
+
+
+def compute_f12(Tcw1, K1, Tcw2, K2):
+    """LocalMapping::ComputeF12 (orbl_compute_f12, host code): the float 4x4 poses and K = (fx, fy, cx, cy) of the two keyframes
+    -> F12 [3, 3] float32, what orbm_search_for_triangulation takes"""
+    T1, T2 = np.ascontiguousarray(Tcw1, np.float32).reshape(16), np.ascontiguousarray(Tcw2, np.float32).reshape(16)
+    k1, k2 = np.ascontiguousarray(np.asarray(K1, np.float32)[:4]), np.ascontiguousarray(np.asarray(K2, np.float32)[:4])
+    F = np.zeros((3, 3), np.float32)
+    _check(matcher_lib().orbl_compute_f12(_p(T1), _p(k1), _p(T2), _p(k2), _p(F)))
+    return F
+
+
+def baseline_ok(view1, view2, monocular, median_depth2=0.0):
+    """the baseline rule of CreateNewMapPoints (orbl_baseline_ok, host code): False = the neighbour is skipped"""
+    a = np.ascontiguousarray(np.asarray(view1, NEWPOINT_VIEW_DTYPE).reshape(1))
+    b = np.ascontiguousarray(np.asarray(view2, NEWPOINT_VIEW_DTYPE).reshape(1))
+    rc = matcher_lib().orbl_baseline_ok(_p(a), _p(b), int(bool(monocular)), float(median_depth2))
+    if rc < 0:
+        _check(rc)
+    return bool(rc)
 
 
 def draw_sets(n, iterations, rng):

@@ -399,6 +399,36 @@ __global__ __launch_bounds__(256) void k_kp_angles(const orbx_keypoint_t *__rest
     if (i < n) a[i] = k[i].angle;
 }
 
+// the node lists of orbm_search_for_triangulation, checked on the host: starts at 0, monotone, every listed index in range and listed once
+int orbx_internal_tri_check(const char *fn, const int32_t *node_qstart, const int32_t *q_items, int nq, const int32_t *node_cstart,
+                            const int32_t *c_items, int nc, int nnodes) {
+    const int tq = node_qstart[nnodes], tc = node_cstart[nnodes];
+    if (node_qstart[0] != 0 || node_cstart[0] != 0 || tq < 0 || tc < 0 || (tq > 0 && !q_items) || (tc > 0 && !c_items)) { orbx_set_error("%s: bad node lists", fn); return ORBX_ERR_ARG; }
+    for (int j = 0; j < nnodes; j++)
+        if (node_qstart[j + 1] < node_qstart[j] || node_cstart[j + 1] < node_cstart[j]) { orbx_set_error("%s: node lists not monotonic at %d", fn, j); return ORBX_ERR_ARG; }
+    std::vector<uint8_t> seen;
+    if (check_items(fn, "q_items", q_items, tq, nq, seen) || check_items(fn, "c_items", c_items, tc, nc, seen)) return ORBX_ERR_ARG;
+    return ORBX_OK;
+}
+// the launch sequence of orbm_search_for_triangulation on arrays that are already device-resident, queued on st: the angles of both
+// sides into d_qa / d_ca, the matches into d_match_q (the caller has set it to -1), *d_out2 = nmatches, d_out2[1] = the overflow word
+// (the caller has zeroed both).  orbl_create_new_map_points (orbx_newpoints.hip) runs it once per neighbour on its own stream.
+void orbx_internal_tri_launch(const orbx_keypoint_t *d_k1, const uint8_t *d_qd, const uint8_t *d_qf, float *d_qa, int nq, const orbx_keypoint_t *d_k2,
+                              const uint8_t *d_cd, const uint8_t *d_cf, float *d_ca, int nc, const int32_t *d_nqs, const int32_t *d_qi,
+                              const int32_t *d_ncs, const int32_t *d_ci, int nnodes, const float *F12_9, float ex, float ey,
+                              const float *scale_factors, const float *level_sigma2, int nlevels, int max_dist, int check_orientation,
+                              int32_t *d_match_q, int32_t *d_out2, hipStream_t st) {
+    TriGeom G;
+    memcpy(G.F, F12_9, sizeof(G.F));
+    G.ex = ex; G.ey = ey;
+    for (int l = 0; l < ORBX_MAX_LEVELS; l++) { G.sf[l] = scale_factors[l < nlevels ? l : nlevels - 1]; G.sig2[l] = level_sigma2[l < nlevels ? l : nlevels - 1]; }
+    hipLaunchKernelGGL(k_kp_angles, dim3((nq + 255) / 256), dim3(256), 0, st, d_k1, nq, d_qa);
+    hipLaunchKernelGGL(k_kp_angles, dim3((nc + 255) / 256), dim3(256), 0, st, d_k2, nc, d_ca);
+    hipLaunchKernelGGL(k_tri_match, dim3((nnodes + 3) / 4), dim3(256), 0, st, d_k1, d_qd, d_qf, d_k2, d_cd, d_cf, d_nqs, d_qi, d_ncs, d_ci, nnodes, G, max_dist,
+                       d_match_q, d_out2 + 1);
+    hipLaunchKernelGGL(k_bow_orient, dim3(1), dim3(256), 0, st, (const float *)d_qa, (const float *)d_ca, nq, d_match_q, check_orientation, d_out2);
+}
+
 extern "C" int orbm_search_for_triangulation(const orbx_keypoint_t *kp1, const uint8_t *q_desc, const uint8_t *q_flags, int nq,
                                              const orbx_keypoint_t *kp2, const uint8_t *c_desc, const uint8_t *c_flags, int nc,
                                              const int32_t *node_qstart, const int32_t *q_items, const int32_t *node_cstart,
@@ -415,11 +445,7 @@ extern "C" int orbm_search_for_triangulation(const orbx_keypoint_t *kp1, const u
     for (int i = 0; i < nq; i++) match_q[i] = -1;
     if (nq == 0 || nc == 0 || nnodes == 0) return ORBX_OK;
     const int tq = node_qstart[nnodes], tc = node_cstart[nnodes];
-    if (node_qstart[0] != 0 || node_cstart[0] != 0 || tq < 0 || tc < 0 || (tq > 0 && !q_items) || (tc > 0 && !c_items)) { orbx_set_error("orbm_search_for_triangulation: bad node lists"); return ORBX_ERR_ARG; }
-    for (int j = 0; j < nnodes; j++)
-        if (node_qstart[j + 1] < node_qstart[j] || node_cstart[j + 1] < node_cstart[j]) { orbx_set_error("orbm_search_for_triangulation: node lists not monotonic at %d", j); return ORBX_ERR_ARG; }
-    std::vector<uint8_t> seen;
-    if (check_items("orbm_search_for_triangulation", "q_items", q_items, tq, nq, seen) || check_items("orbm_search_for_triangulation", "c_items", c_items, tc, nc, seen)) return ORBX_ERR_ARG;
+    if (orbx_internal_tri_check("orbm_search_for_triangulation", node_qstart, q_items, nq, node_cstart, c_items, nc, nnodes)) return ORBX_ERR_ARG;
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t o = off; off += stage_align(bytes); return o; };
     const size_t o_k1 = take((size_t)nq * sizeof(orbx_keypoint_t)), o_qd = take((size_t)nq * 32), o_qf = take(nq), o_qa = take((size_t)nq * 4),
@@ -436,20 +462,12 @@ extern "C" int orbm_search_for_triangulation(const orbx_keypoint_t *kp1, const u
     if (tc > 0) H2DB(o_ci, c_items, (size_t)tc * 4);
     ORBX_HIP(hipMemset(base + o_m, 0xFF, (size_t)nq * 4));
     ORBX_HIP(hipMemset(base + o_out, 0, 16));
-    TriGeom G;
-    memcpy(G.F, F12_9, sizeof(G.F));
-    G.ex = ex; G.ey = ey;
-    for (int l = 0; l < ORBX_MAX_LEVELS; l++) { G.sf[l] = scale_factors[l < nlevels ? l : nlevels - 1]; G.sig2[l] = level_sigma2[l < nlevels ? l : nlevels - 1]; }
     (void)hipGetLastError();
     int32_t *dout = (int32_t *)(base + o_out);
-    hipLaunchKernelGGL(k_kp_angles, dim3((nq + 255) / 256), dim3(256), 0, 0, (const orbx_keypoint_t *)(base + o_k1), nq, (float *)(base + o_qa));
-    hipLaunchKernelGGL(k_kp_angles, dim3((nc + 255) / 256), dim3(256), 0, 0, (const orbx_keypoint_t *)(base + o_k2), nc, (float *)(base + o_ca));
-    hipLaunchKernelGGL(k_tri_match, dim3((nnodes + 3) / 4), dim3(256), 0, 0, (const orbx_keypoint_t *)(base + o_k1), base + o_qd, base + o_qf,
-                       (const orbx_keypoint_t *)(base + o_k2), base + o_cd, base + o_cf, (const int32_t *)(base + o_nqs),
-                       (const int32_t *)(base + o_qi), (const int32_t *)(base + o_ncs), (const int32_t *)(base + o_ci), nnodes, G, max_dist,
-                       (int32_t *)(base + o_m), dout + 1);
-    hipLaunchKernelGGL(k_bow_orient, dim3(1), dim3(256), 0, 0, (const float *)(base + o_qa), (const float *)(base + o_ca), nq,
-                       (int32_t *)(base + o_m), check_orientation, dout);
+    orbx_internal_tri_launch((const orbx_keypoint_t *)(base + o_k1), base + o_qd, base + o_qf, (float *)(base + o_qa), nq, (const orbx_keypoint_t *)(base + o_k2),
+                             base + o_cd, base + o_cf, (float *)(base + o_ca), nc, (const int32_t *)(base + o_nqs), (const int32_t *)(base + o_qi),
+                             (const int32_t *)(base + o_ncs), (const int32_t *)(base + o_ci), nnodes, F12_9, ex, ey, scale_factors, level_sigma2, nlevels,
+                             max_dist, check_orientation, (int32_t *)(base + o_m), dout, 0);
     ORBX_HIP(hipGetLastError());
     int32_t out[2] = {0, 0};
     ORBX_HIP(hipMemcpy(out, dout, 8, hipMemcpyDeviceToHost));

@@ -136,6 +136,16 @@ void orbx_internal_release_init_scratch();                   // orbx_initializer
 void orbx_internal_release_sim3_scratch();                   // orbx_sim3.hip        (thread-local StagePair)
 void orbx_internal_release_pnp_scratch();                    // orbx_pnp.hip         (thread-local StagePair)
 void orbx_internal_release_sim3opt_scratch();                // orbx_sim3opt.hip     (thread-local StagePair)
+void orbx_internal_release_newpoints_scratch();              // orbx_newpoints.hip   (thread-local StagePair)
+// orbx_bow.hip: ORBmatcher::SearchForTriangulation's node-list checks and its launch sequence on device-resident arrays, for its own
+// entry point and for orbl_create_new_map_points (orbx_newpoints.hip)
+int orbx_internal_tri_check(const char *fn, const int32_t *node_qstart, const int32_t *q_items, int nq, const int32_t *node_cstart,
+                            const int32_t *c_items, int nc, int nnodes);
+void orbx_internal_tri_launch(const orbx_keypoint_t *d_k1, const uint8_t *d_qd, const uint8_t *d_qf, float *d_qa, int nq, const orbx_keypoint_t *d_k2,
+                              const uint8_t *d_cd, const uint8_t *d_cf, float *d_ca, int nc, const int32_t *d_nqs, const int32_t *d_qi,
+                              const int32_t *d_ncs, const int32_t *d_ci, int nnodes, const float *F12_9, float ex, float ey,
+                              const float *scale_factors, const float *level_sigma2, int nlevels, int max_dist, int check_orientation,
+                              int32_t *d_match_q, int32_t *d_out2, hipStream_t st);
 #ifdef ORBX_DEVELOPER
 // what the calling thread holds of each of the three, for orbm_debug_thread_scratch (include/orbx_dev.h): no HIP call, nothing allocated
 void orbx_internal_arena_info(int64_t *out5);                // capacity, device, call counter, has a stream, has a completion word

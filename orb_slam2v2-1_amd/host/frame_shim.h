@@ -8,6 +8,8 @@
 #include "Frame.h"
 #include "MapPoint.h"
 #else
+#include <algorithm>
+#include <climits>
 #include <cmath>
 #include <map>
 #include <set>
@@ -20,9 +22,24 @@ namespace ORB_SLAM2 {
 
 class Frame;
 class KeyFrame;
+class MapPoint;
+
+class Map {   // include/Map.h: what LocalMapping::CreateNewMapPoints touches
+public:
+    void AddMapPoint(MapPoint *pMP) { mvpMapPoints.push_back(pMP); }   // src/Map.cc:42-46 (a set there; insertion order is kept here for the tests)
+    std::vector<MapPoint *> GetAllMapPoints() { return mvpMapPoints; }
+    std::vector<MapPoint *> mvpMapPoints;
+};
 
 class MapPoint {
 public:
+    // src/MapPoint.cc:31-50, without the ids: the position, a zero normal, the reference keyframe
+    inline MapPoint(const cv::Mat &Pos, KeyFrame *pRefKF, Map *pMap);
+    // host code after src/MapPoint.cc:252-317 and :340-383, on the shim's members
+    inline void ComputeDistinctiveDescriptors();
+    inline void UpdateNormalAndDepth();
+    KeyFrame *mpRefKF = NULL;
+    Map *mpMap = NULL;
     MapPoint() : mbTrackInView(false), mnTrackScaleLevel(0), mTrackViewCos(1.f), mTrackProjX(0), mTrackProjY(0),
                  mTrackProjXR(0), mbBad(false), nObs(0) { mWorldPos = cv::Mat::zeros(3, 1, CV_32F); }
     // tracking variables set by Frame::isInFrustum (src/Frame.cc:284-340)
@@ -149,10 +166,33 @@ public:
     }
     bool IsInImage(const float &x, const float &y) const { return (x >= mnMinX && x < mnMaxX && y >= mnMinY && y < mnMaxY); }
     float fx = 0, fy = 0, cx = 0, cy = 0, mbf = 0;
+    float invfx = 0, invfy = 0, mb = 0, mfScaleFactor = 0;   // include/KeyFrame.h: read by LocalMapping::CreateNewMapPoints
+    long unsigned int mnId = 0;
     cv::Mat mK;   // include/KeyFrame.h: the 3x3 CV_32F calibration, read by Optimizer::OptimizeSim3
     int N = 0;
-    std::vector<cv::KeyPoint> mvKeysUn;
-    std::vector<float> mvuRight;
+    std::vector<cv::KeyPoint> mvKeys, mvKeysUn;   // mvKeys: the raw keypoints, which UnprojectStereo reads
+    std::vector<float> mvuRight, mvDepth;
+    // the covisibility graph reduced to its result: the ordered list (src/KeyFrame.cc:316-324 returns its first N entries)
+    std::vector<KeyFrame *> mvpOrderedConnectedKeyFrames;
+    std::vector<KeyFrame *> GetBestCovisibilityKeyFrames(const int &n) {
+        if ((int)mvpOrderedConnectedKeyFrames.size() < n) return mvpOrderedConnectedKeyFrames;
+        return std::vector<KeyFrame *>(mvpOrderedConnectedKeyFrames.begin(), mvpOrderedConnectedKeyFrames.begin() + n);
+    }
+    // src/KeyFrame.cc:636-666: z = Rcw.row(2).dot(x3Dw) + zcw (the dot product a double), the sorted depths' entry (size-1)/q.  No map point:
+    // the reference indexes an empty vector; 0 here
+    float ComputeSceneMedianDepth(const int q) {
+        std::vector<float> vDepths;
+        for (int i = 0; i < N; i++)
+            if (mvpMapPoints[i]) {
+                cv::Mat x3Dw = mvpMapPoints[i]->GetWorldPos();
+                double s = 0;
+                for (int k = 0; k < 3; k++) s += (double)Tcw.at<float>(2, k) * (double)x3Dw.at<float>(k);
+                vDepths.push_back((float)(s + (double)Tcw.at<float>(2, 3)));
+            }
+        if (vDepths.empty()) return 0.f;
+        std::sort(vDepths.begin(), vDepths.end());
+        return vDepths[(vDepths.size() - 1) / q];
+    }
     cv::Mat mDescriptors;
     int mnScaleLevels = 0;
     float mfLogScaleFactor = 0.f;
@@ -175,6 +215,57 @@ inline void MapPoint::AddObservation(KeyFrame *pKF, size_t idx) {
     if (mObservations.count(pKF)) return;
     mObservations[pKF] = idx;
     if (pKF->mvuRight[idx] >= 0) nObs += 2; else nObs++;
+}
+inline MapPoint::MapPoint(const cv::Mat &Pos, KeyFrame *pRefKF, Map *pMap) : MapPoint() {
+    mWorldPos = Pos.clone();
+    mpRefKF = pRefKF;
+    mpMap = pMap;
+}
+inline void MapPoint::ComputeDistinctiveDescriptors() {
+    if (mbBad || mObservations.empty()) return;
+    std::vector<cv::Mat> vDescriptors;
+    for (std::map<KeyFrame *, size_t>::iterator mit = mObservations.begin(), mend = mObservations.end(); mit != mend; mit++)
+        if (!mit->first->isBad()) vDescriptors.push_back(mit->first->mDescriptors.row((int)mit->second));
+    if (vDescriptors.empty()) return;
+    const size_t n = vDescriptors.size();
+    std::vector<int> D(n * n, 0);
+    for (size_t i = 0; i < n; i++)
+        for (size_t j = i + 1; j < n; j++) {
+            int d = 0;
+            const unsigned char *a = vDescriptors[i].ptr(0), *b = vDescriptors[j].ptr(0);
+            for (int k = 0; k < 32; k++) d += __builtin_popcount((unsigned)(a[k] ^ b[k]));
+            D[i * n + j] = D[j * n + i] = d;
+        }
+    int BestMedian = INT_MAX, BestIdx = 0;   // the descriptor with least median distance to the rest
+    for (size_t i = 0; i < n; i++) {
+        std::vector<int> vDists(D.begin() + i * n, D.begin() + (i + 1) * n);
+        std::sort(vDists.begin(), vDists.end());
+        const int median = vDists[(size_t)(0.5 * (n - 1))];
+        if (median < BestMedian) { BestMedian = median; BestIdx = (int)i; }
+    }
+    mDescriptor = vDescriptors[BestIdx].clone();
+}
+inline void MapPoint::UpdateNormalAndDepth() {
+    if (mbBad || mObservations.empty() || !mpRefKF) return;
+    float normal[3] = {0.f, 0.f, 0.f};
+    int n = 0;
+    for (std::map<KeyFrame *, size_t>::iterator mit = mObservations.begin(), mend = mObservations.end(); mit != mend; mit++) {
+        cv::Mat Owi = mit->first->GetCameraCenter();
+        float normali[3];
+        double s = 0;
+        for (int k = 0; k < 3; k++) { normali[k] = mWorldPos.at<float>(k) - Owi.at<float>(k); s += (double)normali[k] * (double)normali[k]; }
+        const float inv = (float)(1.0 / std::sqrt(s));   // normal + normali/cv::norm(normali): a scaleAdd with a float factor
+        for (int k = 0; k < 3; k++) normal[k] = normali[k] * inv + normal[k];
+        n++;
+    }
+    cv::Mat Or = mpRefKF->GetCameraCenter();
+    double s = 0;
+    for (int k = 0; k < 3; k++) { const float d = mWorldPos.at<float>(k) - Or.at<float>(k); s += (double)d * (double)d; }
+    const float dist = (float)std::sqrt(s);
+    const int level = mpRefKF->mvKeysUn[mObservations[mpRefKF]].octave;
+    mfMaxDistance = dist * mpRefKF->mvScaleFactors[level];
+    mfMinDistance = mfMaxDistance / mpRefKF->mvScaleFactors[mpRefKF->mnScaleLevels - 1];
+    for (int k = 0; k < 3; k++) mNormalVector.at<float>(k) = (float)((double)normal[k] * (1.0 / n));
 }
 inline void MapPoint::Replace(MapPoint *pMP) {   // without the found/visible counters, descriptor refresh and Map erase
     if (pMP == this) return;
