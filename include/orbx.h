@@ -1083,6 +1083,61 @@ int orbl_create_new_map_points(const orbl_keyframe_t *cur, const uint8_t *q_desc
                                int monocular, int max_dist, int check_orientation, int32_t *match_q, orbl_point_t *points, int32_t *nmatches,
                                int32_t *nnew, uint8_t *skipped, uint8_t *q_flags_out, int device);
 
+/* ---- Optimizer::LocalBundleAdjustment (src/Optimizer.cc:453-780) and Optimizer::BundleAdjustment (:49-237; prefix orbb_) ----------
+ * The bundle adjustment LocalMapping::Run calls after CreateNewMapPoints (src/LocalMapping.cc:89), on flat arrays: 6-DoF keyframe
+ * vertices, 3-DoF map-point vertices (always marginalised, never fixed), one EdgeSE3ProjectXYZ (ur < 0) or EdgeStereoSE3ProjectXYZ
+ * per observation, Levenberg-Marquardt with the Huber kernel over the Schur complement.  A restatement in double with the
+ * reference's float narrowings ("k_lba_*").  The landmark block is block-diagonal and the reduced system, 6 Nf
+ * square for Nf free keyframes, is DENSE here: it is meant for a local window (a few tens of free keyframes; it stays correct for
+ * any Nf memory allows, one workgroup factorises it).  A loop-closure-sized map is outside what it is meant for.
+ * The host drives the iterations and trials: a handful of launches per linearisation and per trial on this thread's stream, one
+ * stream synchronisation per trial, none device-wide.  Every sum has one owner and a fixed order: two calls give the same bytes.
+ * Not pinned to g2o: the order of vertices and edges inside its sums, Eigen's sparse SimplicialLDLT against the dense LDL^T here,
+ * Matrix3d::inverse, the device's sin / cos / sqrt; a zero, negative or non-finite pivot rejects the trial (tempChi = DBL_MAX).
+ *
+ * kfs [K]: Tcw row-major float 4x4, fx fy cx cy, bf = mbf, fixed != 0 for every "fixed camera" of :489-504 and for a local keyframe
+ * with mnId == 0.  pts [P]: world positions.  obs [E] in any order: keyframe kf observes point pt at the undistorted keypoint (u, v),
+ * ur = mvuRight (< 0: a monocular observation), inv_sigma2 = mvInvLevelSigma2[octave]; a keyframe observes a point at most once.
+ * stop (may be NULL) is pbStopFlag, polled exactly where the reference reads it: at :655 (set: the call returns with the inputs
+ * as outputs and nothing erased), before every iteration, after a rejected trial when another would follow, and at :664 (set: no
+ * classification and no second round; the final classification and the outputs still happen).
+ * Tcw_out16 [K][16]: Converter::toCvMat of the estimates, a fixed keyframe's byte for byte as it came in; pts_out3 [P][3];
+ * erase [E]: 1 where the final check (chi2 of the edge's LAST evaluation > 5.991 / 7.815, or a depth that is not positive at the
+ * final estimates) asks for EraseMapPointMatch / EraseObservation.  info, kf_est7 [K][7] (q = x y z w, then t) and pt_est3 [P][3]
+ * (the double estimates) may be NULL.  K, P or E may be 0.
+ * NULL pointers, negative sizes, an index out of range, a (kf, pt) pair that occurs twice, an input that is NaN or infinite, a
+ * negative inv_sigma2, a schedule outside its ranges: ORBX_ERR_ARG, checked before the device is touched.  No usable GPU:
+ * ORBX_ERR_NO_DEVICE; there is no CPU path.  Scratch, pinned mirror and stream are per host thread (orbx_thread_release_scratch). */
+#define ORBB_MAX_ITERATIONS 100   /* per round */
+#define ORBB_STOP_BEFORE 1        /* info->stopped_at: where stop first answered non-zero; 0: it never did.  1: at :655 */
+#define ORBB_STOP_ROUND1 2        /* inside the first optimize() */
+#define ORBB_STOP_BETWEEN 3       /* at :664 */
+#define ORBB_STOP_ROUND2 4        /* inside the second optimize() */
+typedef struct { float Tcw[16]; float fx, fy, cx, cy, bf; int32_t fixed; } orbb_keyframe_t;       /* 88 B */
+typedef struct { float x, y, z; } orbb_point_t;                                                   /* 12 B */
+typedef struct { int32_t kf, pt; float u, v, ur, inv_sigma2; } orbb_observation_t;                /* 24 B */
+/* rounds: 1 or 2 optimize() calls of iterations[r] each, with (robust[r] != 0) or without the Huber kernel of the two deltas; two
+ * rounds have the :664 read of the flag and the classification (chi2 > 5.991 / 7.815 or depth not positive -> level 1) between
+ * them; classify: the final check fills erase; check_stop_first: the :655 read. */
+typedef struct { int32_t rounds, iterations[2], robust[2]; float delta_mono, delta_stereo; int32_t classify, check_stop_first; } orbb_schedule_t;   /* 36 B */
+/* free_poses[r]: keyframes optimised in round r (not fixed, with an edge at level 0); stop_poll: the number of the poll counted in
+ * stopped_at, from 1; polls: how often stop was called */
+typedef struct { int32_t rounds, iterations[2], trials[2], free_poses[2], stopped_at, stop_poll, polls, erased; } orbb_info_t;     /* 44 B */
+int orbb_optimize(const orbb_keyframe_t *kfs, int K, const orbb_point_t *pts, int P, const orbb_observation_t *obs, int E,
+                  const orbb_schedule_t *schedule, int (*stop)(void *), void *stop_user, float *Tcw_out16, float *pts_out3,
+                  uint8_t *erase, orbb_info_t *info, double *kf_est7, double *pt_est3, int device);
+/* The schedule of :569-570, :655-707: {2, {5, 10}, {1, 0}, (float)sqrt(5.991), (float)sqrt(7.815), 1, 1} */
+int orbb_local_bundle_adjustment(const orbb_keyframe_t *kfs, int K, const orbb_point_t *pts, int P, const orbb_observation_t *obs, int E,
+                                 int (*stop)(void *), void *stop_user, float *Tcw_out16, float *pts_out3, uint8_t *erase,
+                                 orbb_info_t *info, double *kf_est7, double *pt_est3, int device);
+/* Optimizer::BundleAdjustment over the same kernels: one optimize(iterations), the Huber kernel iff robust, no classification, no
+ * :655 read; its monocular delta is (float)sqrt(5.99), not 5.991 (:85).  The caller leaves out bad keyframes and points and the
+ * points without an observation (:175-179), and sets fixed for mnId == 0.  What CreateInitialMapMonocular's
+ * GlobalBundleAdjustemnt(mpMap, 20) needs (src/Tracking.cc:700). */
+int orbb_bundle_adjustment(const orbb_keyframe_t *kfs, int K, const orbb_point_t *pts, int P, const orbb_observation_t *obs, int E,
+                           int iterations, int robust, int (*stop)(void *), void *stop_user, float *Tcw_out16, float *pts_out3,
+                           orbb_info_t *info, double *kf_est7, double *pt_est3, int device);
+
 /* The host-array matcher entry points keep grow-only device scratch, a pinned mirror and one non-blocking stream
  * PER HOST THREAD (re-entrant without locks: the reference calls matchers from Tracking, LocalMapping and LoopClosing
  * threads at once, src/LocalMapping.cc:223, src/LoopClosing.cc:249).  Nothing is freed implicitly; a thread calls

@@ -65,6 +65,16 @@ SIM3OPT_PROBLEM_DTYPE = np.dtype([("Tcw1", "<f4", (16,)), ("Tcw2", "<f4", (16,))
                                   ("R", "<f4", (9,)), ("t", "<f4", (3,)), ("th2", "<f4"), ("fix_scale", "<i4")])
 SIM3OPT_INFO_DTYPE = np.dtype([("correspondences", "<i4"), ("bad", "<i4"), ("rounds", "<i4"), ("iterations", "<i4", (2,)),
                                ("trials", "<i4", (2,)), ("reserved", "<i4"), ("q", "<f8", (4,)), ("t", "<f8", (3,)), ("s", "<f8")])
+# orbb_keyframe_t / orbb_point_t / orbb_observation_t / orbb_schedule_t / orbb_info_t (Optimizer::LocalBundleAdjustment, local_bundle_adjustment)
+LBA_KEYFRAME_DTYPE = np.dtype([("Tcw", "<f4", (16,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("bf", "<f4"), ("fixed", "<i4")])
+LBA_POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4")])
+LBA_OBSERVATION_DTYPE = np.dtype([("kf", "<i4"), ("pt", "<i4"), ("u", "<f4"), ("v", "<f4"), ("ur", "<f4"), ("inv_sigma2", "<f4")])
+LBA_SCHEDULE_DTYPE = np.dtype([("rounds", "<i4"), ("iterations", "<i4", (2,)), ("robust", "<i4", (2,)), ("delta_mono", "<f4"), ("delta_stereo", "<f4"),
+                               ("classify", "<i4"), ("check_stop_first", "<i4")])
+LBA_INFO_DTYPE = np.dtype([("rounds", "<i4"), ("iterations", "<i4", (2,)), ("trials", "<i4", (2,)), ("free_poses", "<i4", (2,)), ("stopped_at", "<i4"),
+                           ("stop_poll", "<i4"), ("polls", "<i4"), ("erased", "<i4")])
+LBA_STOP_BEFORE, LBA_STOP_ROUND1, LBA_STOP_BETWEEN, LBA_STOP_ROUND2 = 1, 2, 3, 4      # info["stopped_at"]
+LBA_MAX_ITERATIONS = 100
 # orbl_view_t / orbl_stereo_t / orbl_point_t (LocalMapping::CreateNewMapPoints, triangulate_new_points*)
 NEWPOINT_VIEW_DTYPE = np.dtype([("Tcw", "<f4", (16,)), ("Ow", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"),
                                 ("invfx", "<f4"), ("invfy", "<f4"), ("mb", "<f4"), ("mbf", "<f4"), ("scale_factor", "<f4"), ("nlevels", "<i4")])
@@ -122,6 +132,8 @@ PNP_EXPORTS = ["orbp_pnp_parameters", "orbp_pnp_ransac", "orbp_pnp_ransac_batch"
 SIM3OPT_EXPORTS = ["orbz_optimize_sim3", "orbz_optimize_sim3_batch"]
 # the LocalMapping section (prefix orbl_), apart for the same reason
 NEWPOINTS_EXPORTS = ["orbl_triangulate", "orbl_triangulate_batch", "orbl_baseline_ok", "orbl_compute_f12", "orbl_create_new_map_points"]
+# the bundle adjustment section (prefix orbb_), apart for the same reason
+LBA_EXPORTS = ["orbb_optimize", "orbb_local_bundle_adjustment", "orbb_bundle_adjustment"]
 # what include/orbx_dev.h declares on top: exported by the developer build only
 DEV_EXPORTS = ["orbx_debug_level_points", "orbx_debug_sincosf", "orbx_debug_blur_patches", "orbm_debug_features_in_area",
                "orbx_debug_blurred_level", "orbx_debug_octree_fallbacks", "orbm_debug_match_path", "orbm_debug_resolve_plan",
@@ -299,6 +311,9 @@ def lib(developer=False):
     return _lib
 
 
+LBA_STOP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)      # int (*stop)(void *): pbStopFlag of Optimizer::LocalBundleAdjustment
+
+
 def matcher_lib():
     """The library the matcher functions of this module call: the developer build while default_developer is True (`hooks` fixture),
     so that the path hooks below and orbm_set_thread_option act on the library that ran the call (both are per library)."""
@@ -430,6 +445,9 @@ def _load(path, dev):
     L.orbl_baseline_ok.argtypes = [vp, vp, i32, f32]
     L.orbl_compute_f12.argtypes = [vp, vp, vp, vp, vp]
     L.orbl_create_new_map_points.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32]
+    L.orbb_optimize.argtypes = [vp, i32, vp, i32, vp, i32, vp, LBA_STOP_FN, vp, vp, vp, vp, vp, vp, vp, i32]
+    L.orbb_local_bundle_adjustment.argtypes = [vp, i32, vp, i32, vp, i32, LBA_STOP_FN, vp, vp, vp, vp, vp, vp, vp, i32]
+    L.orbb_bundle_adjustment.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32, LBA_STOP_FN, vp, vp, vp, vp, vp, vp, i32]
     L.orbp_pnp_parameters.argtypes = [i32, C.c_double, i32, i32, i32, f32, C.POINTER(i32), C.POINTER(i32)]
     L.orbp_pnp_ransac.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
     L.orbp_pnp_ransac_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
@@ -1381,6 +1399,68 @@ def optimize_sim3_batch(matches, offsets, problems, device=0):
     ni = np.zeros(max(B, 1), np.int32)
     _check(matcher_lib().orbz_optimize_sim3_batch(_p(m), _p(off), B, _p(pr), _p(So), _p(dropped), _p(ni), _p(infos), int(device)))
     return So[:B], dropped, ni[:B], [_sim3opt_info(infos[b]) for b in range(B)]
+
+
+def lba_schedule(rounds=2, iterations=(5, 10), robust=(1, 0), delta_mono=None, delta_stereo=None, classify=1, check_stop_first=1):
+    """one LBA_SCHEDULE_DTYPE record; the defaults are Optimizer::LocalBundleAdjustment's (src/Optimizer.cc:569-570, :655-707)"""
+    s = np.zeros(1, LBA_SCHEDULE_DTYPE)
+    s["rounds"], s["iterations"], s["robust"] = rounds, (list(iterations) + [0])[:2], (list(robust) + [0])[:2]
+    s["delta_mono"] = np.float32(np.sqrt(5.991)) if delta_mono is None else delta_mono
+    s["delta_stereo"] = np.float32(np.sqrt(7.815)) if delta_stereo is None else delta_stereo
+    s["classify"], s["check_stop_first"] = int(bool(classify)), int(bool(check_stop_first))
+    return s[0]
+
+
+def _lba_run(call, keyframes, points, observations, stop, device):
+    kf = np.ascontiguousarray(keyframes, LBA_KEYFRAME_DTYPE)
+    pt = np.ascontiguousarray(points, LBA_POINT_DTYPE)
+    ob = np.ascontiguousarray(observations, LBA_OBSERVATION_DTYPE)
+    K, P, E = len(kf), len(pt), len(ob)
+    To, Po, erase = np.zeros((K, 4, 4), np.float32), np.zeros((P, 3), np.float32), np.zeros(E, np.uint8)
+    info, ke, pe = np.zeros(1, LBA_INFO_DTYPE), np.zeros((K, 7), np.float64), np.zeros((P, 3), np.float64)
+    raised = []
+
+    def poll(_user):
+        try:
+            return 1 if stop() else 0
+        except BaseException as e:      # noqa: BLE001   an exception cannot cross the C frames: stop the optimisation, raise afterwards
+            raised.append(e)
+            return 1
+    fn = LBA_STOP_FN(poll) if stop is not None else LBA_STOP_FN()
+    rc = call(matcher_lib(), _p(kf), K, _p(pt), P, _p(ob), E, fn, _p(To), _p(Po), _p(erase), _p(info), _p(ke), _p(pe), int(device))
+    if raised:
+        raise raised[0]
+    _check(rc)
+    inf = {k: (int(info[0][k]) if info[0][k].ndim == 0 else [int(x) for x in info[0][k]]) for k in LBA_INFO_DTYPE.names}
+    return To, Po, erase, inf, ke, pe
+
+
+def local_bundle_adjustment(keyframes, points, observations, stop=None, device=0):
+    """Optimizer::LocalBundleAdjustment (orbb_local_bundle_adjustment).  keyframes [K] LBA_KEYFRAME_DTYPE (fixed != 0: a fixed camera,
+    or the local keyframe with mnId == 0), points [P] LBA_POINT_DTYPE, observations [E] LBA_OBSERVATION_DTYPE in any order (ur < 0:
+    monocular), stop: a callable polled where the reference reads pbStopFlag (or None)
+    -> (Tcw [K, 4, 4] float32, points [P, 3] float32, erase [E] uint8, info dict, kf_est [K, 7] float64 (q = x y z w, then t),
+    pt_est [P, 3] float64)."""
+    return _lba_run(lambda L, kf, K, pt, P, ob, E, fn, To, Po, er, info, ke, pe, dev:
+                    L.orbb_local_bundle_adjustment(kf, K, pt, P, ob, E, fn, None, To, Po, er, info, ke, pe, dev),
+                    keyframes, points, observations, stop, device)
+
+
+def bundle_adjustment(keyframes, points, observations, iterations=5, robust=True, stop=None, device=0):
+    """Optimizer::BundleAdjustment (orbb_bundle_adjustment): one optimize(iterations), the Huber kernel iff robust, no classification
+    -> as local_bundle_adjustment (erase is all zero).  Meant for the initial map, not for a loop-closure-sized one: the reduced
+    system is dense."""
+    return _lba_run(lambda L, kf, K, pt, P, ob, E, fn, To, Po, er, info, ke, pe, dev:
+                    L.orbb_bundle_adjustment(kf, K, pt, P, ob, E, int(iterations), int(bool(robust)), fn, None, To, Po, info, ke, pe, dev),
+                    keyframes, points, observations, stop, device)
+
+
+def bundle_adjustment_scheduled(keyframes, points, observations, schedule, stop=None, device=0):
+    """orbb_optimize: the same kernels under a caller-given schedule (lba_schedule)"""
+    sc = np.ascontiguousarray(np.asarray(schedule, LBA_SCHEDULE_DTYPE).reshape(1))
+    return _lba_run(lambda L, kf, K, pt, P, ob, E, fn, To, Po, er, info, ke, pe, dev:
+                    L.orbb_optimize(kf, K, pt, P, ob, E, _p(sc), fn, None, To, Po, er, info, ke, pe, dev),
+                    keyframes, points, observations, stop, device)
 
 
 class NewPointsKeyframe(C.Structure):

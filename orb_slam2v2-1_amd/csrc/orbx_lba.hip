@@ -1,0 +1,914 @@
+// orbx_lba.hip — Optimizer::LocalBundleAdjustment (reference: src/Optimizer.cc:453-780) and Optimizer::BundleAdjustment (:49-237):
+// 6-DoF keyframe vertices (VertexSE3Expmap), 3-DoF map-point vertices (VertexSBAPointXYZ, always marginalised), one binary edge
+// per observation (EdgeSE3ProjectXYZ, EdgeStereoSE3ProjectXYZ), Levenberg-Marquardt over the Schur complement.  A restatement of
+// the reference and of the g2o classes it drives (types_six_dof_expmap, se3quat.h, base_binary_edge.hpp, block_solver.hpp,
+// optimization_algorithm_levenberg, sparse_optimizer), double throughout with the reference's float narrowings; DESIGN.md
+// section 6 has the list.  tests/lba_ref.py is the same arithmetic in numpy, statement for statement.
+//
+// The landmark block is block-diagonal 3x3, every Hpl block belongs to one edge, and the reduced system is 6 Nf square for Nf free
+// keyframes (a few tens): dense and small.  The HOST drives the iterations and trials (lba_drive): it queues a handful of launches
+// per linearisation and per trial on one stream and reads one small record (LbaRec) after each trial - one stream synchronisation,
+// no device-wide one, and the stop flag is polled exactly where the reference reads it.  No cooperative launch, no grid barrier,
+// no wait loop in a kernel, no floating-point atomics.  Every sum has one owner and a fixed order:
+//   Hll / bl of a point        one thread: the point's active observations in ascending input index            (k_lba_point)
+//   Hpp / bp of a free pose    one workgroup: the thread's edges ascending, wave butterfly, the waves in order  (k_lba_pose)
+//   a Schur block (i1, i2)     one workgroup: the shared points in ascending point index, summed the same way   (k_lba_schur)
+//   chi2, computeScale         per-workgroup partial sums, then one workgroup over the partials in order        (k_lba_*_reduce)
+// so two runs give the same bytes.  The reduced system is factorised by ONE workgroup (k_lba_solve): LDL^T without pivoting, in
+// LDS up to LBA_LDS_POSES free poses and in device memory past it - the same code through one pointer, hence the same bytes.
+#ifdef ORBX_LBA_HOST
+// tests/cpp/lba_lockstep.cc compiles this file's kernels AND the driver for the host, one thread per workgroup, the workgroups
+// of a launch one after the other (tests/cpp/hip_lockstep.h comes first): every sum then runs in ascending order, which is
+// tests/lba_ref.py's order - the two must agree bit for bit (tests/test_lba_cpu.py).
+#define LBA_THREADS 1
+#define LBA_LANES 1
+#else
+#include "orbx_stage.h"
+#define LBA_THREADS 256
+#define LBA_LANES 64
+#endif
+#include <float.h>
+#include <math.h>
+#include <algorithm>
+#include <vector>
+
+#define LBA_WAVES ((LBA_THREADS + LBA_LANES - 1) / LBA_LANES)
+#define LBA_LDS_POSES 14    // free poses whose reduced system (6 * 14 = 84 square, 56448 B of doubles) is factorised in LDS, under the 64 KiB a launch gets unasked
+#define LBA_ED 54           // doubles an edge's linearisation leaves: Hll 6 | bl 3 | Hpp 21 | bp 6 | W = Hpl 18
+#define LBA_MAX_TRIALS 10   // g2o's maxTrialsAfterFailure
+
+struct LbaRec { double linChi, maxDiag, tmpChi, scale; int32_t ok, pad; };   // what the host reads after a linearisation (it == 0) and after every trial
+struct LbaDev {
+    int32_t K, P, E, nf;                  // keyframes, points, observations; free poses with an active edge this round (columns)
+    const orbb_keyframe_t *kf; const orbb_point_t *pts; const orbb_observation_t *obs;
+    const int32_t *ptStart, *ptEdges, *kfStart, *kfEdges;   // CSR by point and by keyframe, the edges of an owner in ascending input index
+    const int32_t *col, *kfOfCol;         // per round: keyframe -> column (-1: fixed, or no active edge) and back
+    int32_t *tab;                         // per round: [nf][P] the active edge of (column, point) or -1
+    double *pose[2], *pt[2];              // the estimates t[3] | q[4] (x y z w) per keyframe and xyz per point: current and trial, swapped by the host
+    uint8_t *flag, *erase, *pact;         // edge at level 1; the final classification; point has an active edge
+    double *chi2, *ed, *Hll, *bl, *Dinv, *db, *Hpp, *bp, *S, *xp, *partChi, *partScale;
+    LbaRec *rec;
+    float *outT, *outP; double *estKf, *estPt;
+};
+
+__device__ __forceinline__ double lba_wave_sum(double v) {
+#pragma unroll
+    for (int m = LBA_LANES / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, LBA_LANES);   // a + b == b + a bit for bit: every lane ends with the same sum
+    return v;
+}
+template <int N>
+__device__ __forceinline__ void lba_block_sum(double (&a)[N], double *part) {   // part: LBA_WAVES * N doubles of LDS; the caller owns the barrier before part is used again
+    const int lane = threadIdx.x % LBA_LANES, wave = threadIdx.x / LBA_LANES;
+#pragma unroll
+    for (int k = 0; k < N; k++) a[k] = lba_wave_sum(a[k]);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < N; k++) part[wave * N + k] = a[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        double t = part[k];
+#pragma unroll
+        for (int w = 1; w < LBA_WAVES; w++) t += part[w * N + k];   // ((w0 + w1) + w2) + w3
+        a[k] = t;
+    }
+}
+
+// quat_from_R, normalize_rotation, quat_rotate, quat_to_R and se3_oplus are copies of orbx_poseopt.hip's (that file is unchanged)
+__device__ __forceinline__ void lba_quat_from_R(const double R[9], double q[4]) {
+    double t = R[0] + R[4] + R[8];
+    if (t > 0.0) {
+        t = sqrt(t + 1.0);
+        q[3] = 0.5 * t;
+        t = 0.5 / t;
+        q[0] = (R[7] - R[5]) * t; q[1] = (R[2] - R[6]) * t; q[2] = (R[3] - R[1]) * t;
+    } else {
+        int i = 0;
+        if (R[4] > R[0]) i = 1;
+        if (R[8] > R[i * 4]) i = 2;
+        const int j = (i + 1) % 3, k = (j + 1) % 3;
+        t = sqrt(R[i * 4] - R[j * 4] - R[k * 4] + 1.0);
+        double v[3];
+        v[i] = 0.5 * t;
+        t = 0.5 / t;
+        q[3] = (R[k * 3 + j] - R[j * 3 + k]) * t;
+        v[j] = (R[j * 3 + i] + R[i * 3 + j]) * t;
+        v[k] = (R[k * 3 + i] + R[i * 3 + k]) * t;
+        q[0] = v[0]; q[1] = v[1]; q[2] = v[2];
+    }
+}
+__device__ __forceinline__ void lba_normalize_rotation(double q[4]) {   // se3quat.h:280-285
+    if (q[3] < 0.0) { q[0] = -q[0]; q[1] = -q[1]; q[2] = -q[2]; q[3] = -q[3]; }
+    const double n = sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+    q[0] /= n; q[1] /= n; q[2] /= n; q[3] /= n;
+}
+__device__ __forceinline__ void lba_quat_rotate(const double q[4], const double v[3], double r[3]) {   // Quaternion * Vector3 (_transformVector)
+    double uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]};
+    uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
+    r[0] = (v[0] + q[3] * uv[0]) + (q[1] * uv[2] - q[2] * uv[1]);
+    r[1] = (v[1] + q[3] * uv[1]) + (q[2] * uv[0] - q[0] * uv[2]);
+    r[2] = (v[2] + q[3] * uv[2]) + (q[0] * uv[1] - q[1] * uv[0]);
+}
+__device__ __forceinline__ void lba_quat_to_R(const double q[4], double R[9]) {   // Quaternion::toRotationMatrix
+    const double tx = 2.0 * q[0], ty = 2.0 * q[1], tz = 2.0 * q[2];
+    const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3], txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
+    const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
+    R[0] = 1.0 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
+    R[3] = txy + twz; R[4] = 1.0 - (txx + tzz); R[5] = tyz - twx;
+    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1.0 - (txx + tyy);
+}
+// VertexSE3Expmap::oplusImpl: estimate = SE3Quat::exp(x) * estimate (se3quat.h:223-257, :104-110); x = omega | upsilon; T = t[3] | q[4]
+__device__ __forceinline__ void lba_se3_oplus(double *T, const double x[6]) {
+    const double o0 = x[0], o1 = x[1], o2 = x[2];
+    const double theta = sqrt((o0 * o0 + o1 * o1) + o2 * o2);
+    const double Om[9] = {0.0, -o2, o1, o2, 0.0, -o0, -o1, o0, 0.0};
+    double Om2[9];
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) Om2[r * 3 + c] = (Om[r * 3] * Om[c] + Om[r * 3 + 1] * Om[3 + c]) + Om[r * 3 + 2] * Om[6 + c];
+    double a, b, c2;
+    if (theta < 0.00001) { a = 1.0; b = 1.0; c2 = 1.0; }   // R = I + Omega + Omega^2, V = R
+    else {
+        const double s = sin(theta), co = cos(theta);
+        a = s / theta; b = (1.0 - co) / (theta * theta); c2 = (theta - s) / (theta * theta * theta);
+    }
+    double R[9], V[9];
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+        const double id = (k == 0 || k == 4 || k == 8) ? 1.0 : 0.0;
+        R[k] = (id + a * Om[k]) + b * Om2[k];
+        V[k] = theta < 0.00001 ? R[k] : (id + b * Om[k]) + c2 * Om2[k];
+    }
+    double qe[4], te[3];
+    lba_quat_from_R(R, qe);
+    lba_normalize_rotation(qe);
+#pragma unroll
+    for (int r = 0; r < 3; r++) te[r] = (V[r * 3] * x[3] + V[r * 3 + 1] * x[4]) + V[r * 3 + 2] * x[5];
+    double rt[3], q[4] = {T[3], T[4], T[5], T[6]};
+    lba_quat_rotate(qe, T, rt);
+    const double ax = qe[0], ay = qe[1], az = qe[2], aw = qe[3], bx = q[0], by = q[1], bz = q[2], bw = q[3];
+    T[0] = te[0] + rt[0]; T[1] = te[1] + rt[1]; T[2] = te[2] + rt[2];
+    q[3] = ((aw * bw - ax * bx) - ay * by) - az * bz;
+    q[0] = ((aw * bx + ax * bw) + ay * bz) - az * by;
+    q[1] = ((aw * by + ay * bw) + az * bx) - ax * bz;
+    q[2] = ((aw * bz + az * bw) + ax * by) - ay * bx;
+    lba_normalize_rotation(q);
+    T[3] = q[0]; T[4] = q[1]; T[5] = q[2]; T[6] = q[3];
+}
+
+// the estimates as the reference sets them (:527, :576): SE3Quat(R, t) of the widened float Tcw, the widened float position; every
+// edge at level 0, no evaluation yet (an edge never evaluated reports chi2 = 0, where the reference reads an uninitialised error)
+__global__ __launch_bounds__(LBA_THREADS) void k_lba_init(LbaDev D) {
+    const int i = blockIdx.x * LBA_THREADS + threadIdx.x;
+    if (i < D.K) {
+        const float *Tf = D.kf[i].Tcw;
+        double R[9], T[7];
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) R[r * 3 + c] = (double)Tf[r * 4 + c];
+            T[r] = (double)Tf[r * 4 + 3];
+        }
+        lba_quat_from_R(R, T + 3);
+        lba_normalize_rotation(T + 3);
+#pragma unroll
+        for (int k = 0; k < 7; k++) { D.pose[0][(size_t)i * 7 + k] = T[k]; D.pose[1][(size_t)i * 7 + k] = T[k]; }
+    }
+    if (i < D.P) {
+        const orbb_point_t p = D.pts[i];
+        const double X[3] = {(double)p.x, (double)p.y, (double)p.z};
+#pragma unroll
+        for (int k = 0; k < 3; k++) { D.pt[0][(size_t)i * 3 + k] = X[k]; D.pt[1][(size_t)i * 3 + k] = X[k]; }
+        D.pact[i] = 0;
+    }
+    if (i < D.E) { D.flag[i] = 0; D.erase[i] = 0; D.chi2[i] = 0.0; }
+}
+
+// per round: the active edge of (column, point); tab was filled with -1
+__global__ __launch_bounds__(LBA_THREADS) void k_lba_table(LbaDev D) {
+    const int e = blockIdx.x * LBA_THREADS + threadIdx.x;
+    if (e >= D.E || D.flag[e]) return;
+    const orbb_observation_t o = D.obs[e];
+    const int c = D.col[o.kf];
+    if (c >= 0) D.tab[(size_t)c * D.P + o.pt] = e;
+}
+
+// One active edge per thread at estimate `c`: computeError, chi2, the Huber kernel; its rho[0] into the workgroup's partial sum.
+// LIN: + linearizeOplus and constructQuadraticForm, the edge's own terms left in ed[k * E + e] for their owners to sum.  A monocular
+// edge is the stereo one with a zero third row.
+template <bool LIN>
+__global__ __launch_bounds__(LBA_THREADS) void k_lba_edges(LbaDev D, int c, int robust, double dMono, double dStereo) {
+    __shared__ double part[LBA_WAVES];
+    const int e = blockIdx.x * LBA_THREADS + threadIdx.x;
+    double a1[1] = {0.0};
+    if (e < D.E && !D.flag[e]) {
+        const orbb_observation_t o = D.obs[e];
+        const orbb_keyframe_t *kf = D.kf + o.kf;
+        const double fx = (double)kf->fx, fy = (double)kf->fy, cx = (double)kf->cx, cy = (double)kf->cy, bf = (double)kf->bf;
+        const double *T = D.pose[c] + (size_t)o.kf * 7, *Xp = D.pt[c] + (size_t)o.pt * 3;
+        const double q[4] = {T[3], T[4], T[5], T[6]}, Xw[3] = {Xp[0], Xp[1], Xp[2]};
+        double X[3];
+        lba_quat_rotate(q, Xw, X);   // SE3Quat::map: _r * xyz + _t
+        const double x = X[0] + T[0], y = X[1] + T[1], z = X[2] + T[2];
+        const bool mono = o.ur < 0.f;
+        double e0, e1, e2;
+        if (mono) {   // project2d, then * f + c, in double (types_six_dof_expmap.cpp:141-147)
+            e0 = (double)o.u - ((x / z) * fx + cx);
+            e1 = (double)o.v - ((y / z) * fy + cy);
+            e2 = 0.0;
+        } else {      // cam_project(trans_xyz, const float &bf) (:150-157): invz AND bf are float there, so bf * invz is a float product
+            const float izf = (float)(1.0 / z);
+            const double iz = (double)izf;
+            const double pu = (x * iz) * fx + cx;
+            e0 = (double)o.u - pu;
+            e1 = (double)o.v - ((y * iz) * fy + cy);
+            e2 = (double)o.ur - (pu - (double)(kf->bf * izf));
+        }
+        const double is2 = (double)o.inv_sigma2;
+        const double oe0 = is2 * e0, oe1 = is2 * e1, oe2 = is2 * e2;
+        const double chi2 = (e0 * oe0 + e1 * oe1) + e2 * oe2;
+        const double delta = mono ? dMono : dStereo;
+        const double dsqr = delta * delta;
+        double rho0 = chi2, w = 1.0;
+        if (robust && !(chi2 <= dsqr)) {
+            const double s = sqrt(chi2);
+            rho0 = (2.0 * s) * delta - dsqr;
+            w = delta / s;
+        }
+        D.chi2[e] = chi2;
+        a1[0] = rho0;
+        if (LIN) {
+            double R[9], A[3][3], B[3][6];
+            lba_quat_to_R(q, R);
+            const double z_2 = z * z;
+            if (mono) {   // _jacobianOplusXi = -1./z * tmp * R, tmp = [fx 0 -x/z*fx; 0 fy -y/z*fy] (:115-124)
+                const double s = -1. / z;
+                const double t0[3] = {s * fx, s * 0.0, s * (((-x) / z) * fx)}, t1[3] = {s * 0.0, s * fy, s * (((-y) / z) * fy)};
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    A[0][k] = (t0[0] * R[k] + t0[1] * R[3 + k]) + t0[2] * R[6 + k];
+                    A[1][k] = (t1[0] * R[k] + t1[1] * R[3 + k]) + t1[2] * R[6 + k];
+                    A[2][k] = 0.0;
+                }
+            } else {      // entry by entry (:202-212)
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    A[0][k] = ((-fx) * R[k]) / z + ((fx * x) * R[6 + k]) / z_2;
+                    A[1][k] = ((-fy) * R[3 + k]) / z + ((fy * y) * R[6 + k]) / z_2;
+                    A[2][k] = A[0][k] - (bf * R[6 + k]) / z_2;
+                }
+            }
+            B[0][0] = ((x * y) / z_2) * fx;            // _jacobianOplusXj (:126-138, :214-233)
+            B[0][1] = -(1 + ((x * x) / z_2)) * fx;
+            B[0][2] = (y / z) * fx;
+            B[0][3] = (-1. / z) * fx;
+            B[0][4] = 0.0;
+            B[0][5] = (x / z_2) * fx;
+            B[1][0] = (1 + (y * y) / z_2) * fy;
+            B[1][1] = (((-x) * y) / z_2) * fy;
+            B[1][2] = ((-x) / z) * fy;
+            B[1][3] = 0.0;
+            B[1][4] = (-1. / z) * fy;
+            B[1][5] = (y / z_2) * fy;
+            if (mono) {
+#pragma unroll
+                for (int j = 0; j < 6; j++) B[2][j] = 0.0;
+            } else {
+                B[2][0] = B[0][0] - (bf * y) / z_2;
+                B[2][1] = B[0][1] + (bf * x) / z_2;
+                B[2][2] = B[0][2];
+                B[2][3] = B[0][3];
+                B[2][4] = 0.0;
+                B[2][5] = B[0][5] - bf / z_2;
+            }
+            const double wo = w * is2;   // robustInformation: rho[1] * information; omega_r = -(information * error) * rho[1]
+            double *ed = D.ed + e;
+            const size_t E = (size_t)D.E;
+            int k = 0;
+#pragma unroll
+            for (int j = 0; j < 3; j++)
+#pragma unroll
+                for (int l = j; l < 3; l++, k++) ed[k * E] = ((A[0][j] * wo) * A[0][l] + (A[1][j] * wo) * A[1][l]) + (A[2][j] * wo) * A[2][l];
+#pragma unroll
+            for (int j = 0; j < 3; j++, k++) ed[k * E] = -(w * ((A[0][j] * oe0 + A[1][j] * oe1) + A[2][j] * oe2));
+#pragma unroll
+            for (int j = 0; j < 6; j++)
+#pragma unroll
+                for (int l = j; l < 6; l++, k++) ed[k * E] = ((B[0][j] * wo) * B[0][l] + (B[1][j] * wo) * B[1][l]) + (B[2][j] * wo) * B[2][l];
+#pragma unroll
+            for (int j = 0; j < 6; j++, k++) ed[k * E] = -(w * ((B[0][j] * oe0 + B[1][j] * oe1) + B[2][j] * oe2));
+#pragma unroll
+            for (int j = 0; j < 6; j++)       // W = Hpl = B^T (rho[1] Omega) A, 6 x 3
+#pragma unroll
+                for (int l = 0; l < 3; l++, k++) ed[k * E] = ((B[0][j] * wo) * A[0][l] + (B[1][j] * wo) * A[1][l]) + (B[2][j] * wo) * A[2][l];
+        }
+    }
+    lba_block_sum<1>(a1, part);
+    if (threadIdx.x == 0) D.partChi[blockIdx.x] = a1[0];
+}
+
+// Hll and bl of a point: its active observations in ascending input index.  A point without one has left the problem.
+__global__ __launch_bounds__(LBA_THREADS) void k_lba_point(LbaDev D) {
+    const int p = blockIdx.x * LBA_THREADS + threadIdx.x;
+    if (p >= D.P) return;
+    double acc[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    int n = 0;
+    const size_t E = (size_t)D.E;
+    for (int i = D.ptStart[p]; i < D.ptStart[p + 1]; i++) {
+        const int e = D.ptEdges[i];
+        if (D.flag[e]) continue;
+        n++;
+#pragma unroll
+        for (int k = 0; k < 9; k++) acc[k] += D.ed[k * E + e];
+    }
+    D.pact[p] = n > 0;
+#pragma unroll
+    for (int k = 0; k < 6; k++) D.Hll[(size_t)p * 6 + k] = acc[k];
+#pragma unroll
+    for (int k = 0; k < 3; k++) D.bl[(size_t)p * 3 + k] = acc[6 + k];
+}
+
+// Hpp and bp of a free pose (column blockIdx.x): one workgroup
+__global__ __launch_bounds__(LBA_THREADS) void k_lba_pose(LbaDev D) {
+    __shared__ double part[LBA_WAVES * 27];
+    const int c = blockIdx.x, kf = D.kfOfCol[c];
+    double acc[27];
+#pragma unroll
+    for (int k = 0; k < 27; k++) acc[k] = 0.0;
+    const size_t E = (size_t)D.E;
+    for (int i = D.kfStart[kf] + (int)threadIdx.x; i < D.kfStart[kf + 1]; i += LBA_THREADS) {
+        const int e = D.kfEdges[i];
+        if (D.flag[e]) continue;
+#pragma unroll
+        for (int k = 0; k < 27; k++) acc[k] += D.ed[(9 + k) * E + e];
+    }
+    lba_block_sum<27>(acc, part);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < 21; k++) D.Hpp[(size_t)c * 21 + k] = acc[k];
+#pragma unroll
+        for (int k = 0; k < 6; k++) D.bp[(size_t)c * 6 + k] = acc[21 + k];
+    }
+}
+
+// after a linearisation: activeRobustChi2 from the partial sums, and computeLambdaInit's max |diagonal| over the active vertices
+__global__ __launch_bounds__(LBA_THREADS) void k_lba_lin_reduce(LbaDev D, int nbE) {
+    __shared__ double part[LBA_WAVES];
+    __shared__ double mx[LBA_THREADS];
+    double a1[1] = {0.0}, md = 0.0;
+    for (int i = threadIdx.x; i < nbE; i += LBA_THREADS) a1[0] += D.partChi[i];
+    lba_block_sum<1>(a1, part);
+    for (int i = threadIdx.x; i < D.nf; i += LBA_THREADS) {
+        const double *H = D.Hpp + (size_t)i * 21;
+        md = fmax(fabs(H[0]), md); md = fmax(fabs(H[6]), md); md = fmax(fabs(H[11]), md);
+        md = fmax(fabs(H[15]), md); md = fmax(fabs(H[18]), md); md = fmax(fabs(H[20]), md);
+    }
+    for (int i = threadIdx.x; i < D.P; i += LBA_THREADS) {
+        if (!D.pact[i]) continue;
+        const double *H = D.Hll + (size_t)i * 6;
+        md = fmax(fabs(H[0]), md); md = fmax(fabs(H[3]), md); md = fmax(fabs(H[5]), md);
+    }
+    mx[threadIdx.x] = md;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int i = 1; i < LBA_THREADS; i++) md = fmax(mx[i], md);   // a maximum: any order gives the same value
+        D.rec->linChi = a1[0];
+        D.rec->maxDiag = md;
+    }
+}
+
+// a trial: Dinv = (Hll + lambda I)^-1 in closed form (cofactors over the determinant) and Dinv * bl, per active point
+__global__ __launch_bounds__(LBA_THREADS) void k_lba_dinv(LbaDev D, double lambda) {
+    const int p = blockIdx.x * LBA_THREADS + threadIdx.x;
+    if (p >= D.P || !D.pact[p]) return;
+    const double *H = D.Hll + (size_t)p * 6, *b = D.bl + (size_t)p * 3;
+    const double a00 = H[0] + lambda, a01 = H[1], a02 = H[2], a11 = H[3] + lambda, a12 = H[4], a22 = H[5] + lambda;
+    const double c00 = a11 * a22 - a12 * a12, c01 = a02 * a12 - a01 * a22, c02 = a01 * a12 - a02 * a11;
+    const double c11 = a00 * a22 - a02 * a02, c12 = a01 * a02 - a00 * a12, c22 = a00 * a11 - a01 * a01;
+    const double det = (a00 * c00 + a01 * c01) + a02 * c02;
+    const double id = 1.0 / det;
+    const double i00 = c00 * id, i01 = c01 * id, i02 = c02 * id, i11 = c11 * id, i12 = c12 * id, i22 = c22 * id;
+    double *Di = D.Dinv + (size_t)p * 6, *db = D.db + (size_t)p * 3;
+    Di[0] = i00; Di[1] = i01; Di[2] = i02; Di[3] = i11; Di[4] = i12; Di[5] = i22;
+    db[0] = (i00 * b[0] + i01 * b[1]) + i02 * b[2];
+    db[1] = (i01 * b[0] + i11 * b[1]) + i12 * b[2];
+    db[2] = (i02 * b[0] + i12 * b[1]) + i22 * b[2];
+}
+
+// Block (i1, i2), i1 <= i2, of Hschur = (Hpp + lambda I) - sum_p W Dinv W^T over the points both poses observe, in ascending point
+// index; the diagonal blocks also form bschur = bp - sum_p W Dinv bl.  Only the lower triangle of S is written (row >= column):
+// block (i1, i2) lands transposed at rows 6 i2.., columns 6 i1...
+__global__ __launch_bounds__(LBA_THREADS) void k_lba_schur(LbaDev D, double lambda) {
+    __shared__ double part[LBA_WAVES * 42];
+    const int nf = D.nf, i1 = blockIdx.x / nf, i2 = blockIdx.x % nf;
+    if (i2 < i1) return;   // uniform over the workgroup
+    double acc[42];
+#pragma unroll
+    for (int k = 0; k < 42; k++) acc[k] = 0.0;
+    const size_t E = (size_t)D.E;
+    const int32_t *t1 = D.tab + (size_t)i1 * D.P, *t2 = D.tab + (size_t)i2 * D.P;
+    for (int p = threadIdx.x; p < D.P; p += LBA_THREADS) {
+        const int ea = t1[p], eb = t2[p];
+        if (ea < 0 || eb < 0) continue;
+        const double *Dp = D.Dinv + (size_t)p * 6;
+        const double Di[3][3] = {{Dp[0], Dp[1], Dp[2]}, {Dp[1], Dp[3], Dp[4]}, {Dp[2], Dp[4], Dp[5]}};
+        double Y[6][3], W2[6][3];
+#pragma unroll
+        for (int j = 0; j < 6; j++) {
+            const double w0 = D.ed[(36 + j * 3) * E + ea], w1 = D.ed[(37 + j * 3) * E + ea], w2 = D.ed[(38 + j * 3) * E + ea];
+#pragma unroll
+            for (int l = 0; l < 3; l++) {
+                Y[j][l] = (w0 * Di[0][l] + w1 * Di[1][l]) + w2 * Di[2][l];
+                W2[j][l] = D.ed[(36 + j * 3 + l) * E + eb];
+            }
+            if (i1 == i2) {
+                const double *db = D.db + (size_t)p * 3;
+                acc[36 + j] += (w0 * db[0] + w1 * db[1]) + w2 * db[2];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 6; j++)
+#pragma unroll
+            for (int l = 0; l < 6; l++) acc[j * 6 + l] += (Y[j][0] * W2[l][0] + Y[j][1] * W2[l][1]) + Y[j][2] * W2[l][2];
+    }
+    lba_block_sum<42>(acc, part);
+    if (threadIdx.x == 0) {
+        const size_t n = (size_t)nf * 6;
+        if (i1 == i2) {
+            const double *H = D.Hpp + (size_t)i1 * 21;
+            int k = 0;
+            for (int j = 0; j < 6; j++)
+                for (int l = j; l < 6; l++, k++)   // H's upper entry (j, l) is the lower entry (l, j)
+                    D.S[(size_t)(6 * i1 + l) * n + 6 * i1 + j] = (j == l ? H[k] + lambda : H[k]) - acc[l * 6 + j];
+            for (int j = 0; j < 6; j++) D.xp[6 * i1 + j] = D.bp[(size_t)i1 * 6 + j] - acc[36 + j];
+        } else {
+            for (int j = 0; j < 6; j++)
+                for (int l = 0; l < 6; l++) D.S[(size_t)(6 * i2 + l) * n + 6 * i1 + j] = 0.0 - acc[j * 6 + l];
+        }
+    }
+}
+
+// Hschur xp = bschur (xp holds bschur on entry): right-looking LDL^T without pivoting on the lower triangle, then the two
+// substitutions column by column, so that every entry's updates arrive in one fixed order whatever the number of threads.  A zero,
+// negative or non-finite pivot: ok = 0 and xp = 0 (LinearSolver: !ok -> the trial's tempChi is DBL_MAX).  nf == 0: nothing to solve.
+__global__ __launch_bounds__(LBA_THREADS) void k_lba_solve(LbaDev D, int inLds) {
+    extern __shared__ __align__(16) uint8_t lba_lds[];
+    __shared__ int bad;
+    const int n = D.nf * 6, tid = threadIdx.x;
+    double *A = inLds ? (double *)lba_lds : D.S, *v = D.xp;
+    if (tid == 0) bad = 0;
+    if (inLds)
+        for (int i = tid; i < n * n; i += LBA_THREADS)
+            if (i / n >= i % n) A[i] = D.S[i];
+    __syncthreads();
+    for (int m = 0; m < n; m++) {
+        const double d = A[(size_t)m * n + m];
+        if (tid == 0 && (!(d > 0.0) || !(d <= DBL_MAX))) bad = 1;
+        __syncthreads();   // everyone has read the pivot's column as the last step left it
+        for (int i = m + 1 + tid; i < n; i += LBA_THREADS) A[(size_t)i * n + m] = A[(size_t)i * n + m] / d;
+        __syncthreads();
+        const int r = n - m - 1;
+        for (int t = tid; t < r * r; t += LBA_THREADS) {
+            const int i = m + 1 + t / r, j = m + 1 + t % r;
+            if (j <= i) A[(size_t)i * n + j] -= (A[(size_t)i * n + m] * A[(size_t)j * n + m]) * d;
+        }
+        __syncthreads();
+    }
+    for (int m = 0; m < n; m++) {          // L y = b
+        const double ym = v[m];
+        for (int i = m + 1 + tid; i < n; i += LBA_THREADS) v[i] -= A[(size_t)i * n + m] * ym;
+        __syncthreads();
+    }
+    for (int i = tid; i < n; i += LBA_THREADS) v[i] = v[i] / A[(size_t)i * n + i];
+    __syncthreads();
+    for (int m = n - 1; m >= 0; m--) {     // L^T x = y
+        const double xm = v[m];
+        for (int i = tid; i < m; i += LBA_THREADS) v[i] -= A[(size_t)m * n + i] * xm;
+        __syncthreads();
+    }
+    if (bad)
+        for (int i = tid; i < n; i += LBA_THREADS) v[i] = 0.0;
+    if (tid == 0) D.rec->ok = bad ? 0 : 1;
+}
+
+// The trial estimates from the current ones: workgroups [0, nbK) take the keyframes (exp(xp) * T for a column), the rest the points
+// (xl = Dinv (bl - W^T xp) over the point's active edges in ascending input index, then +=).  A vertex outside the problem, and every
+// vertex after a failed solve, is copied.  Each workgroup leaves its share of computeScale: sum x (lambda x + b).
+__global__ __launch_bounds__(LBA_THREADS) void k_lba_update(LbaDev D, int c, double lambda, int nbK) {
+    __shared__ double part[LBA_WAVES];
+    const int ok = D.rec->ok;
+    double a1[1] = {0.0};
+    if ((int)blockIdx.x < nbK) {
+        const int k = blockIdx.x * LBA_THREADS + threadIdx.x;
+        if (k < D.K) {
+            double T[7];
+#pragma unroll
+            for (int j = 0; j < 7; j++) T[j] = D.pose[c][(size_t)k * 7 + j];
+            const int cl = D.col[k];
+            if (cl >= 0 && ok) {
+                double x[6], s = 0.0;
+#pragma unroll
+                for (int j = 0; j < 6; j++) x[j] = D.xp[cl * 6 + j];
+#pragma unroll
+                for (int j = 0; j < 6; j++) s += x[j] * (lambda * x[j] + D.bp[(size_t)cl * 6 + j]);
+                a1[0] = s;
+                lba_se3_oplus(T, x);
+            }
+#pragma unroll
+            for (int j = 0; j < 7; j++) D.pose[c ^ 1][(size_t)k * 7 + j] = T[j];
+        }
+    } else {
+        const int p = ((int)blockIdx.x - nbK) * LBA_THREADS + threadIdx.x;
+        if (p < D.P) {
+            double X[3] = {D.pt[c][(size_t)p * 3], D.pt[c][(size_t)p * 3 + 1], D.pt[c][(size_t)p * 3 + 2]};
+            if (D.pact[p] && ok) {
+                const double *b = D.bl + (size_t)p * 3, *Dp = D.Dinv + (size_t)p * 6;
+                double cl[3] = {b[0], b[1], b[2]};
+                const size_t E = (size_t)D.E;
+                for (int i = D.ptStart[p]; i < D.ptStart[p + 1]; i++) {
+                    const int e = D.ptEdges[i];
+                    if (D.flag[e]) continue;
+                    const int cc = D.col[D.obs[e].kf];
+                    if (cc < 0) continue;
+                    const double *x = D.xp + cc * 6;
+#pragma unroll
+                    for (int l = 0; l < 3; l++) {
+                        double t = 0.0;
+#pragma unroll
+                        for (int j = 0; j < 6; j++) t += D.ed[(36 + j * 3 + l) * E + e] * x[j];
+                        cl[l] -= t;
+                    }
+                }
+                const double xl[3] = {(Dp[0] * cl[0] + Dp[1] * cl[1]) + Dp[2] * cl[2], (Dp[1] * cl[0] + Dp[3] * cl[1]) + Dp[4] * cl[2],
+                                      (Dp[2] * cl[0] + Dp[4] * cl[1]) + Dp[5] * cl[2]};
+                double s = 0.0;
+#pragma unroll
+                for (int l = 0; l < 3; l++) { s += xl[l] * (lambda * xl[l] + b[l]); X[l] += xl[l]; }
+                a1[0] = s;
+            }
+#pragma unroll
+            for (int l = 0; l < 3; l++) D.pt[c ^ 1][(size_t)p * 3 + l] = X[l];
+        }
+    }
+    lba_block_sum<1>(a1, part);
+    if (threadIdx.x == 0) D.partScale[blockIdx.x] = a1[0];
+}
+
+// after a trial: the trial's activeRobustChi2 and computeScale from the partial sums
+__global__ __launch_bounds__(LBA_THREADS) void k_lba_trial_reduce(LbaDev D, int nbE, int nbS) {
+    __shared__ double part[2][LBA_WAVES];
+    double a1[1] = {0.0}, a2[1] = {0.0};
+    for (int i = threadIdx.x; i < nbE; i += LBA_THREADS) a1[0] += D.partChi[i];
+    for (int i = threadIdx.x; i < nbS; i += LBA_THREADS) a2[0] += D.partScale[i];
+    lba_block_sum<1>(a1, part[0]);
+    lba_block_sum<1>(a2, part[1]);
+    if (threadIdx.x == 0) { D.rec->tmpChi = a1[0]; D.rec->scale = a2[0]; }
+}
+
+// chi2() > th || !isDepthPositive() (:680, :696, :723, :738): chi2 is the edge's LAST evaluation - a rejected trial's, and for an
+// edge at level 1 round 1's -, the depth is computed at the current estimate.  final == 0: setLevel(1); final == 1: the erase flag.
+__global__ __launch_bounds__(LBA_THREADS) void k_lba_classify(LbaDev D, int c, int final) {
+    const int e = blockIdx.x * LBA_THREADS + threadIdx.x;
+    if (e >= D.E) return;
+    const orbb_observation_t o = D.obs[e];
+    const double *T = D.pose[c] + (size_t)o.kf * 7, *Xp = D.pt[c] + (size_t)o.pt * 3;
+    const double q[4] = {T[3], T[4], T[5], T[6]}, Xw[3] = {Xp[0], Xp[1], Xp[2]};
+    double X[3];
+    lba_quat_rotate(q, Xw, X);
+    const double z = X[2] + T[2];
+    const bool out = D.chi2[e] > (o.ur < 0.f ? 5.991 : 7.815) || !(z > 0.0);
+    if (final) D.erase[e] = out ? 1 : 0;
+    else D.flag[e] = out ? 1 : 0;
+}
+
+// Converter::toCvMat(SE3Quat) and toCvMat(Vector3d) (:767, :777): a fixed keyframe, and everything when the call returns at :655,
+// goes out as the bytes that came in; the double estimates beside them (q = x y z w, then t)
+__global__ __launch_bounds__(LBA_THREADS) void k_lba_out(LbaDev D, int c, int untouched) {
+    const int i = blockIdx.x * LBA_THREADS + threadIdx.x;
+    if (i < D.K) {
+        const double *T = D.pose[c] + (size_t)i * 7;
+        float *to = D.outT + (size_t)i * 16;
+        if (D.kf[i].fixed || untouched) {
+            for (int k = 0; k < 16; k++) to[k] = D.kf[i].Tcw[k];
+        } else {
+            const double q[4] = {T[3], T[4], T[5], T[6]};
+            double R[9];
+            lba_quat_to_R(q, R);
+            for (int r = 0; r < 3; r++) {
+                for (int cc = 0; cc < 3; cc++) to[r * 4 + cc] = (float)R[r * 3 + cc];
+                to[r * 4 + 3] = (float)T[r];
+            }
+            to[12] = 0.f; to[13] = 0.f; to[14] = 0.f; to[15] = 1.f;
+        }
+        double *eo = D.estKf + (size_t)i * 7;
+        eo[0] = T[3]; eo[1] = T[4]; eo[2] = T[5]; eo[3] = T[6]; eo[4] = T[0]; eo[5] = T[1]; eo[6] = T[2];
+    }
+    if (i < D.P) {
+        const double *X = D.pt[c] + (size_t)i * 3;
+        for (int k = 0; k < 3; k++) {
+            D.outP[(size_t)i * 3 + k] = (float)X[k];   // the widened float narrows back to itself
+            D.estPt[(size_t)i * 3 + k] = X[k];
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------
+// the argument checks, before a device is touched
+static inline bool lba_finite(float v) { return v >= -FLT_MAX && v <= FLT_MAX; }
+static int lba_check(const char *fn, const orbb_keyframe_t *kfs, int K, const orbb_point_t *pts, int P, const orbb_observation_t *obs, int E,
+                     const orbb_schedule_t *s, float *Tcw_out, float *pts_out, uint8_t *erase) {
+    if (K < 0 || P < 0 || E < 0 || !s || (K > 0 && (!kfs || !Tcw_out)) || (P > 0 && (!pts || !pts_out)) || (E > 0 && (!obs || !erase))) {
+        orbx_set_error("%s: bad arguments", fn); return ORBX_ERR_ARG;
+    }
+    if ((s->rounds != 1 && s->rounds != 2) || !(s->delta_mono >= 0.f) || !lba_finite(s->delta_mono) || !(s->delta_stereo >= 0.f) || !lba_finite(s->delta_stereo)) {
+        orbx_set_error("%s: bad schedule", fn); return ORBX_ERR_ARG;
+    }
+    for (int r = 0; r < s->rounds; r++)
+        if (s->iterations[r] < 0 || s->iterations[r] > ORBB_MAX_ITERATIONS) { orbx_set_error("%s: iterations outside 0..%d", fn, ORBB_MAX_ITERATIONS); return ORBX_ERR_ARG; }
+    for (int k = 0; k < K; k++) {
+        bool ok = lba_finite(kfs[k].fx) && lba_finite(kfs[k].fy) && lba_finite(kfs[k].cx) && lba_finite(kfs[k].cy) && lba_finite(kfs[k].bf);
+        for (int j = 0; j < 16; j++) ok = ok && lba_finite(kfs[k].Tcw[j]);
+        if (!ok) { orbx_set_error("%s: keyframe %d is not finite", fn, k); return ORBX_ERR_ARG; }
+    }
+    for (int p = 0; p < P; p++)
+        if (!lba_finite(pts[p].x) || !lba_finite(pts[p].y) || !lba_finite(pts[p].z)) { orbx_set_error("%s: point %d is not finite", fn, p); return ORBX_ERR_ARG; }
+    std::vector<uint64_t> pairs((size_t)E);
+    for (int e = 0; e < E; e++) {
+        const orbb_observation_t &o = obs[e];
+        if (o.kf < 0 || o.kf >= K || o.pt < 0 || o.pt >= P) { orbx_set_error("%s: observation %d names keyframe %d, point %d", fn, e, o.kf, o.pt); return ORBX_ERR_ARG; }
+        if (!lba_finite(o.u) || !lba_finite(o.v) || !lba_finite(o.ur) || !(o.inv_sigma2 >= 0.f) || !lba_finite(o.inv_sigma2)) {
+            orbx_set_error("%s: observation %d is not finite or its inv_sigma2 is negative", fn, e); return ORBX_ERR_ARG;
+        }
+        pairs[e] = ((uint64_t)(uint32_t)o.kf << 32) | (uint32_t)o.pt;
+    }
+    std::sort(pairs.begin(), pairs.end());
+    for (int e = 1; e < E; e++)
+        if (pairs[e] == pairs[e - 1]) {
+            orbx_set_error("%s: keyframe %d observes point %d twice", fn, (int)(pairs[e] >> 32), (int)(uint32_t)pairs[e]); return ORBX_ERR_ARG;
+        }
+    return ORBX_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// The memory of one call and the four things the driver does with it.  The library: a device block, its pinned mirror and a stream
+// (this thread's StagePair).  The lockstep program: one host block that is both, a launch is a loop over blockIdx.x.
+struct LbaMem {
+    uint8_t *d, *h;
+#ifdef ORBX_LBA_HOST
+    int push(size_t, size_t) { return ORBX_OK; }
+    int fetch(size_t, size_t) { return ORBX_OK; }
+    int fill(size_t off, int byte, size_t bytes) { memset(d + off, byte, bytes); return ORBX_OK; }
+#else
+    hipStream_t st;
+    int push(size_t off, size_t bytes) { ORBX_HIP(hipMemcpyAsync(d + off, h + off, bytes, hipMemcpyHostToDevice, st)); return ORBX_OK; }
+    int fetch(size_t off, size_t bytes) {   // the ONE synchronisation of a trial
+        ORBX_HIP(hipMemcpyAsync(h + off, d + off, bytes, hipMemcpyDeviceToHost, st));
+        ORBX_HIP(hipStreamSynchronize(st));
+        return ORBX_OK;
+    }
+    int fill(size_t off, int byte, size_t bytes) { ORBX_HIP(hipMemsetAsync(d + off, byte, bytes, st)); return ORBX_OK; }
+#endif
+};
+#ifdef ORBX_LBA_HOST
+#define LBA_LAUNCH(kern, grid, lds, ...) do { for (int b_ = 0; b_ < (int)(grid); b_++) { blockIdx.x = b_; kern(__VA_ARGS__); } blockIdx.x = 0; } while (0)
+#define LBA_TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
+struct StagePlan { size_t off = 0; size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; } };
+#else
+#define LBA_LAUNCH(kern, grid, lds, ...) do { hipLaunchKernelGGL(kern, dim3(grid), dim3(LBA_THREADS), lds, M.st, __VA_ARGS__); ORBX_HIP(hipGetLastError()); } while (0)
+#define LBA_TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
+#endif
+
+struct LbaLayout {
+    size_t oKf, oPts, oObs, oPtStart, oPtEdges, oKfStart, oKfEdges, inEnd, oCol, oKfOfCol, oFlag, oRec;
+    size_t oOutT, oOutP, oErase, oEstKf, oEstPt, outEnd;
+    size_t oPose[2], oPt[2], oPact, oChi2, oEd, oHll, oBl, oDinv, oDb, oHpp, oBp, oS, oXp, oPartChi, oPartScale, oTab, total;
+    int nbE, nbK, nbP, nbAll, nfMax;
+};
+static inline int lba_blocks(int n) { return (n + LBA_THREADS - 1) / LBA_THREADS; }
+static LbaLayout lba_layout(const orbb_keyframe_t *kfs, int K, int P, int E) {
+    LbaLayout L;
+    StagePlan pl;
+    const size_t k1 = (size_t)(K > 0 ? K : 1), p1 = (size_t)(P > 0 ? P : 1), e1 = (size_t)(E > 0 ? E : 1);
+    L.nfMax = 0;
+    for (int k = 0; k < K; k++) L.nfMax += kfs[k].fixed ? 0 : 1;
+    const size_t f1 = (size_t)(L.nfMax > 0 ? L.nfMax : 1);
+    L.nbE = lba_blocks(E); L.nbK = lba_blocks(K); L.nbP = lba_blocks(P);
+    L.nbAll = lba_blocks(std::max(K, std::max(P, E)));
+    // uploaded once
+    L.oKf = pl.take(k1 * sizeof(orbb_keyframe_t)); L.oPts = pl.take(p1 * sizeof(orbb_point_t)); L.oObs = pl.take(e1 * sizeof(orbb_observation_t));
+    L.oPtStart = pl.take((p1 + 1) * 4); L.oPtEdges = pl.take(e1 * 4); L.oKfStart = pl.take((k1 + 1) * 4); L.oKfEdges = pl.take(e1 * 4);
+    L.inEnd = pl.off;
+    // uploaded per round; downloaded per round; downloaded per trial
+    L.oCol = pl.take(k1 * 4); L.oKfOfCol = pl.take(k1 * 4); L.oFlag = pl.take(e1); L.oRec = pl.take(sizeof(LbaRec));
+    // downloaded at the end
+    L.oOutT = pl.take(k1 * 64); L.oOutP = pl.take(p1 * 12); L.oErase = pl.take(e1); L.oEstKf = pl.take(k1 * 56); L.oEstPt = pl.take(p1 * 24);
+    L.outEnd = pl.off;
+    // device only
+    for (int i = 0; i < 2; i++) { L.oPose[i] = pl.take(k1 * 56); L.oPt[i] = pl.take(p1 * 24); }
+    L.oPact = pl.take(p1); L.oChi2 = pl.take(e1 * 8); L.oEd = pl.take(e1 * LBA_ED * 8);
+    L.oHll = pl.take(p1 * 48); L.oBl = pl.take(p1 * 24); L.oDinv = pl.take(p1 * 48); L.oDb = pl.take(p1 * 24);
+    L.oHpp = pl.take(f1 * 168); L.oBp = pl.take(f1 * 48); L.oS = pl.take(f1 * f1 * 36 * 8); L.oXp = pl.take(f1 * 48);
+    L.oPartChi = pl.take((size_t)(L.nbE > 0 ? L.nbE : 1) * 8); L.oPartScale = pl.take((size_t)(L.nbK + L.nbP > 0 ? L.nbK + L.nbP : 1) * 8);
+    L.oTab = pl.take(f1 * p1 * 4);
+    L.total = pl.off;
+    return L;
+}
+
+typedef int (*lba_stop_fn)(void *);
+// The schedule of :655-707 and the Levenberg-Marquardt of optimization_algorithm_levenberg.cpp:61-164 under sparse_optimizer.cpp:376.
+// M.h holds the inputs on entry (lba_stage) and the outputs on return.  The loops are bounded by the schedule: iterations x 10 trials.
+static int lba_drive(LbaMem M, const LbaLayout &L, int K, int P, int E, const orbb_schedule_t &sc, lba_stop_fn stop, void *user, orbb_info_t *info) {
+    LbaDev D;
+    uint8_t *d = M.d;
+    D.K = K; D.P = P; D.E = E; D.nf = 0;
+    D.kf = (const orbb_keyframe_t *)(d + L.oKf); D.pts = (const orbb_point_t *)(d + L.oPts); D.obs = (const orbb_observation_t *)(d + L.oObs);
+    D.ptStart = (const int32_t *)(d + L.oPtStart); D.ptEdges = (const int32_t *)(d + L.oPtEdges);
+    D.kfStart = (const int32_t *)(d + L.oKfStart); D.kfEdges = (const int32_t *)(d + L.oKfEdges);
+    D.col = (const int32_t *)(d + L.oCol); D.kfOfCol = (const int32_t *)(d + L.oKfOfCol); D.tab = (int32_t *)(d + L.oTab);
+    for (int i = 0; i < 2; i++) { D.pose[i] = (double *)(d + L.oPose[i]); D.pt[i] = (double *)(d + L.oPt[i]); }
+    D.flag = d + L.oFlag; D.erase = d + L.oErase; D.pact = d + L.oPact;
+    D.chi2 = (double *)(d + L.oChi2); D.ed = (double *)(d + L.oEd); D.Hll = (double *)(d + L.oHll); D.bl = (double *)(d + L.oBl);
+    D.Dinv = (double *)(d + L.oDinv); D.db = (double *)(d + L.oDb); D.Hpp = (double *)(d + L.oHpp); D.bp = (double *)(d + L.oBp);
+    D.S = (double *)(d + L.oS); D.xp = (double *)(d + L.oXp); D.partChi = (double *)(d + L.oPartChi); D.partScale = (double *)(d + L.oPartScale);
+    D.rec = (LbaRec *)(d + L.oRec);
+    D.outT = (float *)(d + L.oOutT); D.outP = (float *)(d + L.oOutP); D.estKf = (double *)(d + L.oEstKf); D.estPt = (double *)(d + L.oEstPt);
+    const orbb_keyframe_t *hkf = (const orbb_keyframe_t *)(M.h + L.oKf);
+    const orbb_observation_t *hobs = (const orbb_observation_t *)(M.h + L.oObs);
+    int32_t *hcol = (int32_t *)(M.h + L.oCol), *hkfOfCol = (int32_t *)(M.h + L.oKfOfCol);
+    const uint8_t *hflag = M.h + L.oFlag;
+    const LbaRec *hrec = (const LbaRec *)(M.h + L.oRec);
+
+    orbb_info_t inf;
+    memset(&inf, 0, sizeof(inf));
+    int polls = 0;
+    auto poll = [&](int where) -> bool {   // OptimizableGraph::terminate(), and the reference's own two reads of the flag
+        if (!stop) return false;
+        polls++;
+        const bool s = stop(user) != 0;
+        if (s && !inf.stopped_at) { inf.stopped_at = where; inf.stop_poll = polls; }
+        return s;
+    };
+    LBA_TRY(M.push(0, L.inEnd));
+    if (L.nbAll) LBA_LAUNCH(k_lba_init, L.nbAll, 0, D);
+    int c = 0;
+    bool untouched = false, classify = sc.classify != 0;
+    if (sc.check_stop_first && poll(ORBB_STOP_BEFORE)) { untouched = true; classify = false; }   // :655: return, nothing written
+    for (int round = 0; round < sc.rounds && !untouched; round++) {
+        if (round == 1) {
+            if (poll(ORBB_STOP_BETWEEN)) break;   // :664: bDoMore = false
+            if (L.nbE) LBA_LAUNCH(k_lba_classify, L.nbE, 0, D, c, 0);
+            LBA_TRY(M.fetch(L.oFlag, (size_t)(E > 0 ? E : 1)));
+        }
+        // initializeOptimization(0): a vertex without an edge at level 0 is not in the problem (sparse_optimizer.cpp:218-259)
+        int nActive = 0, nf = 0;
+        for (int k = 0; k < K; k++) hcol[k] = hkf[k].fixed ? -1 : -2;
+        for (int e = 0; e < E; e++) {
+            if (round == 1 && hflag[e]) continue;
+            nActive++;
+            if (hcol[hobs[e].kf] == -2) hcol[hobs[e].kf] = -3;
+        }
+        for (int k = 0; k < K; k++) {
+            if (hcol[k] == -3) { hkfOfCol[nf] = k; hcol[k] = nf++; }
+            else hcol[k] = -1;
+        }
+        inf.rounds = round + 1;
+        inf.free_poses[round] = nf;
+        if (!nActive) continue;   // optimize(): "0 vertices to optimize", no iteration and no poll
+        D.nf = nf;
+        LBA_TRY(M.push(L.oCol, L.oFlag - L.oCol));
+        if (nf) {
+            LBA_TRY(M.fill(L.oTab, 0xFF, (size_t)nf * P * 4));
+            LBA_LAUNCH(k_lba_table, L.nbE, 0, D);
+        }
+        const int inLds = nf <= LBA_LDS_POSES;
+        const size_t lds = inLds ? (size_t)nf * nf * 36 * 8 : 0;
+        (void)lds;
+        const int robust = sc.robust[round] != 0;
+        const double dMono = (double)sc.delta_mono, dStereo = (double)sc.delta_stereo;
+        const int where = round == 0 ? ORBB_STOP_ROUND1 : ORBB_STOP_ROUND2;
+        double lambda = 0.0, ni = 2.0;
+        int nbadIt = 0;
+        bool ok = true;
+        for (int it = 0; it < sc.iterations[round]; it++) {
+            if (poll(where) || !ok) break;   // for (i = 0; i < iterations && !terminate() && ok; i++)
+            LBA_LAUNCH(k_lba_edges<true>, L.nbE, 0, D, c, robust, dMono, dStereo);
+            LBA_LAUNCH(k_lba_point, L.nbP, 0, D);
+            if (nf) LBA_LAUNCH(k_lba_pose, nf, 0, D);
+            LBA_LAUNCH(k_lba_lin_reduce, 1, 0, D, L.nbE);
+            if (it == 0) {   // computeLambdaInit: tau * max |diagonal|
+                LBA_TRY(M.fetch(L.oRec, sizeof(LbaRec)));
+                lambda = 1e-5 * hrec->maxDiag; ni = 2.0; nbadIt = 0;
+            }
+            double cur = 0.0, iniChi = 0.0, rho = 0.0;
+            int q = 0;
+            bool more;
+            do {
+                LBA_LAUNCH(k_lba_dinv, L.nbP, 0, D, lambda);
+                if (nf) LBA_LAUNCH(k_lba_schur, nf * nf, 0, D, lambda);
+                LBA_LAUNCH(k_lba_solve, 1, lds, D, inLds);
+                LBA_LAUNCH(k_lba_update, L.nbK + L.nbP, 0, D, c, lambda, L.nbK);
+                LBA_LAUNCH(k_lba_edges<false>, L.nbE, 0, D, c ^ 1, robust, dMono, dStereo);
+                LBA_LAUNCH(k_lba_trial_reduce, 1, 0, D, L.nbE, L.nbK + L.nbP);
+                LBA_TRY(M.fetch(L.oRec, sizeof(LbaRec)));
+                if (q == 0) { cur = hrec->linChi; iniChi = cur; }
+                double tmp = hrec->tmpChi;
+                if (!hrec->ok) tmp = DBL_MAX;
+                const double scale = hrec->scale + 1e-3;
+                rho = (cur - tmp) / scale;
+                if (rho > 0.0 && fabs(tmp) <= DBL_MAX) {
+                    const double u = 2.0 * rho - 1.0;
+                    double alpha = 1.0 - (u * u) * u;
+                    alpha = fmin(alpha, 2.0 / 3.0);
+                    lambda *= fmax(1.0 / 3.0, alpha);
+                    ni = 2.0;
+                    cur = tmp;
+                    c ^= 1;   // discardTop: the trial estimates are the current ones
+                } else {
+                    lambda *= ni;
+                    ni *= 2.0;   // pop: the current estimates stand
+                }
+                q++;
+                more = rho < 0.0 && q < LBA_MAX_TRIALS;
+                if (more && poll(where)) more = false;
+            } while (more);
+            inf.iterations[round]++; inf.trials[round] += q;
+            if (q == LBA_MAX_TRIALS || rho == 0.0) { ok = false; continue; }   // Terminate: the loop's condition is read once more
+            if ((iniChi - cur) * 1e3 < iniChi) nbadIt++; else nbadIt = 0;      // the reference's own stop criterion
+            if (nbadIt >= 3) ok = false;
+        }
+    }
+    if (classify && L.nbE) LBA_LAUNCH(k_lba_classify, L.nbE, 0, D, c, 1);
+    if (L.nbAll) LBA_LAUNCH(k_lba_out, L.nbAll, 0, D, c, untouched ? 1 : 0);
+    LBA_TRY(M.fetch(L.oOutT, L.outEnd - L.oOutT));
+    inf.polls = polls;
+    const uint8_t *er = M.h + L.oErase;
+    for (int e = 0; e < E; e++) inf.erased += er[e];
+    if (info) *info = inf;
+    return ORBX_OK;
+}
+
+// the inputs into the mirror, and the per-owner lists: CSR by point and by keyframe, an owner's edges in ascending input index
+static void lba_stage(uint8_t *h, const LbaLayout &L, const orbb_keyframe_t *kfs, int K, const orbb_point_t *pts, int P, const orbb_observation_t *obs, int E) {
+    if (K) memcpy(h + L.oKf, kfs, (size_t)K * sizeof(orbb_keyframe_t));
+    if (P) memcpy(h + L.oPts, pts, (size_t)P * sizeof(orbb_point_t));
+    if (E) memcpy(h + L.oObs, obs, (size_t)E * sizeof(orbb_observation_t));
+    int32_t *ps = (int32_t *)(h + L.oPtStart), *pe = (int32_t *)(h + L.oPtEdges), *ks = (int32_t *)(h + L.oKfStart), *ke = (int32_t *)(h + L.oKfEdges);
+    for (int p = 0; p <= P; p++) ps[p] = 0;
+    for (int k = 0; k <= K; k++) ks[k] = 0;
+    for (int e = 0; e < E; e++) { ps[obs[e].pt + 1]++; ks[obs[e].kf + 1]++; }
+    for (int p = 0; p < P; p++) ps[p + 1] += ps[p];
+    for (int k = 0; k < K; k++) ks[k + 1] += ks[k];
+    std::vector<int32_t> pn(ps, ps + P), kn(ks, ks + K);
+    for (int e = 0; e < E; e++) { pe[pn[obs[e].pt]++] = e; ke[kn[obs[e].kf]++] = e; }
+    memset(h + L.oErase, 0, (size_t)(E > 0 ? E : 1));
+}
+static void lba_results(const uint8_t *h, const LbaLayout &L, int K, int P, int E, float *Tcw_out, float *pts_out, uint8_t *erase, double *kf_est, double *pt_est) {
+    if (K) memcpy(Tcw_out, h + L.oOutT, (size_t)K * 64);
+    if (P) memcpy(pts_out, h + L.oOutP, (size_t)P * 12);
+    if (E) memcpy(erase, h + L.oErase, (size_t)E);
+    if (kf_est && K) memcpy(kf_est, h + L.oEstKf, (size_t)K * 56);
+    if (pt_est && P) memcpy(pt_est, h + L.oEstPt, (size_t)P * 24);
+}
+
+#ifndef ORBX_LBA_HOST
+// host side: this thread's staging pair (orbx_stage.h)
+static thread_local StagePair g_ba;
+void orbx_internal_release_lba_scratch() { g_ba.release(); }
+
+extern "C" int orbb_optimize(const orbb_keyframe_t *kfs, int K, const orbb_point_t *pts, int P, const orbb_observation_t *obs, int E,
+                             const orbb_schedule_t *schedule, int (*stop)(void *), void *stop_user, float *Tcw_out16, float *pts_out3,
+                             uint8_t *erase, orbb_info_t *info, double *kf_est7, double *pt_est3, int device) {
+    const int crc = lba_check("orbb_optimize", kfs, K, pts, P, obs, E, schedule, Tcw_out16, pts_out3, erase);
+    if (crc) return crc;
+    const LbaLayout L = lba_layout(kfs, K, P, E);
+    int rc = g_ba.reserve(device, L.total, (size_t)1 << 20);
+    if (rc) return rc;
+    LbaMem M;
+    M.d = g_ba.d; M.h = g_ba.h; M.st = g_ba.stream;
+    lba_stage(M.h, L, kfs, K, pts, P, obs, E);
+    (void)hipGetLastError();
+    rc = lba_drive(M, L, K, P, E, *schedule, stop, stop_user, info);
+    if (rc) { hipStreamSynchronize(M.st); return rc; }
+    lba_results(M.h, L, K, P, E, Tcw_out16, pts_out3, erase, kf_est7, pt_est3);
+    return ORBX_OK;
+}
+
+extern "C" int orbb_local_bundle_adjustment(const orbb_keyframe_t *kfs, int K, const orbb_point_t *pts, int P, const orbb_observation_t *obs, int E,
+                                            int (*stop)(void *), void *stop_user, float *Tcw_out16, float *pts_out3, uint8_t *erase,
+                                            orbb_info_t *info, double *kf_est7, double *pt_est3, int device) {
+    // optimize(5) with the Huber kernel, the classification, optimize(10) without it over the edges left at level 0 (:569-570, :660-707)
+    const orbb_schedule_t s = {2, {5, 10}, {1, 0}, (float)sqrt(5.991), (float)sqrt(7.815), 1, 1};
+    return orbb_optimize(kfs, K, pts, P, obs, E, &s, stop, stop_user, Tcw_out16, pts_out3, erase, info, kf_est7, pt_est3, device);
+}
+
+extern "C" int orbb_bundle_adjustment(const orbb_keyframe_t *kfs, int K, const orbb_point_t *pts, int P, const orbb_observation_t *obs, int E,
+                                      int iterations, int robust, int (*stop)(void *), void *stop_user, float *Tcw_out16, float *pts_out3,
+                                      orbb_info_t *info, double *kf_est7, double *pt_est3, int device) {
+    // one optimize(nIterations), no classification; thHuber2D = sqrt(5.99) here, not 5.991 (:95-96)
+    const orbb_schedule_t s = {1, {iterations, 0}, {robust ? 1 : 0, 0}, (float)sqrt(5.99), (float)sqrt(7.815), 0, 0};
+    std::vector<uint8_t> erase((size_t)(E > 0 ? E : 1));
+    return orbb_optimize(kfs, K, pts, P, obs, E, &s, stop, stop_user, Tcw_out16, pts_out3, erase.data(), info, kf_est7, pt_est3, device);
+}
+#endif   // ORBX_LBA_HOST

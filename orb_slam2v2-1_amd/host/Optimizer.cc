@@ -1,6 +1,9 @@
 // Optimizer.cc — see Optimizer.h.
 #include "Optimizer.h"
 #include <cstdlib>
+#include <list>
+#include <map>
+#include <mutex>
 #include <stdexcept>
 #include <string>
 #include "orbx.h"
@@ -99,6 +102,198 @@ int Optimizer::OptimizeSim3(KeyFrame *pKF1, KeyFrame *pKF2, std::vector<MapPoint
     if (info.rounds < 2) return 0;   // :1216-1217: returns before the vertex is read back
     g2oS12 = g2o::Sim3(Eigen::Quaterniond(info.q[3], info.q[0], info.q[1], info.q[2]), Eigen::Vector3d(info.t[0], info.t[1], info.t[2]), info.s);
     return nIn;
+}
+
+static int stop_flag_set(void *user) { return *(volatile bool *)user ? 1 : 0; }
+
+static void fill_keyframe(orbb_keyframe_t &k, KeyFrame *pKF, bool fixed) {
+    const cv::Mat T = pKF->GetPose();
+    for (int r = 0; r < 4; r++)
+        for (int c = 0; c < 4; c++) k.Tcw[r * 4 + c] = T.at<float>(r, c);
+    k.fx = pKF->fx; k.fy = pKF->fy; k.cx = pKF->cx; k.cy = pKF->cy; k.bf = pKF->mbf;
+    k.fixed = fixed ? 1 : 0;
+}
+static orbb_observation_t make_observation(KeyFrame *pKFi, size_t idx, int kf, int pt) {
+    const cv::KeyPoint &kpUn = pKFi->mvKeysUn[idx];
+    orbb_observation_t o;
+    o.kf = kf; o.pt = pt; o.u = kpUn.pt.x; o.v = kpUn.pt.y;
+    o.ur = pKFi->mvuRight[idx] < 0 ? -1.f : pKFi->mvuRight[idx];
+    o.inv_sigma2 = pKFi->mvInvLevelSigma2[kpUn.octave];
+    return o;
+}
+static cv::Mat pose_mat(const float *T) {
+    cv::Mat pose(4, 4, CV_32F);
+    for (int r = 0; r < 4; r++)
+        for (int c = 0; c < 4; c++) pose.at<float>(r, c) = T[r * 4 + c];
+    return pose;
+}
+static cv::Mat point_mat(const float *X) {
+    cv::Mat pos(3, 1, CV_32F);
+    for (int k = 0; k < 3; k++) pos.at<float>(k) = X[k];
+    return pos;
+}
+
+void Optimizer::LocalBundleAdjustment(KeyFrame *pKF, bool *pbStopFlag, Map *pMap) {
+    // Local KeyFrames: First Breath Search from Current Keyframe (:455-468)
+    std::list<KeyFrame *> lLocalKeyFrames;
+    lLocalKeyFrames.push_back(pKF);
+    pKF->mnBALocalForKF = pKF->mnId;
+    const std::vector<KeyFrame *> vNeighKFs = pKF->GetVectorCovisibleKeyFrames();
+    for (int i = 0, iend = vNeighKFs.size(); i < iend; i++) {
+        KeyFrame *pKFi = vNeighKFs[i];
+        pKFi->mnBALocalForKF = pKF->mnId;
+        if (!pKFi->isBad()) lLocalKeyFrames.push_back(pKFi);
+    }
+    // Local MapPoints seen in Local KeyFrames (:470-486)
+    std::list<MapPoint *> lLocalMapPoints;
+    for (std::list<KeyFrame *>::iterator lit = lLocalKeyFrames.begin(), lend = lLocalKeyFrames.end(); lit != lend; lit++) {
+        std::vector<MapPoint *> vpMPs = (*lit)->GetMapPointMatches();
+        for (std::vector<MapPoint *>::iterator vit = vpMPs.begin(), vend = vpMPs.end(); vit != vend; vit++) {
+            MapPoint *pMP = *vit;
+            if (pMP)
+                if (!pMP->isBad())
+                    if (pMP->mnBALocalForKF != pKF->mnId) {
+                        lLocalMapPoints.push_back(pMP);
+                        pMP->mnBALocalForKF = pKF->mnId;
+                    }
+        }
+    }
+    // Fixed Keyframes. Keyframes that see Local MapPoints but that are not Local Keyframes (:488-504)
+    std::list<KeyFrame *> lFixedCameras;
+    for (std::list<MapPoint *>::iterator lit = lLocalMapPoints.begin(), lend = lLocalMapPoints.end(); lit != lend; lit++) {
+        std::map<KeyFrame *, size_t> observations = (*lit)->GetObservations();
+        for (std::map<KeyFrame *, size_t>::iterator mit = observations.begin(), mend = observations.end(); mit != mend; mit++) {
+            KeyFrame *pKFi = mit->first;
+            if (pKFi->mnBALocalForKF != pKF->mnId && pKFi->mnBAFixedForKF != pKF->mnId) {
+                pKFi->mnBAFixedForKF = pKF->mnId;
+                if (!pKFi->isBad()) lFixedCameras.push_back(pKFi);
+            }
+        }
+    }
+    // the vertices (:522-546): the local keyframes, then the fixed ones
+    std::vector<orbb_keyframe_t> kfs;
+    std::map<KeyFrame *, int> index;
+    for (std::list<KeyFrame *>::iterator lit = lLocalKeyFrames.begin(), lend = lLocalKeyFrames.end(); lit != lend; lit++) {
+        orbb_keyframe_t k;
+        fill_keyframe(k, *lit, (*lit)->mnId == 0);
+        index[*lit] = (int)kfs.size();
+        kfs.push_back(k);
+    }
+    for (std::list<KeyFrame *>::iterator lit = lFixedCameras.begin(), lend = lFixedCameras.end(); lit != lend; lit++) {
+        orbb_keyframe_t k;
+        fill_keyframe(k, *lit, true);
+        index[*lit] = (int)kfs.size();
+        kfs.push_back(k);
+    }
+    // the points and one edge per observation in a keyframe that is not bad (:572-653)
+    std::vector<orbb_point_t> pts;
+    std::vector<orbb_observation_t> obs;
+    std::vector<KeyFrame *> vpEdgeKF;
+    std::vector<MapPoint *> vpMapPointEdge;
+    for (std::list<MapPoint *>::iterator lit = lLocalMapPoints.begin(), lend = lLocalMapPoints.end(); lit != lend; lit++) {
+        MapPoint *pMP = *lit;
+        const cv::Mat Xw = pMP->GetWorldPos();
+        const orbb_point_t p = {Xw.at<float>(0), Xw.at<float>(1), Xw.at<float>(2)};
+        const int id = (int)pts.size();
+        pts.push_back(p);
+        const std::map<KeyFrame *, size_t> observations = pMP->GetObservations();
+        for (std::map<KeyFrame *, size_t>::const_iterator mit = observations.begin(), mend = observations.end(); mit != mend; mit++) {
+            KeyFrame *pKFi = mit->first;
+            if (pKFi->isBad() || !index.count(pKFi)) continue;
+            obs.push_back(make_observation(pKFi, mit->second, index[pKFi], id));
+            vpEdgeKF.push_back(pKFi);
+            vpMapPointEdge.push_back(pMP);
+        }
+    }
+    const int K = (int)kfs.size(), P = (int)pts.size(), E = (int)obs.size();
+    std::vector<float> Tout((size_t)K * 16 + 1), Pout((size_t)P * 3 + 1);
+    std::vector<uint8_t> erase((size_t)E + 1, 0);
+    orbb_info_t info;
+    const int rc = orbb_local_bundle_adjustment(kfs.data(), K, pts.data(), P, obs.data(), E, pbStopFlag ? stop_flag_set : NULL, pbStopFlag,
+                                                Tout.data(), Pout.data(), erase.data(), &info, NULL, NULL, device);
+    if (rc != ORBX_OK) throw std::runtime_error(std::string("Optimizer::LocalBundleAdjustment: ") + orbx_last_error());
+    if (info.stopped_at == ORBB_STOP_BEFORE) return;   // :655-657
+    // Get Map Mutex (:746-757)
+    std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);
+    for (int e = 0; e < E; e++)
+        if (erase[e]) {
+            KeyFrame *pKFi = vpEdgeKF[e];
+            MapPoint *pMPi = vpMapPointEdge[e];
+            pKFi->EraseMapPointMatch(pMPi);
+            pMPi->EraseObservation(pKFi);
+        }
+    // Recover optimized data (:759-779)
+    for (std::list<KeyFrame *>::iterator lit = lLocalKeyFrames.begin(), lend = lLocalKeyFrames.end(); lit != lend; lit++) {
+        KeyFrame *pKFl = *lit;
+        pKFl->SetPose(pose_mat(Tout.data() + (size_t)index[pKFl] * 16));
+#ifdef ORBX_HAVE_ORBSLAM2
+        pMap->UpdateKeyFrame(pKFl);   // server keyframe
+#endif
+    }
+    int id = 0;
+    for (std::list<MapPoint *>::iterator lit = lLocalMapPoints.begin(), lend = lLocalMapPoints.end(); lit != lend; lit++, id++) {
+        MapPoint *pMP = *lit;
+        pMP->SetWorldPos(point_mat(Pout.data() + (size_t)id * 3));
+        pMP->UpdateNormalAndDepth();
+    }
+}
+
+void Optimizer::GlobalBundleAdjustemnt(Map *pMap, int nIterations, bool *pbStopFlag, const unsigned long nLoopKF, const bool bRobust) {
+    std::vector<KeyFrame *> vpKFs = pMap->GetAllKeyFrames();
+    std::vector<MapPoint *> vpMP = pMap->GetAllMapPoints();
+    BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust);
+}
+
+void Optimizer::BundleAdjustment(const std::vector<KeyFrame *> &vpKFs, const std::vector<MapPoint *> &vpMP, int nIterations, bool *pbStopFlag,
+                                 const unsigned long nLoopKF, const bool bRobust) {
+    if (nLoopKF != 0) throw std::runtime_error("Optimizer::BundleAdjustment: the nLoopKF != 0 write-back (mTcwGBA / mPosGBA) is not built");
+    std::vector<orbb_keyframe_t> kfs;
+    std::map<KeyFrame *, int> index;
+    for (size_t i = 0; i < vpKFs.size(); i++) {   // :71-83
+        KeyFrame *pKF = vpKFs[i];
+        if (pKF->isBad()) continue;
+        orbb_keyframe_t k;
+        fill_keyframe(k, pKF, pKF->mnId == 0);
+        index[pKF] = (int)kfs.size();
+        kfs.push_back(k);
+    }
+    std::vector<orbb_point_t> pts;
+    std::vector<orbb_observation_t> obs;
+    std::vector<int> vnPoint(vpMP.size(), -1);   // -1: vbNotIncludedMP, or bad
+    for (size_t i = 0; i < vpMP.size(); i++) {    // :89-184
+        MapPoint *pMP = vpMP[i];
+        if (pMP->isBad()) continue;
+        const std::map<KeyFrame *, size_t> observations = pMP->GetObservations();
+        const int id = (int)pts.size();
+        int nEdges = 0;
+        for (std::map<KeyFrame *, size_t>::const_iterator mit = observations.begin(); mit != observations.end(); mit++) {
+            KeyFrame *pKF = mit->first;
+            if (pKF->isBad() || !index.count(pKF)) continue;   // pKF->mnId > maxKFid: not among vpKFs
+            nEdges++;
+            obs.push_back(make_observation(pKF, mit->second, index[pKF], id));
+        }
+        if (nEdges == 0) continue;
+        const cv::Mat Xw = pMP->GetWorldPos();
+        const orbb_point_t p = {Xw.at<float>(0), Xw.at<float>(1), Xw.at<float>(2)};
+        pts.push_back(p);
+        vnPoint[i] = id;
+    }
+    const int K = (int)kfs.size(), P = (int)pts.size(), E = (int)obs.size();
+    std::vector<float> Tout((size_t)K * 16 + 1), Pout((size_t)P * 3 + 1);
+    const int rc = orbb_bundle_adjustment(kfs.data(), K, pts.data(), P, obs.data(), E, nIterations, bRobust ? 1 : 0, pbStopFlag ? stop_flag_set : NULL,
+                                          pbStopFlag, Tout.data(), Pout.data(), NULL, NULL, NULL, device);
+    if (rc != ORBX_OK) throw std::runtime_error(std::string("Optimizer::BundleAdjustment: ") + orbx_last_error());
+    for (size_t i = 0; i < vpKFs.size(); i++) {   // :193-210
+        KeyFrame *pKF = vpKFs[i];
+        if (pKF->isBad()) continue;
+        pKF->SetPose(pose_mat(Tout.data() + (size_t)index[pKF] * 16));
+    }
+    for (size_t i = 0; i < vpMP.size(); i++) {    // :213-235
+        if (vnPoint[i] < 0) continue;
+        MapPoint *pMP = vpMP[i];
+        pMP->SetWorldPos(point_mat(Pout.data() + (size_t)vnPoint[i] * 3));
+        pMP->UpdateNormalAndDepth();
+    }
 }
 
 }  // namespace ORB_SLAM2

@@ -1,10 +1,12 @@
-// Optimizer.h — the two DENSE members of ORB_SLAM2::Optimizer (include/Optimizer.h) executed on an MI355X through include/orbx.h:
+// Optimizer.h — the members of ORB_SLAM2::Optimizer (include/Optimizer.h) executed on an MI355X through include/orbx.h:
 // PoseOptimization (src/Optimizer.cc:239-451, orbo_pose_optimization), the pose-only optimisation Tracking runs between its matcher
-// calls (src/Tracking.cc:918, :1041, :1083, :1585-1616), and OptimizeSim3 (src/Optimizer.cc:1051-1246, orbz_optimize_sim3), the
-// refinement of a loop candidate's Sim3 in LoopClosing::ComputeSim3 (src/LoopClosing.cc:336).  Both have ONE free vertex and fixed
-// map points - a 6x6 and a 7x7 normal matrix - and a dense solver in the reference too.  BundleAdjustment, LocalBundleAdjustment and
-// OptimizeEssentialGraph are sparse nonlinear least squares over many vertices, another shape of problem, and are not part of this
-// library: keep the reference's own (g2o) for them.
+// calls (src/Tracking.cc:918, :1041, :1083, :1585-1616); OptimizeSim3 (src/Optimizer.cc:1051-1246, orbz_optimize_sim3), the
+// refinement of a loop candidate's Sim3 in LoopClosing::ComputeSim3 (src/LoopClosing.cc:336); LocalBundleAdjustment (:453-780,
+// orbb_local_bundle_adjustment), the mapping thread's bundle adjustment (src/LocalMapping.cc:89), and BundleAdjustment /
+// GlobalBundleAdjustemnt (:41-237, orbb_bundle_adjustment) for the map CreateInitialMapMonocular builds (src/Tracking.cc:700).  The
+// first two have ONE free vertex; the bundle adjustments marginalise the points, and the reduced system of a local window - a few tens
+// of keyframes - is dense and small.  OptimizeEssentialGraph and a bundle adjustment of a loop-closure-sized map are sparse problems of
+// another shape and are not part of this library: keep the reference's own (g2o) for them.
 #ifndef ORBX_OPTIMIZER_H
 #define ORBX_OPTIMIZER_H
 #include "frame_shim.h"
@@ -27,6 +29,20 @@ public:
     // Throws std::runtime_error with orbx_last_error() when the library reports an error (no GPU among them).
     static int OptimizeSim3(KeyFrame *pKF1, KeyFrame *pKF2, std::vector<MapPoint *> &vpMatches1, g2o::Sim3 &g2oS12, const float th2,
                             const bool bFixScale);
+    // The reference's signature and semantics (:453-780): the three lists of :455-504 with the mnBALocalForKF / mnBAFixedForKF marks, one
+    // observation per (map point, keyframe that is not bad), the flat call, then under pMap->mMutexMapUpdate EraseMapPointMatch /
+    // EraseObservation for every flagged observation, SetPose for the local keyframes, SetWorldPos and UpdateNormalAndDepth for the
+    // local points.  *pbStopFlag is read where the reference reads it; set at :655 the call returns with nothing written.  The local
+    // keyframe with mnId == 0 is fixed and keeps its pose byte for byte (the reference writes it back through its quaternion).
+    // Throws std::runtime_error with orbx_last_error() when the library reports an error (no GPU among them).
+    void static LocalBundleAdjustment(KeyFrame *pKF, bool *pbStopFlag, Map *pMap);
+    // :49-237 and :41-46 with the write-back of nLoopKF == 0 (SetPose, SetWorldPos, UpdateNormalAndDepth).  The nLoopKF != 0 branch
+    // (mTcwGBA, mPosGBA, mnBAGlobalForKF: the loop closer's global adjustment) is NOT built: the shim does not carry those members and
+    // a loop-closure-sized map is outside what the dense reduced system is meant for; it throws std::runtime_error.
+    void static BundleAdjustment(const std::vector<KeyFrame *> &vpKFs, const std::vector<MapPoint *> &vpMP, int nIterations = 5,
+                                 bool *pbStopFlag = NULL, const unsigned long nLoopKF = 0, const bool bRobust = true);
+    void static GlobalBundleAdjustemnt(Map *pMap, int nIterations = 5, bool *pbStopFlag = NULL, const unsigned long nLoopKF = 0,
+                                       const bool bRobust = true);
     static int device;   // GPU used (default: ORBX_DEVICE or 0)
 };
 

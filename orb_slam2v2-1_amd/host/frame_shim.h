@@ -12,6 +12,7 @@
 #include <climits>
 #include <cmath>
 #include <map>
+#include <mutex>
 #include <set>
 #include <vector>
 #include "cv_shim.h"
@@ -24,8 +25,12 @@ class Frame;
 class KeyFrame;
 class MapPoint;
 
-class Map {   // include/Map.h: what LocalMapping::CreateNewMapPoints touches
+class Map {   // include/Map.h: what LocalMapping::CreateNewMapPoints and Optimizer::LocalBundleAdjustment / GlobalBundleAdjustemnt touch
 public:
+    void AddKeyFrame(KeyFrame *pKF) { mvpKeyFrames.push_back(pKF); }   // src/Map.cc:33-40 (a set there)
+    std::vector<KeyFrame *> GetAllKeyFrames() { return mvpKeyFrames; }
+    std::vector<KeyFrame *> mvpKeyFrames;
+    std::mutex mMutexMapUpdate;
     void AddMapPoint(MapPoint *pMP) { mvpMapPoints.push_back(pMP); }   // src/Map.cc:42-46 (a set there; insertion order is kept here for the tests)
     std::vector<MapPoint *> GetAllMapPoints() { return mvpMapPoints; }
     std::vector<MapPoint *> mvpMapPoints;
@@ -60,6 +65,10 @@ public:
     bool IsInKeyFrame(KeyFrame *pKF) { return mObservations.count(pKF) != 0; }            // src/MapPoint.cc
     int GetIndexInKeyFrame(KeyFrame *pKF) { return mObservations.count(pKF) ? (int)mObservations[pKF] : -1; }
     inline void AddObservation(KeyFrame *pKF, size_t idx);                                // src/MapPoint.cc:108-119
+    inline void EraseObservation(KeyFrame *pKF);                                          // src/MapPoint.cc:121-147
+    inline void SetBadFlag();                                                             // src/MapPoint.cc:161-180, without the Map erase
+    void SetWorldPos(const cv::Mat &Pos) { mWorldPos = Pos.clone(); }                     // src/MapPoint.cc:83-88
+    long unsigned int mnId = 0, mnBALocalForKF = 0;   // include/MapPoint.h: read and written by Optimizer::LocalBundleAdjustment
     inline void Replace(MapPoint *pMP);                                                   // src/MapPoint.cc:187-225
     std::map<KeyFrame *, size_t> GetObservations() { return mObservations; }
     void SetDescriptor(const cv::Mat &d) { mDescriptor = d.clone(); }   // the store at src/MapPoint.cc:313-316 (test shim only)
@@ -143,6 +152,12 @@ public:
     void AddMapPoint(MapPoint *pMP, const size_t &idx) { mvpMapPoints[idx] = pMP; }
     void ReplaceMapPointMatch(const size_t &idx, MapPoint *pMP) { mvpMapPoints[idx] = pMP; }
     void EraseMapPointMatch(const size_t &idx) { mvpMapPoints[idx] = static_cast<MapPoint *>(NULL); }
+    void EraseMapPointMatch(MapPoint *pMP) {   // src/KeyFrame.cc:223-228
+        int idx = pMP->GetIndexInKeyFrame(this);
+        if (idx >= 0) mvpMapPoints[idx] = static_cast<MapPoint *>(NULL);
+    }
+    long unsigned int mnBALocalForKF = 0, mnBAFixedForKF = 0;   // include/KeyFrame.h: the marks of Optimizer::LocalBundleAdjustment
+    std::vector<KeyFrame *> GetVectorCovisibleKeyFrames() { return mvpOrderedConnectedKeyFrames; }   // src/KeyFrame.cc:310-314
     cv::Mat GetPose() { return Tcw.clone(); }
     cv::Mat GetRotation() {
         cv::Mat R(3, 3, CV_32F);
@@ -215,6 +230,23 @@ inline void MapPoint::AddObservation(KeyFrame *pKF, size_t idx) {
     if (mObservations.count(pKF)) return;
     mObservations[pKF] = idx;
     if (pKF->mvuRight[idx] >= 0) nObs += 2; else nObs++;
+}
+inline void MapPoint::EraseObservation(KeyFrame *pKF) {
+    bool bBad = false;
+    if (mObservations.count(pKF)) {
+        int idx = (int)mObservations[pKF];
+        if (pKF->mvuRight[idx] >= 0) nObs -= 2; else nObs--;
+        mObservations.erase(pKF);
+        if (mpRefKF == pKF) mpRefKF = mObservations.empty() ? NULL : mObservations.begin()->first;
+        if (nObs <= 2) bBad = true;   // if only 2 observations or less, discard point
+    }
+    if (bBad) SetBadFlag();
+}
+inline void MapPoint::SetBadFlag() {
+    std::map<KeyFrame *, size_t> obs = mObservations;
+    mbBad = true;
+    mObservations.clear();
+    for (std::map<KeyFrame *, size_t>::iterator mit = obs.begin(), mend = obs.end(); mit != mend; mit++) mit->first->EraseMapPointMatch(mit->second);
 }
 inline MapPoint::MapPoint(const cv::Mat &Pos, KeyFrame *pRefKF, Map *pMap) : MapPoint() {
     mWorldPos = Pos.clone();
