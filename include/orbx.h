@@ -1138,6 +1138,44 @@ int orbb_bundle_adjustment(const orbb_keyframe_t *kfs, int K, const orbb_point_t
                            int iterations, int robust, int (*stop)(void *), void *stop_user, float *Tcw_out16, float *pts_out3,
                            orbb_info_t *info, double *kf_est7, double *pt_est3, int device);
 
+/* ---- Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:783-1049; prefix orbg_) ----------------------------------------------------
+ * The pose graph LoopClosing::CorrectLoop optimises after it has fused the loop (src/LoopClosing.cc:576), on flat arrays: one
+ * VertexSim3Expmap (7 unknowns) per keyframe, one EdgeSim3 (7 residuals, identity information, numeric Jacobians with delta = 1e-9)
+ * per edge, no robust kernel, Levenberg-Marquardt from lambda = 1e-16 over the whole Hpp (no vertex is marginalised).  Double
+ * throughout; DESIGN.md section 6, "k_eg_*".  The host computes the symbolic factorisation once per call (ordering, elimination
+ * tree, block pattern with fill, the update list of every block); the device factorises by a left-looking block LDL^T without
+ * pivoting, one launch per level of the elimination tree.  The host drives iterations and trials with one stream synchronisation per
+ * trial.  Every sum has one owner and a fixed order: two calls give the same bytes.
+ *
+ * vertices [N]: Scw = the vScw entry (CorrectedSim3's, or Sim3(Rcw, tcw, 1) of the keyframe's pose widened), Snc with has_nc != 0 =
+ * the NonCorrectedSim3 entry, fixed != 0 for pLoopKF.  Any number of vertices may be fixed, none included (the reference runs either
+ * way); a vertex without an edge keeps its estimate.  edges [E]: vertex 0 of the EdgeSim3 is i, vertex 1 is j; kind 0 (a loop
+ * connection, :854-882) measures Scw[j] * Scw[i]^-1, kind 1 (spanning tree, loop, covisibility, :885-985) takes Snc for an end whose
+ * has_nc is set; a pair may occur any number of times.  points [P]: ref = the vertex of mnCorrectedReference or of the reference
+ * keyframe (:1025-1034).  iterations: 0..ORBG_MAX_ITERATIONS (the reference: 20).
+ * Tcw_out16 [N][16]: [R, t / s] of every estimate, a fixed vertex's too (:1001-1011); pts_out3 [P][3]: correctedSwr.map(Srw.map(P))
+ * in double, narrowed (:1037-1045); est_out8 [N][8] (may be NULL): the estimates q (x y z w), t, s; info may be NULL.
+ * NULL pointers, negative sizes, an index out of range, i == j, a value that is NaN or infinite, s <= 0, iterations outside its
+ * range: ORBX_ERR_ARG before a device is touched.  Connectivity is not checked: a component that does not reach a fixed vertex
+ * leaves a singular matrix that only lambda regularises, as in the reference.  Scratch per host thread (orbx_thread_release_scratch). */
+#define ORBG_MAX_ITERATIONS 64
+#define ORBG_END_ITERATIONS 0     /* info->end: every iteration asked for has run */
+#define ORBG_END_QMAX 1           /* ten trials of one iteration were rejected */
+#define ORBG_END_RHO0 2           /* a trial's rho was exactly 0 */
+#define ORBG_END_SOLVER 3         /* as ORBG_END_QMAX or ORBG_END_RHO0, and the last trial's factorisation met a bad pivot */
+#define ORBG_END_NBAD 4           /* three iterations in a row gained less than 1e-3 of their chi2: the reference's _nBad >= 3 (optimization_algorithm_levenberg.cpp:152-160) */
+typedef struct { double q[4], t[3], s; } orbg_sim3_t;                                   /* 64 B; q = x y z w */
+typedef struct { orbg_sim3_t Scw, Snc; int32_t has_nc, fixed; } orbg_vertex_t;          /* 136 B */
+typedef struct { int32_t i, j, kind; } orbg_edge_t;                                     /* 12 B */
+typedef struct { float x, y, z; int32_t ref; } orbg_point_t;                            /* 16 B */
+/* trials: their total; trials_it[k]: of iteration k; free_vertices: columns (not fixed, with an edge); blocks: 7x7 blocks of the
+ * factor, the diagonal ones included; levels: launch levels of the elimination tree; launches: kernel launches of the call */
+typedef struct { int32_t iterations, trials, end, free_vertices, blocks, levels, launches, pad; double chi2_first, chi2_last;
+                 int32_t trials_it[ORBG_MAX_ITERATIONS]; } orbg_info_t;                 /* 304 B */
+int orbg_optimize_essential_graph(const orbg_vertex_t *vertices, int N, const orbg_edge_t *edges, int E, const orbg_point_t *points, int P,
+                                  int fix_scale, int iterations, float *Tcw_out16, float *pts_out3, double *est_out8, orbg_info_t *info,
+                                  int device);
+
 /* The host-array matcher entry points keep grow-only device scratch, a pinned mirror and one non-blocking stream
  * PER HOST THREAD (re-entrant without locks: the reference calls matchers from Tracking, LocalMapping and LoopClosing
  * threads at once, src/LocalMapping.cc:223, src/LoopClosing.cc:249).  Nothing is freed implicitly; a thread calls

@@ -75,6 +75,15 @@ LBA_INFO_DTYPE = np.dtype([("rounds", "<i4"), ("iterations", "<i4", (2,)), ("tri
                            ("stop_poll", "<i4"), ("polls", "<i4"), ("erased", "<i4")])
 LBA_STOP_BEFORE, LBA_STOP_ROUND1, LBA_STOP_BETWEEN, LBA_STOP_ROUND2 = 1, 2, 3, 4      # info["stopped_at"]
 LBA_MAX_ITERATIONS = 100
+# orbg_sim3_t / orbg_vertex_t / orbg_edge_t / orbg_point_t / orbg_info_t (Optimizer::OptimizeEssentialGraph, optimize_essential_graph)
+EG_SIM3_DTYPE = np.dtype([("q", "<f8", (4,)), ("t", "<f8", (3,)), ("s", "<f8")])      # q = x y z w
+EG_VERTEX_DTYPE = np.dtype([("Scw", EG_SIM3_DTYPE), ("Snc", EG_SIM3_DTYPE), ("has_nc", "<i4"), ("fixed", "<i4")])
+EG_EDGE_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("kind", "<i4")])      # kind 0: loop connection, 1: spanning tree / loop / covisibility
+EG_POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("ref", "<i4")])
+EG_MAX_ITERATIONS = 64
+EG_INFO_DTYPE = np.dtype([("iterations", "<i4"), ("trials", "<i4"), ("end", "<i4"), ("free_vertices", "<i4"), ("blocks", "<i4"), ("levels", "<i4"),
+                          ("launches", "<i4"), ("pad", "<i4"), ("chi2_first", "<f8"), ("chi2_last", "<f8"), ("trials_it", "<i4", (EG_MAX_ITERATIONS,))])
+EG_END_ITERATIONS, EG_END_QMAX, EG_END_RHO0, EG_END_SOLVER, EG_END_NBAD = 0, 1, 2, 3, 4      # info["end"]
 # orbl_view_t / orbl_stereo_t / orbl_point_t (LocalMapping::CreateNewMapPoints, triangulate_new_points*)
 NEWPOINT_VIEW_DTYPE = np.dtype([("Tcw", "<f4", (16,)), ("Ow", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"),
                                 ("invfx", "<f4"), ("invfy", "<f4"), ("mb", "<f4"), ("mbf", "<f4"), ("scale_factor", "<f4"), ("nlevels", "<i4")])
@@ -134,6 +143,8 @@ SIM3OPT_EXPORTS = ["orbz_optimize_sim3", "orbz_optimize_sim3_batch"]
 NEWPOINTS_EXPORTS = ["orbl_triangulate", "orbl_triangulate_batch", "orbl_baseline_ok", "orbl_compute_f12", "orbl_create_new_map_points"]
 # the bundle adjustment section (prefix orbb_), apart for the same reason
 LBA_EXPORTS = ["orbb_optimize", "orbb_local_bundle_adjustment", "orbb_bundle_adjustment"]
+# the essential graph section (prefix orbg_), apart for the same reason
+ESSENTIAL_EXPORTS = ["orbg_optimize_essential_graph"]
 # what include/orbx_dev.h declares on top: exported by the developer build only
 DEV_EXPORTS = ["orbx_debug_level_points", "orbx_debug_sincosf", "orbx_debug_blur_patches", "orbm_debug_features_in_area",
                "orbx_debug_blurred_level", "orbx_debug_octree_fallbacks", "orbm_debug_match_path", "orbm_debug_resolve_plan",
@@ -448,6 +459,7 @@ def _load(path, dev):
     L.orbb_optimize.argtypes = [vp, i32, vp, i32, vp, i32, vp, LBA_STOP_FN, vp, vp, vp, vp, vp, vp, vp, i32]
     L.orbb_local_bundle_adjustment.argtypes = [vp, i32, vp, i32, vp, i32, LBA_STOP_FN, vp, vp, vp, vp, vp, vp, vp, i32]
     L.orbb_bundle_adjustment.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32, LBA_STOP_FN, vp, vp, vp, vp, vp, vp, i32]
+    L.orbg_optimize_essential_graph.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, i32]
     L.orbp_pnp_parameters.argtypes = [i32, C.c_double, i32, i32, i32, f32, C.POINTER(i32), C.POINTER(i32)]
     L.orbp_pnp_ransac.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
     L.orbp_pnp_ransac_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
@@ -1461,6 +1473,66 @@ def bundle_adjustment_scheduled(keyframes, points, observations, schedule, stop=
     return _lba_run(lambda L, kf, K, pt, P, ob, E, fn, To, Po, er, info, ke, pe, dev:
                     L.orbb_optimize(kf, K, pt, P, ob, E, _p(sc), fn, None, To, Po, er, info, ke, pe, dev),
                     keyframes, points, observations, stop, device)
+
+
+def optimize_essential_graph(vertices, edges, points, fix_scale, iterations=20, device=0):
+    """Optimizer::OptimizeEssentialGraph (orbg_optimize_essential_graph).  vertices [N] EG_VERTEX_DTYPE (Scw: the CorrectedSim3 entry or
+    Sim3(Rcw, tcw, 1) of the pose; Snc with has_nc: the NonCorrectedSim3 entry; fixed: pLoopKF), edges [E] EG_EDGE_DTYPE
+    (essential_graph_edges builds them), points [P] EG_POINT_DTYPE (ref: the vertex of mnCorrectedReference or of the reference keyframe)
+    -> (Tcw [N, 4, 4] float32 = [R, t / s], points [P, 3] float32, est [N, 8] float64 (q = x y z w, t, s), info dict)."""
+    vt = np.ascontiguousarray(vertices, EG_VERTEX_DTYPE)
+    ed = np.ascontiguousarray(edges, EG_EDGE_DTYPE)
+    pt = np.ascontiguousarray(points, EG_POINT_DTYPE)
+    N, E, P = len(vt), len(ed), len(pt)
+    To, Po, est, info = np.zeros((N, 4, 4), np.float32), np.zeros((P, 3), np.float32), np.zeros((N, 8), np.float64), np.zeros(1, EG_INFO_DTYPE)
+    _check(matcher_lib().orbg_optimize_essential_graph(_p(vt), N, _p(ed), E, _p(pt), P, int(bool(fix_scale)), int(iterations), _p(To), _p(Po),
+                                                       _p(est), _p(info), int(device)))
+    inf = {k: (info[0][k].item() if info[0][k].ndim == 0 else [int(x) for x in info[0][k]]) for k in EG_INFO_DTYPE.names}
+    return To, Po, est, inf
+
+
+def essential_graph_edges(mnid, bad, parent, children, loop_edges, covisibles, weight, loop_connections, cur, loop, min_feat=100):
+    """The edges Optimizer::OptimizeEssentialGraph builds (src/Optimizer.cc:849-985), restated for flat inputs - a pure function, no
+    device.  The keyframes are numbered as vpKFs lists them: mnid [K], bad [K]; parent [K]: an index or -1; children, loop_edges [K]:
+    sets of indices; covisibles [K]: GetCovisiblesByWeight(min_feat) as lists of indices; weight(a, b): GetWeight; loop_connections:
+    {index: set of indices}; cur, loop: pCurKF and pLoopKF.  Where the reference walks a std::set or std::map of pointers (an order
+    that is the allocator's), this walks in ascending mnId.  A bad keyframe has no vertex and no edge: the reference would hand
+    g2o a null vertex there (a bad keyframe has left the map by then).
+    -> (vertex [K]: the dense vertex index or -1, edges EG_EDGE_DTYPE: the loop connections (kind 0) first, then per keyframe its
+    spanning-tree edge, its loop edges and its covisibility edges (kind 1))."""
+    K = len(mnid)
+    bad = [bool(b) for b in bad]
+    vertex, n = [-1] * K, 0
+    for k in range(K):
+        if not bad[k]:
+            vertex[k] = n
+            n += 1
+    by_id = lambda idx: sorted(idx, key=lambda a: mnid[a])      # noqa: E731
+    edges, inserted = [], set()
+    for k in by_id(loop_connections):
+        for c in by_id(loop_connections[k]):
+            if (mnid[k] != mnid[cur] or mnid[c] != mnid[loop]) and weight(k, c) < min_feat:
+                continue
+            if bad[k] or bad[c]:
+                continue
+            edges.append((vertex[k], vertex[c], 0))
+            inserted.add((min(mnid[k], mnid[c]), max(mnid[k], mnid[c])))
+    for k in range(K):
+        if bad[k]:
+            continue
+        par = parent[k]
+        if par >= 0 and not bad[par]:
+            edges.append((vertex[k], vertex[par], 1))
+        for l in by_id(loop_edges[k]):
+            if mnid[l] < mnid[k] and not bad[l]:
+                edges.append((vertex[k], vertex[l], 1))
+        for c in covisibles[k]:
+            if c != par and c not in children[k] and c not in loop_edges[k]:
+                if not bad[c] and mnid[c] < mnid[k]:
+                    if (min(mnid[k], mnid[c]), max(mnid[k], mnid[c])) in inserted:
+                        continue
+                    edges.append((vertex[k], vertex[c], 1))
+    return np.array(vertex, np.int32), (np.array(edges, EG_EDGE_DTYPE) if edges else np.zeros(0, EG_EDGE_DTYPE))
 
 
 class NewPointsKeyframe(C.Structure):

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "liborbx_hip.so")
 SOURCES = ["orbx_extract.hip", "orbx_pyramid.hip", "orbx_fast.hip", "orbx_octree.hip", "orbx_octree_wide.hip", "orbx_describe.hip",
-           "orbx_match.hip", "orbx_match_fast.hip", "orbx_bow.hip", "orbx_rgbd.hip", "orbx_rectify.hip", "orbx_cloud.hip", "orbx_octomap.hip", "orbx_kfdb.hip", "orbx_poseopt.hip", "orbx_initializer.hip", "orbx_sim3.hip", "orbx_pnp.hip", "orbx_sim3opt.hip", "orbx_newpoints.hip", "orbx_lba.hip"]
+           "orbx_match.hip", "orbx_match_fast.hip", "orbx_bow.hip", "orbx_rgbd.hip", "orbx_rectify.hip", "orbx_cloud.hip", "orbx_octomap.hip", "orbx_kfdb.hip", "orbx_poseopt.hip", "orbx_initializer.hip", "orbx_sim3.hip", "orbx_pnp.hip", "orbx_sim3opt.hip", "orbx_newpoints.hip", "orbx_lba.hip", "orbx_essential.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared",
          "-Wall", "-Wno-unused-value", "-Wno-unused-result"]
 

@@ -47,6 +47,7 @@ extern "C" int orbx_thread_release_scratch(void) {
     orbx_internal_release_sim3opt_scratch();
     orbx_internal_release_newpoints_scratch();
     orbx_internal_release_lba_scratch();
+    orbx_internal_release_essential_scratch();
     return ORBX_OK;
 }
 #ifdef ORBX_DEVELOPER

@@ -1,9 +1,11 @@
 // Optimizer.cc — see Optimizer.h.
 #include "Optimizer.h"
+#include <algorithm>
 #include <cstdlib>
 #include <list>
 #include <map>
 #include <mutex>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include "orbx.h"
@@ -293,6 +295,130 @@ void Optimizer::BundleAdjustment(const std::vector<KeyFrame *> &vpKFs, const std
         MapPoint *pMP = vpMP[i];
         pMP->SetWorldPos(point_mat(Pout.data() + (size_t)vnPoint[i] * 3));
         pMP->UpdateNormalAndDepth();
+    }
+}
+
+// ---- OptimizeEssentialGraph (src/Optimizer.cc:783-1049) ----------------------------------------------------------------------------
+static orbg_sim3_t flat_sim3(const g2o::Sim3 &S) {
+    orbg_sim3_t o;
+    o.q[0] = S.rotation().x(); o.q[1] = S.rotation().y(); o.q[2] = S.rotation().z(); o.q[3] = S.rotation().w();
+    for (int k = 0; k < 3; k++) o.t[k] = S.translation()[k];
+    o.s = S.scale();
+    return o;
+}
+static bool by_mnid(KeyFrame *a, KeyFrame *b) { return a->mnId < b->mnId; }
+static std::vector<KeyFrame *> sorted_by_mnid(const std::set<KeyFrame *> &s) {   // the reference walks such a set in pointer order
+    std::vector<KeyFrame *> v(s.begin(), s.end());
+    std::sort(v.begin(), v.end(), by_mnid);
+    return v;
+}
+
+void Optimizer::OptimizeEssentialGraph(Map *pMap, KeyFrame *pLoopKF, KeyFrame *pCurKF, const LoopClosing::KeyFrameAndPose &NonCorrectedSim3,
+                                       const LoopClosing::KeyFrameAndPose &CorrectedSim3,
+                                       const std::map<KeyFrame *, std::set<KeyFrame *> > &LoopConnections, const bool &bFixScale) {
+    const std::vector<KeyFrame *> vpKFs = pMap->GetAllKeyFrames();
+    const std::vector<MapPoint *> vpMPs = pMap->GetAllMapPoints();
+    const int minFeat = 100;
+    // Set KeyFrame vertices (:811-846): mnId -> dense vertex index, a bad keyframe has none
+    std::map<KeyFrame *, int> vertexOf;
+    std::map<unsigned long, int> vertexOfId;
+    std::vector<orbg_vertex_t> vertices;
+    for (size_t i = 0; i < vpKFs.size(); i++) {
+        KeyFrame *pKF = vpKFs[i];
+        if (pKF->isBad()) continue;
+        orbg_vertex_t v;
+        LoopClosing::KeyFrameAndPose::const_iterator it = CorrectedSim3.find(pKF);
+        if (it != CorrectedSim3.end()) v.Scw = flat_sim3(it->second);
+        else v.Scw = flat_sim3(g2o::Sim3(Converter::toMatrix3d(pKF->GetRotation()), Converter::toVector3d(pKF->GetTranslation()), 1.0));
+        LoopClosing::KeyFrameAndPose::const_iterator itn = NonCorrectedSim3.find(pKF);
+        v.has_nc = itn != NonCorrectedSim3.end() ? 1 : 0;
+        v.Snc = v.has_nc ? flat_sim3(itn->second) : v.Scw;
+        v.fixed = pKF == pLoopKF ? 1 : 0;
+        vertexOf[pKF] = (int)vertices.size();
+        vertexOfId[pKF->mnId] = (int)vertices.size();
+        vertices.push_back(v);
+    }
+    std::vector<orbg_edge_t> edges;
+    std::set<std::pair<long unsigned int, long unsigned int> > sInsertedEdges;
+    // Set Loop edges (:854-882), the map's keys and every set in ascending mnId
+    std::vector<KeyFrame *> keys;
+    for (std::map<KeyFrame *, std::set<KeyFrame *> >::const_iterator mit = LoopConnections.begin(); mit != LoopConnections.end(); mit++) keys.push_back(mit->first);
+    std::sort(keys.begin(), keys.end(), by_mnid);
+    for (size_t k = 0; k < keys.size(); k++) {
+        KeyFrame *pKF = keys[k];
+        const long unsigned int nIDi = pKF->mnId;
+        const std::vector<KeyFrame *> conn = sorted_by_mnid(LoopConnections.find(pKF)->second);
+        for (size_t c = 0; c < conn.size(); c++) {
+            const long unsigned int nIDj = conn[c]->mnId;
+            if ((nIDi != pCurKF->mnId || nIDj != pLoopKF->mnId) && pKF->GetWeight(conn[c]) < minFeat) continue;
+            if (!vertexOf.count(pKF) || !vertexOf.count(conn[c])) continue;   // a bad keyframe: the reference would hand g2o a null vertex
+            const orbg_edge_t e = {vertexOf[pKF], vertexOf[conn[c]], 0};
+            edges.push_back(e);
+            sInsertedEdges.insert(std::make_pair(std::min(nIDi, nIDj), std::max(nIDi, nIDj)));
+        }
+    }
+    // Set normal edges (:885-985)
+    for (size_t i = 0; i < vpKFs.size(); i++) {
+        KeyFrame *pKF = vpKFs[i];
+        if (!vertexOf.count(pKF)) continue;
+        const int vi = vertexOf[pKF];
+        KeyFrame *pParentKF = pKF->GetParent();
+        if (pParentKF && vertexOf.count(pParentKF)) {   // spanning tree edge
+            const orbg_edge_t e = {vi, vertexOf[pParentKF], 1};
+            edges.push_back(e);
+        }
+        const std::set<KeyFrame *> sLoopEdges = pKF->GetLoopEdges();
+        const std::vector<KeyFrame *> vLoop = sorted_by_mnid(sLoopEdges);
+        for (size_t l = 0; l < vLoop.size(); l++)
+            if (vLoop[l]->mnId < pKF->mnId && vertexOf.count(vLoop[l])) {
+                const orbg_edge_t e = {vi, vertexOf[vLoop[l]], 1};
+                edges.push_back(e);
+            }
+        const std::vector<KeyFrame *> vpConnectedKFs = pKF->GetCovisiblesByWeight(minFeat);
+        for (std::vector<KeyFrame *>::const_iterator vit = vpConnectedKFs.begin(); vit != vpConnectedKFs.end(); vit++) {
+            KeyFrame *pKFn = *vit;
+            if (pKFn && pKFn != pParentKF && !pKF->hasChild(pKFn) && !sLoopEdges.count(pKFn)) {
+                if (!pKFn->isBad() && pKFn->mnId < pKF->mnId) {
+                    if (sInsertedEdges.count(std::make_pair(std::min(pKF->mnId, pKFn->mnId), std::max(pKF->mnId, pKFn->mnId)))) continue;
+                    if (!vertexOf.count(pKFn)) continue;
+                    const orbg_edge_t e = {vi, vertexOf[pKFn], 1};
+                    edges.push_back(e);
+                }
+            }
+        }
+    }
+    // the points of :1018-1048; one whose reference keyframe has no vertex is left as it is (the reference reads a default Sim3 there)
+    std::vector<orbg_point_t> points;
+    std::vector<MapPoint *> moved;
+    for (size_t i = 0; i < vpMPs.size(); i++) {
+        MapPoint *pMP = vpMPs[i];
+        if (pMP->isBad()) continue;
+        unsigned long nIDr;
+        if (pMP->mnCorrectedByKF == pCurKF->mnId) nIDr = pMP->mnCorrectedReference;
+        else {
+            KeyFrame *pRefKF = pMP->GetReferenceKeyFrame();
+            if (!pRefKF) continue;
+            nIDr = pRefKF->mnId;
+        }
+        if (!vertexOfId.count(nIDr)) continue;
+        const cv::Mat P3Dw = pMP->GetWorldPos();
+        const orbg_point_t p = {P3Dw.at<float>(0), P3Dw.at<float>(1), P3Dw.at<float>(2), vertexOfId[nIDr]};
+        points.push_back(p);
+        moved.push_back(pMP);
+    }
+    const int N = (int)vertices.size(), E = (int)edges.size(), P = (int)points.size();
+    std::vector<float> Tout((size_t)N * 16 + 1), Pout((size_t)P * 3 + 1);
+    const int rc = orbg_optimize_essential_graph(vertices.data(), N, edges.data(), E, points.data(), P, bFixScale ? 1 : 0, 20, Tout.data(), Pout.data(),
+                                                 NULL, NULL, device);
+    if (rc != ORBX_OK) throw std::runtime_error(std::string("Optimizer::OptimizeEssentialGraph: ") + orbx_last_error());
+    std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);
+    // SE3 pose recovering (:994-1015), a bad keyframe skipped (the reference dereferences its missing vertex); UpdateKeyFrame of the
+    // multi-agent server is the caller's
+    for (size_t i = 0; i < vpKFs.size(); i++)
+        if (vertexOf.count(vpKFs[i])) vpKFs[i]->SetPose(pose_mat(Tout.data() + (size_t)vertexOf[vpKFs[i]] * 16));
+    for (size_t i = 0; i < moved.size(); i++) {
+        moved[i]->SetWorldPos(point_mat(Pout.data() + i * 3));
+        moved[i]->UpdateNormalAndDepth();
     }
 }
 

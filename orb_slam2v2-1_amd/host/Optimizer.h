@@ -5,8 +5,12 @@
 // orbb_local_bundle_adjustment), the mapping thread's bundle adjustment (src/LocalMapping.cc:89), and BundleAdjustment /
 // GlobalBundleAdjustemnt (:41-237, orbb_bundle_adjustment) for the map CreateInitialMapMonocular builds (src/Tracking.cc:700).  The
 // first two have ONE free vertex; the bundle adjustments marginalise the points, and the reduced system of a local window - a few tens
-// of keyframes - is dense and small.  OptimizeEssentialGraph and a bundle adjustment of a loop-closure-sized map are sparse problems of
-// another shape and are not part of this library: keep the reference's own (g2o) for them.
+// of keyframes - is dense and small.  OptimizeEssentialGraph (:783-1049, orbg_optimize_essential_graph), the pose graph
+// LoopClosing::CorrectLoop optimises (src/LoopClosing.cc:576), is here too: an earlier version of this comment filed it under "sparse,
+// not part of this library", which was a statement about storage, not about the arithmetic - the block pattern is fixed, the host
+// does the symbolic factorisation once per call and the device the 7x7 block arithmetic.  A bundle adjustment of a
+// loop-closure-sized map (the loop closer's global one) is the one member that is not part of this library: keep the reference's
+// own (g2o) for it.
 #ifndef ORBX_OPTIMIZER_H
 #define ORBX_OPTIMIZER_H
 #include "frame_shim.h"
@@ -43,6 +47,18 @@ public:
                                  bool *pbStopFlag = NULL, const unsigned long nLoopKF = 0, const bool bRobust = true);
     void static GlobalBundleAdjustemnt(Map *pMap, int nIterations = 5, bool *pbStopFlag = NULL, const unsigned long nLoopKF = 0,
                                        const bool bRobust = true);
+    // The reference's signature (:783-1049).  One vertex per keyframe of the map that is not bad (CorrectedSim3's entry or Sim3(Rcw, tcw,
+    // 1) of its pose; NonCorrectedSim3's entry beside it; pLoopKF fixed), the four edge groups of :849-985 with every rule (minFeat =
+    // 100, sInsertedEdges, the mnId comparisons, hasChild, sLoopEdges.count), one point per map point that is not bad (its vertex from
+    // mnCorrectedReference or the reference keyframe), the flat call with 20 iterations, then under pMap->mMutexMapUpdate SetPose,
+    // SetWorldPos and UpdateNormalAndDepth.  Differences, all stated: LoopConnections and every std::set of keyframes are walked in
+    // ascending mnId (the reference walks them in pointer order, which only orders g2o's sums); a bad keyframe gets no vertex, no edge
+    // and no write-back (the reference's write-back loop dereferences its missing vertex); a point whose reference keyframe has no
+    // vertex is left alone; pMap->UpdateKeyFrame (the multi-agent server) stays the caller's.  Throws std::runtime_error with
+    // orbx_last_error() when the library reports an error (no GPU among them).
+    void static OptimizeEssentialGraph(Map *pMap, KeyFrame *pLoopKF, KeyFrame *pCurKF, const LoopClosing::KeyFrameAndPose &NonCorrectedSim3,
+                                       const LoopClosing::KeyFrameAndPose &CorrectedSim3,
+                                       const std::map<KeyFrame *, std::set<KeyFrame *> > &LoopConnections, const bool &bFixScale);
     static int device;   // GPU used (default: ORBX_DEVICE or 0)
 };
 

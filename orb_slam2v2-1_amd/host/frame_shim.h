@@ -34,6 +34,7 @@ public:
     void AddMapPoint(MapPoint *pMP) { mvpMapPoints.push_back(pMP); }   // src/Map.cc:42-46 (a set there; insertion order is kept here for the tests)
     std::vector<MapPoint *> GetAllMapPoints() { return mvpMapPoints; }
     std::vector<MapPoint *> mvpMapPoints;
+    inline long unsigned int GetMaxKFid();   // src/Map.cc:106-110 (kept as a member there; the largest mnId in the map here)
 };
 
 class MapPoint {
@@ -69,6 +70,8 @@ public:
     inline void SetBadFlag();                                                             // src/MapPoint.cc:161-180, without the Map erase
     void SetWorldPos(const cv::Mat &Pos) { mWorldPos = Pos.clone(); }                     // src/MapPoint.cc:83-88
     long unsigned int mnId = 0, mnBALocalForKF = 0;   // include/MapPoint.h: read and written by Optimizer::LocalBundleAdjustment
+    long unsigned int mnCorrectedByKF = 0, mnCorrectedReference = 0;   // include/MapPoint.h: set by LoopClosing::CorrectLoop, read by Optimizer::OptimizeEssentialGraph
+    KeyFrame *GetReferenceKeyFrame() { return mpRefKF; }   // src/MapPoint.cc:96-100
     inline void Replace(MapPoint *pMP);                                                   // src/MapPoint.cc:187-225
     std::map<KeyFrame *, size_t> GetObservations() { return mObservations; }
     void SetDescriptor(const cv::Mat &d) { mDescriptor = d.clone(); }   // the store at src/MapPoint.cc:313-316 (test shim only)
@@ -157,6 +160,23 @@ public:
         if (idx >= 0) mvpMapPoints[idx] = static_cast<MapPoint *>(NULL);
     }
     long unsigned int mnBALocalForKF = 0, mnBAFixedForKF = 0;   // include/KeyFrame.h: the marks of Optimizer::LocalBundleAdjustment
+    // the spanning tree, the loop edges and the covisibility weights, as far as Optimizer::OptimizeEssentialGraph reads them
+    // (src/KeyFrame.cc:137-146, :326-359, :404-448)
+    KeyFrame *mpParent = NULL;
+    std::set<KeyFrame *> mspChildrens, mspLoopEdges;
+    std::map<KeyFrame *, int> mConnectedKeyFrameWeights;
+    KeyFrame *GetParent() { return mpParent; }
+    bool hasChild(KeyFrame *pKF) { return mspChildrens.count(pKF) != 0; }
+    std::set<KeyFrame *> GetLoopEdges() { return mspLoopEdges; }
+    int GetWeight(KeyFrame *pKF) { return mConnectedKeyFrameWeights.count(pKF) ? mConnectedKeyFrameWeights[pKF] : 0; }
+    std::vector<KeyFrame *> GetCovisiblesByWeight(const int &w) {   // the head of the ordered list whose weight is at least w
+        std::vector<KeyFrame *> v;
+        for (size_t i = 0; i < mvpOrderedConnectedKeyFrames.size(); i++) {
+            if (GetWeight(mvpOrderedConnectedKeyFrames[i]) < w) break;
+            v.push_back(mvpOrderedConnectedKeyFrames[i]);
+        }
+        return v;
+    }
     std::vector<KeyFrame *> GetVectorCovisibleKeyFrames() { return mvpOrderedConnectedKeyFrames; }   // src/KeyFrame.cc:310-314
     cv::Mat GetPose() { return Tcw.clone(); }
     cv::Mat GetRotation() {
@@ -218,6 +238,11 @@ public:
     cv::Mat Tcw = cv::Mat::eye(4, 4, CV_32F), Ow = cv::Mat::zeros(3, 1, CV_32F);
 };
 
+inline long unsigned int Map::GetMaxKFid() {
+    long unsigned int m = 0;
+    for (size_t i = 0; i < mvpKeyFrames.size(); i++) m = std::max(m, mvpKeyFrames[i]->mnId);
+    return m;
+}
 inline int MapPoint::PredictScale(const float &currentDist, KeyFrame *pKF) {
     using namespace std;
     float ratio = mfMaxDistance / currentDist;

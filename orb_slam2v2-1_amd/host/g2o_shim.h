@@ -8,8 +8,11 @@
 #pragma once
 #ifdef ORBX_HAVE_ORBSLAM2
 #include "Converter.h"
+#include "LoopClosing.h"
 #else
 #include <cmath>
+#include <functional>
+#include <map>
 #include "cv_shim.h"
 
 namespace Eigen {
@@ -123,6 +126,11 @@ protected:
 }  // namespace g2o
 
 namespace ORB_SLAM2 {
+class KeyFrame;
+class LoopClosing {   // include/LoopClosing.h:50-51: the one name Optimizer::OptimizeEssentialGraph's signature needs (without Eigen's allocator)
+public:
+    typedef std::map<KeyFrame *, g2o::Sim3, std::less<KeyFrame *> > KeyFrameAndPose;
+};
 class Converter {   // src/Converter.cc:105-151
 public:
     static Eigen::Matrix3d toMatrix3d(const cv::Mat &cvMat3) {
