@@ -107,6 +107,8 @@ int orbx_debug_last_plan(const orbx_extractor_t *h, int32_t *out, int n_out);
 int orbx_debug_size_plan(int nfeatures, float scale_factor, int nlevels, int w, int h, int pyr_tile, float *tables, int32_t *nfeat_umax,
                          uint8_t *geom, int geom_bytes, int32_t *tab, int tab_cap, int64_t *scalars, int n_scalars);
 
+/* The records k_pyr_level's waves read (csrc/orbx_size_plan.h: plan_pyr_records) have a hook of their own, declared in orbx_dev_pyr.h. */
+
 /* The per-thread scratch of the matchers as the CALLING host thread holds it, read only: no HIP call,
  * nothing allocated, works without a GPU and on a thread that never called a matcher (capacities 0, devices -1).
  *   out (ORBM_DEBUG_THREAD_SCRATCH_INTS): arena capacity in bytes, arena device (-1: none), arena call counter, 1 / 0 the arena has a

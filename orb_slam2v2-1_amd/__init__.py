@@ -151,6 +151,8 @@ DEV_EXPORTS = ["orbx_debug_level_points", "orbx_debug_sincosf", "orbx_debug_blur
                "orbm_debug_stereo_path", "orbx_debug_plan_chunk", "orbx_debug_last_plan", "orbm_debug_thread_scratch",
                "orbx_debug_size_plan", "orbx_debug_set_alloc_fill", "orbx_debug_alloc_fill_stats", "orbx_debug_stall_stream",
                "orbx_debug_streams"]
+# what include/orbx_dev_pyr.h declares: the developer build's hook for k_pyr_level's records (debug_pyr_records)
+DEV_PYR_EXPORTS = ["orbx_debug_pyr_records"]
 # include/orbx_dev.h: the int64 record of orbx_debug_size_plan, field order
 SIZE_PLAN_FIELDS = ["max_kp", "totalCells", "maxNodeCap", "lvlKpCap", "pyrImgBytes", "slotsPerImg", "keysPerImg", "fastTileStride", "fastScoreStride",
                     "fastTileRows", "fastLdsPerWave", "totalStrips", "stripLevels", "octLdsBytes", "octPyrLdsBytes", "octPyrWords", "octBigMask",
@@ -477,6 +479,7 @@ def _load(path, dev):
         L.orbx_debug_last_plan.argtypes = [vp, vp, i32]
         L.orbm_debug_thread_scratch.argtypes = [vp, i32]
         L.orbx_debug_size_plan.argtypes = [i32, f32, i32, i32, i32, i32, vp, vp, vp, i32, vp, i32, vp, i32]
+        L.orbx_debug_pyr_records.argtypes = [vp, i32, f32, i32, i32, i32, vp, i32, vp, i32, vp, i32]
         L.orbx_debug_set_alloc_fill.argtypes = [i32, C.c_uint32]
         L.orbx_debug_alloc_fill_stats.argtypes = [vp]
         L.orbx_debug_stall_stream.argtypes = [vp, i32, i32]
@@ -947,6 +950,28 @@ def debug_size_plan(nfeatures, scale_factor, nlevels, w, h, tile=0):
         n = len(SIZE_PLAN_FIELDS)
         d.update({k: int(v) for k, v in zip(SIZE_PLAN_FIELDS, sc)}, geom=geom, tab=tab, stripBase=sc[n:n + 17].astype(np.int32),
                  chains=sc[n + 17:].astype(np.int32).reshape(2, 8, 8))
+    return d
+
+
+def debug_pyr_records(nfeatures=0, scale_factor=0.0, nlevels=0, w=0, h=0, extractor=None):
+    """Test hook: k_pyr_level's column and band records (csrc/orbx_size_plan.h: plan_pyr_records).  Without `extractor` what the image size
+    decides, no HIP call (works without a GPU); with a developer-build ORBextractor the records of its planned size read back from its device
+    buffers.  -> dict: status, message and, for an accepted size, cols (uint32 [n, 4]: A, oa | ob << 8 | valid << 16, aa, ab), bands (uint32
+    words), nxc[16], colOff[16], nbands[2][16], bandOff[2][16] ([0] the 8-row form, [1] the 16-row form; word offsets, -1 = not built)."""
+    L = extractor._L if extractor is not None else lib(True)
+    hh = extractor._h if extractor is not None else None
+    idx = np.zeros(2 + 6 * 16, np.int32)
+    cols, bands = np.zeros(0, np.uint32), np.zeros(0, np.uint32)
+    for _ in range(2):   # the second call with room for the words the first one counted
+        rc = L.orbx_debug_pyr_records(hh, int(nfeatures), float(scale_factor), int(nlevels), int(w), int(h), _p(cols), len(cols), _p(bands), len(bands),
+                                      _p(idx), len(idx))
+        if rc != ORBX_OK or (len(cols) == idx[0] and len(bands) == idx[1]):
+            break
+        cols, bands = np.zeros(int(idx[0]), np.uint32), np.zeros(int(idx[1]), np.uint32)
+    d = dict(status=rc, message=L.orbx_last_error().decode() if rc else "")
+    if rc == ORBX_OK:
+        d.update(cols=cols.reshape(-1, 4), bands=bands, nxc=idx[2:18].copy(), colOff=idx[18:34].copy(), nbands=idx[34:66].reshape(2, 16).copy(),
+                 bandOff=idx[66:98].reshape(2, 16).copy())
     return d
 
 

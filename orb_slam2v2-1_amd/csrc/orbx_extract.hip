@@ -11,6 +11,7 @@
 #include "orbx_extract_dev.h"
 #ifdef ORBX_DEVELOPER
 #include "orbx_dev.h"
+#include "orbx_dev_pyr.h"
 #endif
 #include <math.h>
 #include <float.h>
@@ -219,6 +220,8 @@ static std::vector<PlanBuffer> plan_buffers(orbx_extractor *h, const SizePlan &s
         {(void **)&h->d_octLeaf, sizeof(uint32_t) * slots * (size_t)sp.octPyrWords, false},
         {(void **)&h->d_octBest, sizeof(uint32_t) * slots * (size_t)sp.maxNodeCap, false},
         {(void **)&h->d_octState, sizeof(int32_t) * slots * 4, true},
+        {(void **)&h->d_pyrCols, sizeof(PyrColRec) * std::max<size_t>(h->pr.cols.size(), 1), false},
+        {(void **)&h->d_pyrBands, sizeof(uint32_t) * std::max<size_t>(h->pr.bands.size(), 1), false},
     };
     if (sp.octSliceStride > 0) {   // shared sweeps of large levels in a batch (OctSrc::nslice): best-key partials beside the count partials of d_octPart, arrival counters
         v.push_back({(void **)&h->d_octPartBest, sizeof(uint32_t) * slots * OCT_MAX_SLICES * (size_t)sp.octSliceStride, false});
@@ -235,6 +238,7 @@ static void free_plan(orbx_extractor *h) {
     hipFree(h->d_pyrNext); h->d_pyrNext = nullptr; h->pyrNextBytes = 0;
     hipFree(h->d_blur); hipFree(h->d_blurAlt); h->d_blur = h->d_blurAlt = nullptr; h->blurBytes = h->blurAltBytes = 0; h->blurMaskLast = h->blurMaskAlt = 0;
     h->sp = SizePlan();
+    h->pr = PyrRecords();
     h->pw = h->ph = h->pB = 0;
 }
 
@@ -295,18 +299,23 @@ static int ensure_plan(orbx_extractor *h, int w, int hgt, int B) {
     const SizeInput in = {w, hgt, h->nlevels, h->scale_factor, h->tb, h->opt[3]};
     const int rc = plan_size(in, &sp);
     if (rc) return rc;
+    PyrRecords pr;
+    plan_pyr_records(in, sp, &pr);
     ORBX_HIP(hipSetDevice(h->device));
     if (h->last_valid) ORBX_HIP(hipStreamSynchronize(h->last_stream));
     for (int i = 0; i < ORBX_SIDE_STREAMS; i++) ORBX_HIP(hipStreamSynchronize(h->side[i]));
     if (h->pw == w && h->ph == hgt) B = std::max(B, h->pB);   // (an unchanged size keeps the larger capacity)
     free_plan(h);
     h->sp = std::move(sp);
+    h->pr = std::move(pr);
     for (const PlanBuffer &b : plan_buffers(h, h->sp, B)) {
         ORBX_HIP(scratch_malloc(b.ptr, b.bytes));
         if (b.zero) ORBX_HIP(hipMemset(*b.ptr, 0, b.bytes));
     }
     ORBX_HIP(hipMemcpy(h->d_geom, h->sp.geom, sizeof(LevelGeom) * ORBX_MAX_LEVELS, hipMemcpyHostToDevice));
     if (!h->sp.tab.empty()) ORBX_HIP(hipMemcpy(h->d_tab, h->sp.tab.data(), sizeof(int32_t) * h->sp.tab.size(), hipMemcpyHostToDevice));
+    if (!h->pr.cols.empty()) ORBX_HIP(hipMemcpy(h->d_pyrCols, h->pr.cols.data(), sizeof(PyrColRec) * h->pr.cols.size(), hipMemcpyHostToDevice));
+    if (!h->pr.bands.empty()) ORBX_HIP(hipMemcpy(h->d_pyrBands, h->pr.bands.data(), sizeof(uint32_t) * h->pr.bands.size(), hipMemcpyHostToDevice));
     h->pw = w; h->ph = hgt; h->pB = B;
     return ORBX_OK;
 }
@@ -448,10 +457,17 @@ static void launch_pyramid(orbx_extractor *h, const uint8_t *d_imgs, uint8_t *py
         // 16 output rows per wave while that still leaves every SIMD several waves (8192 = 8 per SIMD), else 8; same pixels either way
         const int nxc = (h->sp.geom[l].w + 1 + 127) / 128, nb16 = (h->sp.geom[l].h + 15) / 16, nb8 = (h->sp.geom[l].h + 7) / 8;
         const bool tall = h->scale_factor <= 1.25f && (h->opt[22] == 0 ? (size_t)nxc * nb16 * B >= 8192 : h->opt[22] == 2);   // (beyond 1.25 the 16-row form cannot cover a band from 22 source rows)
+        // the wave's set-up comes from the records of the planned size (plan_pyr_records): the level's column records, the form's band
+        // records, and the reciprocals with which the kernel divides by the chunk count and by the grid width on the scalar unit
+        const PyrColRec *cols = h->d_pyrCols + h->pr.colOff[l];
+        const int f = tall ? 1 : 0, nb = tall ? nb16 : nb8, gx = (nxc * nb + 3) / 4;
+        const uint32_t *bands = h->d_pyrBands + h->pr.bandOff[f][l];
         if (tall)
-            hipLaunchKernelGGL((k_pyr_level<16, 22>), dim3((nxc * nb16 + 3) / 4, B), dim3(256), 0, st, pyr, h->sp.pyrImgBytes, h->d_geom, l, h->d_tab, nxc, nb16);
+            hipLaunchKernelGGL((k_pyr_level<16, 22>), dim3(gx, B), dim3(256), 0, st, pyr, h->sp.pyrImgBytes, h->d_geom, l, h->d_tab, nxc, nb, cols, bands,
+                               pyr_rcp((uint32_t)nxc), pyr_rcp((uint32_t)gx));
         else
-            hipLaunchKernelGGL((k_pyr_level<8, 12>), dim3((nxc * nb8 + 3) / 4, B), dim3(256), 0, st, pyr, h->sp.pyrImgBytes, h->d_geom, l, h->d_tab, nxc, nb8);
+            hipLaunchKernelGGL((k_pyr_level<8, 12>), dim3(gx, B), dim3(256), 0, st, pyr, h->sp.pyrImgBytes, h->d_geom, l, h->d_tab, nxc, nb, cols, bands,
+                               pyr_rcp((uint32_t)nxc), pyr_rcp((uint32_t)gx));
     }
     if (lastSingle < nl - 1)
         hipLaunchKernelGGL(k_pyramid_fused, dim3(h->sp.pyrTilesX * h->sp.pyrTilesY, B), dim3(256), h->sp.pyrLdsBytes, st, d_imgs,
@@ -1365,6 +1381,7 @@ extern "C" int orbx_fast_kernels(const orbx_extractor_t *h, int B, int *strips, 
 #ifdef ORBX_DEVELOPER
 // The launch rule by itself (no HIP call, no handle): PlanInput in, ChunkPlan out, both as flat int32 arrays (include/orbx_dev.h).
 static_assert(ORBX_DEBUG_SIZE_PLAN_INTS == 31 + ORBX_MAX_LEVELS + 1 + 2 * 8 * (int)(sizeof(ChainPlan) / sizeof(int)), "include/orbx_dev.h and orbx_size_plan.h disagree");
+static_assert(ORBX_DEBUG_PYR_RECORDS_INTS == 2 + 6 * ORBX_MAX_LEVELS && sizeof(PyrColRec) == 16, "include/orbx_dev_pyr.h and orbx_size_plan.h disagree");
 static_assert(ORBX_DEBUG_PLAN_INPUT_INTS == ORBX_PLAN_INPUT_INTS && ORBX_DEBUG_CHUNK_PLAN_INTS == ORBX_CHUNK_PLAN_INTS, "include/orbx_dev.h and orbx_plan.h disagree");
 extern "C" int orbx_debug_plan_chunk(const int32_t *in, int n_in, int32_t *out, int n_out) {
     PlanInput pi;
@@ -1402,6 +1419,48 @@ extern "C" int orbx_debug_size_plan(int nfeatures, float scale_factor, int nleve
     int64_t *o = std::copy(v, v + 31, scalars);
     o = std::copy(sp.stripBase, sp.stripBase + ORBX_MAX_LEVELS + 1, o);
     std::copy((const int *)sp.chains, (const int *)sp.chains + 2 * 8 * 8, o);
+    return ORBX_OK;
+}
+// k_pyr_level's records (include/orbx_dev_pyr.h): h == NULL what plan_pyr_records builds for the size, by itself; h != NULL what the handle's
+// device buffers hold for its planned size
+extern "C" int orbx_debug_pyr_records(orbx_extractor_t *h, int nfeatures, float scale_factor, int nlevels, int w, int hgt, uint32_t *cols, int cols_cap,
+                                      uint32_t *bands, int bands_cap, int32_t *index, int n_index) {
+    if (!index || n_index != ORBX_DEBUG_PYR_RECORDS_INTS || cols_cap < 0 || bands_cap < 0 || (cols_cap > 0 && !cols) || (bands_cap > 0 && !bands)) {
+        orbx_set_error("orbx_debug_pyr_records: bad arguments");
+        return ORBX_ERR_ARG;
+    }
+    PyrRecords built;
+    const PyrRecords *pr = &built;
+    if (h) {
+        if (h->pw == 0) { orbx_set_error("orbx_debug_pyr_records: the handle has no plan yet"); return ORBX_ERR_ARG; }
+        pr = &h->pr;
+    } else {
+        if (nfeatures < 1 || nlevels < 1 || nlevels > ORBX_MAX_LEVELS || !(scale_factor > 1.0f)) { orbx_set_error("orbx_debug_pyr_records: bad arguments"); return ORBX_ERR_ARG; }
+        SizeInput in = {};
+        in.w = w; in.h = hgt; in.nlevels = nlevels; in.scale_factor = scale_factor;
+        extractor_tables(nfeatures, in.scale_factor, nlevels, &in.tb);
+        SizePlan sp;
+        const int rc = plan_size(in, &sp);
+        if (rc) return rc;
+        plan_pyr_records(in, sp, &built);
+    }
+    const size_t colWords = pr->cols.size() * 4, bandWords = pr->bands.size();
+    const size_t nc = std::min((size_t)cols_cap, colWords), nb = std::min((size_t)bands_cap, bandWords);
+    if (h) {
+        ORBX_HIP(hipSetDevice(h->device));
+        if (h->last_valid) ORBX_HIP(hipStreamSynchronize(h->last_stream));
+        if (nc) ORBX_HIP(hipMemcpy(cols, h->d_pyrCols, sizeof(uint32_t) * nc, hipMemcpyDeviceToHost));
+        if (nb) ORBX_HIP(hipMemcpy(bands, h->d_pyrBands, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost));
+    } else {
+        if (nc) memcpy(cols, pr->cols.data(), sizeof(uint32_t) * nc);
+        if (nb) memcpy(bands, pr->bands.data(), sizeof(uint32_t) * nb);
+    }
+    int32_t *o = index;
+    *o++ = (int32_t)colWords; *o++ = (int32_t)bandWords;
+    o = std::copy(pr->nxc, pr->nxc + ORBX_MAX_LEVELS, o);
+    o = std::copy(pr->colOff, pr->colOff + ORBX_MAX_LEVELS, o);
+    o = std::copy(pr->nbands[0], pr->nbands[0] + 2 * ORBX_MAX_LEVELS, o);
+    std::copy(pr->bandOff[0], pr->bandOff[0] + 2 * ORBX_MAX_LEVELS, o);
     return ORBX_OK;
 }
 // the plan chunk 0 of the handle's last extraction call executed

@@ -99,7 +99,7 @@ __global__ void k_pyramid_fused(const uint8_t *src, int sstride, size_t simg, ui
                                 int maxPar, int l0);                                                             // orbx_pyramid.hip
 template <int RW, int SR>
 __global__ void k_pyr_level(uint8_t *pyr, size_t pyrImgBytes, const LevelGeom *geom, int l, const int32_t *tab, int nxc,
-                            int nbands);                                                                         // orbx_pyramid.hip
+                            int nbands, const PyrColRec *cols, const uint32_t *bands, uint32_t rcpNxc, uint32_t rcpNbx);   // orbx_pyramid.hip
 template <bool FULL>
 __global__ void k_pyr_pad(const uint8_t *img, int sstride, size_t simg, uint8_t *pyr, size_t pyrImgBytes, const LevelGeom *geom,
                           int l0);                                                                               // orbx_pyramid.hip

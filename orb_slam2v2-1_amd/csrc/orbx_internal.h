@@ -66,6 +66,8 @@ struct orbx_extractor {
     // device buffers
     LevelGeom *d_geom;
     int32_t *d_tab;
+    PyrRecords pr;       // k_pyr_level's column and band records of the planned size (plan_pyr_records), uploaded with geom and tab
+    PyrColRec *d_pyrCols; uint32_t *d_pyrBands;
     uint8_t *d_pyr;
     uint32_t *d_cellCnt, *d_cellRaw, *d_slots, *d_cand, *d_lvlKp;
     uint16_t *d_nodeOf;

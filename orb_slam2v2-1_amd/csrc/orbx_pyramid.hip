@@ -138,7 +138,9 @@ __global__ __launch_bounds__(256) void k_pyramid_fused(
 //  * k_pyr_level: a wave owns 128 output columns x RW (8 or 16) output rows; a lane owns TWO fixed
 //    columns (2j-1, 2j: the pair is 2-byte aligned in the padded row), so everything that depends
 //    on the column — source offset, v_perm selector that lifts the two source bytes into a u16
-//    pair, the packed (a0,a1) — is set up once.  Per source row and lane: ONE aligned 8-byte load,
+//    pair, the packed (a0,a1) — comes from the lane's column record and what depends on the band
+//    of rows from the wave's band record, both built once per image size (plan_pyr_records,
+//    orbx_size_plan.h): a wave derives nothing from the resize tables.  Per source row and lane: ONE aligned 8-byte load,
 //    two v_perm + two v_dot2_u32_u16 (the horizontal pass of both columns); consecutive output
 //    rows share a source row (sy advances by 1 or 2), which is kept in registers, so a row costs
 //    ~1.2 loads.  Vertical pass and rounding exactly as cv::resize's VResizeLinear (8UC1, <= 3.3).
@@ -155,82 +157,91 @@ __global__ __launch_bounds__(256) void k_pyramid_fused(
 // (b << 12) * ((S >> 4) << 4) is (b * (S >> 4)) >> 16 exactly.  v_mul_hi_u32_u24 is a full-rate instruction; the multiply + shift it
 // replaces were two.
 __device__ __forceinline__ uint32_t vmulhi24(uint32_t a, uint32_t b) { return __umulhi(a & 0xFFFFFFu, b & 0xFFFFFFu); }   // (the masks are known no-ops: they let the compiler pick the 24-bit form)
+// floor(n / d) of wave-uniform operands on the scalar unit: m = pyr_rcp(d) from the host (orbx_size_plan.h) is at most 2^32 / d and
+// more than 2^32 / d - 2, so the high half of n * m is the quotient or one below it for every 32-bit n; one compare puts it right.
+// (A plain `/` of uniform values runs on the vector ALU - v_rcp_iflag_f32 and four v_mul_hi_u32 - with a readfirstlane behind it.)
+__device__ __forceinline__ uint32_t udiv_rcp(uint32_t n, uint32_t d, uint32_t m) {
+    const uint32_t q = __umulhi(n, m);
+    return n - q * d >= d ? q + 1 : q;
+}
 template <int RW, int SR>
 __global__ __launch_bounds__(256) void k_pyr_level(uint8_t *__restrict__ pyr, size_t pyrImgBytes,
                                                    const LevelGeom *__restrict__ geom, int l,
-                                                   const int32_t *__restrict__ tab, int nxc, int nbands) {
-    static_assert((RW == 8 || RW == 16) && SR <= 32, "row table: one lane per output row, a 32-bit mask of source rows");
-    constexpr int RWM = RW - 1;
-    int bx, b;
-    xcd_block_map(bx, b);
-    const int wave = __builtin_amdgcn_readfirstlane(bx * 4 + (threadIdx.x >> 6)), lane = threadIdx.x & 63;
+                                                   const int32_t *__restrict__ tab, int nxc, int nbands,
+                                                   const PyrColRec *__restrict__ cols, const uint32_t *__restrict__ bands,
+                                                   uint32_t rcpNxc, uint32_t rcpNbx) {
+    static_assert((RW == 8 || RW == 16) && SR <= 32, "a 32-bit mask of source rows");
+    constexpr int BW = PYR_BAND_HEAD + SR;   // words of a band record (pyr_band_words)
+    // xcd_block_map (orbx_internal.h) with the division by the grid width done by udiv_rcp: everything here is blockIdx / argument
+    // arithmetic, so image, band and chunk never leave the scalar unit
+    const uint32_t nbx = gridDim.x, total = nbx * gridDim.y, lin = blockIdx.y * nbx + blockIdx.x;
+    const uint32_t xcd = lin & 7u, pos = xcd * (total >> 3) + min(xcd, total & 7u) + (lin >> 3);
+    const uint32_t b = udiv_rcp(pos, nbx, rcpNbx), bx = pos - b * nbx;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(bx * 4 + (threadIdx.x >> 6))), lane = threadIdx.x & 63;
     if (wave >= nxc * nbands) return;
-    const int band = wave / nxc, xc = wave - band * nxc;
+    const int band = (int)udiv_rcp((uint32_t)wave, (uint32_t)nxc, rcpNxc), xc = wave - band * nxc;
+    // the lane's column record (one 16-byte load) and the wave's band record (lane i loads word i: the table is padded by a wave's worth
+    // of words, so no clamp), both through a scalar base and the lane's 32-bit offset, both built once per image size by
+    // plan_pyr_records (orbx_size_plan.h).  A word of the band record reaches the scalar unit by v_readlane with a FIXED lane.
+    // (Read with scalar loads the record costs no vector instruction at all, but 30 more scalar registers per wave: alone on the GPU
+    // that form is as fast, beside k_describe its level-1 launch took 94 us against 32 and the step 0.563 ms against 0.537.)
+    const uint4 cr = ((const uint4 *)(cols + xc * 64))[lane];
+    const uint32_t vrec = (bands + (uint32_t)band * (uint32_t)BW)[lane];
+#define PYR_REC(i) ((uint32_t)__builtin_amdgcn_readlane((int)vrec, (i)))
+    const int nrow = (int)PYR_REC(PYR_BAND_NROW);
+    const uint32_t mask = PYR_REC(PYR_BAND_MASK), regular = PYR_REC(PYR_BAND_REGULAR);
+    const int lastk = (int)PYR_REC(PYR_BAND_LASTK);   // source rows past the last output row's second one are neither fetched nor filtered
     const LevelGeom G = geom[l];
-    const int sw = geom[l - 1].w, sh = geom[l - 1].h, sps = geom[l - 1].pstride;
+    const int sh = geom[l - 1].h, sps = geom[l - 1].pstride;
     uint8_t *base = pyr + (size_t)b * pyrImgBytes;
     const uint8_t *srow0 = base + geom[l - 1].poff + (size_t)ORBX_EDGE * sps;   // padded row of source row 0
     uint8_t *drow0 = base + G.poff + (size_t)ORBX_EDGE * G.pstride + ORBX_EDGE;
-    const int x0 = xc * 128 + 2 * lane - 1, x1 = x0 + 1;
+    const int x0 = xc * 128 + 2 * lane - 1;
     // The pair store is 2-byte aligned (ORBX_EDGE + x0 is even).  Columns -1 and w fall on frame bytes
     // next to the inner row, which k_pyr_pad rewrites afterwards; lanes further right store nothing.
-    const bool vst = x0 < G.w;
-    const int xa = min(max(x0, 0), G.w - 1), xb = min(x1, G.w - 1);
-    const int ca = ORBX_EDGE + tab[G.xofsOff + xa], cb = ORBX_EDGE + tab[G.xofsOff + xb];   // byte column in the padded source row
-    const uint32_t aa = (uint32_t)tab[G.xalphaOff + xa], ab = (uint32_t)tab[G.xalphaOff + xb];
-    const int A = ca & ~3;                         // cb - ca <= 2: both byte pairs lie inside [A, A+8)
-    const uint32_t oa = (uint32_t)(ca - A), ob = (uint32_t)(cb - A);
-    const uint32_t selA = oa | ((oa + 1) << 16) | 0x0C000C00u, selB = ob | ((ob + 1) << 16) | 0x0C000C00u;
-    (void)sw;
-    const int y0 = band * RW, nrow = min(RW, G.h - y0);
-    // fast path: the band's source rows rf .. rf+SR-1 are fetched up front (one memory latency per
-    // wave), then consumed in order.  Lane i < RW holds the row table of output row y0+i; bit k of
-    // `mask` says "the output row whose second source row is rf+k is due after source row k".
-    const int yl = min(y0 + (lane & RWM), G.h - 1);
-    const int vsy = tab[G.yofsOff + yl];
-    const uint32_t vbt = (uint32_t)tab[G.ybetaOff + yl];
-    const int rf = __builtin_amdgcn_readfirstlane(vsy);
-    const int kk = vsy + 1 - rf;
-    const int prevsy = __shfl_up(vsy, 1);
-    const bool okl = (lane & RWM) >= nrow || (rf >= 0 && vsy + 1 <= sh - 1 && kk < SR && ((lane & RWM) == 0 || vsy > prevsy));
-    constexpr unsigned long long rowLanes = (1ull << RW) - 1ull;
-    const bool regular = (__ballot(okl) & rowLanes) == rowLanes;
+    const bool vst = cr.y >= 0x10000u;
+    const int A = (int)cr.x;                       // cb - ca <= 2: both byte pairs lie inside [A, A+8)
+    const uint32_t aa = cr.z, ab = cr.w;
+    const uint32_t selA = (cr.y & 0xFFu) * 0x10001u + 0x0C010C00u, selB = ((cr.y >> 8) & 0xFFu) * 0x10001u + 0x0C010C00u;   // o | (o + 1) << 16 | 0x0C000C00
+    const int y0 = band * RW;
+    // fast path: the band's source rows rf .. rf+lastk are fetched up front (one memory latency per wave), then consumed in order.
+    // Bit k of `mask` says "the output row whose second source row is rf+k is due after source row k"; that row's betas are words
+    // HEAD + k of the record (b0 << 12 | b1).
     if (regular) {
-        uint32_t m = (lane & RWM) < nrow ? 1u << (kk & 31) : 0u;
-        m |= __shfl_xor(m, 1); m |= __shfl_xor(m, 2); m |= __shfl_xor(m, 4);
-        if (RW == 16) m |= __shfl_xor(m, 8);
-        const uint32_t mask = __builtin_amdgcn_readfirstlane(m);
-        const int lastk = 31 - __builtin_clz(mask | 1u);   // source rows past the last output row's second one are neither fetched nor filtered
         // Both levels through buffer descriptors (orbx_bufaddr.h), one per (image, level): the source from its padded row of source
         // row 0 to the level's end, the destination the whole padded level.  The lane's part of an address is its 32-bit column
         // offset, the row is a SCALAR byte offset: no per-lane address arithmetic, no 64-bit pointer per row in vector registers.
         const orbx_buf_t srcBuf = buf_make(srow0, (uint32_t)sps * (uint32_t)(geom[l - 1].prows - ORBX_EDGE));
         const orbx_buf_t dstBuf = buf_make(base + G.poff, (uint32_t)G.pstride * (uint32_t)G.prows);
         uint2 q[SR];   // rows past lastk stay unset: the load and its use sit under the same wave-uniform guard
+        uint32_t srow = PYR_REC(PYR_BAND_SROW);   // rf * sps: a regular band's source rows are never clamped
 #pragma unroll
-        for (int k = 0; k < SR; k++) {
-            if (k > lastk) continue;   // wave-uniform
-            q[k] = buf_load_b64(srcBuf, (uint32_t)A, (uint32_t)(min(rf + k, sh - 1) * sps));   // 32-bit scalar product (a padded level is far smaller than 4 GiB)
+        for (int k = 0; k < SR - 1; k++) {   // (the last row, which few bands need, is fetched below: all SR in flight at once cost one more register)
+            if (k > 1 && k > lastk) continue;   // wave-uniform (a regular band has an output row, so lastk >= 1: rows 0 and 1 need no guard)
+            q[k] = buf_load_b64(srcBuf, (uint32_t)A, srow);
+            srow += (uint32_t)sps;
         }
         uint32_t tpa = 0, tpb = 0;
-        int cnt = 0;
-        uint32_t drow = (uint32_t)((ORBX_EDGE + y0) * G.pstride + ORBX_EDGE - 1);   // scalar; the lane's column x0 = xoff - 1 with xoff >= 0
-        const uint32_t xoff = (uint32_t)(x0 + 1);
+        // scalar: the band's first row, column -1, plus the wave's 128-column chunk; the lane's part is just its pair, 2 * lane
+        uint32_t drow = PYR_REC(PYR_BAND_DROW) + (uint32_t)xc * 128u;
+        const uint32_t xoff = 2u * (uint32_t)lane;
 #pragma unroll
         for (int k = 0; k < SR; k++) {
-            if (k > lastk) continue;   // wave-uniform
+            if (k > 1 && k > lastk) continue;   // wave-uniform (a regular band has an output row, so lastk >= 1: rows 0 and 1 need no guard)
             const uint32_t tca = udot2_u16(__builtin_amdgcn_perm(q[k].y, q[k].x, selA), aa) & 0x7FFF0u;
             const uint32_t tcb = udot2_u16(__builtin_amdgcn_perm(q[k].y, q[k].x, selB), ab) & 0x7FFF0u;
             if (k > 0 && ((mask >> k) & 1u)) {   // wave-uniform
-                const uint32_t bb = (uint32_t)__builtin_amdgcn_readlane((int)vbt, cnt);
-                const uint32_t b0 = (bb & 0xFFFu) << 12, b1 = ((bb >> 16) & 0xFFFu) << 12;   // scalar; beta <= 2048
-                const uint32_t pa = (vmulhi24(b0, tpa) + vmulhi24(b1, tca) + 2) >> 2;
-                const uint32_t pb = (vmulhi24(b0, tpb) + vmulhi24(b1, tcb) + 2) >> 2;
-                if (vst) buf_store_b16(dstBuf, xoff, drow, (uint16_t)(pa | (pb << 8)));
+                const uint32_t bw = PYR_REC(PYR_BAND_HEAD + k), b0 = bw & 0xFFF000u, b1 = (bw & 0xFFFu) << 12;   // scalar: the record holds b0 << 12 | b1 (beta <= 2048)
+                const uint32_t sa = vmulhi24(b0, tpa) + vmulhi24(b1, tca) + 2;   // <= 1022
+                uint32_t sb = vmulhi24(b0, tpb) + vmulhi24(b1, tcb) + 2;
+                // (sa >> 2) | (sb >> 2) << 8 in three instructions (shift, mask, shift-or).  The empty asm keeps sb whole: left to itself the
+                // compiler folds its + 2 into a shift-add whose constant 0x80 has to be moved into a vector register for every row.
+                asm("" : "+v"(sb));
+                if (vst) buf_store_b16(dstBuf, xoff, drow, (uint16_t)(((sb & 0x3FCu) << 6) | (sa >> 2)));
                 drow += (uint32_t)G.pstride;
-                cnt++;
             }
             tpa = tca; tpb = tcb;
+            if (k == 1 && SR - 1 <= lastk) q[SR - 1] = buf_load_b64(srcBuf, (uint32_t)A, srow);   // the registers of rows 0 and 1 are free now; srow = row SR-1 here
         }
         return;
     }
@@ -263,6 +274,7 @@ __global__ __launch_bounds__(256) void k_pyr_level(uint8_t *__restrict__ pyr, si
         if (vst) *(uint16_t *)(drow0 + (size_t)y * G.pstride + x0) = (uint16_t)(pa | (pb << 8));
     }
 }
+#undef PYR_REC
 
 // FULL: every dword of the padded level from the input image (level 0).  !FULL: only the dwords
 // that contain frame bytes, gathered from the level's own inner pixels (levels >= 1, blockIdx.y).
@@ -502,7 +514,7 @@ __global__ __launch_bounds__(256) void k_pyr_chain(uint8_t *__restrict__ pyr, si
     }
 }
 
-template __global__ void k_pyr_level<8, 12>(uint8_t *, size_t, const LevelGeom *, int, const int32_t *, int, int);
-template __global__ void k_pyr_level<16, 22>(uint8_t *, size_t, const LevelGeom *, int, const int32_t *, int, int);
+template __global__ void k_pyr_level<8, 12>(uint8_t *, size_t, const LevelGeom *, int, const int32_t *, int, int, const PyrColRec *, const uint32_t *, uint32_t, uint32_t);
+template __global__ void k_pyr_level<16, 22>(uint8_t *, size_t, const LevelGeom *, int, const int32_t *, int, int, const PyrColRec *, const uint32_t *, uint32_t, uint32_t);
 template __global__ void k_pyr_pad<true>(const uint8_t *, int, size_t, uint8_t *, size_t, const LevelGeom *, int);
 template __global__ void k_pyr_pad<false>(const uint8_t *, int, size_t, uint8_t *, size_t, const LevelGeom *, int);

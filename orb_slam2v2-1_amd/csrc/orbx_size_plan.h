@@ -433,3 +433,96 @@ static inline int plan_size(const SizeInput &in, SizePlan *out) {
     *out = std::move(p);
     return ORBX_OK;
 }
+
+// ---- k_pyr_level's per-wave set-up, tabulated (orbx_pyramid.hip).  Everything a wave of the level kernel used to derive from the
+// resize tables before its first source-row load depends on the image size alone, so it is built here, once per size:
+//  * one column record per (level l >= 1, lane slot).  A level has nxc * 64 slots, nxc = ceil((w + 1) / 128): whole waves, so the
+//    kernel's 16-byte load needs no clamp.  Slot j owns the columns x0 = 2j - 1 and x0 + 1; the columns -1 and >= w read the
+//    nearest inner column (offsets that stay inside the source row) and slots with x0 >= w store nothing.
+//  * one band record per (level l >= 1, form RW in {8, 16}, band of RW output rows): the first source row, which source rows an
+//    output row is due after, and that row's betas.  The betas are indexed by SOURCE-ROW STEP k (the output row whose second source
+//    row is rf + k), not by output row: the kernel's loop over source rows is unrolled, so every beta sits at a FIXED word of the
+//    record (lane i of the wave loads word i, a row fetches its word by v_readlane with a constant lane) and no row needs an indexed
+//    fetch.  A word is b0 << 12 | b1: one scalar AND gives b0 as v_mul_hi_u32_u24 takes it, an AND and a shift b1.  The table ends
+//    with a wave's worth of zero words, so that the lanes past a record's end load inside it too.
+// The 16-row records exist only up to scale factor 1.25: beyond it launch_pyramid never picks that form.
+struct PyrColRec {          // 16 bytes, one lane's load
+    uint32_t A;             // aligned byte offset in the padded source row: both byte pairs lie inside [A, A + 8)
+    uint32_t sel;           // oa | ob << 8 | storeValid << 16: byte offsets of the two pairs from A (the v_perm selectors follow)
+    uint32_t aa, ab;        // packed (a0, a1) of the two columns
+};
+#define PYR_BAND_HEAD 8     // words in front of a band record's betas
+enum { PYR_BAND_RF = 0, PYR_BAND_MASK = 1, PYR_BAND_LASTK = 2, PYR_BAND_NROW = 3, PYR_BAND_REGULAR = 4, PYR_BAND_DROW = 5, PYR_BAND_SROW = 6 };
+static inline int pyr_band_sr(int rw) { return rw == 16 ? 22 : 12; }                         // source rows a band of rw output rows fetches up front
+static inline int pyr_band_words(int rw) { return PYR_BAND_HEAD + pyr_band_sr(rw); }   // head, then b0 << 12 | b1 per source-row step
+struct PyrRecords {
+    std::vector<PyrColRec> cols;
+    std::vector<uint32_t> bands;
+    int nxc[ORBX_MAX_LEVELS], colOff[ORBX_MAX_LEVELS];           // waves per row band; first column record of the level
+    int nbands[2][ORBX_MAX_LEVELS], bandOff[2][ORBX_MAX_LEVELS];   // [0] the 8-row form, [1] the 16-row form: bands; first WORD of the level's records (-1: not built)
+};
+// floor(2^32 / d) rounded down once more where d is a power of two: udiv_rcp (orbx_pyramid.hip) divides by it with scalar multiplies
+static inline uint32_t pyr_rcp(uint32_t d) { return 0xFFFFFFFFu / std::max(d, 1u); }
+
+// Plain C++, no HIP call: reads the SizeInput and the resize tables of the plan.
+static inline void plan_pyr_records(const SizeInput &in, const SizePlan &sp, PyrRecords *out) {
+    PyrRecords r = {};
+    const std::vector<int32_t> &tab = sp.tab;
+    for (int l = 0; l < ORBX_MAX_LEVELS; l++) r.bandOff[0][l] = r.bandOff[1][l] = -1;
+    for (int l = 1; l < in.nlevels; l++) {
+        const LevelGeom &G = sp.geom[l], &S = sp.geom[l - 1];
+        const int nxc = (G.w + 1 + 127) / 128;
+        r.nxc[l] = nxc;
+        r.colOff[l] = (int)r.cols.size();
+        for (int j = 0; j < nxc * 64; j++) {
+            const int x0 = 2 * j - 1, x1 = x0 + 1;
+            const int xa = std::min(std::max(x0, 0), G.w - 1), xb = std::min(x1, G.w - 1);
+            const int ca = ORBX_EDGE + tab[G.xofsOff + xa], cb = ORBX_EDGE + tab[G.xofsOff + xb];   // byte column in the padded source row
+            PyrColRec c;
+            c.A = (uint32_t)(ca & ~3);                  // cb - ca <= 2 (scale factor <= 3)
+            c.sel = (uint32_t)(ca - (int)c.A) | ((uint32_t)(cb - (int)c.A) << 8) | (x0 < G.w ? 1u << 16 : 0u);
+            c.aa = (uint32_t)tab[G.xalphaOff + xa];
+            c.ab = (uint32_t)tab[G.xalphaOff + xb];
+            r.cols.push_back(c);
+        }
+        for (int f = 0; f < 2; f++) {
+            const int RW = f ? 16 : 8, SR = pyr_band_sr(RW), words = pyr_band_words(RW);
+            if (f == 1 && !(in.scale_factor <= 1.25f)) continue;
+            const int nb = (G.h + RW - 1) / RW;
+            r.nbands[f][l] = nb;
+            r.bandOff[f][l] = (int)r.bands.size();
+            r.bands.resize(r.bands.size() + (size_t)nb * words, 0u);
+            for (int band = 0; band < nb; band++) {
+                uint32_t *w = &r.bands[(size_t)r.bandOff[f][l] + (size_t)band * words];
+                const int y0 = band * RW, nrow = std::min(RW, G.h - y0);
+                const int rf = tab[G.yofsOff + y0];
+                // the rule of the fast path: every row's two source rows exist unclamped, lie within the SR rows fetched up front, and
+                // no two output rows share their second source row
+                bool regular = rf >= 0;
+                uint32_t mask = 0;
+                for (int i = 0; i < nrow && regular; i++) {
+                    const int sy = tab[G.yofsOff + y0 + i], kk = sy + 1 - rf;
+                    regular = sy + 1 <= S.h - 1 && kk < SR && (i == 0 || sy > tab[G.yofsOff + y0 + i - 1]);
+                    if (regular) mask |= 1u << kk;
+                }
+                w[PYR_BAND_RF] = (uint32_t)rf;
+                w[PYR_BAND_NROW] = (uint32_t)nrow;
+                w[PYR_BAND_DROW] = (uint32_t)((ORBX_EDGE + y0) * G.pstride + ORBX_EDGE - 1);   // byte offset of column -1 of the band's first row in the padded level
+                if (!regular) continue;   // the row-by-row path reads the tables itself: the rest of the record stays zero
+                w[PYR_BAND_REGULAR] = 1;
+                w[PYR_BAND_MASK] = mask;
+                int lastk = 0;
+                while ((mask >> lastk) > 1u) lastk++;
+                w[PYR_BAND_LASTK] = (uint32_t)lastk;
+                w[PYR_BAND_SROW] = (uint32_t)(rf * S.pstride);   // byte offset of source row rf from the padded row of source row 0
+                for (int i = 0; i < nrow; i++) {
+                    const int kk = tab[G.yofsOff + y0 + i] + 1 - rf;
+                    const uint32_t bb = (uint32_t)tab[G.ybetaOff + y0 + i];
+                    w[PYR_BAND_HEAD + kk] = ((bb & 0xFFFu) << 12) | ((bb >> 16) & 0xFFFu);   // beta <= 2048: 12 bits each
+                }
+            }
+        }
+    }
+    r.bands.resize(r.bands.size() + 64, 0u);   // lane i of a wave loads word i of its record: whole waves past the last record too
+    *out = std::move(r);
+}
