@@ -21,6 +21,7 @@
 // tests/cpp/essential_lockstep.cc compiles this file's kernels AND the driver for the host, one thread per workgroup, the
 // workgroups of a launch one after the other (tests/cpp/hip_lockstep.h comes first): every sum then runs in ascending order, which
 // is tests/essential_ref.py's order - the two must agree bit for bit (tests/test_essential_cpu.py).
+#include "orbx_stage_plan.h"
 #define EG_THREADS 1
 #define EG_LANES 1
 #else
@@ -32,6 +33,7 @@
 #include <math.h>
 #include <algorithm>
 #include <vector>
+#include "orbx_g2omath.h"
 
 #define EG_WAVES ((EG_THREADS + EG_LANES - 1) / EG_LANES)
 #define EG_SLOTS 16         // threads an edge gets in a linearisation: 7 columns of side i | 7 of side j | the error itself | idle
@@ -55,144 +57,8 @@ struct EgDev {
     EgRec *rec;
     float *outT, *outP; double *outE;
 };
+// block_sum and the quaternion and Sim3 functions (sim3_mul, sim3_inverse, sim3_map, sim3_exp) are orbx_g2omath.h's
 
-__device__ __forceinline__ double eg_wave_sum(double v) {
-#pragma unroll
-    for (int m = EG_LANES / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, EG_LANES);
-    return v;
-}
-__device__ __forceinline__ double eg_block_sum(double v, double *part) {   // part: EG_WAVES doubles of LDS
-    const int lane = threadIdx.x % EG_LANES, wave = threadIdx.x / EG_LANES;
-    v = eg_wave_sum(v);
-    if (lane == 0) part[wave] = v;
-    __syncthreads();
-    double t = part[0];
-#pragma unroll
-    for (int w = 1; w < EG_WAVES; w++) t += part[w];
-    return t;
-}
-
-// Eigen::Quaternion(Matrix3), Quaternion * Vector3, toRotationMatrix, Sim3::operator*, Sim3::inverse and Sim3(Vector7d): copies of
-// orbx_sim3opt.hip's s3o_* (that file is unchanged)
-template <int I>
-__device__ __forceinline__ void eg_quat_from_R_case(const double R[9], double q[4]) {   // the branch of a non-positive trace, largest diagonal entry I
-    constexpr int J = (I + 1) % 3, K = (J + 1) % 3;
-    double t = sqrt(R[I * 4] - R[J * 4] - R[K * 4] + 1.0);
-    q[I] = 0.5 * t;
-    t = 0.5 / t;
-    q[3] = (R[K * 3 + J] - R[J * 3 + K]) * t;
-    q[J] = (R[J * 3 + I] + R[I * 3 + J]) * t;
-    q[K] = (R[K * 3 + I] + R[I * 3 + K]) * t;
-}
-__device__ __forceinline__ void eg_quat_from_R(const double R[9], double q[4]) {   // s3o_quat_from_R with its index arithmetic as three cases: no array is indexed by a variable
-    double t = R[0] + R[4] + R[8];
-    if (t > 0.0) {
-        t = sqrt(t + 1.0);
-        q[3] = 0.5 * t;
-        t = 0.5 / t;
-        q[0] = (R[7] - R[5]) * t; q[1] = (R[2] - R[6]) * t; q[2] = (R[3] - R[1]) * t;
-    } else {
-        int i = 0;
-        if (R[4] > R[0]) i = 1;
-        if (R[8] > (i ? R[4] : R[0])) i = 2;
-        if (i == 0) eg_quat_from_R_case<0>(R, q);
-        else if (i == 1) eg_quat_from_R_case<1>(R, q);
-        else eg_quat_from_R_case<2>(R, q);
-    }
-}
-__device__ __forceinline__ void eg_quat_rotate(const double q[4], const double v[3], double r[3]) {
-    double uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]};
-    uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
-    r[0] = (v[0] + q[3] * uv[0]) + (q[1] * uv[2] - q[2] * uv[1]);
-    r[1] = (v[1] + q[3] * uv[1]) + (q[2] * uv[0] - q[0] * uv[2]);
-    r[2] = (v[2] + q[3] * uv[2]) + (q[0] * uv[1] - q[1] * uv[0]);
-}
-__device__ __forceinline__ void eg_quat_to_R(const double q[4], double R[9]) {
-    const double tx = 2.0 * q[0], ty = 2.0 * q[1], tz = 2.0 * q[2];
-    const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3], txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
-    const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
-    R[0] = 1.0 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
-    R[3] = txy + twz; R[4] = 1.0 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1.0 - (txx + tyy);
-}
-__device__ __forceinline__ EgS3 eg_mul(const EgS3 &a, const EgS3 &b) {   // sim3.h:266-272: the quaternion product is not normalised
-    EgS3 r;
-    const double ax = a.q[0], ay = a.q[1], az = a.q[2], aw = a.q[3], bx = b.q[0], by = b.q[1], bz = b.q[2], bw = b.q[3];
-    r.q[3] = ((aw * bw - ax * bx) - ay * by) - az * bz;
-    r.q[0] = ((aw * bx + ax * bw) + ay * bz) - az * by;
-    r.q[1] = ((aw * by + ay * bw) + az * bx) - ax * bz;
-    r.q[2] = ((aw * bz + az * bw) + ax * by) - ay * bx;
-    double rt[3];
-    eg_quat_rotate(a.q, b.t, rt);
-    r.t[0] = a.s * rt[0] + a.t[0]; r.t[1] = a.s * rt[1] + a.t[1]; r.t[2] = a.s * rt[2] + a.t[2];
-    r.s = a.s * b.s;
-    return r;
-}
-__device__ __forceinline__ EgS3 eg_inverse(const EgS3 &a) {   // sim3.h:233-236
-    EgS3 r;
-    r.q[0] = -a.q[0]; r.q[1] = -a.q[1]; r.q[2] = -a.q[2]; r.q[3] = a.q[3];
-    const double k = -1. / a.s;
-    const double v[3] = {k * a.t[0], k * a.t[1], k * a.t[2]};
-    eg_quat_rotate(r.q, v, r.t);
-    r.s = 1. / a.s;
-    return r;
-}
-__device__ __forceinline__ void eg_map(const EgS3 &S, const double p[3], double r[3]) {   // sim3.h:144-146: s * (r * xyz) + t
-    double v[3];
-    eg_quat_rotate(S.q, p, v);
-    r[0] = S.s * v[0] + S.t[0]; r[1] = S.s * v[1] + S.t[1]; r[2] = S.s * v[2] + S.t[2];
-}
-// Sim3(const Vector7d &update) (sim3.h:70-142), update = omega | upsilon | sigma, its four branches as written
-__device__ __forceinline__ EgS3 eg_exp(const double u[7]) {
-    const double o0 = u[0], o1 = u[1], o2 = u[2], sigma = u[6];
-    const double theta = sqrt((o0 * o0 + o1 * o1) + o2 * o2);
-    const double Om[9] = {0.0, -o2, o1, o2, 0.0, -o0, -o1, o0, 0.0};
-    double Om2[9];
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) Om2[r * 3 + c] = (Om[r * 3] * Om[c] + Om[r * 3 + 1] * Om[3 + c]) + Om[r * 3 + 2] * Om[6 + c];
-    EgS3 S;
-    S.s = exp(sigma);
-    const double eps = 0.00001;
-    double A, B, Cc, ra, rb;   // R = (I + ra Omega) + rb Omega^2
-    if (fabs(sigma) < eps) {
-        Cc = 1.0;
-        if (theta < eps) {
-            A = 1. / 2.; B = 1. / 6.; ra = 1.0; rb = 1.0;
-        } else {
-            const double theta2 = theta * theta, si = sin(theta), co = cos(theta);
-            A = (1.0 - co) / theta2;
-            B = (theta - si) / (theta2 * theta);
-            ra = si / theta; rb = (1.0 - co) / (theta * theta);
-        }
-    } else {
-        Cc = (S.s - 1.0) / sigma;
-        if (theta < eps) {
-            const double sigma2 = sigma * sigma;
-            A = ((sigma - 1.0) * S.s + 1.0) / sigma2;
-            B = ((0.5 * sigma2 - sigma + 1.0) * S.s) / (sigma2 * sigma);
-            ra = 1.0; rb = 1.0;
-        } else {
-            const double si = sin(theta), co = cos(theta);
-            ra = si / theta; rb = (1.0 - co) / (theta * theta);
-            const double a = S.s * si, b = S.s * co, theta2 = theta * theta, sigma2 = sigma * sigma, c = theta2 + sigma2;
-            A = (a * sigma + (1.0 - b) * theta) / (theta * c);
-            B = ((Cc - ((b - 1.0) * sigma + a * theta) / c) * 1.) / theta2;
-        }
-    }
-    double R[9], W[9];
-#pragma unroll
-    for (int k = 0; k < 9; k++) {
-        const double id = (k == 0 || k == 4 || k == 8) ? 1.0 : 0.0;
-        R[k] = (id + ra * Om[k]) + rb * Om2[k];
-        W[k] = (A * Om[k] + B * Om2[k]) + Cc * id;
-    }
-    eg_quat_from_R(R, S.q);
-#pragma unroll
-    for (int r = 0; r < 3; r++) S.t[r] = (W[r * 3] * u[3] + W[r * 3 + 1] * u[4]) + W[r * 3 + 2] * u[5];
-    return S;
-}
 // W.lu().solve(t) for a 3x3 W: partial pivoting - in column k the row of the largest |entry| among rows k.., the FIRST one on a
 // tie - then the unit lower and the upper substitution.  A zero pivot divides by zero as Eigen's does.
 __device__ __forceinline__ void eg_lu3_solve(double W[9], const double t[3], double x[3]) {
@@ -233,7 +99,7 @@ __device__ __forceinline__ void eg_lu3_solve(double W[9], const double t[3], dou
 __device__ __forceinline__ void eg_log(const EgS3 &S, double res[7]) {
     const double sigma = log(S.s);
     double R[9];
-    eg_quat_to_R(S.q, R);
+    quat_to_R(S.q, R);
     const double d = 0.5 * (((R[0] + R[4]) + R[8]) - 1.0);
     const double dR[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
     const double eps = 0.00001;
@@ -279,7 +145,7 @@ __device__ __forceinline__ void eg_log(const EgS3 &S, double res[7]) {
 }
 // EdgeSim3::computeError (types_seven_dof_expmap.h:106-114): (C * v1 * v2^-1).log()
 __device__ __forceinline__ void eg_error(const EgS3 &Cm, const EgS3 &Si, const EgS3 &Sj, double e[7]) {
-    eg_log(eg_mul(eg_mul(Cm, Si), eg_inverse(Sj)), e);
+    eg_log(sim3_mul(sim3_mul(Cm, Si), sim3_inverse(Sj)), e);
 }
 
 // the estimates as the reference sets them (:820-834) and every edge's measurement (:859-869, :891-916)
@@ -291,7 +157,7 @@ __global__ __launch_bounds__(EG_THREADS) void k_eg_init(EgDev D) {
         const orbg_vertex_t *vi = D.vtx + e.i, *vj = D.vtx + e.j;
         const bool nc = e.kind != 0;
         const EgS3 Siw = (nc && vi->has_nc) ? vi->Snc : vi->Scw, Sjw = (nc && vj->has_nc) ? vj->Snc : vj->Scw;
-        D.meas[i] = eg_mul(Sjw, eg_inverse(Siw));
+        D.meas[i] = sim3_mul(Sjw, sim3_inverse(Siw));
     }
 }
 
@@ -322,7 +188,7 @@ __global__ __launch_bounds__(EG_THREADS) void k_eg_edges(EgDev D, int c) {
 #pragma unroll
                     for (int k = 0; k < 7; k++) u[k] = k == col ? (s ? -EG_DELTA : EG_DELTA) : 0.0;
                     if (D.fixScale) u[6] = 0.0;
-                    const EgS3 Sp = eg_mul(eg_exp(u), side ? Sj : Si);
+                    const EgS3 Sp = sim3_mul(sim3_exp(u), side ? Sj : Si);
                     const EgS3 Sa = side ? Si : Sp, Sb = side ? Sp : Sj;
                     eg_error(Cm, Sa, Sb, e2[s]);
                 }
@@ -333,7 +199,7 @@ __global__ __launch_bounds__(EG_THREADS) void k_eg_edges(EgDev D, int c) {
             }
         }
     }
-    chi = eg_block_sum(chi, part);
+    chi = block_sum<EG_LANES, EG_WAVES>(chi, part);
     if (threadIdx.x == 0) D.partChi[blockIdx.x] = chi;
 }
 
@@ -526,11 +392,11 @@ __global__ __launch_bounds__(EG_THREADS) void k_eg_update(EgDev D, int c, double
             if (D.fixScale) x[6] = 0.0;
 #pragma unroll
             for (int j = 0; j < 7; j++) sc += x[j] * (lambda * x[j] + D.b[col * 7 + j]);
-            S = eg_mul(eg_exp(x), S);
+            S = sim3_mul(sim3_exp(x), S);
         }
         D.est[c ^ 1][v] = S;
     }
-    sc = eg_block_sum(sc, part);
+    sc = block_sum<EG_LANES, EG_WAVES>(sc, part);
     if (threadIdx.x == 0) D.partScale[blockIdx.x] = sc;
 }
 
@@ -540,8 +406,8 @@ __global__ __launch_bounds__(EG_THREADS) void k_eg_reduce(EgDev D, int nbE, int 
     double a1 = 0.0, a2 = 0.0;
     for (int i = threadIdx.x; i < nbE; i += EG_THREADS) a1 += D.partChi[i];
     for (int i = threadIdx.x; i < nbS; i += EG_THREADS) a2 += D.partScale[i];
-    a1 = eg_block_sum(a1, part[0]);
-    a2 = eg_block_sum(a2, part[1]);
+    a1 = block_sum<EG_LANES, EG_WAVES>(a1, part[0]);
+    a2 = block_sum<EG_LANES, EG_WAVES>(a2, part[1]);
     if (threadIdx.x == 0) {
         if (lin) D.rec->linChi = a1;
         else { D.rec->tmpChi = a1; D.rec->scale = a2; }
@@ -554,7 +420,7 @@ __global__ __launch_bounds__(EG_THREADS) void k_eg_out(EgDev D, int c) {
     if (i < D.N) {
         const EgS3 S = D.est[c][i];
         double R[9];
-        eg_quat_to_R(S.q, R);
+        quat_to_R(S.q, R);
         const double is = 1. / S.s;
         float *to = D.outT + (size_t)i * 16;
         for (int r = 0; r < 3; r++) {
@@ -569,8 +435,8 @@ __global__ __launch_bounds__(EG_THREADS) void k_eg_out(EgDev D, int c) {
         const orbg_point_t p = D.pts[i];
         const double X[3] = {(double)p.x, (double)p.y, (double)p.z};
         double Xr[3], Xw[3];
-        eg_map(D.vtx[p.ref].Scw, X, Xr);
-        eg_map(eg_inverse(D.est[c][p.ref]), Xr, Xw);
+        sim3_map(D.vtx[p.ref].Scw, X, Xr);
+        sim3_map(sim3_inverse(D.est[c][p.ref]), Xr, Xw);
         for (int k = 0; k < 3; k++) D.outP[(size_t)i * 3 + k] = (float)Xw[k];
     }
 }
@@ -747,7 +613,6 @@ struct EgMem {
 };
 #ifdef ORBX_EG_HOST
 #define EG_LAUNCH(kern, grid, ...) do { for (int b_ = 0; b_ < (int)(grid); b_++) { blockIdx.x = b_; kern(__VA_ARGS__); } blockIdx.x = 0; nlaunch++; } while (0)
-struct StagePlan { size_t off = 0; size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; } };
 #else
 #define EG_LAUNCH(kern, grid, ...) do { hipLaunchKernelGGL(kern, dim3(grid), dim3(EG_THREADS), 0, M.st, __VA_ARGS__); ORBX_HIP(hipGetLastError()); nlaunch++; } while (0)
 #endif

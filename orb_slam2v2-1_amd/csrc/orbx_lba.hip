@@ -20,6 +20,7 @@
 // tests/cpp/lba_lockstep.cc compiles this file's kernels AND the driver for the host, one thread per workgroup, the workgroups
 // of a launch one after the other (tests/cpp/hip_lockstep.h comes first): every sum then runs in ascending order, which is
 // tests/lba_ref.py's order - the two must agree bit for bit (tests/test_lba_cpu.py).
+#include "orbx_stage_plan.h"
 #define LBA_THREADS 1
 #define LBA_LANES 1
 #else
@@ -31,6 +32,7 @@
 #include <math.h>
 #include <algorithm>
 #include <vector>
+#include "orbx_g2omath.h"
 
 #define LBA_WAVES ((LBA_THREADS + LBA_LANES - 1) / LBA_LANES)
 #define LBA_LDS_POSES 14    // free poses whose reduced system (6 * 14 = 84 square, 56448 B of doubles) is factorised in LDS, under the 64 KiB a launch gets unasked
@@ -50,113 +52,7 @@ struct LbaDev {
     LbaRec *rec;
     float *outT, *outP; double *estKf, *estPt;
 };
-
-__device__ __forceinline__ double lba_wave_sum(double v) {
-#pragma unroll
-    for (int m = LBA_LANES / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, LBA_LANES);   // a + b == b + a bit for bit: every lane ends with the same sum
-    return v;
-}
-template <int N>
-__device__ __forceinline__ void lba_block_sum(double (&a)[N], double *part) {   // part: LBA_WAVES * N doubles of LDS; the caller owns the barrier before part is used again
-    const int lane = threadIdx.x % LBA_LANES, wave = threadIdx.x / LBA_LANES;
-#pragma unroll
-    for (int k = 0; k < N; k++) a[k] = lba_wave_sum(a[k]);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < N; k++) part[wave * N + k] = a[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; k++) {
-        double t = part[k];
-#pragma unroll
-        for (int w = 1; w < LBA_WAVES; w++) t += part[w * N + k];   // ((w0 + w1) + w2) + w3
-        a[k] = t;
-    }
-}
-
-// quat_from_R, normalize_rotation, quat_rotate, quat_to_R and se3_oplus are copies of orbx_poseopt.hip's (that file is unchanged)
-__device__ __forceinline__ void lba_quat_from_R(const double R[9], double q[4]) {
-    double t = R[0] + R[4] + R[8];
-    if (t > 0.0) {
-        t = sqrt(t + 1.0);
-        q[3] = 0.5 * t;
-        t = 0.5 / t;
-        q[0] = (R[7] - R[5]) * t; q[1] = (R[2] - R[6]) * t; q[2] = (R[3] - R[1]) * t;
-    } else {
-        int i = 0;
-        if (R[4] > R[0]) i = 1;
-        if (R[8] > R[i * 4]) i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        t = sqrt(R[i * 4] - R[j * 4] - R[k * 4] + 1.0);
-        double v[3];
-        v[i] = 0.5 * t;
-        t = 0.5 / t;
-        q[3] = (R[k * 3 + j] - R[j * 3 + k]) * t;
-        v[j] = (R[j * 3 + i] + R[i * 3 + j]) * t;
-        v[k] = (R[k * 3 + i] + R[i * 3 + k]) * t;
-        q[0] = v[0]; q[1] = v[1]; q[2] = v[2];
-    }
-}
-__device__ __forceinline__ void lba_normalize_rotation(double q[4]) {   // se3quat.h:280-285
-    if (q[3] < 0.0) { q[0] = -q[0]; q[1] = -q[1]; q[2] = -q[2]; q[3] = -q[3]; }
-    const double n = sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-    q[0] /= n; q[1] /= n; q[2] /= n; q[3] /= n;
-}
-__device__ __forceinline__ void lba_quat_rotate(const double q[4], const double v[3], double r[3]) {   // Quaternion * Vector3 (_transformVector)
-    double uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]};
-    uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
-    r[0] = (v[0] + q[3] * uv[0]) + (q[1] * uv[2] - q[2] * uv[1]);
-    r[1] = (v[1] + q[3] * uv[1]) + (q[2] * uv[0] - q[0] * uv[2]);
-    r[2] = (v[2] + q[3] * uv[2]) + (q[0] * uv[1] - q[1] * uv[0]);
-}
-__device__ __forceinline__ void lba_quat_to_R(const double q[4], double R[9]) {   // Quaternion::toRotationMatrix
-    const double tx = 2.0 * q[0], ty = 2.0 * q[1], tz = 2.0 * q[2];
-    const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3], txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
-    const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
-    R[0] = 1.0 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
-    R[3] = txy + twz; R[4] = 1.0 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1.0 - (txx + tyy);
-}
-// VertexSE3Expmap::oplusImpl: estimate = SE3Quat::exp(x) * estimate (se3quat.h:223-257, :104-110); x = omega | upsilon; T = t[3] | q[4]
-__device__ __forceinline__ void lba_se3_oplus(double *T, const double x[6]) {
-    const double o0 = x[0], o1 = x[1], o2 = x[2];
-    const double theta = sqrt((o0 * o0 + o1 * o1) + o2 * o2);
-    const double Om[9] = {0.0, -o2, o1, o2, 0.0, -o0, -o1, o0, 0.0};
-    double Om2[9];
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) Om2[r * 3 + c] = (Om[r * 3] * Om[c] + Om[r * 3 + 1] * Om[3 + c]) + Om[r * 3 + 2] * Om[6 + c];
-    double a, b, c2;
-    if (theta < 0.00001) { a = 1.0; b = 1.0; c2 = 1.0; }   // R = I + Omega + Omega^2, V = R
-    else {
-        const double s = sin(theta), co = cos(theta);
-        a = s / theta; b = (1.0 - co) / (theta * theta); c2 = (theta - s) / (theta * theta * theta);
-    }
-    double R[9], V[9];
-#pragma unroll
-    for (int k = 0; k < 9; k++) {
-        const double id = (k == 0 || k == 4 || k == 8) ? 1.0 : 0.0;
-        R[k] = (id + a * Om[k]) + b * Om2[k];
-        V[k] = theta < 0.00001 ? R[k] : (id + b * Om[k]) + c2 * Om2[k];
-    }
-    double qe[4], te[3];
-    lba_quat_from_R(R, qe);
-    lba_normalize_rotation(qe);
-#pragma unroll
-    for (int r = 0; r < 3; r++) te[r] = (V[r * 3] * x[3] + V[r * 3 + 1] * x[4]) + V[r * 3 + 2] * x[5];
-    double rt[3], q[4] = {T[3], T[4], T[5], T[6]};
-    lba_quat_rotate(qe, T, rt);
-    const double ax = qe[0], ay = qe[1], az = qe[2], aw = qe[3], bx = q[0], by = q[1], bz = q[2], bw = q[3];
-    T[0] = te[0] + rt[0]; T[1] = te[1] + rt[1]; T[2] = te[2] + rt[2];
-    q[3] = ((aw * bw - ax * bx) - ay * by) - az * bz;
-    q[0] = ((aw * bx + ax * bw) + ay * bz) - az * by;
-    q[1] = ((aw * by + ay * bw) + az * bx) - ax * bz;
-    q[2] = ((aw * bz + az * bw) + ax * by) - ay * bx;
-    lba_normalize_rotation(q);
-    T[3] = q[0]; T[4] = q[1]; T[5] = q[2]; T[6] = q[3];
-}
+// block_sum, the quaternion functions and se3_oplus are orbx_g2omath.h's; part: LBA_WAVES * K doubles of LDS
 
 // the estimates as the reference sets them (:527, :576): SE3Quat(R, t) of the widened float Tcw, the widened float position; every
 // edge at level 0, no evaluation yet (an edge never evaluated reports chi2 = 0, where the reference reads an uninitialised error)
@@ -171,8 +67,8 @@ __global__ __launch_bounds__(LBA_THREADS) void k_lba_init(LbaDev D) {
             for (int c = 0; c < 3; c++) R[r * 3 + c] = (double)Tf[r * 4 + c];
             T[r] = (double)Tf[r * 4 + 3];
         }
-        lba_quat_from_R(R, T + 3);
-        lba_normalize_rotation(T + 3);
+        quat_from_R(R, T + 3);
+        normalize_rotation(T + 3);
 #pragma unroll
         for (int k = 0; k < 7; k++) { D.pose[0][(size_t)i * 7 + k] = T[k]; D.pose[1][(size_t)i * 7 + k] = T[k]; }
     }
@@ -210,7 +106,7 @@ __global__ __launch_bounds__(LBA_THREADS) void k_lba_edges(LbaDev D, int c, int 
         const double *T = D.pose[c] + (size_t)o.kf * 7, *Xp = D.pt[c] + (size_t)o.pt * 3;
         const double q[4] = {T[3], T[4], T[5], T[6]}, Xw[3] = {Xp[0], Xp[1], Xp[2]};
         double X[3];
-        lba_quat_rotate(q, Xw, X);   // SE3Quat::map: _r * xyz + _t
+        quat_rotate(q, Xw, X);   // SE3Quat::map: _r * xyz + _t
         const double x = X[0] + T[0], y = X[1] + T[1], z = X[2] + T[2];
         const bool mono = o.ur < 0.f;
         double e0, e1, e2;
@@ -241,7 +137,7 @@ __global__ __launch_bounds__(LBA_THREADS) void k_lba_edges(LbaDev D, int c, int 
         a1[0] = rho0;
         if (LIN) {
             double R[9], A[3][3], B[3][6];
-            lba_quat_to_R(q, R);
+            quat_to_R(q, R);
             const double z_2 = z * z;
             if (mono) {   // _jacobianOplusXi = -1./z * tmp * R, tmp = [fx 0 -x/z*fx; 0 fy -y/z*fy] (:115-124)
                 const double s = -1. / z;
@@ -305,7 +201,7 @@ __global__ __launch_bounds__(LBA_THREADS) void k_lba_edges(LbaDev D, int c, int 
                 for (int l = 0; l < 3; l++, k++) ed[k * E] = ((B[0][j] * wo) * A[0][l] + (B[1][j] * wo) * A[1][l]) + (B[2][j] * wo) * A[2][l];
         }
     }
-    lba_block_sum<1>(a1, part);
+    block_sum<LBA_LANES, LBA_WAVES>(a1, part);
     if (threadIdx.x == 0) D.partChi[blockIdx.x] = a1[0];
 }
 
@@ -344,7 +240,7 @@ __global__ __launch_bounds__(LBA_THREADS) void k_lba_pose(LbaDev D) {
 #pragma unroll
         for (int k = 0; k < 27; k++) acc[k] += D.ed[(9 + k) * E + e];
     }
-    lba_block_sum<27>(acc, part);
+    block_sum<LBA_LANES, LBA_WAVES>(acc, part);
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int k = 0; k < 21; k++) D.Hpp[(size_t)c * 21 + k] = acc[k];
@@ -359,7 +255,7 @@ __global__ __launch_bounds__(LBA_THREADS) void k_lba_lin_reduce(LbaDev D, int nb
     __shared__ double mx[LBA_THREADS];
     double a1[1] = {0.0}, md = 0.0;
     for (int i = threadIdx.x; i < nbE; i += LBA_THREADS) a1[0] += D.partChi[i];
-    lba_block_sum<1>(a1, part);
+    block_sum<LBA_LANES, LBA_WAVES>(a1, part);
     for (int i = threadIdx.x; i < D.nf; i += LBA_THREADS) {
         const double *H = D.Hpp + (size_t)i * 21;
         md = fmax(fabs(H[0]), md); md = fmax(fabs(H[6]), md); md = fmax(fabs(H[11]), md);
@@ -433,7 +329,7 @@ __global__ __launch_bounds__(LBA_THREADS) void k_lba_schur(LbaDev D, double lamb
 #pragma unroll
             for (int l = 0; l < 6; l++) acc[j * 6 + l] += (Y[j][0] * W2[l][0] + Y[j][1] * W2[l][1]) + Y[j][2] * W2[l][2];
     }
-    lba_block_sum<42>(acc, part);
+    block_sum<LBA_LANES, LBA_WAVES>(acc, part);
     if (threadIdx.x == 0) {
         const size_t n = (size_t)nf * 6;
         if (i1 == i2) {
@@ -514,7 +410,7 @@ __global__ __launch_bounds__(LBA_THREADS) void k_lba_update(LbaDev D, int c, dou
 #pragma unroll
                 for (int j = 0; j < 6; j++) s += x[j] * (lambda * x[j] + D.bp[(size_t)cl * 6 + j]);
                 a1[0] = s;
-                lba_se3_oplus(T, x);
+                se3_oplus(T, T + 3, x);
             }
 #pragma unroll
             for (int j = 0; j < 7; j++) D.pose[c ^ 1][(size_t)k * 7 + j] = T[j];
@@ -552,7 +448,7 @@ __global__ __launch_bounds__(LBA_THREADS) void k_lba_update(LbaDev D, int c, dou
             for (int l = 0; l < 3; l++) D.pt[c ^ 1][(size_t)p * 3 + l] = X[l];
         }
     }
-    lba_block_sum<1>(a1, part);
+    block_sum<LBA_LANES, LBA_WAVES>(a1, part);
     if (threadIdx.x == 0) D.partScale[blockIdx.x] = a1[0];
 }
 
@@ -562,8 +458,8 @@ __global__ __launch_bounds__(LBA_THREADS) void k_lba_trial_reduce(LbaDev D, int 
     double a1[1] = {0.0}, a2[1] = {0.0};
     for (int i = threadIdx.x; i < nbE; i += LBA_THREADS) a1[0] += D.partChi[i];
     for (int i = threadIdx.x; i < nbS; i += LBA_THREADS) a2[0] += D.partScale[i];
-    lba_block_sum<1>(a1, part[0]);
-    lba_block_sum<1>(a2, part[1]);
+    block_sum<LBA_LANES, LBA_WAVES>(a1, part[0]);
+    block_sum<LBA_LANES, LBA_WAVES>(a2, part[1]);
     if (threadIdx.x == 0) { D.rec->tmpChi = a1[0]; D.rec->scale = a2[0]; }
 }
 
@@ -576,7 +472,7 @@ __global__ __launch_bounds__(LBA_THREADS) void k_lba_classify(LbaDev D, int c, i
     const double *T = D.pose[c] + (size_t)o.kf * 7, *Xp = D.pt[c] + (size_t)o.pt * 3;
     const double q[4] = {T[3], T[4], T[5], T[6]}, Xw[3] = {Xp[0], Xp[1], Xp[2]};
     double X[3];
-    lba_quat_rotate(q, Xw, X);
+    quat_rotate(q, Xw, X);
     const double z = X[2] + T[2];
     const bool out = D.chi2[e] > (o.ur < 0.f ? 5.991 : 7.815) || !(z > 0.0);
     if (final) D.erase[e] = out ? 1 : 0;
@@ -595,7 +491,7 @@ __global__ __launch_bounds__(LBA_THREADS) void k_lba_out(LbaDev D, int c, int un
         } else {
             const double q[4] = {T[3], T[4], T[5], T[6]};
             double R[9];
-            lba_quat_to_R(q, R);
+            quat_to_R(q, R);
             for (int r = 0; r < 3; r++) {
                 for (int cc = 0; cc < 3; cc++) to[r * 4 + cc] = (float)R[r * 3 + cc];
                 to[r * 4 + 3] = (float)T[r];
@@ -674,7 +570,6 @@ struct LbaMem {
 #ifdef ORBX_LBA_HOST
 #define LBA_LAUNCH(kern, grid, lds, ...) do { for (int b_ = 0; b_ < (int)(grid); b_++) { blockIdx.x = b_; kern(__VA_ARGS__); } blockIdx.x = 0; } while (0)
 #define LBA_TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
-struct StagePlan { size_t off = 0; size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; } };
 #else
 #define LBA_LAUNCH(kern, grid, lds, ...) do { hipLaunchKernelGGL(kern, dim3(grid), dim3(LBA_THREADS), lds, M.st, __VA_ARGS__); ORBX_HIP(hipGetLastError()); } while (0)
 #define LBA_TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)

@@ -22,6 +22,7 @@
 #endif
 #include <float.h>
 #include <math.h>
+#include "orbx_g2omath.h"
 
 #define PO_WAVES ((PO_THREADS + PO_LANES - 1) / PO_LANES)
 #define PO_LDS_EDGES 1536   // observations staged in LDS (32 B each, 48 KiB: with the static arrays under the 64 KiB a launch gets unasked); the rest is read from HBM / L2
@@ -32,112 +33,7 @@ struct PoseProblem { int32_t off, n; orbm_camera_t cam; float Tcw[16]; };
 struct PoseDevSrc { const orbx_keypoint_t *kun; const float *uright; const orbo_worldpos_t *pts; float is2[ORBX_MAX_LEVELS]; int nlevels; float dMono, dStereo; };
 struct Se3 { double t[3], q[4]; };   // q = x y z w
 struct PoCam { double fx, fy, cx, cy, bf; float dMono, dStereo; };
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int m = PO_LANES / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, PO_LANES);   // a + b == b + a bit for bit: every lane ends with the same sum
-    return v;
-}
-template <int K>
-__device__ __forceinline__ void block_sum(double (&a)[K], double *part) {
-    const int lane = threadIdx.x % PO_LANES, wave = threadIdx.x / PO_LANES;
-#pragma unroll
-    for (int k = 0; k < K; k++) a[k] = wave_sum(a[k]);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < K; k++) part[wave * K + k] = a[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; k++) {
-        double t = part[k];
-#pragma unroll
-        for (int w = 1; w < PO_WAVES; w++) t += part[w * K + k];   // ((w0 + w1) + w2) + w3
-        a[k] = t;
-    }
-}
-
-// Eigen::Quaternion(Matrix3) (Shoemake), as SE3Quat(R, t) and SE3Quat::exp use it
-__device__ __forceinline__ void quat_from_R(const double R[9], double q[4]) {
-    double t = R[0] + R[4] + R[8];
-    if (t > 0.0) {
-        t = sqrt(t + 1.0);
-        q[3] = 0.5 * t;
-        t = 0.5 / t;
-        q[0] = (R[7] - R[5]) * t; q[1] = (R[2] - R[6]) * t; q[2] = (R[3] - R[1]) * t;
-    } else {
-        int i = 0;
-        if (R[4] > R[0]) i = 1;
-        if (R[8] > R[i * 4]) i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        t = sqrt(R[i * 4] - R[j * 4] - R[k * 4] + 1.0);
-        double v[3];
-        v[i] = 0.5 * t;
-        t = 0.5 / t;
-        q[3] = (R[k * 3 + j] - R[j * 3 + k]) * t;
-        v[j] = (R[j * 3 + i] + R[i * 3 + j]) * t;
-        v[k] = (R[k * 3 + i] + R[i * 3 + k]) * t;
-        q[0] = v[0]; q[1] = v[1]; q[2] = v[2];
-    }
-}
-__device__ __forceinline__ void normalize_rotation(double q[4]) {   // se3quat.h:280-285
-    if (q[3] < 0.0) { q[0] = -q[0]; q[1] = -q[1]; q[2] = -q[2]; q[3] = -q[3]; }
-    const double n = sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-    q[0] /= n; q[1] /= n; q[2] /= n; q[3] /= n;
-}
-__device__ __forceinline__ void quat_rotate(const double q[4], const double v[3], double r[3]) {   // Quaternion * Vector3 (_transformVector)
-    double uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]};
-    uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
-    r[0] = (v[0] + q[3] * uv[0]) + (q[1] * uv[2] - q[2] * uv[1]);
-    r[1] = (v[1] + q[3] * uv[1]) + (q[2] * uv[0] - q[0] * uv[2]);
-    r[2] = (v[2] + q[3] * uv[2]) + (q[0] * uv[1] - q[1] * uv[0]);
-}
-__device__ __forceinline__ void quat_to_R(const double q[4], double R[9]) {   // Quaternion::toRotationMatrix
-    const double tx = 2.0 * q[0], ty = 2.0 * q[1], tz = 2.0 * q[2];
-    const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3], txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
-    const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
-    R[0] = 1.0 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
-    R[3] = txy + twz; R[4] = 1.0 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1.0 - (txx + tyy);
-}
-// VertexSE3Expmap::oplusImpl: estimate = SE3Quat::exp(x) * estimate (se3quat.h:223-257, :104-110); x = omega | upsilon
-__device__ __forceinline__ void se3_oplus(Se3 &T, const double x[6]) {
-    const double o0 = x[0], o1 = x[1], o2 = x[2];
-    const double theta = sqrt((o0 * o0 + o1 * o1) + o2 * o2);
-    const double Om[9] = {0.0, -o2, o1, o2, 0.0, -o0, -o1, o0, 0.0};
-    double Om2[9];
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) Om2[r * 3 + c] = (Om[r * 3] * Om[c] + Om[r * 3 + 1] * Om[3 + c]) + Om[r * 3 + 2] * Om[6 + c];
-    double a, b, c2;
-    if (theta < 0.00001) { a = 1.0; b = 1.0; c2 = 1.0; }   // R = I + Omega + Omega^2, V = R
-    else {
-        const double s = sin(theta), co = cos(theta);
-        a = s / theta; b = (1.0 - co) / (theta * theta); c2 = (theta - s) / (theta * theta * theta);
-    }
-    double R[9], V[9];
-#pragma unroll
-    for (int k = 0; k < 9; k++) {
-        const double id = (k == 0 || k == 4 || k == 8) ? 1.0 : 0.0;
-        R[k] = (id + a * Om[k]) + b * Om2[k];
-        V[k] = theta < 0.00001 ? R[k] : (id + b * Om[k]) + c2 * Om2[k];
-    }
-    double qe[4], te[3];
-    quat_from_R(R, qe);
-    normalize_rotation(qe);
-#pragma unroll
-    for (int r = 0; r < 3; r++) te[r] = (V[r * 3] * x[3] + V[r * 3 + 1] * x[4]) + V[r * 3 + 2] * x[5];
-    double rt[3];
-    quat_rotate(qe, T.t, rt);
-    const double ax = qe[0], ay = qe[1], az = qe[2], aw = qe[3], bx = T.q[0], by = T.q[1], bz = T.q[2], bw = T.q[3];
-    T.t[0] = te[0] + rt[0]; T.t[1] = te[1] + rt[1]; T.t[2] = te[2] + rt[2];
-    T.q[3] = ((aw * bw - ax * bx) - ay * by) - az * bz;
-    T.q[0] = ((aw * bx + ax * bw) + ay * bz) - az * by;
-    T.q[1] = ((aw * by + ay * bw) + az * bx) - ax * bz;
-    T.q[2] = ((aw * bz + az * bw) + ax * by) - ay * bx;
-    normalize_rotation(T.q);
-}
+// block_sum, the quaternion functions, se3_oplus and the LDL^T are orbx_g2omath.h's
 
 // One edge at pose T: project, error, chi2, Huber; LIN: + its share of H (21 upper entries, row-major), b (6) in acc[0..26].
 // acc[27] += rho[0].  Returns the plain chi2 (BaseEdge::chi2).  A monocular edge is the stereo one with a zero third row.
@@ -212,59 +108,6 @@ __device__ __forceinline__ double edge_eval(const orbo_observation_t &o, const P
     return chi2;
 }
 
-// (H + lambda I) x = b by an unpivoted LDL^T in double.  false when a pivot is not positive (LinearSolverDense: !isPositive()): then
-// x = 0 and the caller leaves the pose unchanged for that trial (tempChi = DBL_MAX rejects it), where g2o applies whatever x its
-// solver still held before it restores the estimate.  Where Eigen's pivoted LDLT would decide differently (a singular H) the
-// behaviour is not pinned.
-__device__ __forceinline__ bool solve6(const double *Hu, const double *b, double lambda, double *x) {
-    double A[6][6], L[6][6], D[6];
-    int k = 0;
-#pragma unroll
-    for (int j = 0; j < 6; j++)
-#pragma unroll
-        for (int l = j; l < 6; l++, k++) { A[j][l] = Hu[k]; A[l][j] = Hu[k]; }
-#pragma unroll
-    for (int j = 0; j < 6; j++) A[j][j] += lambda;
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-        double d = A[j][j];
-#pragma unroll
-        for (int m = 0; m < j; m++) d -= (L[j][m] * L[j][m]) * D[m];
-        if (!(d > 0.0) || !(d <= DBL_MAX)) ok = false;
-        D[j] = d;
-#pragma unroll
-        for (int i = j + 1; i < 6; i++) {
-            double s = A[i][j];
-#pragma unroll
-            for (int m = 0; m < j; m++) s -= (L[i][m] * L[j][m]) * D[m];
-            L[i][j] = s / d;
-        }
-    }
-    double yv[6];
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        double s = b[i];
-#pragma unroll
-        for (int m = 0; m < i; m++) s -= L[i][m] * yv[m];
-        yv[i] = s;
-    }
-#pragma unroll
-    for (int i = 0; i < 6; i++) yv[i] = yv[i] / D[i];
-#pragma unroll
-    for (int i = 5; i >= 0; i--) {
-        double s = yv[i];
-#pragma unroll
-        for (int m = i + 1; m < 6; m++) s -= L[m][i] * x[m];
-        x[i] = s;
-    }
-    if (!ok) {
-#pragma unroll
-        for (int i = 0; i < 6; i++) x[i] = 0.0;
-    }
-    return ok;
-}
-
 __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(const PoseProblem *__restrict__ probs, const orbo_observation_t *__restrict__ obs,
                                                          PoseDevSrc src, uint8_t *__restrict__ outl, float *__restrict__ chi,
                                                          float *__restrict__ Tout, int32_t *__restrict__ ngood,
@@ -336,7 +179,7 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(const PoseProblem *__re
                     const orbo_observation_t o = load(i);
                     if (o.valid && !fl[i]) ch[i] = (float)edge_eval<true>(o, cam, T, robust, acc);
                 }
-                block_sum<PO_NACC>(acc, part[buf]); buf ^= 1;
+                block_sum<PO_LANES, PO_WAVES>(acc, part[buf]); buf ^= 1;
                 double cur = acc[27];
                 const double iniChi = cur;
                 if (it == 0) {   // computeLambdaInit: tau * max |diag H|
@@ -350,8 +193,8 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(const PoseProblem *__re
                 for (int trial = 0; trial < 10; trial++) {
                     const Se3 backup = T;
                     double x[6];
-                    const bool ok = solve6(acc, acc + 21, lambda, x);
-                    if (ok) se3_oplus(T, x);
+                    const bool ok = ldlt_solve<6>(acc, acc + 21, lambda, x);
+                    if (ok) se3_oplus(T.t, T.q, x);
                     double a1[1] = {0.0}, tmpacc[PO_NACC];
                     tmpacc[27] = 0.0;
                     for (int i = tid; i < n; i += PO_THREADS) {
@@ -359,7 +202,7 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(const PoseProblem *__re
                         if (o.valid && !fl[i]) ch[i] = (float)edge_eval<false>(o, cam, T, robust, tmpacc);
                     }
                     a1[0] = tmpacc[27];
-                    block_sum<1>(a1, part[buf]); buf ^= 1;
+                    block_sum<PO_LANES, PO_WAVES>(a1, part[buf]); buf ^= 1;
                     double tmp = a1[0];
                     if (!ok) tmp = DBL_MAX;
                     double scale = 0.0;

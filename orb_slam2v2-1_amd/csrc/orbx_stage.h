@@ -1,5 +1,5 @@
 // orbx_stage.h — the per-host-thread staging pair: a device scratch block, a pinned host mirror of the same
-// layout and a non-blocking stream, grow-only.  An entry point lays its arrays out with StagePlan, fills the mirror, moves its
+// layout and a non-blocking stream, grow-only.  An entry point lays its arrays out with StagePlan (orbx_stage_plan.h), fills the mirror, moves its
 // inputs with ONE upload and its results with ONE download + ONE synchronisation of that stream: no hipMalloc per call and no
 // device-wide synchronisation, so other threads' extractors and matchers keep running (the reference's Tracking / LocalMapping /
 // LoopClosing threads call matchers and solvers concurrently, src/LocalMapping.cc:223, src/LoopClosing.cc:249).
@@ -7,8 +7,7 @@
 // orbx_sim3.hip, orbx_pnp.hip, orbx_sim3opt.hip, orbx_newpoints.hip, orbx_lba.hip, orbx_essential.hip.
 #pragma once
 #include "orbx_internal.h"
-
-static inline size_t stage_align(size_t x) { return (x + 255) & ~(size_t)255; }
+#include "orbx_stage_plan.h"   // stage_align, StagePlan: no HIP in them
 
 struct StagePair {
     uint8_t *d = nullptr, *h = nullptr; size_t cap = 0; int device = -1; hipStream_t stream = nullptr;
@@ -40,12 +39,4 @@ struct StagePair {
         cap = c;
         return ORBX_OK;
     }
-};
-
-// layout of one call inside a StagePair: take() hands out 256-B aligned offsets; everything taken before mark_inputs() is
-// uploaded in one copy; off is then the call's need
-struct StagePlan {
-    size_t off = 0, in_end = 0;
-    size_t take(size_t bytes) { const size_t o = off; off += stage_align(bytes); return o; }
-    void mark_inputs() { in_end = off; }
 };

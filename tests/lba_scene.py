@@ -32,14 +32,16 @@ def rodrigues(rvec):
 
 
 def make(seed, nfree, nfixed, npts, stereo=0.0, outliers=0.0, noise=0.7, rot=0.01, trans=0.05, ptnoise=0.08, first_id0=False,
-         behind=False, grazing=False, dead_point=False, dead_pose=False, shuffle=False, idle=0):
+         behind=False, grazing=False, dead_point=False, dead_pose=False, shuffle=False, idle=0, turned=False):
     """-> dict(kfs, pts, obs, true_poses [K, 4, 4], true_pts [P, 3], gross [E] bool, special: names -> indices).
     stereo: the fraction of stereo observations (0: monocular only, 1: stereo only).  first_id0: the first local keyframe is fixed
     (mnId == 0).  behind: one more point BEHIND keyframe 0, observed by keyframes 0 and 1.  grazing: one more point in the image plane
     of keyframe 0 (depth 0 at the truth), seen by it with inv_sigma2 = 0 (chi2 = 0: only the depth test can flag it) and by two others.
     dead_point: one more point whose observations are all gross outliers.  dead_pose: one more free keyframe whose observations are
     all gross outliers.  shuffle: the observations in a random order.  idle: that many fixed keyframes without any observation IN FRONT of
-    the others, so that the keyframes that matter lie past the first workgroup of a kernel that takes one keyframe per thread."""
+    the others, so that the keyframes that matter lie past the first workgroup of a kernel that takes one keyframe per thread.
+    turned: three keyframes around the points whose Tcw are rotations of 3 rad about x, y and z - a negative trace with each diagonal
+    entry the largest once, where the path's keyframes (a few hundredths of a radian) all have a positive one."""
     rng = np.random.default_rng(seed)
     K = nfree + nfixed
     fx, fy, cx, cy, bf = CAM
@@ -52,6 +54,14 @@ def make(seed, nfree, nfixed, npts, stereo=0.0, outliers=0.0, noise=0.7, rot=0.0
     Ts = np.array(Ts)
     z = rng.uniform(4.0, 20.0, npts)
     Xw = np.stack([rng.uniform(-0.45, 0.45, npts) * z + 0.3 * K, rng.uniform(-0.12, 0.12, npts) * z, z + 0.1 * K], 1)
+    if turned:      # Rcw = 3 rad about x, y, z; every keyframe 16 m from the middle of the points, which lie closer together, looking at it
+        assert K == 3
+        mid = np.array([0.3 * K, 0.0, 12.0 + 0.1 * K])
+        Xw = mid + (Xw - mid) * [0.35, 0.5, 1.0]
+        for i in range(K):
+            Ts[i] = np.eye(4)
+            Ts[i, :3, :3] = rodrigues(3.0 * np.eye(3)[i])
+            Ts[i, :3, 3] = -Ts[i, :3, :3] @ (mid - 16.0 * Ts[i, 2, :3])      # the optical axis in the world is the third row of Rcw
     special = {}
     extra = []
     if behind:
@@ -161,6 +171,7 @@ CASES = {
     "nfL+1": dict(seed=513, nfree=L + 1, nfixed=2, npts=120, stereo=0.5, outliers=0.05),
     "wide": dict(seed=514, nfree=6, nfixed=2, npts=300, stereo=0.3, outliers=0.05),
     "many_kf": dict(seed=515, nfree=4, nfixed=2, npts=50, stereo=0.5, idle=300),
+    "turned": dict(seed=516, nfree=2, nfixed=1, npts=12, stereo=0.5, turned=True),
 }
 _cache, _refs = {}, {}
 

@@ -23,10 +23,12 @@ def pose(rvec, t):
     return T
 
 
-def make(seed, n, mono=0.0, outliers=0.0, invalid=0.0, noise=0.7, rot=0.01, trans=0.15):
-    """-> dict(obs [n] OBS_DTYPE, cam, Tcw_true float64 4x4, Tcw0 float32 4x4 (the guess), octave [n], gross [n] bool)"""
+def make(seed, n, mono=0.0, outliers=0.0, invalid=0.0, noise=0.7, rot=0.01, trans=0.15, rvec=None):
+    """-> dict(obs [n] OBS_DTYPE, cam, Tcw_true float64 4x4, Tcw0 float32 4x4 (the guess), octave [n], gross [n] bool)
+    rvec: the true rotation vector, instead of a small drawn one (the same numbers are drawn either way)"""
     rng = np.random.default_rng(seed)
-    Ttrue = pose(rng.normal(0, 0.05, 3), rng.normal(0, 1.0, 3))
+    r0, t0 = rng.normal(0, 0.05, 3), rng.normal(0, 1.0, 3)
+    Ttrue = pose(r0 if rvec is None else rvec, t0)
     z = rng.uniform(4.0, 60.0, n)
     u = rng.uniform(130, W - 30, n)                                # ur = u - bf / z stays positive down to z = 4
     v = rng.uniform(20, H - 20, n)
@@ -56,6 +58,8 @@ def make(seed, n, mono=0.0, outliers=0.0, invalid=0.0, noise=0.7, rot=0.01, tran
 # 0 / 2: fewer than 3 correspondences; 3: the minimum; 9 / 10: the `< 10` break; 63-65: a wave's edge; 255-257: the workgroup's edge and
 # the strided loop; then the mixes, each edge kind alone, invalid entries in between, and a start far enough off for a rejected trial;
 # 1536 / 1537: the last edge the kernel stages in LDS (PO_LDS_EDGES) and the first it reads from memory; 2000: well past the stage.
+# rot3x / y / z: a true pose turned 3 rad about one axis - the rotation's trace is negative and its largest diagonal entry is that
+# axis's, the three branches of quat_from_R every other scene (a rotation of ~0.05 rad) leaves alone; both edge kinds.
 CASES = {
     "n0": dict(seed=100, n=0), "n2": dict(seed=102, n=2), "n3": dict(seed=103, n=3), "n9": dict(seed=109, n=9), "n10": dict(seed=110, n=10),
     "n63": dict(seed=163, n=63, mono=0.3, outliers=0.2), "n64": dict(seed=164, n=64, mono=0.3, outliers=0.2),
@@ -67,6 +71,8 @@ CASES = {
     "far": dict(seed=200, n=200, mono=0.3, outliers=0.2, rot=0.2, trans=2.0),
     "n1536": dict(seed=1536, n=1536, mono=0.3, outliers=0.2, invalid=0.05), "n1537": dict(seed=1537, n=1537, mono=0.3, outliers=0.2, invalid=0.05),
     "n2000": dict(seed=2000, n=2000, mono=0.3, outliers=0.2, invalid=0.05),
+    "rot3x": dict(seed=3002, n=12, mono=0.4, rvec=(3.0, 0.0, 0.0)), "rot3y": dict(seed=3103, n=12, mono=0.4, rvec=(0.0, 3.0, 0.0)),
+    "rot3z": dict(seed=3202, n=12, mono=0.4, rvec=(0.0, 0.0, 3.0)),
 }
 
 

@@ -41,12 +41,15 @@ def project(K, X):
 
 
 def make(seed, n, outliers=0.0, gross_first=None, noise=0.7, rot=0.025, trans=0.04, dscale=0.015, scale=1.12, fix_scale=False, K1=K_A,
-         K2=K_A, th2=TH2):
+         K2=K_A, th2=TH2, rvec=None):
     """-> dict(matches [n] MATCH_DTYPE, prob [1] PROBLEM_DTYPE record, true (the true Sim3 S12), gross [n] bool, octave [n, 2]).
-    gross_first = g: exactly the first g matches are gross outliers (instead of the fraction `outliers`)."""
+    gross_first = g: exactly the first g matches are gross outliers (instead of the fraction `outliers`).  rvec: the true rotation
+    vector, instead of a small drawn one (the same numbers are drawn either way); turned about x or y the points lie BEHIND camera 2,
+    which neither edge asks about (the reference has no depth test here)."""
     rng = np.random.default_rng(seed)
     s_true = 1.0 if fix_scale else scale * float(np.exp(rng.normal(0, 0.03)))
-    St = R.Sim3(R.quat_from_R(rodrigues(rng.normal(0, 0.06, 3))), rng.normal(0, 0.25, 3), s_true)
+    r_true = rng.normal(0, 0.06, 3)
+    St = R.Sim3(R.quat_from_R(rodrigues(r_true if rvec is None else rvec)), rng.normal(0, 0.25, 3), s_true)
     Tcw1 = pose(rng.normal(0, 0.3, 3), rng.normal(0, 2.0, 3)).astype(np.float32)
     Tcw2 = pose(rng.normal(0, 0.3, 3), rng.normal(0, 2.0, 3)).astype(np.float32)
     z = rng.uniform(4.0, 30.0, n)
@@ -89,7 +92,8 @@ L = lds_rows()
 # then the `< 10` return; 10: the smallest that runs both rounds; clean64: no drop, so the second round has 5 iterations; out65: drops,
 # so it has 10, and one match past a wave; fix_scale65: update[6] = 0; drop_below10: 14 matches of which 6 are gross - 8 < 10 survive
 # round one; far: a start far enough off that a trial is rejected; L, L + 1, 1.3 L: the last match staged in LDS, the first read from
-# memory, and more than a workgroup's worth past it; mixed300: two different cameras.
+# memory, and more than a workgroup's worth past it; mixed300: two different cameras; rot3x / y / z: S12 turned 3 rad about one axis -
+# a rotation of negative trace whose largest diagonal entry is that axis's, the three branches of quat_from_R no other scene reaches.
 CASES = {
     "n0": dict(seed=400, n=0), "n9": dict(seed=409, n=9), "n10": dict(seed=410, n=10),
     "clean64": dict(seed=464, n=64), "out65": dict(seed=465, n=65, outliers=0.2),
@@ -99,6 +103,8 @@ CASES = {
     "nL": dict(seed=3024, n=L, outliers=0.2), "nL+1": dict(seed=1025, n=L + 1, outliers=0.2),
     "n1.3L": dict(seed=4331, n=L + L * 3 // 10, outliers=0.2),
     "mixed300": dict(seed=300, n=300, outliers=0.25, K1=K_A, K2=K_B),
+    "rot3x": dict(seed=431, n=12, rvec=(3.0, 0.0, 0.0)), "rot3y": dict(seed=432, n=12, rvec=(0.0, 3.0, 0.0)),
+    "rot3z": dict(seed=433, n=12, rvec=(0.0, 0.0, 3.0)),
 }
 _cache = {}
 
