@@ -249,29 +249,62 @@ __global__ __launch_bounds__(LBA_THREADS) void k_lba_pose(LbaDev D) {
     }
 }
 
-// after a linearisation: activeRobustChi2 from the partial sums, and computeLambdaInit's max |diagonal| over the active vertices
+// after a linearisation: activeRobustChi2 from the partial sums, and computeLambdaInit's max |diagonal| over the active vertices.
+// computeLambdaInit (optimization_algorithm_levenberg.cpp:171-178) walks the diagonal - the poses' entries, then the points' - with
+// maxDiagonal = std::max(fabs(h), maxDiagonal), which keeps its FIRST argument unless that is the smaller one: a NaN entry replaces
+// the running maximum, and the entry after it replaces the NaN.  So the result is the maximum over the entries after the last NaN,
+// and NaN when the last entry is one.  Without a NaN that is the plain maximum (from 0).
 __global__ __launch_bounds__(LBA_THREADS) void k_lba_lin_reduce(LbaDev D, int nbE) {
     __shared__ double part[LBA_WAVES];
     __shared__ double mx[LBA_THREADS];
+    __shared__ long long at[LBA_THREADS];
+    const int dp[6] = {0, 6, 11, 15, 18, 20}, dl[3] = {0, 3, 5};
+    const int tid = threadIdx.x;
     double a1[1] = {0.0}, md = 0.0;
-    for (int i = threadIdx.x; i < nbE; i += LBA_THREADS) a1[0] += D.partChi[i];
+    for (int i = tid; i < nbE; i += LBA_THREADS) a1[0] += D.partChi[i];
     block_sum<LBA_LANES, LBA_WAVES>(a1, part);
-    for (int i = threadIdx.x; i < D.nf; i += LBA_THREADS) {
-        const double *H = D.Hpp + (size_t)i * 21;
-        md = fmax(fabs(H[0]), md); md = fmax(fabs(H[6]), md); md = fmax(fabs(H[11]), md);
-        md = fmax(fabs(H[15]), md); md = fmax(fabs(H[18]), md); md = fmax(fabs(H[20]), md);
-    }
-    for (int i = threadIdx.x; i < D.P; i += LBA_THREADS) {
+    long long last = -1;               // the last NaN's place in computeLambdaInit's walk
+    for (int i = tid; i < D.nf; i += LBA_THREADS)
+        for (int j = 0; j < 6; j++) {
+            const double h = D.Hpp[(size_t)i * 21 + dp[j]];
+            if (h != h) last = (long long)i * 6 + j;
+            md = fmax(fabs(h), md);    // fmax drops a NaN: the plain maximum, which is the answer when there is none
+        }
+    for (int i = tid; i < D.P; i += LBA_THREADS) {
         if (!D.pact[i]) continue;
-        const double *H = D.Hll + (size_t)i * 6;
-        md = fmax(fabs(H[0]), md); md = fmax(fabs(H[3]), md); md = fmax(fabs(H[5]), md);
+        for (int l = 0; l < 3; l++) {
+            const double h = D.Hll[(size_t)i * 6 + dl[l]];
+            if (h != h) last = (long long)D.nf * 6 + (long long)i * 3 + l;
+            md = fmax(fabs(h), md);
+        }
     }
-    mx[threadIdx.x] = md;
+    at[tid] = last; mx[tid] = md;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int i = 1; i < LBA_THREADS; i++) md = fmax(mx[i], md);   // a maximum: any order gives the same value
+    for (int s = LBA_THREADS / 2; s > 0; s >>= 1) {   // maxima of numbers: any order gives the same value
+        if (tid < s) { at[tid] = at[tid + s] > at[tid] ? at[tid + s] : at[tid]; mx[tid] = fmax(mx[tid + s], mx[tid]); }
+        __syncthreads();
+    }
+    last = at[0];
+    if (last >= 0) {                   // uniform over the workgroup: a NaN on the diagonal, so only the entries after the last one count
+        md = -1.0;                     // -1: no such entry yet (every |h| is at least 0)
+        for (int i = tid; i < D.nf; i += LBA_THREADS)
+            for (int j = 0; j < 6; j++)
+                if ((long long)i * 6 + j > last) md = fmax(fabs(D.Hpp[(size_t)i * 21 + dp[j]]), md);
+        for (int i = tid; i < D.P; i += LBA_THREADS) {
+            if (!D.pact[i]) continue;
+            for (int l = 0; l < 3; l++)
+                if ((long long)D.nf * 6 + (long long)i * 3 + l > last) md = fmax(fabs(D.Hll[(size_t)i * 6 + dl[l]]), md);
+        }
+        mx[tid] = md;                  // nobody reads mx between the loop's last barrier and the next one
+        __syncthreads();
+        for (int s = LBA_THREADS / 2; s > 0; s >>= 1) {
+            if (tid < s) mx[tid] = fmax(mx[tid + s], mx[tid]);
+            __syncthreads();
+        }
+    }
+    if (tid == 0) {
         D.rec->linChi = a1[0];
-        D.rec->maxDiag = md;
+        D.rec->maxDiag = mx[0] >= 0.0 ? mx[0] : NAN;
     }
 }
 
@@ -392,6 +425,9 @@ __global__ __launch_bounds__(LBA_THREADS) void k_lba_solve(LbaDev D, int inLds) 
 // The trial estimates from the current ones: workgroups [0, nbK) take the keyframes (exp(xp) * T for a column), the rest the points
 // (xl = Dinv (bl - W^T xp) over the point's active edges in ascending input index, then +=).  A vertex outside the problem, and every
 // vertex after a failed solve, is copied.  Each workgroup leaves its share of computeScale: sum x (lambda x + b).
+// After a failed solve g2o's x is what the call before left there (block_solver.hpp:447-457 returns before writing it; solver.cpp:54
+// allocates it without clearing), so the first failure reads memory nobody wrote.  Here x is zero then, and computeScale still runs
+// over every entry as :185-187 does: 0 * (lambda * 0 + b) is NaN where b or lambda is not finite, and the trial is rejected.
 __global__ __launch_bounds__(LBA_THREADS) void k_lba_update(LbaDev D, int c, double lambda, int nbK) {
     __shared__ double part[LBA_WAVES];
     const int ok = D.rec->ok;
@@ -403,14 +439,14 @@ __global__ __launch_bounds__(LBA_THREADS) void k_lba_update(LbaDev D, int c, dou
 #pragma unroll
             for (int j = 0; j < 7; j++) T[j] = D.pose[c][(size_t)k * 7 + j];
             const int cl = D.col[k];
-            if (cl >= 0 && ok) {
+            if (cl >= 0) {
                 double x[6], s = 0.0;
 #pragma unroll
-                for (int j = 0; j < 6; j++) x[j] = D.xp[cl * 6 + j];
+                for (int j = 0; j < 6; j++) x[j] = D.xp[cl * 6 + j];   // zero after a failed solve
 #pragma unroll
                 for (int j = 0; j < 6; j++) s += x[j] * (lambda * x[j] + D.bp[(size_t)cl * 6 + j]);
                 a1[0] = s;
-                se3_oplus(T, T + 3, x);
+                if (ok) se3_oplus(T, T + 3, x);
             }
 #pragma unroll
             for (int j = 0; j < 7; j++) D.pose[c ^ 1][(size_t)k * 7 + j] = T[j];
@@ -419,11 +455,11 @@ __global__ __launch_bounds__(LBA_THREADS) void k_lba_update(LbaDev D, int c, dou
         const int p = ((int)blockIdx.x - nbK) * LBA_THREADS + threadIdx.x;
         if (p < D.P) {
             double X[3] = {D.pt[c][(size_t)p * 3], D.pt[c][(size_t)p * 3 + 1], D.pt[c][(size_t)p * 3 + 2]};
-            if (D.pact[p] && ok) {
+            if (D.pact[p]) {
                 const double *b = D.bl + (size_t)p * 3, *Dp = D.Dinv + (size_t)p * 6;
                 double cl[3] = {b[0], b[1], b[2]};
                 const size_t E = (size_t)D.E;
-                for (int i = D.ptStart[p]; i < D.ptStart[p + 1]; i++) {
+                for (int i = D.ptStart[p]; ok && i < D.ptStart[p + 1]; i++) {
                     const int e = D.ptEdges[i];
                     if (D.flag[e]) continue;
                     const int cc = D.col[D.obs[e].kf];
@@ -437,11 +473,12 @@ __global__ __launch_bounds__(LBA_THREADS) void k_lba_update(LbaDev D, int c, dou
                         cl[l] -= t;
                     }
                 }
-                const double xl[3] = {(Dp[0] * cl[0] + Dp[1] * cl[1]) + Dp[2] * cl[2], (Dp[1] * cl[0] + Dp[3] * cl[1]) + Dp[4] * cl[2],
-                                      (Dp[2] * cl[0] + Dp[4] * cl[1]) + Dp[5] * cl[2]};
+                double xl[3] = {(Dp[0] * cl[0] + Dp[1] * cl[1]) + Dp[2] * cl[2], (Dp[1] * cl[0] + Dp[3] * cl[1]) + Dp[4] * cl[2],
+                                (Dp[2] * cl[0] + Dp[4] * cl[1]) + Dp[5] * cl[2]};
+                if (!ok) xl[0] = xl[1] = xl[2] = 0.0;
                 double s = 0.0;
 #pragma unroll
-                for (int l = 0; l < 3; l++) { s += xl[l] * (lambda * xl[l] + b[l]); X[l] += xl[l]; }
+                for (int l = 0; l < 3; l++) { s += xl[l] * (lambda * xl[l] + b[l]); if (ok) X[l] += xl[l]; }
                 a1[0] = s;
             }
 #pragma unroll

@@ -538,7 +538,7 @@ def optimize(vertices, edges, points, fix_scale, iterations=20, order=None, pert
         if it == 0:
             lam, ni, nbad = 1e-16, 2.0, 0
         q, rho, ini = 0, 0.0, 0.0
-        rhos = []
+        rhos, tmps, oks = [], [], []
         while True:
             x, last_ok, _ = factor_solve(sym, Hd, Hoff, b, lam)
             trial = tuple(a.copy() for a in est)
@@ -562,6 +562,7 @@ def optimize(vertices, edges, points, fix_scale, iterations=20, order=None, pert
                 cur = ini = lin_chi
                 if it == 0:
                     info["chi2_first"] = cur
+            tmps.append(tmp); oks.append(last_ok)
             if not last_ok:
                 tmp = DBL_MAX
             with np.errstate(all="ignore"):
@@ -584,7 +585,7 @@ def optimize(vertices, edges, points, fix_scale, iterations=20, order=None, pert
         info["trials_it"][info["iterations"]] = q
         info["iterations"] += 1
         info["trials"] += q
-        tr.iterations.append(dict(chi2=ini, chi2_after=cur, rho=rhos))
+        tr.iterations.append(dict(chi2=ini, chi2_after=cur, rho=rhos, tmp=tmps, ok=oks))
         if q == MAX_TRIALS or rho == 0.0:
             ok = False
             info["end"] = END_SOLVER if not last_ok else END_QMAX if q == MAX_TRIALS else END_RHO0

@@ -115,6 +115,11 @@ def _ring(n, band, seed, fix_scale, sd=0.0, **kw):
 # under a bound (csrc/orbx_essential.hip keeps only the 7x7 diagonal block there), so no case sits on either side of one; the
 # constants that choose a path are the 256 threads of a workgroup (wide: 316 edges, 80 vertices x 7 rows and 49-entry blocks on
 # both sides of it) and the 16 slots of an edge.
+# The Levenberg branches (optimization_algorithm_levenberg.cpp:100-161; tests/test_lm_branches_cpu.py counts them): every case
+# accepts one trial per iteration until it ends.  The fixed-scale cases end by ten rejected trials whose rho is rounding noise;
+# ring_free_scale, branches and ring_rejected by ten rejected trials with |rho| far above it (ring_rejected: [1, 1, 10], rho from
+# -1.2 to -0.23, after two accepted steps - so `iterations=2` and `iterations=3` must leave the same estimates); ring_nbad by three
+# iterations of negligible gain (ORBG_END_NBAD, trials [1, 1, 1, 1, 1], every |rho| >= 3.6e-5).
 CASES = {
     "chain": dict(seed=701, n=12, groups=[[10, 11]]),
     "ring_fixed_scale": _ring(24, 3, 752, True),
@@ -129,6 +134,8 @@ CASES = {
     "branches": dict(seed=710, n=11, parents=[-1, 0, 1, 2, 3, 4, 5, 6, 7, 8, 0], extra=[(i, i - 2, 1) for i in range(2, 10)],
                      groups=[[3], [6], [8, 9], [10]], group_scale=[1.0, None, None, 1.02], group_pure=[False, False, False, True],
                      fix_scale=False, sd=0.004, group_rot=0.05, angle=[0.3 * k for k in range(10)] + [-0.3]),
+    "ring_nbad": _ring(24, 3, 752, True, group_rot=0.5),
+    "ring_rejected": _ring(24, 3, 703, False, sd=0.002, group_rot=3.0),
 }
 _cache, _refs = {}, {}
 
@@ -155,3 +162,18 @@ def reference(name):
         dev = max([0.0] + [float(np.abs(d["est"] - ref["est"]).max()) for d in draws])
         _refs[name] = (sc, ref, draws, dev)
     return _refs[name]
+
+
+_cuts = {}
+
+
+def reference_cut(name, iterations):
+    """reference() for a call cut short after `iterations` iterations: S is the spread of THAT run over its 16 draws"""
+    if (name, iterations) not in _cuts:
+        sc = case(name)
+        ref = run(sc, iterations=iterations)
+        rng = np.random.default_rng(4321)
+        draws = [run(sc, order=rng, perturb=rng, iterations=iterations) for _ in range(DRAWS)]
+        dev = max([0.0] + [float(np.abs(d["est"] - ref["est"]).max()) for d in draws])
+        _cuts[(name, iterations)] = (sc, ref, draws, dev)
+    return _cuts[(name, iterations)]

@@ -266,15 +266,20 @@ class Round:
         po = self.sum_pose(ed[self.pe][:, 9:36])
         self.Hll, self.bl, self.Hpp, self.bp = pt[:, :6], pt[:, 6:], po[:, :21], po[:, 21:]
         self.W = ed[:, 36:].reshape(-1, 6, 3)
+        # computeLambdaInit, optimization_algorithm_levenberg.cpp:171-178: maxDiagonal = std::max(fabs(h), maxDiagonal) over the poses'
+        # diagonals, then the points'.  std::max(a, b) is (a < b) ? b : a, so a NaN h replaces the running maximum and the next h
+        # replaces the NaN: the maximum over the entries after the last NaN, NaN when the last entry is one
+        diag = np.concatenate([np.abs(self.Hpp[:, DIAG6]).reshape(-1), np.abs(self.Hll[self.pact][:, DIAG3]).reshape(-1)])
         md = 0.0
-        if self.nf:
-            md = max(md, float(np.abs(self.Hpp[:, DIAG6]).max()))
-        if self.pact.any():
-            md = max(md, float(np.abs(self.Hll[self.pact][:, DIAG3]).max()))
+        for a in diag.tolist():
+            md = md if a < md else a
         return md
 
     def solve(self, lam):
-        """one trial's linear step -> (ok, xp [nf, 6], xl [P, 3]); x = 0 after a bad pivot"""
+        """one trial's linear step -> (ok, xp [nf, 6], xl [P, 3]); x = 0 after a bad pivot.  (g2o's x then is what the solve before
+        left - block_solver.hpp:447-457 returns before writing it - and at a call's first solve what `new double[]` held,
+        solver.cpp:54: uninitialised memory.  Zero is the kernels' deterministic choice, as for a never-evaluated edge's chi2;
+        computeScale below still runs over every entry, so a non-finite b makes the scale NaN as :185-187 would with x = 0.)"""
         pb, nf, W = self.pb, self.nf, self.W
         with np.errstate(all="ignore"):
             H = self.Hll
@@ -354,7 +359,9 @@ class Round:
 def optimize(kfs, pts, obs, schedule=None, stop=None, order=None, perturb=None, exact_invz=False):
     """-> dict(Tcw [K, 4, 4] float32, pts [P, 3] float32, erase [E] uint8, kf_est [K, 7] (q, t), pt_est [P, 3], info, trace).
     stop: a callable polled where the reference reads pbStopFlag.  trace[r] = dict(iterations, trials, accepted, chis (the chi2 after
-    every accepted trial, from the first linearisation's), min_abs_rho); trace_class = per classification dict(min_margin, min_depth)."""
+    every accepted trial, from the first linearisation's), min_abs_rho, and per iteration trials_it, rhos_it, tmps_it (the trial's
+    chi2 as summed, before a failed solve makes it DBL_MAX) and oks_it (the solver's ok); ends: how the round's loop terminated);
+    trace_class = per classification dict(min_margin, min_depth, flags, depth [E] = |z|)."""
     sc = schedule_local() if schedule is None else schedule
     pb = Problem(kfs, pts, obs, exact_invz)
     K, P, E = pb.K, pb.P, pb.E
@@ -378,7 +385,7 @@ def optimize(kfs, pts, obs, schedule=None, stop=None, order=None, perturb=None, 
         with np.errstate(all="ignore"):
             out = (last > pb.thr) | ~(z > 0.0)
             trace_class.append(dict(min_margin=float(np.abs(last / pb.thr - 1.0).min()) if E else np.inf,
-                                    min_depth=float(np.abs(z).min()) if E else np.inf, flags=out.copy()))
+                                    min_depth=float(np.abs(z).min()) if E else np.inf, flags=out.copy(), depth=np.abs(z)))
         return out
 
     untouched = False
@@ -396,7 +403,7 @@ def optimize(kfs, pts, obs, schedule=None, stop=None, order=None, perturb=None, 
         R = Round(pb, active, order)
         info["rounds"] = rnd + 1
         info["free_poses"][rnd] = R.nf
-        tr = dict(iterations=0, trials=0, accepted=[], chis=[], min_abs_rho=np.inf)
+        tr = dict(iterations=0, trials=0, accepted=[], chis=[], min_abs_rho=np.inf, trials_it=[], rhos_it=[], tmps_it=[], oks_it=[], ends=[])
         trace.append(tr)
         if not active.any():
             continue
@@ -416,6 +423,7 @@ def optimize(kfs, pts, obs, schedule=None, stop=None, order=None, perturb=None, 
                 lam, ni, nbad_it = 1e-5 * md, 2.0, 0
                 tr["chis"].append(cur)
             rho, q = 0.0, 0
+            tr["rhos_it"].append([]); tr["tmps_it"].append([]); tr["oks_it"].append([])
             while True:
                 ok, xp, xl = R.solve(lam)
                 tposes, tpoints = poses.copy(), points.copy()
@@ -429,11 +437,14 @@ def optimize(kfs, pts, obs, schedule=None, stop=None, order=None, perturb=None, 
                 ev = pb.evaluate(tposes, tpoints, robust, dM, dS, False)
                 last[active] = ev["chi2"][active]
                 tmp = R.chi(ev["rho0"])
+                tr["tmps_it"][-1].append(tmp)
+                tr["oks_it"][-1].append(ok)
                 if not ok:
                     tmp = DBL_MAX
                 with np.errstate(all="ignore"):
                     rho = (cur - tmp) / (sc_ + 1e-3)
                 tr["min_abs_rho"] = min(tr["min_abs_rho"], abs(rho)) if rho == rho else 0.0
+                tr["rhos_it"][-1].append(rho)
                 if rho > 0.0 and abs(tmp) <= DBL_MAX:
                     u = 2.0 * rho - 1.0
                     alpha = min(1.0 - (u * u) * u, 2.0 / 3.0)
@@ -455,13 +466,16 @@ def optimize(kfs, pts, obs, schedule=None, stop=None, order=None, perturb=None, 
                     break
             tr["iterations"] += 1
             tr["trials"] += q
+            tr["trials_it"].append(q)
             info["iterations"][rnd], info["trials"][rnd] = tr["iterations"], tr["trials"]
             if q == MAX_TRIALS or rho == 0.0:
                 ok_loop = False
+                tr["ends"].append("qmax" if q == MAX_TRIALS else "rho0")
                 continue
             nbad_it = nbad_it + 1 if (ini - cur) * 1e3 < ini else 0
             if nbad_it >= 3:
                 ok_loop = False
+                tr["ends"].append("nbad")
     erase = np.zeros(E, np.uint8)
     if do_classify:
         erase = classify().astype(np.uint8)

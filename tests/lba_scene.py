@@ -32,7 +32,7 @@ def rodrigues(rvec):
 
 
 def make(seed, nfree, nfixed, npts, stereo=0.0, outliers=0.0, noise=0.7, rot=0.01, trans=0.05, ptnoise=0.08, first_id0=False,
-         behind=False, grazing=False, dead_point=False, dead_pose=False, shuffle=False, idle=0, turned=False):
+         behind=False, grazing=False, dead_point=False, dead_pose=False, shuffle=False, idle=0, turned=False, plane_point=False):
     """-> dict(kfs, pts, obs, true_poses [K, 4, 4], true_pts [P, 3], gross [E] bool, special: names -> indices).
     stereo: the fraction of stereo observations (0: monocular only, 1: stereo only).  first_id0: the first local keyframe is fixed
     (mnId == 0).  behind: one more point BEHIND keyframe 0, observed by keyframes 0 and 1.  grazing: one more point in the image plane
@@ -41,7 +41,9 @@ def make(seed, nfree, nfixed, npts, stereo=0.0, outliers=0.0, noise=0.7, rot=0.0
     all gross outliers.  shuffle: the observations in a random order.  idle: that many fixed keyframes without any observation IN FRONT of
     the others, so that the keyframes that matter lie past the first workgroup of a kernel that takes one keyframe per thread.
     turned: three keyframes around the points whose Tcw are rotations of 3 rad about x, y and z - a negative trace with each diagonal
-    entry the largest once, where the path's keyframes (a few hundredths of a radian) all have a positive one."""
+    entry the largest once, where the path's keyframes (a few hundredths of a radian) all have a positive one.
+    plane_point: the first fixed keyframe's Tcw is the identity, and the first point it observes starts with z == 0.0 exactly: that
+    edge's depth is an exact zero, 1 / z is infinite, and every linearisation of round 1 holds non-finite entries."""
     rng = np.random.default_rng(seed)
     K = nfree + nfixed
     fx, fy, cx, cy, bf = CAM
@@ -52,6 +54,9 @@ def make(seed, nfree, nfixed, npts, stereo=0.0, outliers=0.0, noise=0.7, rot=0.0
         Twc[:3, 3] = [0.6 * i + rng.normal(0, 0.05), rng.normal(0, 0.05), 0.25 * i]
         Ts.append(np.linalg.inv(Twc))
     Ts = np.array(Ts)
+    if plane_point:
+        assert nfixed > 0
+        Ts[nfree] = np.eye(4)
     z = rng.uniform(4.0, 20.0, npts)
     Xw = np.stack([rng.uniform(-0.45, 0.45, npts) * z + 0.3 * K, rng.uniform(-0.12, 0.12, npts) * z, z + 0.1 * K], 1)
     if turned:      # Rcw = 3 rad about x, y, z; every keyframe 16 m from the middle of the points, which lie closer together, looking at it
@@ -138,6 +143,10 @@ def make(seed, nfree, nfixed, npts, stereo=0.0, outliers=0.0, noise=0.7, rot=0.0
     pts = np.zeros(P, R.PT_DTYPE)
     X0 = Xw + rng.normal(0, ptnoise, Xw.shape)
     pts["x"], pts["y"], pts["z"] = X0[:, 0], X0[:, 1], X0[:, 2]
+    if plane_point:
+        special["plane_kf"] = nfree
+        special["plane_point"] = int(obs["pt"][obs["kf"] == nfree][0])
+        pts["z"][special["plane_point"]] = 0.0
     if idle:
         front = np.zeros(idle, R.KF_DTYPE)
         front["Tcw"] = np.eye(4, dtype=np.float32).reshape(-1)
@@ -154,6 +163,11 @@ L = lds_poses()
 # 256 or 64): name -> make() arguments.  The constants that choose a path: LBA_LDS_POSES (nfL, nfL+1) and the 256 threads of a
 # workgroup - observations (every case has more), points (wide: 300) and keyframes (many_kf: 306) on both sides of it.  No kernel
 # loops by lane over a point's observations (a point is one thread), so there is no case of a point seen by more than 64 keyframes.
+# The Levenberg branches (optimization_algorithm_levenberg.cpp:100-161; tests/test_lm_branches_cpu.py counts them): most cases accept
+# every trial; outliers and shuffled reject once and accept (AAAAAAAArA); nf0 rejects in a row without a free pose; far_start rejects
+# four times in a row with four free poses and recovers (ArrrrAA, every |rho| > 1e-4); far_outliers rejects in three iterations
+# (AAArrArrArrrrrA, its last |rho| 6e-9); plane_point fails every solve of round 1 (tempChi = DBL_MAX, a NaN rho, one trial per
+# iteration) and leaves round 1 with every estimate as it came.
 CASES = {
     "mono": dict(seed=501, nfree=4, nfixed=2, npts=60),
     "stereo": dict(seed=502, nfree=4, nfixed=2, npts=60, stereo=1.0),
@@ -172,7 +186,22 @@ CASES = {
     "wide": dict(seed=514, nfree=6, nfixed=2, npts=300, stereo=0.3, outliers=0.05),
     "many_kf": dict(seed=515, nfree=4, nfixed=2, npts=50, stereo=0.5, idle=300),
     "turned": dict(seed=516, nfree=2, nfixed=1, npts=12, stereo=0.5, turned=True),
+    "far_start": dict(seed=901, nfree=4, nfixed=2, npts=40, stereo=0.5, rot=0.2, trans=0.8, ptnoise=0.8),
+    "far_outliers": dict(seed=905, nfree=4, nfixed=2, npts=40, stereo=0.5, outliers=0.1, rot=1.2, trans=4.0, ptnoise=3.0),
+    "plane_point": dict(seed=518, nfree=4, nfixed=2, npts=50, stereo=0.5, rot=0.001, trans=0.005, ptnoise=0.008, plane_point=True),
 }
+# The cases whose counts are compared in every round whatever min |rho| says: the restatement reports min |rho| = 0 for a NaN rho,
+# and plane_point's round 1 is five NaN rhos - a NaN is no rounding noise about zero, both sides must reject on it.
+COUNTS_ALWAYS = ("plane_point",)
+
+
+def depth_exempt(name):
+    """-> the edges whose depth is an exact 0.0 by construction (plane_point: a point with z == 0.0 seen by a keyframe whose Tcw is
+    the identity): z > 0 on an exact zero is not decided by rounding, so the |depth| > MARGIN condition leaves that one edge out"""
+    sc = case(name)
+    if "plane_point" not in sc["special"]:
+        return np.zeros(len(sc["obs"]), bool)
+    return (sc["obs"]["kf"] == sc["special"]["plane_kf"]) & (sc["obs"]["pt"] == sc["special"]["plane_point"])
 _cache, _refs = {}, {}
 
 

@@ -4,7 +4,8 @@ and levels equal; the double estimates within 64 x S, where S is the deviation t
 order of its sums over edges and vertices, sin / cos / acos / log / exp moved by +-2 ulp) - the kernels differ from it by the order
 of their chi2 and computeScale sums and by the device's elementary functions; the float outputs within 1 ulp + 64 x S; the trials of
 every iteration whose min |rho| exceeds 1e-6 equal, and the totals where every iteration's does (at or below it the sign of rho is
-rounding noise, and how many such iterations follow differs between the restatement's own draws); two runs byte-identical; iterations = 1; argument
+rounding noise, and how many such iterations follow differs between the restatement's own draws); two runs byte-identical; iterations = 1;
+ten rejected trials leave nothing behind (iterations = 2 against 3); argument
 errors; empty problems; a second host thread before and after orbx_thread_release_scratch; fresh scratch filled.
 
 The numeric Jacobian divides rounding noise by 2e-9, so S is near 1e-7 where a residual remains at the optimum, and near 1e-14 where
@@ -28,9 +29,15 @@ t, s of every vertex; end and trials are kernels / restatement, trials per itera
     kinds                6.951e-07  0.000e+00  0.00 S    1 / 1    1 1 1 1 10 / 1 1 1 1 10             24      9      456
     wide                 1.446e-07  0.000e+00  0.00 S    1 / 1    1 1 1 10   / 1 1 1 10              532     79     3151
     branches             6.376e-06  1.387e-09  0.00 S    1 / 1    1 10       / 1 10                   25      9      351
+    ring_nbad            4.319e-06  2.159e-06  0.50 S    4 / 4    1 1 1 1 1  / 1 1 1 1 1             123     23      387
+    ring_rejected        3.452e-04  2.039e-04  0.59 S    1 / 1    1 1 10     / 1 1 10                123     23      890
     ring_fixed_scale, 1  5.965e-07  0.000e+00  0.00 S    0 / 0    1          / 1                     123     23       79
     ring_free_scale, 1   1.780e-06  0.000e+00  0.00 S    0 / 0    1          / 1                     123     23       79
-(`, 1`: iterations = 1.  end 1: ten rejected trials, 0: the iterations asked for.)  The float outputs differ from the restatement's
+    ring_rejected, 2     4.151e-04  2.039e-04  0.49 S    0 / 0    1 1        / 1 1                   123     23      156
+(`, 1`, `, 2`: iterations = 1, 2.  end 1: ten rejected trials, 0: the iterations asked for, 4: three iterations of negligible gain.)
+ring_rejected does not converge (its second accepted step has rho = 0.86 and ten rejected trials follow, rho from -1.2 to -0.23),
+so its S is large and 64 x S says little; the call with iterations = 3 returned the bytes of the call with iterations = 2 in est,
+Tcw and the points, and an info that differs in iterations, trials, trials_it, end and launches alone.  The float outputs differ from the restatement's
 in their last place at most.  The iterations whose min |rho| is at or below 1e-6 are not compared in their counts: clique's fourth
 (1.7e-27), where the kernels reject and the restatement accepts once more; from the second or third iteration on every
 fixed-scale case is there.  Where a residual remains at the optimum the way a converged call ends is decided by the sign of such a
@@ -108,6 +115,23 @@ def test_one_iteration(pkg, name):
     res = call(pkg, sc, iterations=1)
     assert res[3]["iterations"] == 1
     compare(name + ", one iteration", res, ref, dev)
+
+
+def test_ten_popped_trials_leave_nothing_behind(pkg):
+    """ring_rejected runs [1, 1, 10]: its third iteration is ten rejected trials (rho from -1.2 to -0.23), each of them popped.  So
+    the call with iterations=3 must return the bytes of the call with iterations=2 in est, Tcw and the points, and an info that
+    differs in iterations, trials, trials_it, end and launches alone - a check that needs no tolerance, where 64 x S = 0.02 of the
+    full comparison says little.  The call cut short is compared with the restatement cut short, S being that run's own spread."""
+    sc, ref2, _, dev2 = S.reference_cut("ring_rejected", 2)
+    r2, r3 = call(pkg, sc, iterations=2), call(pkg, sc, iterations=3)
+    i2, i3 = r2[3], r3[3]
+    assert (i2["iterations"], i2["end"], list(i2["trials_it"][:3])) == (2, R.END_ITERATIONS, [1, 1, 0])
+    assert (i3["iterations"], i3["end"], list(i3["trials_it"][:3])) == (3, R.END_QMAX, [1, 1, 10])
+    assert r2[2].tobytes() == r3[2].tobytes() and r2[0].tobytes() == r3[0].tobytes() and r2[1].tobytes() == r3[1].tobytes()
+    assert {k for k in i2 if str(i2[k]) != str(i3[k])} == {"iterations", "trials", "trials_it", "end", "launches"}
+    compare("ring_rejected, 2 iterations", r2, ref2, dev2)
+    ref3 = S.reference("ring_rejected")[1]
+    assert ref3["info"]["iterations"] == 3 and ref3["est"].tobytes() == ref2["est"].tobytes()      # the restatement's two calls agree the same way
 
 
 def test_empty_and_edgeless_problems(pkg):

@@ -4,7 +4,9 @@ every output byte - the double estimates, the counts and the stop polls included
 every stop position and under BundleAdjustment's schedule.  (2) The restatement is checked by itself, since there is no g2o to link:
 both edge types' Jacobians against central differences of the error, one Schur step against numpy.linalg.solve of the full system,
 a noise-free scene converges to the truth, the total chi2 never rises across accepted trials, each scene reaches the branch it is
-named for.  (3) The conditions of the GPU comparison are asserted on the restatement alone.  (4) The same program under
+named for.  (3) The conditions of the GPU comparison are asserted on the restatement alone, per draw (plane_point's one edge whose
+depth is an exact 0.0 is left out of the depth condition, and its counts are demanded equal in every draw although its NaN rho reads
+as min |rho| = 0; the Levenberg branches the scenes enter are counted in tests/test_lm_branches_cpu.py).  (4) The same program under
 AddressSanitizer / UBSan, once.  (5) The C ABI's exports, record layouts and argument errors."""
 import ctypes as C
 import os
@@ -232,9 +234,17 @@ def test_chi2_never_rises_and_conditions_of_the_gpu_comparison(name):
         c = np.array(tr["chis"])
         assert (np.diff(c) <= 0).all(), c
     assert len(ref["trace_class"]) == 2
-    for cl in ref["trace_class"]:
-        assert cl["min_margin"] > S.MARGIN and cl["min_depth"] > S.MARGIN, (name, cl["min_margin"], cl["min_depth"])
-    assert ref["trace"][0]["min_abs_rho"] > 1e-6
+    keep = ~S.depth_exempt(name)      # plane_point: one edge's depth is an exact 0.0 by construction, which rounding does not decide
+    for r in [ref] + draws:
+        for cl in r["trace_class"]:
+            assert cl["min_margin"] > S.MARGIN and cl["depth"][keep].min() > S.MARGIN, (name, cl["min_margin"], cl["depth"][keep].min())
+            assert (cl["depth"][~keep] == 0.0).all()
+    if name in S.COUNTS_ALWAYS:       # a NaN rho (reported as min |rho| = 0) is compared in its counts all the same: every draw has them
+        for d in draws:
+            assert d["info"]["iterations"] == ref["info"]["iterations"] and d["info"]["trials"] == ref["info"]["trials"]
+            assert [t["accepted"] for t in d["trace"]] == [t["accepted"] for t in ref["trace"]]
+    else:
+        assert ref["trace"][0]["min_abs_rho"] > 1e-6
     for d in draws:
         assert (d["erase"] == ref["erase"]).all() and (d["flag"] == ref["flag"]).all() and d["info"]["free_poses"] == ref["info"]["free_poses"]
     print("%s: S = %.3e over %d draws" % (name, dev, len(draws)))
