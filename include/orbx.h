@@ -1089,7 +1089,7 @@ int orbl_create_new_map_points(const orbl_keyframe_t *cur, const uint8_t *q_desc
  * per observation, Levenberg-Marquardt with the Huber kernel over the Schur complement.  A restatement in double with the
  * reference's float narrowings ("k_lba_*").  The landmark block is block-diagonal and the reduced system, 6 Nf
  * square for Nf free keyframes, is DENSE here: it is meant for a local window (a few tens of free keyframes; it stays correct for
- * any Nf memory allows, one workgroup factorises it).  A loop-closure-sized map is outside what it is meant for.
+ * any Nf memory allows, one workgroup factorises it).  For a loop-closure-sized map: orbb_global_bundle_adjustment, below.
  * The host drives the iterations and trials: a handful of launches per linearisation and per trial on this thread's stream, one
  * stream synchronisation per trial, none device-wide.  Every sum has one owner and a fixed order: two calls give the same bytes.
  * Not pinned to g2o: the order of vertices and edges inside its sums, Eigen's sparse SimplicialLDLT against the dense LDL^T here,
@@ -1137,6 +1137,25 @@ int orbb_local_bundle_adjustment(const orbb_keyframe_t *kfs, int K, const orbb_p
 int orbb_bundle_adjustment(const orbb_keyframe_t *kfs, int K, const orbb_point_t *pts, int P, const orbb_observation_t *obs, int E,
                            int iterations, int robust, int (*stop)(void *), void *stop_user, float *Tcw_out16, float *pts_out3,
                            orbb_info_t *info, double *kf_est7, double *pt_est3, int device);
+/* The BLOCKED reduced-system path, for a loop-closure-sized map (LoopClosing::RunGlobalBundleAdjustment's
+ * GlobalBundleAdjustemnt(mpMap, 10, &mbStopGBA, nLoopKF, false), src/LoopClosing.cc:659): the same edges, Jacobians, Schur
+ * complement and Levenberg-Marquardt, but the Schur complement is summed from the pairs of keyframes that do co-observe a point
+ * (per round the host builds the block pattern and each block's contributions; no [Nf][P] table), and the dense LDL^T is blocked
+ * over the whole GPU in panels of 8 poses: factorise the diagonal block, solve the rows below it, update the trailing lower
+ * triangle tile by tile; the substitutions are blocked the same way.  Every entry of the factor and of the solution receives the
+ * operations of the one-workgroup factorisation in the same order, so one thread per workgroup gives the same bytes on both
+ * paths; the matrix is still dense (n^2 doubles, n = 6 Nf).  The functions above keep their path: nothing switches by size.
+ * binfo (may be NULL), per round: blocks of the pattern (the diagonal ones included), panels = ceil(Nf / 8), contributions summed
+ * over the blocks; launches: kernel launches of the call.  Arguments, errors and scratch as for orbb_optimize. */
+typedef struct { int32_t blocks[2], panels[2]; int64_t contributions[2], launches; } orbb_blocked_info_t;   /* per round; 40 B */
+int orbb_optimize_blocked(const orbb_keyframe_t *kfs, int K, const orbb_point_t *pts, int P, const orbb_observation_t *obs, int E,
+                          const orbb_schedule_t *schedule, int (*stop)(void *), void *stop_user, float *Tcw_out16, float *pts_out3,
+                          uint8_t *erase, orbb_info_t *info, double *kf_est7, double *pt_est3, orbb_blocked_info_t *binfo, int device);
+/* orbb_bundle_adjustment's schedule on the blocked path: one optimize(iterations), the Huber kernel iff robust, the monocular
+ * delta (float)sqrt(5.99), no classification and no :655 read.  The caller writes mTcwGBA / mPosGBA from the outputs. */
+int orbb_global_bundle_adjustment(const orbb_keyframe_t *kfs, int K, const orbb_point_t *pts, int P, const orbb_observation_t *obs, int E,
+                                  int iterations, int robust, int (*stop)(void *), void *stop_user, float *Tcw_out16, float *pts_out3,
+                                  orbb_info_t *info, double *kf_est7, double *pt_est3, orbb_blocked_info_t *binfo, int device);
 
 /* ---- Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:783-1049; prefix orbg_) ----------------------------------------------------
  * The pose graph LoopClosing::CorrectLoop optimises after it has fused the loop (src/LoopClosing.cc:576), on flat arrays: one

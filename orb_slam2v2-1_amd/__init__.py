@@ -73,6 +73,9 @@ LBA_SCHEDULE_DTYPE = np.dtype([("rounds", "<i4"), ("iterations", "<i4", (2,)), (
                                ("classify", "<i4"), ("check_stop_first", "<i4")])
 LBA_INFO_DTYPE = np.dtype([("rounds", "<i4"), ("iterations", "<i4", (2,)), ("trials", "<i4", (2,)), ("free_poses", "<i4", (2,)), ("stopped_at", "<i4"),
                            ("stop_poll", "<i4"), ("polls", "<i4"), ("erased", "<i4")])
+# orbb_blocked_info_t: per round the blocks of the reduced system's pattern, the panels of the blocked LDL^T and the contributions summed
+# into the blocks; launches: kernel launches of the call
+LBA_BLOCKED_INFO_DTYPE = np.dtype([("blocks", "<i4", (2,)), ("panels", "<i4", (2,)), ("contributions", "<i8", (2,)), ("launches", "<i8")])
 LBA_STOP_BEFORE, LBA_STOP_ROUND1, LBA_STOP_BETWEEN, LBA_STOP_ROUND2 = 1, 2, 3, 4      # info["stopped_at"]
 LBA_MAX_ITERATIONS = 100
 # orbg_sim3_t / orbg_vertex_t / orbg_edge_t / orbg_point_t / orbg_info_t (Optimizer::OptimizeEssentialGraph, optimize_essential_graph)
@@ -142,7 +145,7 @@ SIM3OPT_EXPORTS = ["orbz_optimize_sim3", "orbz_optimize_sim3_batch"]
 # the LocalMapping section (prefix orbl_), apart for the same reason
 NEWPOINTS_EXPORTS = ["orbl_triangulate", "orbl_triangulate_batch", "orbl_baseline_ok", "orbl_compute_f12", "orbl_create_new_map_points"]
 # the bundle adjustment section (prefix orbb_), apart for the same reason
-LBA_EXPORTS = ["orbb_optimize", "orbb_local_bundle_adjustment", "orbb_bundle_adjustment"]
+LBA_EXPORTS = ["orbb_optimize", "orbb_local_bundle_adjustment", "orbb_bundle_adjustment", "orbb_optimize_blocked", "orbb_global_bundle_adjustment"]
 # the essential graph section (prefix orbg_), apart for the same reason
 ESSENTIAL_EXPORTS = ["orbg_optimize_essential_graph"]
 # what include/orbx_dev.h declares on top: exported by the developer build only
@@ -461,6 +464,8 @@ def _load(path, dev):
     L.orbb_optimize.argtypes = [vp, i32, vp, i32, vp, i32, vp, LBA_STOP_FN, vp, vp, vp, vp, vp, vp, vp, i32]
     L.orbb_local_bundle_adjustment.argtypes = [vp, i32, vp, i32, vp, i32, LBA_STOP_FN, vp, vp, vp, vp, vp, vp, vp, i32]
     L.orbb_bundle_adjustment.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32, LBA_STOP_FN, vp, vp, vp, vp, vp, vp, i32]
+    L.orbb_optimize_blocked.argtypes = [vp, i32, vp, i32, vp, i32, vp, LBA_STOP_FN, vp, vp, vp, vp, vp, vp, vp, vp, i32]
+    L.orbb_global_bundle_adjustment.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32, LBA_STOP_FN, vp, vp, vp, vp, vp, vp, vp, i32]
     L.orbg_optimize_essential_graph.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, i32]
     L.orbp_pnp_parameters.argtypes = [i32, C.c_double, i32, i32, i32, f32, C.POINTER(i32), C.POINTER(i32)]
     L.orbp_pnp_ransac.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
@@ -1448,7 +1453,7 @@ def lba_schedule(rounds=2, iterations=(5, 10), robust=(1, 0), delta_mono=None, d
     return s[0]
 
 
-def _lba_run(call, keyframes, points, observations, stop, device):
+def _lba_run(call, keyframes, points, observations, stop, device, binfo=None):
     kf = np.ascontiguousarray(keyframes, LBA_KEYFRAME_DTYPE)
     pt = np.ascontiguousarray(points, LBA_POINT_DTYPE)
     ob = np.ascontiguousarray(observations, LBA_OBSERVATION_DTYPE)
@@ -1469,6 +1474,8 @@ def _lba_run(call, keyframes, points, observations, stop, device):
         raise raised[0]
     _check(rc)
     inf = {k: (int(info[0][k]) if info[0][k].ndim == 0 else [int(x) for x in info[0][k]]) for k in LBA_INFO_DTYPE.names}
+    if binfo is not None:      # the blocked path's record, filled by the call
+        inf.update({k: (int(binfo[0][k]) if binfo[0][k].ndim == 0 else [int(x) for x in binfo[0][k]]) for k in LBA_BLOCKED_INFO_DTYPE.names})
     return To, Po, erase, inf, ke, pe
 
 
@@ -1485,16 +1492,33 @@ def local_bundle_adjustment(keyframes, points, observations, stop=None, device=0
 
 def bundle_adjustment(keyframes, points, observations, iterations=5, robust=True, stop=None, device=0):
     """Optimizer::BundleAdjustment (orbb_bundle_adjustment): one optimize(iterations), the Huber kernel iff robust, no classification
-    -> as local_bundle_adjustment (erase is all zero).  Meant for the initial map, not for a loop-closure-sized one: the reduced
-    system is dense."""
+    -> as local_bundle_adjustment (erase is all zero).  Meant for the initial map: one workgroup factorises the reduced system.
+    For a loop-closure-sized map call global_bundle_adjustment, the same arithmetic on the blocked path."""
     return _lba_run(lambda L, kf, K, pt, P, ob, E, fn, To, Po, er, info, ke, pe, dev:
                     L.orbb_bundle_adjustment(kf, K, pt, P, ob, E, int(iterations), int(bool(robust)), fn, None, To, Po, info, ke, pe, dev),
                     keyframes, points, observations, stop, device)
 
 
-def bundle_adjustment_scheduled(keyframes, points, observations, schedule, stop=None, device=0):
-    """orbb_optimize: the same kernels under a caller-given schedule (lba_schedule)"""
+def global_bundle_adjustment(keyframes, points, observations, iterations=10, robust=False, stop=None, device=0):
+    """Optimizer::GlobalBundleAdjustemnt of a loop-closure-sized map (orbb_global_bundle_adjustment; the defaults are
+    LoopClosing::RunGlobalBundleAdjustment's): bundle_adjustment's schedule on the blocked reduced-system path - the Schur complement
+    summed from the keyframe pairs that co-observe a point, the dense LDL^T blocked over the whole GPU
+    -> as bundle_adjustment; info also carries blocks, panels, contributions (per round) and launches."""
+    binfo = np.zeros(1, LBA_BLOCKED_INFO_DTYPE)
+    return _lba_run(lambda L, kf, K, pt, P, ob, E, fn, To, Po, er, info, ke, pe, dev:
+                    L.orbb_global_bundle_adjustment(kf, K, pt, P, ob, E, int(iterations), int(bool(robust)), fn, None, To, Po, info, ke, pe, _p(binfo), dev),
+                    keyframes, points, observations, stop, device, binfo)
+
+
+def bundle_adjustment_scheduled(keyframes, points, observations, schedule, stop=None, device=0, blocked=False):
+    """orbb_optimize: the same kernels under a caller-given schedule (lba_schedule); blocked: orbb_optimize_blocked, the blocked
+    reduced-system path (info then also carries blocks, panels, contributions and launches)"""
     sc = np.ascontiguousarray(np.asarray(schedule, LBA_SCHEDULE_DTYPE).reshape(1))
+    if blocked:
+        binfo = np.zeros(1, LBA_BLOCKED_INFO_DTYPE)
+        return _lba_run(lambda L, kf, K, pt, P, ob, E, fn, To, Po, er, info, ke, pe, dev:
+                        L.orbb_optimize_blocked(kf, K, pt, P, ob, E, _p(sc), fn, None, To, Po, er, info, ke, pe, _p(binfo), dev),
+                        keyframes, points, observations, stop, device, binfo)
     return _lba_run(lambda L, kf, K, pt, P, ob, E, fn, To, Po, er, info, ke, pe, dev:
                     L.orbb_optimize(kf, K, pt, P, ob, E, _p(sc), fn, None, To, Po, er, info, ke, pe, dev),
                     keyframes, points, observations, stop, device)

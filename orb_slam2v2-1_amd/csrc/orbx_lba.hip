@@ -16,6 +16,10 @@
 //   chi2, computeScale         per-workgroup partial sums, then one workgroup over the partials in order        (k_lba_*_reduce)
 // so two runs give the same bytes.  The reduced system is factorised by ONE workgroup (k_lba_solve): LDL^T without pivoting, in
 // LDS up to LBA_LDS_POSES free poses and in device memory past it - the same code through one pointer, hence the same bytes.
+// A loop-closure-sized map (orbb_global_bundle_adjustment, orbb_optimize_blocked) takes the BLOCKED path between Dinv and the update:
+// the Schur complement from the host-built list of co-observing pairs (k_gba_schur) and a dense LDL^T blocked over the grid in
+// panels of GBA_PANEL_POSES poses (k_gba_diag / rows / trail, the substitutions likewise), every entry with k_lba_solve's operations
+// in k_lba_solve's order.
 #ifdef ORBX_LBA_HOST
 // tests/cpp/lba_lockstep.cc compiles this file's kernels AND the driver for the host, one thread per workgroup, the workgroups
 // of a launch one after the other (tests/cpp/hip_lockstep.h comes first): every sum then runs in ascending order, which is
@@ -38,6 +42,10 @@
 #define LBA_LDS_POSES 14    // free poses whose reduced system (6 * 14 = 84 square, 56448 B of doubles) is factorised in LDS, under the 64 KiB a launch gets unasked
 #define LBA_ED 54           // doubles an edge's linearisation leaves: Hll 6 | bl 3 | Hpp 21 | bp 6 | W = Hpl 18
 #define LBA_MAX_TRIALS 10   // g2o's maxTrialsAfterFailure
+#define GBA_PANEL_POSES 8   // the blocked path (k_gba_*): poses of one panel of the blocked LDL^T, 6 * 8 = 48 columns; its diagonal block (18432 B) is factorised in LDS
+#define GBA_NB (6 * GBA_PANEL_POSES)
+#define GBA_TILE 64         // edge of a tile of the trailing update: 256 threads, a 4 x 4 micro-tile each
+#define GBA_TS (GBA_TILE + 1)   // a staged strip's row stride in LDS: the odd stride spreads the transposing stores over the banks
 
 struct LbaRec { double linChi, maxDiag, tmpChi, scale; int32_t ok, pad; };   // what the host reads after a linearisation (it == 0) and after every trial
 struct LbaDev {
@@ -45,7 +53,10 @@ struct LbaDev {
     const orbb_keyframe_t *kf; const orbb_point_t *pts; const orbb_observation_t *obs;
     const int32_t *ptStart, *ptEdges, *kfStart, *kfEdges;   // CSR by point and by keyframe, the edges of an owner in ascending input index
     const int32_t *col, *kfOfCol;         // per round: keyframe -> column (-1: fixed, or no active edge) and back
-    int32_t *tab;                         // per round: [nf][P] the active edge of (column, point) or -1
+    int32_t *tab;                         // per round: [nf][P] the active edge of (column, point) or -1 (the dense path only)
+    const int32_t *blk, *ca, *cb;         // the blocked path, per round: the pattern's blocks (i1, i2), i1 <= i2, sorted; a block's contributions (edge of i1, edge of i2)
+    const long long *blkStart;            // ... in ascending point index, as a CSR over the blocks
+    int32_t *bad;                         // the blocked path: a pivot of this trial was not > 0 or not finite
     double *pose[2], *pt[2];              // the estimates t[3] | q[4] (x y z w) per keyframe and xyz per point: current and trial, swapped by the host
     uint8_t *flag, *erase, *pact;         // edge at level 1; the final classification; point has an active edge
     double *chi2, *ed, *Hll, *bl, *Dinv, *db, *Hpp, *bp, *S, *xp, *partChi, *partScale;
@@ -422,6 +433,213 @@ __global__ __launch_bounds__(LBA_THREADS) void k_lba_solve(LbaDev D, int inLds) 
     if (tid == 0) D.rec->ok = bad ? 0 : 1;
 }
 
+// ------------------------------------------------------------------------------------
+// The blocked reduced-system path (orbb_optimize_blocked, orbb_global_bundle_adjustment): k_gba_schur and the k_gba_* factorisation
+// stand where k_lba_table, k_lba_schur and k_lba_solve stand on the dense path; everything before Dinv and from k_lba_update on is
+// shared.  The contract: every entry of S, of the factor and of the solution receives exactly the operations k_lba_solve applies to
+// it, in the same order - updates x -= (L_im * L_jm) * d_m in ascending m, then the division by the pivot; forward substitution in
+// ascending m, backward in descending m; no contraction.  Blocking changes which thread does an operation, never its rounding, so
+// one thread per workgroup gives tests/lba_ref.py's bytes and the factor does not depend on the launch shape.  Hence no matrix
+// cores and no skipping of structurally zero tiles (-0.0 - (-0.0) changes a sign bit).
+//
+// Block `blockIdx.x` of the pattern, one WORKGROUP its owner: the block's contributions W_a Dinv W_b^T in ascending point index,
+// the thread's terms ascending, wave butterfly, the waves in order - k_lba_schur's sum over a list instead of a [nf][P] table, and
+// its inner expressions.  S was cleared on the stream: a block outside the pattern is +0.0, which is what k_lba_schur writes there.
+__global__ __launch_bounds__(LBA_THREADS) void k_gba_schur(LbaDev D, double lambda) {
+    __shared__ double part[LBA_WAVES * 42];
+    const int b = blockIdx.x, nf = D.nf, i1 = D.blk[2 * b], i2 = D.blk[2 * b + 1];
+    double acc[42];
+#pragma unroll
+    for (int k = 0; k < 42; k++) acc[k] = 0.0;
+    const size_t E = (size_t)D.E;
+    const long long t1 = D.blkStart[b + 1];
+    for (long long t = D.blkStart[b] + (long long)threadIdx.x; t < t1; t += LBA_THREADS) {
+        const int ea = D.ca[t], eb = D.cb[t];
+        const size_t p = (size_t)D.obs[ea].pt;
+        const double *Dp = D.Dinv + p * 6;
+        const double Di[3][3] = {{Dp[0], Dp[1], Dp[2]}, {Dp[1], Dp[3], Dp[4]}, {Dp[2], Dp[4], Dp[5]}};
+        double Y[6][3], W2[6][3];
+#pragma unroll
+        for (int j = 0; j < 6; j++) {
+            const double w0 = D.ed[(36 + j * 3) * E + ea], w1 = D.ed[(37 + j * 3) * E + ea], w2 = D.ed[(38 + j * 3) * E + ea];
+#pragma unroll
+            for (int l = 0; l < 3; l++) {
+                Y[j][l] = (w0 * Di[0][l] + w1 * Di[1][l]) + w2 * Di[2][l];
+                W2[j][l] = D.ed[(36 + j * 3 + l) * E + eb];
+            }
+            if (i1 == i2) {
+                const double *db = D.db + p * 3;
+                acc[36 + j] += (w0 * db[0] + w1 * db[1]) + w2 * db[2];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 6; j++)
+#pragma unroll
+            for (int l = 0; l < 6; l++) acc[j * 6 + l] += (Y[j][0] * W2[l][0] + Y[j][1] * W2[l][1]) + Y[j][2] * W2[l][2];
+    }
+    block_sum<LBA_LANES, LBA_WAVES>(acc, part);
+    if (threadIdx.x == 0) {
+        const size_t n = (size_t)nf * 6;
+        if (i1 == i2) {
+            const double *H = D.Hpp + (size_t)i1 * 21;
+            int k = 0;
+            for (int j = 0; j < 6; j++)
+                for (int l = j; l < 6; l++, k++)
+                    D.S[(size_t)(6 * i1 + l) * n + 6 * i1 + j] = (j == l ? H[k] + lambda : H[k]) - acc[l * 6 + j];
+            for (int j = 0; j < 6; j++) D.xp[6 * i1 + j] = D.bp[(size_t)i1 * 6 + j] - acc[36 + j];
+        } else {
+            for (int j = 0; j < 6; j++)
+                for (int l = 0; l < 6; l++) D.S[(size_t)(6 * i2 + l) * n + 6 * i1 + j] = 0.0 - acc[j * 6 + l];
+        }
+    }
+}
+
+// A panel is the columns [c0, c0 + w) of S, w = GBA_NB but for the last.  Its launches: k_gba_diag (one workgroup), and where rows
+// lie below it k_gba_rows (one thread per row) and k_gba_trail (one workgroup per 64 x 64 tile of the trailing lower triangle).
+//
+// The panel's diagonal block in LDS: k_lba_solve's elimination on w columns - every update from the columns left of c0 has
+// arrived through k_gba_trail in ascending m - and the forward substitution's steps inside the block.  The pivot is judged at the
+// moment it is used, by k_lba_solve's rule; the verdict outlives the launch in D.bad.
+__global__ __launch_bounds__(LBA_THREADS) void k_gba_diag(LbaDev D, int n, int c0, int w) {
+    __shared__ double A[GBA_NB * GBA_NB];
+    const int tid = threadIdx.x;
+    double *v = D.xp + c0;
+    for (int t = tid; t < w * w; t += LBA_THREADS) {
+        const int i = t / w, j = t % w;
+        if (j <= i) A[i * GBA_NB + j] = D.S[(size_t)(c0 + i) * n + c0 + j];
+    }
+    __syncthreads();
+    for (int m = 0; m < w; m++) {
+        const double d = A[m * GBA_NB + m];
+        if (tid == 0 && (!(d > 0.0) || !(d <= DBL_MAX))) *D.bad = 1;
+        __syncthreads();
+        for (int i = m + 1 + tid; i < w; i += LBA_THREADS) A[i * GBA_NB + m] = A[i * GBA_NB + m] / d;
+        __syncthreads();
+        const int r = w - m - 1;
+        for (int t = tid; t < r * r; t += LBA_THREADS) {
+            const int i = m + 1 + t / r, j = m + 1 + t % r;
+            if (j <= i) A[i * GBA_NB + j] -= (A[i * GBA_NB + m] * A[j * GBA_NB + m]) * d;
+        }
+        __syncthreads();
+    }
+    for (int m = 0; m < w; m++) {          // L y = b inside the block
+        const double ym = v[m];
+        for (int i = m + 1 + tid; i < w; i += LBA_THREADS) v[i] -= A[i * GBA_NB + m] * ym;
+        __syncthreads();
+    }
+    for (int t = tid; t < w * w; t += LBA_THREADS) {
+        const int i = t / w, j = t % w;
+        if (j <= i) D.S[(size_t)(c0 + i) * n + c0 + j] = A[i * GBA_NB + j];
+    }
+}
+
+// The rows below a full panel, one thread per row i >= c0 + GBA_NB with the row's 48 entries in registers: column m is divided by
+// its pivot, then entry j > m takes (L_im * L_jm) * d_m - ascending m per entry, the division last.  Then the row's share of the
+// forward substitution, v[i] -= L_im * y_m over the panel in ascending m (y of the panel is final: k_gba_diag ran before).
+__global__ __launch_bounds__(LBA_THREADS) void k_gba_rows(LbaDev D, int n, int c0) {
+    __shared__ double Ld[GBA_NB * GBA_NB];
+    __shared__ double dd[GBA_NB], yy[GBA_NB];
+    const int tid = threadIdx.x;
+    for (int t = tid; t < GBA_NB * GBA_NB; t += LBA_THREADS) Ld[t] = D.S[(size_t)(c0 + t / GBA_NB) * n + c0 + t % GBA_NB];
+    for (int t = tid; t < GBA_NB; t += LBA_THREADS) { dd[t] = D.S[(size_t)(c0 + t) * n + c0 + t]; yy[t] = D.xp[c0 + t]; }
+    __syncthreads();
+    const int i = c0 + GBA_NB + (int)blockIdx.x * LBA_THREADS + tid;
+    if (i >= n) return;
+    double *row = D.S + (size_t)i * n + c0;
+    double x[GBA_NB];
+#pragma unroll
+    for (int m = 0; m < GBA_NB; m++) x[m] = row[m];
+#pragma unroll
+    for (int m = 0; m < GBA_NB; m++) {
+        const double d = dd[m];
+        x[m] = x[m] / d;
+#pragma unroll
+        for (int j = m + 1; j < GBA_NB; j++) x[j] -= (x[m] * Ld[j * GBA_NB + m]) * d;
+    }
+    double vi = D.xp[i];
+#pragma unroll
+    for (int m = 0; m < GBA_NB; m++) { row[m] = x[m]; vi -= x[m] * yy[m]; }
+    D.xp[i] = vi;
+}
+
+// Tile `blockIdx.x` of the lower triangle right of and below a full panel, tiles counted row by row: entry (i, j), j <= i, takes
+// (L_im * L_jm) * d_m for the panel's m in ascending order.  The two strips of the panel - the tile's rows and the rows that are
+// its columns - are staged transposed in LDS, [m][row]; a thread holds a 4 x 4 micro-tile.  Every tile is updated whatever it
+// holds: a zero tile is not skipped.
+__global__ __launch_bounds__(LBA_THREADS) void k_gba_trail(LbaDev D, int n, int c0) {
+    __shared__ double Lr[GBA_NB * GBA_TS], Lc[GBA_NB * GBA_TS];
+    __shared__ double dd[GBA_NB];
+    const int tid = threadIdx.x, c1 = c0 + GBA_NB, t = blockIdx.x;
+    int I = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+    while (I * (I + 1) / 2 > t) I--;
+    while ((I + 1) * (I + 2) / 2 <= t) I++;
+    const int J = t - I * (I + 1) / 2, r0 = c1 + I * GBA_TILE, q0 = c1 + J * GBA_TILE;
+    for (int s = tid; s < GBA_NB * GBA_TILE; s += LBA_THREADS) {
+        const int m = s % GBA_NB, r = s / GBA_NB;
+        Lr[m * GBA_TS + r] = r0 + r < n ? D.S[(size_t)(r0 + r) * n + c0 + m] : 0.0;
+        Lc[m * GBA_TS + r] = q0 + r < n ? D.S[(size_t)(q0 + r) * n + c0 + m] : 0.0;
+    }
+    for (int s = tid; s < GBA_NB; s += LBA_THREADS) dd[s] = D.S[(size_t)(c0 + s) * n + c0 + s];
+    __syncthreads();
+    for (int mt = tid; mt < (GBA_TILE / 4) * (GBA_TILE / 4); mt += LBA_THREADS) {
+        const int ty = mt / (GBA_TILE / 4), tx = mt % (GBA_TILE / 4), i0 = r0 + ty * 4, j0 = q0 + tx * 4;
+        if (i0 >= n || j0 > i0 + 3) continue;   // below the matrix, or wholly above the diagonal
+        double acc[4][4];
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+#pragma unroll
+            for (int c = 0; c < 4; c++) acc[r][c] = (i0 + r < n && j0 + c <= i0 + r) ? D.S[(size_t)(i0 + r) * n + j0 + c] : 0.0;
+#pragma unroll 4
+        for (int m = 0; m < GBA_NB; m++) {
+            const double d = dd[m];
+            double a[4], b[4];
+#pragma unroll
+            for (int r = 0; r < 4; r++) { a[r] = Lr[m * GBA_TS + ty * 4 + r]; b[r] = Lc[m * GBA_TS + tx * 4 + r]; }
+#pragma unroll
+            for (int r = 0; r < 4; r++)
+#pragma unroll
+                for (int c = 0; c < 4; c++) acc[r][c] -= (a[r] * b[c]) * d;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+#pragma unroll
+            for (int c = 0; c < 4; c++)
+                if (i0 + r < n && j0 + c <= i0 + r) D.S[(size_t)(i0 + r) * n + j0 + c] = acc[r][c];
+    }
+}
+
+// y / D, before any backward step
+__global__ __launch_bounds__(LBA_THREADS) void k_gba_scale(LbaDev D, int n) {
+    const int i = blockIdx.x * LBA_THREADS + threadIdx.x;
+    if (i < n) D.xp[i] = D.xp[i] / D.S[(size_t)i * n + i];
+}
+
+// L^T x = y, the panels from the last to the first: inside the panel's block in descending m (one workgroup), then every entry left
+// of the panel takes the panel's m in descending order (k_gba_back_rows, one thread per entry) - descending m per entry overall
+__global__ __launch_bounds__(LBA_THREADS) void k_gba_back_diag(LbaDev D, int n, int c0, int w) {
+    const int tid = threadIdx.x;
+    double *v = D.xp + c0;
+    for (int m = w - 1; m >= 0; m--) {
+        const double xm = v[m];
+        for (int i = tid; i < m; i += LBA_THREADS) v[i] -= D.S[(size_t)(c0 + m) * n + c0 + i] * xm;
+        __syncthreads();
+    }
+}
+__global__ __launch_bounds__(LBA_THREADS) void k_gba_back_rows(LbaDev D, int n, int c0, int w) {
+    const int i = blockIdx.x * LBA_THREADS + threadIdx.x;
+    if (i >= c0) return;
+    double vi = D.xp[i];
+    for (int m = c0 + w - 1; m >= c0; m--) vi -= D.S[(size_t)m * n + i] * D.xp[m];
+    D.xp[i] = vi;
+}
+
+// k_lba_solve's end: after a bad pivot x = 0 and ok = 0.  n == 0: one workgroup, ok = 1.
+__global__ __launch_bounds__(LBA_THREADS) void k_gba_finish(LbaDev D, int n) {
+    const int i = blockIdx.x * LBA_THREADS + threadIdx.x, bad = *D.bad;
+    if (bad && i < n) D.xp[i] = 0.0;
+    if (i == 0) D.rec->ok = bad ? 0 : 1;
+}
+
 // The trial estimates from the current ones: workgroups [0, nbK) take the keyframes (exp(xp) * T for a column), the rest the points
 // (xl = Dinv (bl - W^T xp) over the point's active edges in ascending input index, then +=).  A vertex outside the problem, and every
 // vertex after a failed solve, is copied.  Each workgroup leaves its share of computeScale: sum x (lambda x + b).
@@ -605,10 +823,10 @@ struct LbaMem {
 #endif
 };
 #ifdef ORBX_LBA_HOST
-#define LBA_LAUNCH(kern, grid, lds, ...) do { for (int b_ = 0; b_ < (int)(grid); b_++) { blockIdx.x = b_; kern(__VA_ARGS__); } blockIdx.x = 0; } while (0)
+#define LBA_LAUNCH(kern, grid, lds, ...) do { nlaunch++; for (int b_ = 0; b_ < (int)(grid); b_++) { blockIdx.x = b_; kern(__VA_ARGS__); } blockIdx.x = 0; } while (0)
 #define LBA_TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
 #else
-#define LBA_LAUNCH(kern, grid, lds, ...) do { hipLaunchKernelGGL(kern, dim3(grid), dim3(LBA_THREADS), lds, M.st, __VA_ARGS__); ORBX_HIP(hipGetLastError()); } while (0)
+#define LBA_LAUNCH(kern, grid, lds, ...) do { nlaunch++; hipLaunchKernelGGL(kern, dim3(grid), dim3(LBA_THREADS), lds, M.st, __VA_ARGS__); ORBX_HIP(hipGetLastError()); } while (0)
 #define LBA_TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
 #endif
 
@@ -616,10 +834,14 @@ struct LbaLayout {
     size_t oKf, oPts, oObs, oPtStart, oPtEdges, oKfStart, oKfEdges, inEnd, oCol, oKfOfCol, oFlag, oRec;
     size_t oOutT, oOutP, oErase, oEstKf, oEstPt, outEnd;
     size_t oPose[2], oPt[2], oPact, oChi2, oEd, oHll, oBl, oDinv, oDb, oHpp, oBp, oS, oXp, oPartChi, oPartScale, oTab, total;
+    size_t oBlk, oBlkStart, oCa, oCb, oBad, nbMax, ncMax;   // the blocked path: the pattern and its contributions (uploaded per round), the pivot flag
     int nbE, nbK, nbP, nbAll, nfMax;
 };
 static inline int lba_blocks(int n) { return (n + LBA_THREADS - 1) / LBA_THREADS; }
-static LbaLayout lba_layout(const orbb_keyframe_t *kfs, int K, int P, int E) {
+// blocked (obs is read then): no [nf][P] table; room for the largest pattern a round can have, which is round 1's with every edge
+// active - sum_p d_p (d_p + 1) / 2 contributions for d_p observations of point p by keyframes that are not fixed, and at most that
+// many blocks and at most nf (nf + 1) / 2
+static LbaLayout lba_layout(const orbb_keyframe_t *kfs, int K, int P, int E, const orbb_observation_t *obs = nullptr, int blocked = 0) {
     LbaLayout L;
     StagePlan pl;
     const size_t k1 = (size_t)(K > 0 ? K : 1), p1 = (size_t)(P > 0 ? P : 1), e1 = (size_t)(E > 0 ? E : 1);
@@ -643,15 +865,82 @@ static LbaLayout lba_layout(const orbb_keyframe_t *kfs, int K, int P, int E) {
     L.oHll = pl.take(p1 * 48); L.oBl = pl.take(p1 * 24); L.oDinv = pl.take(p1 * 48); L.oDb = pl.take(p1 * 24);
     L.oHpp = pl.take(f1 * 168); L.oBp = pl.take(f1 * 48); L.oS = pl.take(f1 * f1 * 36 * 8); L.oXp = pl.take(f1 * 48);
     L.oPartChi = pl.take((size_t)(L.nbE > 0 ? L.nbE : 1) * 8); L.oPartScale = pl.take((size_t)(L.nbK + L.nbP > 0 ? L.nbK + L.nbP : 1) * 8);
-    L.oTab = pl.take(f1 * p1 * 4);
+    L.oTab = pl.take(blocked ? 0 : f1 * p1 * 4);
+    L.nbMax = L.ncMax = 0;
+    if (blocked) {
+        std::vector<size_t> deg((size_t)P, 0);
+        for (int e = 0; e < E; e++)
+            if (!kfs[obs[e].kf].fixed) deg[obs[e].pt]++;
+        for (int p = 0; p < P; p++) L.ncMax += deg[p] * (deg[p] + 1) / 2;
+        L.nbMax = std::min(L.ncMax, (size_t)L.nfMax * ((size_t)L.nfMax + 1) / 2);
+    }
+    L.oBlk = pl.take((L.nbMax + 1) * 8); L.oBlkStart = pl.take((L.nbMax + 1) * 8);
+    L.oCa = pl.take((L.ncMax + 1) * 4); L.oCb = pl.take((L.ncMax + 1) * 4); L.oBad = pl.take(4);
     L.total = pl.off;
     return L;
+}
+
+// The blocked path's pattern of a round, into the mirror: the blocks (i1 <= i2) that share an active point, sorted, and per block
+// its contributions (edge of i1, edge of i2) in ascending point index - the order of tests/lba_ref.py: Round.sum_schur.  Column by
+// column: the column's active edges sorted by point, each paired with the point's active edges in columns >= i1 (a diagonal block
+// pairs an edge with itself).  Two passes over the same walk, count and place.  -> the number of blocks, contributions in *nc.
+static size_t gba_pattern(uint8_t *h, const LbaLayout &L, int nf, bool useFlag, size_t *nc) {
+    const orbb_observation_t *obs = (const orbb_observation_t *)(h + L.oObs);
+    const int32_t *ptStart = (const int32_t *)(h + L.oPtStart), *ptEdges = (const int32_t *)(h + L.oPtEdges);
+    const int32_t *kfStart = (const int32_t *)(h + L.oKfStart), *kfEdges = (const int32_t *)(h + L.oKfEdges);
+    const int32_t *col = (const int32_t *)(h + L.oCol), *kfOfCol = (const int32_t *)(h + L.oKfOfCol);
+    const uint8_t *flag = h + L.oFlag;
+    int32_t *blk = (int32_t *)(h + L.oBlk), *ca = (int32_t *)(h + L.oCa), *cb = (int32_t *)(h + L.oCb);
+    long long *blkStart = (long long *)(h + L.oBlkStart);
+    std::vector<long long> cnt((size_t)nf, 0);
+    std::vector<int32_t> touched;
+    std::vector<std::pair<int32_t, int32_t> > mine;   // (point, edge) of the column
+    size_t nb = 0;
+    long long run = 0;
+    for (int i1 = 0; i1 < nf; i1++) {
+        const int kf = kfOfCol[i1];
+        mine.clear(); touched.clear();
+        for (int i = kfStart[kf]; i < kfStart[kf + 1]; i++) {
+            const int e = kfEdges[i];
+            if (!(useFlag && flag[e])) mine.push_back(std::make_pair(obs[e].pt, e));
+        }
+        std::sort(mine.begin(), mine.end());
+        for (int pass = 0; pass < 2; pass++) {
+            for (size_t a = 0; a < mine.size(); a++) {
+                const int p = mine[a].first;
+                for (int i = ptStart[p]; i < ptStart[p + 1]; i++) {
+                    const int eb = ptEdges[i];
+                    if (useFlag && flag[eb]) continue;
+                    const int i2 = col[obs[eb].kf];
+                    if (i2 < i1) continue;   // a fixed keyframe (-1), or the block belongs to column i2
+                    if (pass == 0) { if (cnt[i2]++ == 0) touched.push_back(i2); }
+                    else { ca[cnt[i2]] = mine[a].second; cb[cnt[i2]] = eb; cnt[i2]++; }
+                }
+            }
+            if (pass == 0) {
+                std::sort(touched.begin(), touched.end());
+                for (size_t k = 0; k < touched.size(); k++) {
+                    const int i2 = touched[k];
+                    blk[2 * nb] = i1; blk[2 * nb + 1] = i2; blkStart[nb] = run;
+                    const long long c = cnt[i2];
+                    cnt[i2] = run;            // pass 1 places from here
+                    run += c; nb++;
+                }
+            } else {
+                for (size_t k = 0; k < touched.size(); k++) cnt[touched[k]] = 0;
+            }
+        }
+    }
+    blkStart[nb] = run;
+    *nc = (size_t)run;
+    return nb;
 }
 
 typedef int (*lba_stop_fn)(void *);
 // The schedule of :655-707 and the Levenberg-Marquardt of optimization_algorithm_levenberg.cpp:61-164 under sparse_optimizer.cpp:376.
 // M.h holds the inputs on entry (lba_stage) and the outputs on return.  The loops are bounded by the schedule: iterations x 10 trials.
-static int lba_drive(LbaMem M, const LbaLayout &L, int K, int P, int E, const orbb_schedule_t &sc, lba_stop_fn stop, void *user, orbb_info_t *info) {
+static int lba_drive(LbaMem M, const LbaLayout &L, int K, int P, int E, const orbb_schedule_t &sc, lba_stop_fn stop, void *user, orbb_info_t *info,
+                     int blocked = 0, orbb_blocked_info_t *binfo = nullptr) {
     LbaDev D;
     uint8_t *d = M.d;
     D.K = K; D.P = P; D.E = E; D.nf = 0;
@@ -672,8 +961,13 @@ static int lba_drive(LbaMem M, const LbaLayout &L, int K, int P, int E, const or
     const uint8_t *hflag = M.h + L.oFlag;
     const LbaRec *hrec = (const LbaRec *)(M.h + L.oRec);
 
+    D.blk = (const int32_t *)(d + L.oBlk); D.blkStart = (const long long *)(d + L.oBlkStart);
+    D.ca = (const int32_t *)(d + L.oCa); D.cb = (const int32_t *)(d + L.oCb); D.bad = (int32_t *)(d + L.oBad);
     orbb_info_t inf;
     memset(&inf, 0, sizeof(inf));
+    orbb_blocked_info_t bi;
+    memset(&bi, 0, sizeof(bi));
+    long long nlaunch = 0;   // LBA_LAUNCH counts
     int polls = 0;
     auto poll = [&](int where) -> bool {   // OptimizableGraph::terminate(), and the reference's own two reads of the flag
         if (!stop) return false;
@@ -710,7 +1004,14 @@ static int lba_drive(LbaMem M, const LbaLayout &L, int K, int P, int E, const or
         if (!nActive) continue;   // optimize(): "0 vertices to optimize", no iteration and no poll
         D.nf = nf;
         LBA_TRY(M.push(L.oCol, L.oFlag - L.oCol));
-        if (nf) {
+        const int n = nf * 6, panels = (nf + GBA_PANEL_POSES - 1) / GBA_PANEL_POSES;
+        size_t nb = 0, nc = 0;
+        if (blocked) {
+            nb = gba_pattern(M.h, L, nf, round == 1, &nc);
+            bi.blocks[round] = (int32_t)nb; bi.panels[round] = panels; bi.contributions[round] = (int64_t)nc;
+            LBA_TRY(M.push(L.oBlk, (nb + 1) * 8)); LBA_TRY(M.push(L.oBlkStart, (nb + 1) * 8));
+            LBA_TRY(M.push(L.oCa, (nc + 1) * 4)); LBA_TRY(M.push(L.oCb, (nc + 1) * 4));
+        } else if (nf) {
             LBA_TRY(M.fill(L.oTab, 0xFF, (size_t)nf * P * 4));
             LBA_LAUNCH(k_lba_table, L.nbE, 0, D);
         }
@@ -738,8 +1039,29 @@ static int lba_drive(LbaMem M, const LbaLayout &L, int K, int P, int E, const or
             bool more;
             do {
                 LBA_LAUNCH(k_lba_dinv, L.nbP, 0, D, lambda);
-                if (nf) LBA_LAUNCH(k_lba_schur, nf * nf, 0, D, lambda);
-                LBA_LAUNCH(k_lba_solve, 1, lds, D, inLds);
+                if (blocked) {
+                    // S and the pivot flag start every trial as zeros: a block outside the pattern is zero, not scratch
+                    LBA_TRY(M.fill(L.oS, 0, (size_t)n * (size_t)n * 8)); LBA_TRY(M.fill(L.oBad, 0, 4));
+                    if (nb) LBA_LAUNCH(k_gba_schur, nb, 0, D, lambda);
+                    for (int c0 = 0; c0 < n; c0 += GBA_NB) {
+                        const int w = std::min(GBA_NB, n - c0), below = n - c0 - w, tiles = (below + GBA_TILE - 1) / GBA_TILE;
+                        LBA_LAUNCH(k_gba_diag, 1, 0, D, n, c0, w);
+                        if (below > 0) {
+                            LBA_LAUNCH(k_gba_rows, lba_blocks(below), 0, D, n, c0);
+                            LBA_LAUNCH(k_gba_trail, tiles * (tiles + 1) / 2, 0, D, n, c0);
+                        }
+                    }
+                    if (n) LBA_LAUNCH(k_gba_scale, lba_blocks(n), 0, D, n);
+                    for (int c0 = (panels - 1) * GBA_NB; c0 >= 0 && n; c0 -= GBA_NB) {
+                        const int w = std::min(GBA_NB, n - c0);
+                        LBA_LAUNCH(k_gba_back_diag, 1, 0, D, n, c0, w);
+                        if (c0 > 0) LBA_LAUNCH(k_gba_back_rows, lba_blocks(c0), 0, D, n, c0, w);
+                    }
+                    LBA_LAUNCH(k_gba_finish, std::max(1, lba_blocks(n)), 0, D, n);
+                } else {
+                    if (nf) LBA_LAUNCH(k_lba_schur, nf * nf, 0, D, lambda);
+                    LBA_LAUNCH(k_lba_solve, 1, lds, D, inLds);
+                }
                 LBA_LAUNCH(k_lba_update, L.nbK + L.nbP, 0, D, c, lambda, L.nbK);
                 LBA_LAUNCH(k_lba_edges<false>, L.nbE, 0, D, c ^ 1, robust, dMono, dStereo);
                 LBA_LAUNCH(k_lba_trial_reduce, 1, 0, D, L.nbE, L.nbK + L.nbP);
@@ -778,6 +1100,8 @@ static int lba_drive(LbaMem M, const LbaLayout &L, int K, int P, int E, const or
     const uint8_t *er = M.h + L.oErase;
     for (int e = 0; e < E; e++) inf.erased += er[e];
     if (info) *info = inf;
+    bi.launches = nlaunch;
+    if (binfo) *binfo = bi;
     return ORBX_OK;
 }
 
@@ -809,22 +1133,35 @@ static void lba_results(const uint8_t *h, const LbaLayout &L, int K, int P, int 
 static thread_local StagePair g_ba;
 void orbx_internal_release_lba_scratch() { g_ba.release(); }
 
-extern "C" int orbb_optimize(const orbb_keyframe_t *kfs, int K, const orbb_point_t *pts, int P, const orbb_observation_t *obs, int E,
-                             const orbb_schedule_t *schedule, int (*stop)(void *), void *stop_user, float *Tcw_out16, float *pts_out3,
-                             uint8_t *erase, orbb_info_t *info, double *kf_est7, double *pt_est3, int device) {
-    const int crc = lba_check("orbb_optimize", kfs, K, pts, P, obs, E, schedule, Tcw_out16, pts_out3, erase);
+// one call on this thread's staging pair; blocked: the k_gba_* reduced-system path
+static int lba_run(const char *fn, const orbb_keyframe_t *kfs, int K, const orbb_point_t *pts, int P, const orbb_observation_t *obs, int E,
+                   const orbb_schedule_t *schedule, int (*stop)(void *), void *stop_user, float *Tcw_out16, float *pts_out3,
+                   uint8_t *erase, orbb_info_t *info, double *kf_est7, double *pt_est3, int blocked, orbb_blocked_info_t *binfo, int device) {
+    const int crc = lba_check(fn, kfs, K, pts, P, obs, E, schedule, Tcw_out16, pts_out3, erase);
     if (crc) return crc;
-    const LbaLayout L = lba_layout(kfs, K, P, E);
+    const LbaLayout L = lba_layout(kfs, K, P, E, obs, blocked);
     int rc = g_ba.reserve(device, L.total, (size_t)1 << 20);
     if (rc) return rc;
     LbaMem M;
     M.d = g_ba.d; M.h = g_ba.h; M.st = g_ba.stream;
     lba_stage(M.h, L, kfs, K, pts, P, obs, E);
     (void)hipGetLastError();
-    rc = lba_drive(M, L, K, P, E, *schedule, stop, stop_user, info);
+    rc = lba_drive(M, L, K, P, E, *schedule, stop, stop_user, info, blocked, binfo);
     if (rc) { hipStreamSynchronize(M.st); return rc; }
     lba_results(M.h, L, K, P, E, Tcw_out16, pts_out3, erase, kf_est7, pt_est3);
     return ORBX_OK;
+}
+
+extern "C" int orbb_optimize(const orbb_keyframe_t *kfs, int K, const orbb_point_t *pts, int P, const orbb_observation_t *obs, int E,
+                             const orbb_schedule_t *schedule, int (*stop)(void *), void *stop_user, float *Tcw_out16, float *pts_out3,
+                             uint8_t *erase, orbb_info_t *info, double *kf_est7, double *pt_est3, int device) {
+    return lba_run("orbb_optimize", kfs, K, pts, P, obs, E, schedule, stop, stop_user, Tcw_out16, pts_out3, erase, info, kf_est7, pt_est3, 0, nullptr, device);
+}
+
+extern "C" int orbb_optimize_blocked(const orbb_keyframe_t *kfs, int K, const orbb_point_t *pts, int P, const orbb_observation_t *obs, int E,
+                                     const orbb_schedule_t *schedule, int (*stop)(void *), void *stop_user, float *Tcw_out16, float *pts_out3,
+                                     uint8_t *erase, orbb_info_t *info, double *kf_est7, double *pt_est3, orbb_blocked_info_t *binfo, int device) {
+    return lba_run("orbb_optimize_blocked", kfs, K, pts, P, obs, E, schedule, stop, stop_user, Tcw_out16, pts_out3, erase, info, kf_est7, pt_est3, 1, binfo, device);
 }
 
 extern "C" int orbb_local_bundle_adjustment(const orbb_keyframe_t *kfs, int K, const orbb_point_t *pts, int P, const orbb_observation_t *obs, int E,
@@ -842,5 +1179,14 @@ extern "C" int orbb_bundle_adjustment(const orbb_keyframe_t *kfs, int K, const o
     const orbb_schedule_t s = {1, {iterations, 0}, {robust ? 1 : 0, 0}, (float)sqrt(5.99), (float)sqrt(7.815), 0, 0};
     std::vector<uint8_t> erase((size_t)(E > 0 ? E : 1));
     return orbb_optimize(kfs, K, pts, P, obs, E, &s, stop, stop_user, Tcw_out16, pts_out3, erase.data(), info, kf_est7, pt_est3, device);
+}
+
+extern "C" int orbb_global_bundle_adjustment(const orbb_keyframe_t *kfs, int K, const orbb_point_t *pts, int P, const orbb_observation_t *obs, int E,
+                                             int iterations, int robust, int (*stop)(void *), void *stop_user, float *Tcw_out16, float *pts_out3,
+                                             orbb_info_t *info, double *kf_est7, double *pt_est3, orbb_blocked_info_t *binfo, int device) {
+    // orbb_bundle_adjustment's schedule (:95-96) on the blocked path
+    const orbb_schedule_t s = {1, {iterations, 0}, {robust ? 1 : 0, 0}, (float)sqrt(5.99), (float)sqrt(7.815), 0, 0};
+    std::vector<uint8_t> erase((size_t)(E > 0 ? E : 1));
+    return orbb_optimize_blocked(kfs, K, pts, P, obs, E, &s, stop, stop_user, Tcw_out16, pts_out3, erase.data(), info, kf_est7, pt_est3, binfo, device);
 }
 #endif   // ORBX_LBA_HOST

@@ -248,7 +248,6 @@ void Optimizer::GlobalBundleAdjustemnt(Map *pMap, int nIterations, bool *pbStopF
 
 void Optimizer::BundleAdjustment(const std::vector<KeyFrame *> &vpKFs, const std::vector<MapPoint *> &vpMP, int nIterations, bool *pbStopFlag,
                                  const unsigned long nLoopKF, const bool bRobust) {
-    if (nLoopKF != 0) throw std::runtime_error("Optimizer::BundleAdjustment: the nLoopKF != 0 write-back (mTcwGBA / mPosGBA) is not built");
     std::vector<orbb_keyframe_t> kfs;
     std::map<KeyFrame *, int> index;
     for (size_t i = 0; i < vpKFs.size(); i++) {   // :71-83
@@ -282,6 +281,26 @@ void Optimizer::BundleAdjustment(const std::vector<KeyFrame *> &vpKFs, const std
     }
     const int K = (int)kfs.size(), P = (int)pts.size(), E = (int)obs.size();
     std::vector<float> Tout((size_t)K * 16 + 1), Pout((size_t)P * 3 + 1);
+    if (nLoopKF != 0) {
+        // The loop closer's adjustment of the whole map (src/LoopClosing.cc:659): the blocked reduced-system path, and the write-back of
+        // :204-209 and :229-234 - the results go beside the map (mTcwGBA, mPosGBA) with the mnBAGlobalForKF mark, the map itself is
+        // left as it is for LoopClosing::RunGlobalBundleAdjustment to correct under its own lock
+        const int rcg = orbb_global_bundle_adjustment(kfs.data(), K, pts.data(), P, obs.data(), E, nIterations, bRobust ? 1 : 0,
+                                                      pbStopFlag ? stop_flag_set : NULL, pbStopFlag, Tout.data(), Pout.data(), NULL, NULL, NULL, NULL, device);
+        if (rcg != ORBX_OK) throw std::runtime_error(std::string("Optimizer::BundleAdjustment: ") + orbx_last_error());
+        for (size_t i = 0; i < vpKFs.size(); i++) {
+            KeyFrame *pKF = vpKFs[i];
+            if (pKF->isBad()) continue;
+            pKF->mTcwGBA = pose_mat(Tout.data() + (size_t)index[pKF] * 16);
+            pKF->mnBAGlobalForKF = nLoopKF;
+        }
+        for (size_t i = 0; i < vpMP.size(); i++) {
+            if (vnPoint[i] < 0) continue;
+            vpMP[i]->mPosGBA = point_mat(Pout.data() + (size_t)vnPoint[i] * 3);
+            vpMP[i]->mnBAGlobalForKF = nLoopKF;
+        }
+        return;
+    }
     const int rc = orbb_bundle_adjustment(kfs.data(), K, pts.data(), P, obs.data(), E, nIterations, bRobust ? 1 : 0, pbStopFlag ? stop_flag_set : NULL,
                                           pbStopFlag, Tout.data(), Pout.data(), NULL, NULL, NULL, device);
     if (rc != ORBX_OK) throw std::runtime_error(std::string("Optimizer::BundleAdjustment: ") + orbx_last_error());

@@ -3,14 +3,15 @@
 // calls (src/Tracking.cc:918, :1041, :1083, :1585-1616); OptimizeSim3 (src/Optimizer.cc:1051-1246, orbz_optimize_sim3), the
 // refinement of a loop candidate's Sim3 in LoopClosing::ComputeSim3 (src/LoopClosing.cc:336); LocalBundleAdjustment (:453-780,
 // orbb_local_bundle_adjustment), the mapping thread's bundle adjustment (src/LocalMapping.cc:89), and BundleAdjustment /
-// GlobalBundleAdjustemnt (:41-237, orbb_bundle_adjustment) for the map CreateInitialMapMonocular builds (src/Tracking.cc:700).  The
+// GlobalBundleAdjustemnt (:41-237) - orbb_bundle_adjustment for the map CreateInitialMapMonocular builds (src/Tracking.cc:700, nLoopKF
+// == 0), orbb_global_bundle_adjustment for the loop closer's adjustment of the whole map (src/LoopClosing.cc:659, nLoopKF != 0).  The
 // first two have ONE free vertex; the bundle adjustments marginalise the points, and the reduced system of a local window - a few tens
 // of keyframes - is dense and small.  OptimizeEssentialGraph (:783-1049, orbg_optimize_essential_graph), the pose graph
 // LoopClosing::CorrectLoop optimises (src/LoopClosing.cc:576), is here too: an earlier version of this comment filed it under "sparse,
 // not part of this library", which was a statement about storage, not about the arithmetic - the block pattern is fixed, the host
-// does the symbolic factorisation once per call and the device the 7x7 block arithmetic.  A bundle adjustment of a
-// loop-closure-sized map (the loop closer's global one) is the one member that is not part of this library: keep the reference's
-// own (g2o) for it.
+// does the symbolic factorisation once per call and the device the 7x7 block arithmetic.  The bundle adjustment of a
+// loop-closure-sized map has the same arithmetic as the local one and another reduced-system path: the Schur complement summed over
+// the keyframe pairs that co-observe a point, the dense LDL^T blocked over the whole GPU.  No member of the optimiser is left to g2o.
 #ifndef ORBX_OPTIMIZER_H
 #define ORBX_OPTIMIZER_H
 #include "frame_shim.h"
@@ -40,9 +41,12 @@ public:
     // keyframe with mnId == 0 is fixed and keeps its pose byte for byte (the reference writes it back through its quaternion).
     // Throws std::runtime_error with orbx_last_error() when the library reports an error (no GPU among them).
     void static LocalBundleAdjustment(KeyFrame *pKF, bool *pbStopFlag, Map *pMap);
-    // :49-237 and :41-46 with the write-back of nLoopKF == 0 (SetPose, SetWorldPos, UpdateNormalAndDepth).  The nLoopKF != 0 branch
-    // (mTcwGBA, mPosGBA, mnBAGlobalForKF: the loop closer's global adjustment) is NOT built: the shim does not carry those members and
-    // a loop-closure-sized map is outside what the dense reduced system is meant for; it throws std::runtime_error.
+    // :49-237 and :41-46.  nLoopKF == 0: orbb_bundle_adjustment and the write-back into the map (SetPose, SetWorldPos,
+    // UpdateNormalAndDepth).  nLoopKF != 0 (the loop closer's global adjustment): orbb_global_bundle_adjustment, and the results go
+    // beside the map - mTcwGBA (4x4 CV_32F) and mnBAGlobalForKF = nLoopKF on every keyframe that is not bad, mPosGBA (3x1 CV_32F) and
+    // mnBAGlobalForKF on every point of the problem; no SetPose, SetWorldPos or UpdateNormalAndDepth, and a bad point or one without
+    // a usable observation (vbNotIncludedMP) is untouched.  *pbStopFlag is &mbStopGBA's: read before every iteration and after a
+    // rejected trial.  Throws std::runtime_error with orbx_last_error() when the library reports an error.
     void static BundleAdjustment(const std::vector<KeyFrame *> &vpKFs, const std::vector<MapPoint *> &vpMP, int nIterations = 5,
                                  bool *pbStopFlag = NULL, const unsigned long nLoopKF = 0, const bool bRobust = true);
     void static GlobalBundleAdjustemnt(Map *pMap, int nIterations = 5, bool *pbStopFlag = NULL, const unsigned long nLoopKF = 0,

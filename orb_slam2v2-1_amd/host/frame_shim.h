@@ -71,6 +71,8 @@ public:
     void SetWorldPos(const cv::Mat &Pos) { mWorldPos = Pos.clone(); }                     // src/MapPoint.cc:83-88
     long unsigned int mnId = 0, mnBALocalForKF = 0;   // include/MapPoint.h: read and written by Optimizer::LocalBundleAdjustment
     long unsigned int mnCorrectedByKF = 0, mnCorrectedReference = 0;   // include/MapPoint.h: set by LoopClosing::CorrectLoop, read by Optimizer::OptimizeEssentialGraph
+    cv::Mat mPosGBA;                      // include/MapPoint.h: written by Optimizer::BundleAdjustment with nLoopKF != 0 (3x1 CV_32F), read by
+    long unsigned int mnBAGlobalForKF = 0;   // LoopClosing::RunGlobalBundleAdjustment
     KeyFrame *GetReferenceKeyFrame() { return mpRefKF; }   // src/MapPoint.cc:96-100
     inline void Replace(MapPoint *pMP);                                                   // src/MapPoint.cc:187-225
     std::map<KeyFrame *, size_t> GetObservations() { return mObservations; }
@@ -160,6 +162,8 @@ public:
         if (idx >= 0) mvpMapPoints[idx] = static_cast<MapPoint *>(NULL);
     }
     long unsigned int mnBALocalForKF = 0, mnBAFixedForKF = 0;   // include/KeyFrame.h: the marks of Optimizer::LocalBundleAdjustment
+    cv::Mat mTcwGBA, mTcwBefGBA;          // include/KeyFrame.h: mTcwGBA (4x4 CV_32F) and the mark are written by Optimizer::BundleAdjustment with
+    long unsigned int mnBAGlobalForKF = 0;   // nLoopKF != 0; mTcwBefGBA is LoopClosing::RunGlobalBundleAdjustment's own
     // the spanning tree, the loop edges and the covisibility weights, as far as Optimizer::OptimizeEssentialGraph reads them
     // (src/KeyFrame.cc:137-146, :326-359, :404-448)
     KeyFrame *mpParent = NULL;
