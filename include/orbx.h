@@ -129,6 +129,39 @@ int orbx_extract_batch_device(orbx_extractor_t *h, const uint8_t *d_imgs, int B,
 int orbx_extract_batch_device_prefetch(orbx_extractor_t *h, const uint8_t *d_imgs, int B, int w, int hgt, int stride,
                                        size_t image_stride_bytes, void *side_stream);
 
+/* In-place input of the batched mode: the caller puts its frames where pyramid level 0 would be copied to, and the copy goes away
+ * (one pass over every image per call: 60 MB read and 67 MB written per 128 images of 1241x376).
+ * orbx_level0_layout: the layout, a pure function of the size and the levels (no HIP call, works without a GPU) - exactly what a handle
+ * with these levels plans for level 0, and it refuses the sizes such a handle refuses (ORBX_ERR_ARG / ORBX_ERR_UNSUPPORTED, reason in
+ * orbx_last_error).  An image is `prows` rows of `pstride` bytes; pixel (0,0) is at byte `pixel0_offset` = 19 * pstride + 19, pixel
+ * (x, y) at pixel0_offset + y * pstride + x; images are at least `image_bytes` apart.  Everything of an image's bytes outside its w x h
+ * pixels - the margins - is the caller's: its contents are unspecified, the library neither takes results from it nor writes it.
+ * A producer that copies frames with a copy engine (hipMemcpy2DAsync, pitch = pstride) pays the same for this layout as for a dense one. */
+typedef struct {
+    int32_t pstride;         /* bytes from a row to the next (a multiple of 64) */
+    int32_t prows;           /* rows of an image: hgt + 2 * 19 */
+    uint64_t pixel0_offset;  /* byte offset of pixel (0,0) inside an image */
+    uint64_t image_bytes;    /* bytes of one image, with the slack wide loads at its end may touch (a multiple of 256) */
+} orbx_level0_layout_t;
+int orbx_level0_layout(int w, int hgt, int nlevels, float scale_factor, orbx_level0_layout_t *out);
+/* orbx_extract_batch_device on B images in that layout: image b starts at d_level0 + b * image_stride_bytes (64-byte aligned,
+ * image_stride_bytes a multiple of 64 and >= image_bytes).  Level 0 is read where it is; the handle's pyramid block holds the levels >= 1.
+ * Same outputs, bit for bit, as orbx_extract_batch_device on the same pixels.
+ * Contract: the images must stay unchanged until everything that reads level 0 has FINISHED - this call, and the stereo matcher call that
+ * works on its pyramid: orbm_stereo_batch_device, or the lagged orbm_stereo_batch_device_prev issued after the NEXT extraction call.
+ * (orbx_extract_batch_device lets go of its images once the call itself has run.)  orbx_pyramid_host / orbx_pyramid_device of level 0
+ * copy it into the pyramid block on demand and need the images unchanged as well.
+ * The call copies level 0 after all - same results, no error - when the level-wide blur takes level 0 (ORBX_OPT_BLUR_FORM /
+ * ORBX_OPT_BLUR_THRESHOLD), when the call - or the smallest chunk ORBX_OPT_CHUNKS cuts it into - has at most 4 images (the latency
+ * forms of the pyramid start from the pyramid block) or when a developer option picks another pyramid form; the images are then free
+ * when the call has run.
+ * orbx_extract_batch_device_padded_prefetch: the companion of orbx_extract_batch_device_prefetch, with the same pairing rule (the next
+ * padded call with the same arguments takes the pyramid built ahead). */
+int orbx_extract_batch_device_padded(orbx_extractor_t *h, const uint8_t *d_level0, int B, int w, int hgt, size_t image_stride_bytes,
+                                     orbx_keypoint_t *d_kps, uint8_t *d_desc, int32_t *d_counts, int cap, void *stream);
+int orbx_extract_batch_device_padded_prefetch(orbx_extractor_t *h, const uint8_t *d_level0, int B, int w, int hgt,
+                                              size_t image_stride_bytes, void *side_stream);
+
 /* Two (default) or three pyramid buffers per handle.  With three, the pyramid built ahead gets a buffer of its own and the previous
  * call's pyramid stays valid across orbx_extract_batch_device_prefetch, so the pattern below may issue the prefetch of batch i+1
  * BEFORE orbm_stereo_batch_device_prev of batch i-1 on the side stream (the matcher then runs beside the descriptor kernel of batch i

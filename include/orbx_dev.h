@@ -147,4 +147,6 @@ int orbx_debug_streams(orbx_extractor_t *h, void **out, int n_out);
 #ifdef __cplusplus
 }
 #endif
+/* Which input form an extraction call ran - level 0 read in place or copied - is declared in orbx_dev_level0.h, which comes with this header. */
+#include "orbx_dev_level0.h"
 #endif

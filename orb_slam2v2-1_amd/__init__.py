@@ -131,6 +131,7 @@ EXPORTS = [
     "orbx_octree_device", "orbx_octomap_bt", "orbx_octomap_bytes_bound",
     "orbv_score_l1", "orbv_db_create", "orbv_db_destroy", "orbv_db_add", "orbv_db_erase", "orbv_db_clear", "orbv_db_set_covisible",
     "orbv_db_info", "orbv_db_score", "orbv_db_detect_loop", "orbv_db_detect_reloc",
+    "orbx_level0_layout", "orbx_extract_batch_device_padded", "orbx_extract_batch_device_padded_prefetch",
 ]
 # the optimiser section of include/orbx.h (prefix orbo_), listed apart: EXPORTS is compared with the header's orbx_ / orbm_ / orbv_ names
 POSE_EXPORTS = ["orbo_pose_optimization", "orbo_pose_optimization_batch", "orbo_pose_optimization_device"]
@@ -156,6 +157,8 @@ DEV_EXPORTS = ["orbx_debug_level_points", "orbx_debug_sincosf", "orbx_debug_blur
                "orbx_debug_streams"]
 # what include/orbx_dev_pyr.h declares: the developer build's hook for k_pyr_level's records (debug_pyr_records)
 DEV_PYR_EXPORTS = ["orbx_debug_pyr_records"]
+# what include/orbx_dev_level0.h declares: which input form the last extraction call ran (ORBextractor.level0_in_place)
+DEV_LEVEL0_EXPORTS = ["orbx_debug_level0_in_place"]
 # include/orbx_dev.h: the int64 record of orbx_debug_size_plan, field order
 SIZE_PLAN_FIELDS = ["max_kp", "totalCells", "maxNodeCap", "lvlKpCap", "pyrImgBytes", "slotsPerImg", "keysPerImg", "fastTileStride", "fastScoreStride",
                     "fastTileRows", "fastLdsPerWave", "totalStrips", "stripLevels", "octLdsBytes", "octPyrLdsBytes", "octPyrWords", "octBigMask",
@@ -205,6 +208,20 @@ class OctreeInfo(C.Structure):
 
     def as_dict(self):
         return {f: int(getattr(self, f)) for f, _ in self._fields_ if f != "reserved"}
+
+
+class Level0Layout(C.Structure):
+    """orbx_level0_layout_t: the layout of in-place input (orbx_level0_layout / orbx_extract_batch_device_padded)."""
+    _fields_ = [("pstride", C.c_int32), ("prows", C.c_int32), ("pixel0_offset", C.c_uint64), ("image_bytes", C.c_uint64)]
+
+
+def level0_layout(w, h, nlevels=8, scale_factor=1.2, developer=False):
+    """No HIP call (works without a GPU): where a caller of ORBextractor.extract_batch_device_padded puts a w x h frame -> dict(pstride,
+    prows, pixel0_offset, image_bytes); raises OrbxError for a size an extractor with these levels refuses."""
+    L = lib(developer)
+    out = Level0Layout()
+    _check(L.orbx_level0_layout(int(w), int(h), int(nlevels), float(scale_factor), C.byref(out)), L)
+    return {f: int(getattr(out, f)) for f, _ in out._fields_}
 
 
 class GridGeom(C.Structure):
@@ -360,6 +377,9 @@ def _load(path, dev):
     L.orbx_extract_batch.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32, vp]
     L.orbx_extract_batch_device.argtypes = [vp, vp, i32, i32, i32, i32, sz, vp, vp, vp, i32, vp]
     L.orbx_extract_batch_device_prefetch.argtypes = [vp, vp, i32, i32, i32, i32, sz, vp]
+    L.orbx_extract_batch_device_padded.argtypes = [vp, vp, i32, i32, i32, sz, vp, vp, vp, i32, vp]
+    L.orbx_extract_batch_device_padded_prefetch.argtypes = [vp, vp, i32, i32, i32, sz, vp]
+    L.orbx_level0_layout.argtypes = [i32, i32, i32, f32, C.POINTER(Level0Layout)]
     L.orbx_stream_wait_fast_stage.argtypes = [vp, vp]
     L.orbx_side_stream.argtypes = [vp]
     L.orbx_side_stream.restype = vp
@@ -485,6 +505,7 @@ def _load(path, dev):
         L.orbm_debug_thread_scratch.argtypes = [vp, i32]
         L.orbx_debug_size_plan.argtypes = [i32, f32, i32, i32, i32, i32, vp, vp, vp, i32, vp, i32, vp, i32]
         L.orbx_debug_pyr_records.argtypes = [vp, i32, f32, i32, i32, i32, vp, i32, vp, i32, vp, i32]
+        L.orbx_debug_level0_in_place.argtypes = [vp]
         L.orbx_debug_set_alloc_fill.argtypes = [i32, C.c_uint32]
         L.orbx_debug_alloc_fill_stats.argtypes = [vp]
         L.orbx_debug_stall_stream.argtypes = [vp, i32, i32]
@@ -649,6 +670,23 @@ class ORBextractor:
     def prefetch_batch_device(self, d_imgs, B, w, h, stride, image_stride, side_stream=0):
         """Start the pyramid of the NEXT batch now (orbx_extract_batch_device_prefetch): the images must be complete in HBM."""
         self._ck(self._L.orbx_extract_batch_device_prefetch(self._h, d_imgs, B, w, h, stride, image_stride, side_stream))
+
+    def extract_batch_device_padded(self, d_level0, B, w, h, image_stride, d_kps, d_desc, d_counts, cap, stream=0):
+        """extract_batch_device on images in the layout of level0_layout() (orbx_extract_batch_device_padded): level 0 is read in place,
+        so the images must stay unchanged until the stereo matcher call that works on this call's pyramid has finished."""
+        self._ck(self._L.orbx_extract_batch_device_padded(self._h, d_level0, B, w, h, image_stride, d_kps, d_desc, d_counts, cap, stream))
+        self._shape = (h, w)
+
+    def prefetch_batch_device_padded(self, d_level0, B, w, h, image_stride, side_stream=0):
+        """prefetch_batch_device for images in the layout of level0_layout() (orbx_extract_batch_device_padded_prefetch)."""
+        self._ck(self._L.orbx_extract_batch_device_padded_prefetch(self._h, d_level0, B, w, h, image_stride, side_stream))
+
+    def level0_in_place(self):
+        """Developer build: 1 iff the last extraction call read level 0 in place from the caller's images (orbx_debug_level0_in_place)."""
+        rc = self._L.orbx_debug_level0_in_place(self._h)
+        if rc < 0:
+            self._ck(rc)
+        return rc
 
     def side_stream(self):
         """hipStream_t of the handle's own side stream (orbx_side_stream)."""

@@ -45,7 +45,7 @@ OBJ = os.path.join(HERE, "lib", "obj")
 
 def _deps():
     return [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [
-        os.path.join(ROOT, "include", f) for f in ("orbx.h", "orbx_dev.h", "orbx_dev_pyr.h", "orb_pattern_31.inc")]
+        os.path.join(ROOT, "include", f) for f in ("orbx.h", "orbx_dev.h", "orbx_dev_pyr.h", "orbx_dev_level0.h", "orb_pattern_31.inc")]
 
 
 def _compile_link(out, defines, verbose):

@@ -361,7 +361,7 @@ __global__ __launch_bounds__(64 * DESC_WAVES) __attribute__((amdgpu_waves_per_eu
     const uint8_t *__restrict__ pyr, size_t pyrImgBytes, const LevelGeom *__restrict__ geom, int nlevels,
     const uint32_t *__restrict__ lvlKp, int lvlKpCap, const int32_t *__restrict__ lvlCnt,
     orbx_keypoint_t *__restrict__ kps, uint8_t *__restrict__ desc, int32_t *__restrict__ counts, int cap, uint8_t *__restrict__ dbgBlur,
-    const uint8_t *__restrict__ blur, unsigned blurMask, DescGroup grp) {
+    const uint8_t *__restrict__ blur, unsigned blurMask, DescGroup grp, Level0 lv0) {
     __shared__ __align__(16) uint8_t smem[DESC_WAVES * DESC_LDS_PER_WAVE];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     int bx, b;
@@ -439,7 +439,7 @@ __global__ __launch_bounds__(64 * DESC_WAVES) __attribute__((amdgpu_waves_per_eu
     uint8_t *Bl = P;                                                  // blurred [37][40], in place of the patch (TCOLS * BSTRIDE <= PROWS * PSTRIDE)
 
     // ---- stage the 43x43 patch with aligned dword loads (pstride is a multiple of 64)
-    const uint8_t *lvl = pyr + (size_t)b * pyrImgBytes + g.poff;
+    const uint8_t *lvl = level_base(pyr, pyrImgBytes, lv0, b, l, g.poff);
     // byte offset of the patch origin inside the level: the same in every lane (one keypoint per wave) - made scalar so that
     // the staging loads are "scalar base + 32-bit lane offset" (a padded level is far smaller than 4 GiB)
     const size_t a = (size_t)(uint32_t)__builtin_amdgcn_readfirstlane((cy + ORBX_EDGE - PR) * g.pstride + (cx + ORBX_EDGE - PR));
@@ -449,11 +449,15 @@ __global__ __launch_bounds__(64 * DESC_WAVES) __attribute__((amdgpu_waves_per_eu
     // The 19-px REFLECT_101 frame of the levels >= 1 is only ever read HERE, by the few keypoints closer than PR to a
     // level's edge (the frame of level 0 comes with the copy of the input).  Those keypoints mirror the coordinates
     // themselves, so the pipeline never writes the frames of levels >= 1 (orbx_pyramid_host writes them on demand).
+    // Level 0 read in place from the caller's images (lv0.base) has no frame either - its margins are the caller's, their
+    // contents unspecified - and its edge keypoints take the same branch.
 #ifdef ORBX_PHASE_MARKERS   // the counted build keeps the hot path only: no edge keypoint, no level-wide blur, no test hook
+    // (it counts instructions, its results are not used: an edge keypoint stages whatever the frame holds - unwritten for the levels >= 1,
+    // and with in-place input, which pipeline.FrontEnd takes by default, the caller's margins at level 0; the loads stay inside the level)
     const bool edge = false;
     blurMask = 0; dbgBlur = nullptr;
 #else
-    const bool edge = l > 0 && (cx < PR || cy < PR || cx + PR >= g.w || cy + PR >= g.h);   // wave-uniform
+    const bool edge = (l > 0 || lv0.base != nullptr) && (cx < PR || cy < PR || cx + PR >= g.w || cy + PR >= g.h);   // wave-uniform
 #endif
     // Level blurred as a whole by k_blur_levels (levels whose keypoints' 37x37 blocks add up to more pixels than the level has):
     // stage the 31 rows of the IC_Angle disc from the level and the 37x37 block from the blurred level; no blur passes here.
@@ -685,7 +689,7 @@ __global__ __launch_bounds__(64 * DESC_WAVES) __attribute__((amdgpu_waves_per_eu
 
 #define ORBX_DESC_INSTANCE(G, S)                                                                                                             \
     template __global__ void k_describe<G, S>(const uint8_t *, size_t, const LevelGeom *, int, const uint32_t *, int, const int32_t *, \
-                                              orbx_keypoint_t *, uint8_t *, int32_t *, int, uint8_t *, const uint8_t *, unsigned, DescGroup);
+                                              orbx_keypoint_t *, uint8_t *, int32_t *, int, uint8_t *, const uint8_t *, unsigned, DescGroup, Level0);
 ORBX_DESC_INSTANCE(ORBX_GAUSS_ROUND_HALF_UP, false)
 ORBX_DESC_INSTANCE(ORBX_GAUSS_ROUND_HALF_UP, true)
 ORBX_DESC_INSTANCE(ORBX_GAUSS_ROUND_SSE2, false)

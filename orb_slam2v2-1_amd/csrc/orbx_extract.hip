@@ -12,6 +12,7 @@
 #ifdef ORBX_DEVELOPER
 #include "orbx_dev.h"
 #include "orbx_dev_pyr.h"
+#include "orbx_dev_level0.h"
 #endif
 #include <math.h>
 #include <float.h>
@@ -412,21 +413,8 @@ static int launch_blur(orbx_extractor *h, const uint8_t *pyr, uint8_t **blurBuf,
 // K1: ComputePyramid of B images into pyr.  Developer knob 5: 0 / 2 = one launch per level (the default), 1 = every level in the
 // fused launch, 3 = hybrid.
 static bool pyramid_fused_all(const orbx_extractor *h) { return h->opt[5] == 1 || h->scale_factor > 3.0; }
-static void launch_pyramid(orbx_extractor *h, const uint8_t *d_imgs, uint8_t *pyr, int B, int stride, size_t img_stride, hipStream_t st) {
-    const int nl = h->nlevels;
-    if (pyramid_fused_all(h)) {   // writes every frame itself (a lane's two source byte pairs fit 8 bytes only up to scale 3)
-        hipLaunchKernelGGL(k_pyramid_fused, dim3(h->sp.pyrTilesX * h->sp.pyrTilesY, B), dim3(256), h->sp.pyrLdsBytes, st, d_imgs,
-                           stride, img_stride, pyr, h->sp.pyrImgBytes, h->d_geom, nl, h->d_tab, h->sp.pyrXSpanOff,
-                           h->sp.pyrYSpanOff, h->sp.pyrTilesX, h->sp.pyrTilesY, h->sp.pyrBufBytes, h->sp.pyrMaxPar, 0);
-        return;
-    }
-    // Hybrid form (developer knob 5 = 3, parity-tested, NOT used by default): levels 1, 2 one launch each, levels 3.. from ONE launch
-    // that chains them through LDS - VERDICT r01's proposal for the launch-latency-bound small levels.  Measured: one 1241x376
-    // image 193 us per orbx_extract call against 184 us with seven launches (the chain's five barriers and its generic per-pixel
-    // indexing cost more than five ~4-us launches), and for a batch it spends five times the instructions per pixel while the
-    // pyramid runs beside VALU-bound kernels.
-    const bool hybrid = h->opt[5] == 3;
-    const int lastSingle = hybrid ? std::min(2, nl - 1) : nl - 1;
+// Level 0 of a batch: the copy of the input into the padded level (with its REFLECT_101 frame).
+static void launch_pad0(orbx_extractor *h, const uint8_t *d_imgs, uint8_t *pyr, int B, int stride, size_t img_stride, hipStream_t st) {
     const LevelGeom &g0 = h->sp.geom[0];
     // level 0 of a small batch: source rows staged in LDS (ORBX_OPT_PAD_FORM: 0 = by batch size, 1 = never, 2 = always) - the image of a latency
     // call is read in pinned host memory, where each byte should cross the bus once, in aligned transactions
@@ -443,6 +431,38 @@ static void launch_pyramid(orbx_extractor *h, const uint8_t *d_imgs, uint8_t *py
         hipLaunchKernelGGL(k_pyr_pad<true>, dim3(gx, rowBlocks + edgeRows, B), dim3(threads), 0, st, d_imgs, stride, img_stride, pyr,
                            h->sp.pyrImgBytes, h->d_geom, 0);
     }
+}
+// In-place input (orbx_extract_batch_device_padded) is taken when nothing of the call wants level 0 inside the pyramid block: not the
+// level-wide blur of level 0 (k_blur_levels reads the frame), not the forms of a latency call (B <= ORBX_HIST_IMAGES: level chains and
+// the LDS-staged copy, which start from the pyramid block), not a developer knob that picks another pyramid form.  Otherwise the call
+// copies level 0 as a dense call does - same results, and orbx_debug_level0_in_place tells which it was.
+// The pyramid is launched per CHUNK (ORBX_OPT_CHUNKS; launch_pipeline cuts the call, launch_pyramid picks its forms from the chunk's
+// images), so the batch size that counts is the smallest chunk's: nch = the chunks the call's pyramid launches are cut into (1 for a
+// pyramid built ahead, which is one launch of the whole batch).
+static bool level0_in_place_ok(const orbx_extractor *h, int B, int nch) {
+    BlurPlan bp;
+    int tiles = 0;
+    if (blur_plan(h, bp, tiles) & 1u) return false;
+    const int smallest = B / std::max(nch, 1);   // launch_pipeline: chunk c gets (B - b0) / (nch - c) images, the first one the fewest
+    return smallest > ORBX_HIST_IMAGES && !pyramid_fused_all(h) && (h->opt[5] == 0 || h->opt[5] == 2) && h->opt[24] != 2;
+}
+// lv0.base != NULL: level 0 stays where it is (the caller's images, in the padded level's layout); level 1 is resized from there.
+static void launch_pyramid(orbx_extractor *h, const uint8_t *d_imgs, uint8_t *pyr, int B, int stride, size_t img_stride, hipStream_t st, const Level0 &lv0) {
+    const int nl = h->nlevels;
+    if (pyramid_fused_all(h)) {   // writes every frame itself (a lane's two source byte pairs fit 8 bytes only up to scale 3)
+        hipLaunchKernelGGL(k_pyramid_fused, dim3(h->sp.pyrTilesX * h->sp.pyrTilesY, B), dim3(256), h->sp.pyrLdsBytes, st, d_imgs,
+                           stride, img_stride, pyr, h->sp.pyrImgBytes, h->d_geom, nl, h->d_tab, h->sp.pyrXSpanOff,
+                           h->sp.pyrYSpanOff, h->sp.pyrTilesX, h->sp.pyrTilesY, h->sp.pyrBufBytes, h->sp.pyrMaxPar, 0);
+        return;
+    }
+    // Hybrid form (developer knob 5 = 3, parity-tested, NOT used by default): levels 1, 2 one launch each, levels 3.. from ONE launch
+    // that chains them through LDS - VERDICT r01's proposal for the launch-latency-bound small levels.  Measured: one 1241x376
+    // image 193 us per orbx_extract call against 184 us with seven launches (the chain's five barriers and its generic per-pixel
+    // indexing cost more than five ~4-us launches), and for a batch it spends five times the instructions per pixel while the
+    // pyramid runs beside VALU-bound kernels.
+    const bool hybrid = h->opt[5] == 3;
+    const int lastSingle = hybrid ? std::min(2, nl - 1) : nl - 1;
+    if (!lv0.base) launch_pad0(h, d_imgs, pyr, B, stride, img_stride, st);
     // ORBX_OPT_PYRAMID_FORM = 4 (and small batches by default, ORBX_OPT_PYR_CHAINS): the levels in chains, one launch per chain
     const int cv = h->opt[25] == 3 ? 1 : 0;   // ORBX_OPT_PYR_CHAINS: 2 / 3 = chains of up to 4 / 7 levels (0: the default, 1: never)
     if (h->sp.nChains[cv] > 0 && !hybrid && (h->opt[5] == 4 || (h->opt[5] == 0 && h->opt[25] != 1 && B <= ORBX_HIST_IMAGES))) {
@@ -464,10 +484,10 @@ static void launch_pyramid(orbx_extractor *h, const uint8_t *d_imgs, uint8_t *py
         const uint32_t *bands = h->d_pyrBands + h->pr.bandOff[f][l];
         if (tall)
             hipLaunchKernelGGL((k_pyr_level<16, 22>), dim3(gx, B), dim3(256), 0, st, pyr, h->sp.pyrImgBytes, h->d_geom, l, h->d_tab, nxc, nb, cols, bands,
-                               pyr_rcp((uint32_t)nxc), pyr_rcp((uint32_t)gx));
+                               pyr_rcp((uint32_t)nxc), pyr_rcp((uint32_t)gx), lv0);
         else
             hipLaunchKernelGGL((k_pyr_level<8, 12>), dim3(gx, B), dim3(256), 0, st, pyr, h->sp.pyrImgBytes, h->d_geom, l, h->d_tab, nxc, nb, cols, bands,
-                               pyr_rcp((uint32_t)nxc), pyr_rcp((uint32_t)gx));
+                               pyr_rcp((uint32_t)nxc), pyr_rcp((uint32_t)gx), lv0);
     }
     if (lastSingle < nl - 1)
         hipLaunchKernelGGL(k_pyramid_fused, dim3(h->sp.pyrTilesX * h->sp.pyrTilesY, B), dim3(256), h->sp.pyrLdsBytes, st, d_imgs,
@@ -480,6 +500,7 @@ struct ChunkView {
     const uint8_t *imgs; uint8_t *pyr; uint32_t *cellCnt, *cellRaw, *slots, *cand, *lvlKp; uint16_t *nodeOf;
     int32_t *candCnt, *lvlCnt, *octFallback, *sparse; orbx_keypoint_t *kps; uint8_t *desc; int32_t *counts;
     int b0;            // first image of the chunk
+    Level0 lv0;        // level 0 read in place (base != NULL): the chunk's first image in the caller's buffer
     size_t octSlot0;   // first (image, level) slot of the chunk in the multi-workgroup quad-tree scratch (d_octPart / Leaf / Best / State)
 };
 static ChunkView chunk_view(const orbx_extractor *h, const uint8_t *d_imgs, size_t img_stride, orbx_keypoint_t *d_kps, uint8_t *d_desc,
@@ -494,6 +515,8 @@ static ChunkView chunk_view(const orbx_extractor *h, const uint8_t *d_imgs, size
     v.candCnt = h->d_candCnt + z * h->nlevels; v.lvlCnt = h->d_lvlCnt + z * h->nlevels; v.octFallback = h->d_octFallback + z * h->nlevels;
     v.kps = d_kps + z * cap; v.desc = d_desc + z * cap * 32; v.counts = d_counts + b0;
     v.octSlot0 = z * h->nlevels; v.b0 = b0;
+    v.lv0 = h->lv0;
+    if (v.lv0.base) v.lv0.base += z * v.lv0.imgBytes;
     return v;
 }
 
@@ -532,7 +555,7 @@ static PlanInput plan_input(const orbx_extractor *h, int B, int nch, bool prof, 
     hipLaunchKernelGGL((k_fast_cells<EST, SP>), dim3((h->sp.totalCells + FAST_WAVES - 1) / FAST_WAVES, B), dim3(64 * FAST_WAVES), \
                        (size_t)(LDSW) * FAST_WAVES, st, v.pyr, h->sp.pyrImgBytes, h->d_geom, nl, h->sp.totalCells, v.cellCnt, v.cellRaw, v.slots, \
                        h->sp.slotsPerImg, h->ini_th, h->min_th, h->sp.fastTileStride, h->sp.fastScoreStride, h->sp.fastTileRows, \
-                       (LDSW), p.fastPhase, cb, (unsigned)p.stripLevels, v.sparse, (SP) ? FastHist{} : fhist)
+                       (LDSW), p.fastPhase, cb, (unsigned)p.stripLevels, v.sparse, (SP) ? FastHist{} : fhist, v.lv0)
 #define ORBX_LAUNCH_FAST_ES(SP, LDSW)                         \
     switch (p.es) {                                           \
     case 44: ORBX_LAUNCH_FAST(44, SP, LDSW); break;           \
@@ -558,7 +581,7 @@ static int launch_chunk(orbx_extractor *h, const ChunkView &v, int B, int stride
     orbx_keypoint_t *d_kps = v.kps; uint8_t *d_desc = v.desc; int32_t *d_counts = v.counts;
     if (prof) ORBX_HIP(hipEventRecord(ev[0], st));
     if (!skipPyr) {   // K1 (skipped when the pyramid was built ahead: then its level-wide blur was, too)
-        launch_pyramid(h, v.imgs, v.pyr, B, stride, img_stride, st);
+        launch_pyramid(h, v.imgs, v.pyr, B, stride, img_stride, st, v.lv0);
         unsigned m = 0;
         rc = launch_blur(h, h->d_pyr, &h->d_blur, &h->blurBytes, v.b0, B, st, &m);
         if (rc) return rc;
@@ -594,7 +617,7 @@ static int launch_chunk(orbx_extractor *h, const ChunkView &v, int B, int stride
         if (p.earlyLv) {   // the strips of the levels [0, earlyLv) first; their quad-tree starts beside the FAST of the rest
             hipLaunchKernelGGL(k_fast_strips, dim3((sA + FAST_WAVES - 1) / FAST_WAVES, B), dim3(64 * FAST_WAVES), 0, st,
                                v.pyr, h->sp.pyrImgBytes, h->d_geom, nl, sA, h->sp.totalCells, v.cellCnt, v.cellRaw,
-                               v.slots, h->sp.slotsPerImg, h->ini_th, h->min_th, sb, spf, 0, p.compact ? 1 : 0);
+                               v.slots, h->sp.slotsPerImg, h->ini_th, h->min_th, sb, spf, 0, p.compact ? 1 : 0, v.lv0);
             ORBX_HIP(hipEventRecord(h->evGather, st));
             ORBX_HIP(hipStreamWaitEvent(s2, h->evGather, 0));
             ORBX_OCT_PYR_ON(s2, dim3(B, p.earlyLv), 0, 0, 0, osrc);
@@ -603,11 +626,11 @@ static int launch_chunk(orbx_extractor *h, const ChunkView &v, int B, int stride
         if (p.strips && h->sp.totalStrips > sA)
             hipLaunchKernelGGL(k_fast_strips, dim3((h->sp.totalStrips - sA + FAST_WAVES - 1) / FAST_WAVES, B), dim3(64 * FAST_WAVES), 0, st,
                                v.pyr, h->sp.pyrImgBytes, h->d_geom, nl, h->sp.totalStrips, h->sp.totalCells, v.cellCnt, v.cellRaw,
-                               v.slots, h->sp.slotsPerImg, h->ini_th, h->min_th, sb, spf, sA, p.compact ? 1 : 0);
+                               v.slots, h->sp.slotsPerImg, h->ini_th, h->min_th, sb, spf, sA, p.compact ? 1 : 0, v.lv0);
         if (p.compact && p.sparseForm == 1) {   // the flagged (image, level)s: the strip kernel's compaction twin
             hipLaunchKernelGGL(k_fast_strips_sparse, dim3((h->sp.totalStrips + FAST_WAVES - 1) / FAST_WAVES, B), dim3(64 * FAST_WAVES), 0, st,
                                v.pyr, h->sp.pyrImgBytes, h->d_geom, nl, h->sp.totalStrips, h->sp.totalCells, v.cellCnt, v.cellRaw,
-                               v.slots, h->sp.slotsPerImg, h->ini_th, h->min_th, sb, v.sparse);
+                               v.slots, h->sp.slotsPerImg, h->ini_th, h->min_th, sb, v.sparse, v.lv0);
         } else if (p.compact) {   // ORBX_OPT_SPARSE_FORM = 2: the cell kernel's compaction form (+ the queue of 16-bit entries behind a wave's tiles)
             const int ldsw = h->sp.fastLdsPerWave + ((32 * h->sp.fastTileRows + 15) & ~15);
             ORBX_LAUNCH_FAST_ES(true, ldsw);
@@ -719,21 +742,21 @@ static int launch_chunk(orbx_extractor *h, const ChunkView &v, int B, int stride
             const int nbB = gB.copyBlock0 = desc_level_blocks(p.aSplit, nl, bound, gB.blk0);
             gB.taps = taps;
             hipLaunchKernelGGL(kDesc, dim3(nbB, B), dim3(64 * DESC_WAVES), descPad, st, v.pyr, h->sp.pyrImgBytes, h->d_geom, nl,
-                               v.lvlKp, h->sp.lvlKpCap, v.lvlCnt, kB, dB, d_counts, cap, (uint8_t *)nullptr, blurp, h->blurMaskLast, gB);
+                               v.lvlKp, h->sp.lvlKpCap, v.lvlCnt, kB, dB, d_counts, cap, (uint8_t *)nullptr, blurp, h->blurMaskLast, gB, v.lv0);
             ORBX_HIP(hipStreamWaitEvent(st, h->evOctA, 0));
             DescGroup gA = {0, p.aSplit, 1, 0, kB, dB};
             const int nbA = gA.copyBlock0 = desc_level_blocks(0, p.aSplit, bound, gA.blk0);
             gA.taps = taps;
             hipLaunchKernelGGL(kDesc, dim3(nbA + (maxoB + DESC_COPY_PER_BLOCK - 1) / DESC_COPY_PER_BLOCK, B), dim3(64 * DESC_WAVES), descPad, st,
                                v.pyr, h->sp.pyrImgBytes, h->d_geom, nl, v.lvlKp, h->sp.lvlKpCap, v.lvlCnt, d_kps, d_desc, d_counts, cap,
-                               (uint8_t *)nullptr, blurp, h->blurMaskLast, gA);
+                               (uint8_t *)nullptr, blurp, h->blurMaskLast, gA, v.lv0);
         } else {
             DescGroup gAll = {0, nl, 1, 0, nullptr, nullptr};
             const int nb = gAll.copyBlock0 = desc_level_blocks(0, nl, bound, gAll.blk0);
             gAll.taps = taps;
             gAll.hostDelta = h->descHostDelta;   // latency form: records also stored into their pinned host twin
             hipLaunchKernelGGL(kDesc, dim3(nb, B), dim3(64 * DESC_WAVES), descPad, st, v.pyr, h->sp.pyrImgBytes, h->d_geom, nl,
-                               v.lvlKp, h->sp.lvlKpCap, v.lvlCnt, d_kps, d_desc, d_counts, cap, h->d_dbgBlur, blurp, h->blurMaskLast, gAll);
+                               v.lvlKp, h->sp.lvlKpCap, v.lvlCnt, d_kps, d_desc, d_counts, cap, h->d_dbgBlur, blurp, h->blurMaskLast, gAll, v.lv0);
         }
     }
     if (prof) ORBX_HIP(hipEventRecord(ev[4], st));
@@ -751,7 +774,11 @@ static int launch_chunk(orbx_extractor *h, const ChunkView &v, int B, int stride
 // depend on the chunking), and the caller's stream waits for the side streams at the end, so the call keeps its stream semantics.
 static int launch_pipeline(orbx_extractor *h, const uint8_t *d_imgs, int B, int w, int hgt, int stride,
                            size_t img_stride, orbx_keypoint_t *d_kps, uint8_t *d_desc, int32_t *d_counts,
-                           int cap, hipStream_t st, bool skipPyr = false) {
+                           int cap, hipStream_t st, bool skipPyr = false, Level0 lv0 = Level0{}) {
+    // where level 0 of this call's pyramid lives: a pyramid built ahead brought its own answer with its buffer (the caller rotated it
+    // in), any other call overwrites d_pyr and says it here (lv0.base != NULL: in-place input; every other entry point copies)
+    if (!skipPyr) h->lv0 = lv0;
+    h->lv0Stale = h->lv0.base ? B : 0;
     // profiling 1: events at every stage boundary; 2: only around the FAST stage (an event costs ~4.5 us of idle GPU, so
     // a throughput measurement brackets just the kernel it reports); mode 3 = mode 2 on every 4th call only
     const bool prof = h->profiling == 1, profFast = h->profiling != 0 && (h->profiling != 3 || (h->prof_calls++ & 3) == 0);
@@ -793,24 +820,45 @@ static int launch_pipeline(orbx_extractor *h, const uint8_t *d_imgs, int B, int 
     return ORBX_OK;
 }
 
-extern "C" int orbx_extract_batch_device(orbx_extractor_t *h, const uint8_t *d_imgs, int B, int w, int hgt,
-                                         int stride, size_t image_stride_bytes, orbx_keypoint_t *d_kps,
-                                         uint8_t *d_desc, int32_t *d_counts, int cap, void *stream) {
-    if (!h || !d_imgs || !d_kps || !d_desc || !d_counts || B < 1 || w < 1 || hgt < 1 || stride < w || cap < 1) {
-        orbx_set_error("orbx_extract_batch_device: bad arguments");
+// In-place input: d_imgs is the base of B images in the layout of orbx_level0_layout (the padded level 0 of the plan; margins the
+// caller's, contents unspecified).  Checked against the plan, then restated as the dense call the copy path would get - pixel (0,0) of
+// image 0, rows pstride apart - plus *lv0, set iff the call may read level 0 where it is (level0_in_place_ok).
+static int padded_input(const orbx_extractor *h, const char *fn, const uint8_t **d_imgs, int B, int nch, int *stride, size_t image_stride_bytes, Level0 *lv0) {
+    const LevelGeom &g0 = h->sp.geom[0];
+    const size_t need = level0_image_bytes(g0);
+    if (image_stride_bytes < need || (image_stride_bytes & 63) || ((uintptr_t)*d_imgs & 63)) {
+        orbx_set_error("%s: images of the orbx_level0_layout are %zu bytes, 64-byte aligned and a multiple of 64 bytes apart (got %zu bytes apart)", fn, need,
+                       image_stride_bytes);
+        return ORBX_ERR_ARG;
+    }
+    *lv0 = level0_in_place_ok(h, B, nch) ?Level0{*d_imgs, image_stride_bytes} : Level0{};
+    *d_imgs += (size_t)ORBX_EDGE * g0.pstride + ORBX_EDGE;
+    *stride = g0.pstride;
+    return ORBX_OK;
+}
+
+static int extract_batch_device_impl(orbx_extractor_t *h, const char *fn, bool padded, const uint8_t *d_imgs, int B, int w, int hgt,
+                                     int stride, size_t image_stride_bytes, orbx_keypoint_t *d_kps,
+                                     uint8_t *d_desc, int32_t *d_counts, int cap, void *stream) {
+    if (!h || !d_imgs || !d_kps || !d_desc || !d_counts || B < 1 || w < 1 || hgt < 1 || (!padded && stride < w) || cap < 1) {
+        orbx_set_error("%s: bad arguments", fn);
         return ORBX_ERR_ARG;
     }
     ORBX_HIP(hipSetDevice(h->device));
     int rc = ensure_plan(h, w, hgt, B);
     if (rc) return rc;
+    Level0 lv0 = {};
+    // (decided for the call that builds its own pyramid, in launch_pipeline's chunks: one that takes a pyramid built ahead keeps what
+    // the prefetch decided for that buffer and ignores this)
+    if (padded) { rc = padded_input(h, fn, &d_imgs, B, chunk_count(h->opt, B, h->profiling == 1, false), &stride, image_stride_bytes, &lv0); if (rc) return rc; }
     hipStream_t st = (hipStream_t)stream;  // NULL = the HIP default (null) stream, as in every HIP API
     // the pyramid of exactly this batch was built ahead (orbx_extract_batch_device_prefetch): take that buffer, skip K1
     const bool three = h->pyrBuffers == 3;
     const bool ahead = h->pfValid && (three ? h->d_pyrNext != nullptr : h->d_pyrAlt != nullptr) && h->pfImgs == d_imgs && h->pfB == B && h->pfW == w && h->pfH == hgt && h->pfStride == stride &&
-                       h->pfImgStride == image_stride_bytes && h->opt[9] == 0;
+                       h->pfImgStride == image_stride_bytes && (h->pfPadded != 0) == padded && h->opt[9] == 0;
     h->pfValid = 0;
     h->prevPyrValid = ahead ? 1 : 0;   // the buffers swap: the other one keeps the previous call's pyramid until the next one is built into it
-    if (ahead) {
+    if (ahead) {   // (where level 0 of a pyramid lives - Level0 - moves with its buffer)
         if (three) {   // previous <- current <- next <- (old previous: its matcher was issued on the side stream before the next prefetch is)
             if (h->pyrAltBytes < h->sp.pyrImgBytes * (size_t)h->pB) {   // first rotation: the "previous" buffer does not exist yet
                 ORBX_HIP(hipStreamSynchronize(h->side[0]));
@@ -820,23 +868,37 @@ extern "C" int orbx_extract_batch_device(orbx_extractor_t *h, const uint8_t *d_i
             }
             uint8_t *oldPrev = h->d_pyrAlt;
             h->d_pyrAlt = h->d_pyr; h->d_pyr = h->d_pyrNext; h->d_pyrNext = oldPrev;
-        } else
+            h->lv0Alt = h->lv0; h->lv0 = h->lv0Next; h->lv0Next = Level0{};
+        } else {
             std::swap(h->d_pyr, h->d_pyrAlt);
+            std::swap(h->lv0, h->lv0Alt);
+        }
         std::swap(h->d_blur, h->d_blurAlt); std::swap(h->blurBytes, h->blurAltBytes); std::swap(h->blurMaskLast, h->blurMaskAlt);
         ORBX_HIP(hipStreamWaitEvent(st, h->evPrefetch, 0));
     }
-    return launch_pipeline(h, d_imgs, B, w, hgt, stride, image_stride_bytes, d_kps, d_desc, d_counts, cap, st, ahead);
+    return launch_pipeline(h, d_imgs, B, w, hgt, stride, image_stride_bytes, d_kps, d_desc, d_counts, cap, st, ahead, lv0);
+}
+extern "C" int orbx_extract_batch_device(orbx_extractor_t *h, const uint8_t *d_imgs, int B, int w, int hgt,
+                                         int stride, size_t image_stride_bytes, orbx_keypoint_t *d_kps,
+                                         uint8_t *d_desc, int32_t *d_counts, int cap, void *stream) {
+    return extract_batch_device_impl(h, "orbx_extract_batch_device", false, d_imgs, B, w, hgt, stride, image_stride_bytes, d_kps, d_desc, d_counts, cap, stream);
+}
+extern "C" int orbx_extract_batch_device_padded(orbx_extractor_t *h, const uint8_t *d_level0, int B, int w, int hgt, size_t image_stride_bytes,
+                                                orbx_keypoint_t *d_kps, uint8_t *d_desc, int32_t *d_counts, int cap, void *stream) {
+    return extract_batch_device_impl(h, "orbx_extract_batch_device_padded", true, d_level0, B, w, hgt, 0, image_stride_bytes, d_kps, d_desc, d_counts, cap, stream);
 }
 
 // Software pipelining across batches: start ComputePyramid of the NEXT batch now, into the handle's second pyramid buffer, on a
 // stream of the handle's own.  It is ordered behind the FAST stage of the extraction call issued last, i.e. it runs beside that
 // call's gather / quad-tree (latency-bound), descriptors and the stereo matcher instead of in front of the next call's FAST.
-extern "C" int orbx_extract_batch_device_prefetch(orbx_extractor_t *h, const uint8_t *d_imgs, int B, int w, int hgt, int stride,
-                                                  size_t image_stride_bytes, void *side_stream) {
-    if (!h || !d_imgs || B < 1 || w < 1 || hgt < 1 || stride < w) { orbx_set_error("orbx_extract_batch_device_prefetch: bad arguments"); return ORBX_ERR_ARG; }
+static int prefetch_impl(orbx_extractor_t *h, const char *fn, bool padded, const uint8_t *d_imgs, int B, int w, int hgt, int stride,
+                         size_t image_stride_bytes, void *side_stream) {
+    if (!h || !d_imgs || B < 1 || w < 1 || hgt < 1 || (!padded && stride < w)) { orbx_set_error("%s: bad arguments", fn); return ORBX_ERR_ARG; }
     ORBX_HIP(hipSetDevice(h->device));
     int rc = ensure_plan(h, w, hgt, B);
     if (rc) return rc;
+    Level0 lv0 = {};
+    if (padded) { rc = padded_input(h, fn, &d_imgs, B, 1, &stride, image_stride_bytes, &lv0); if (rc) return rc; }   // one pyramid launch of the whole batch
     const size_t need = h->sp.pyrImgBytes * (size_t)h->pB;
     const bool three = h->pyrBuffers == 3;
     uint8_t **tgt = three ? &h->d_pyrNext : &h->d_pyrAlt;
@@ -853,13 +915,23 @@ extern "C" int orbx_extract_batch_device_prefetch(orbx_extractor_t *h, const uin
     if (h->pfUsed && h->last_valid) ORBX_HIP(hipStreamWaitEvent(sd, h->evFastDone, 0));   // (the first time there is no such event yet: the
     else if (h->last_valid) ORBX_HIP(hipStreamSynchronize(h->last_stream));             //  second buffer is new, wait for the handle to be idle)
     h->pfUsed = 1;
-    launch_pyramid(h, d_imgs, *tgt, B, stride, image_stride_bytes, sd);
+    launch_pyramid(h, d_imgs, *tgt, B, stride, image_stride_bytes, sd, lv0);
+    (three ? h->lv0Next : h->lv0Alt) = lv0;
     rc = launch_blur(h, *tgt, &h->d_blurAlt, &h->blurAltBytes, 0, B, sd, &h->blurMaskAlt);
     if (rc) return rc;
     ORBX_HIP(hipGetLastError());
     ORBX_HIP(hipEventRecord(h->evPrefetch, sd));
     h->pfValid = 1; h->pfImgs = d_imgs; h->pfB = B; h->pfW = w; h->pfH = hgt; h->pfStride = stride; h->pfImgStride = image_stride_bytes;
+    h->pfPadded = padded;
     return ORBX_OK;
+}
+extern "C" int orbx_extract_batch_device_prefetch(orbx_extractor_t *h, const uint8_t *d_imgs, int B, int w, int hgt, int stride,
+                                                  size_t image_stride_bytes, void *side_stream) {
+    return prefetch_impl(h, "orbx_extract_batch_device_prefetch", false, d_imgs, B, w, hgt, stride, image_stride_bytes, side_stream);
+}
+extern "C" int orbx_extract_batch_device_padded_prefetch(orbx_extractor_t *h, const uint8_t *d_level0, int B, int w, int hgt,
+                                                         size_t image_stride_bytes, void *side_stream) {
+    return prefetch_impl(h, "orbx_extract_batch_device_padded_prefetch", true, d_level0, B, w, hgt, 0, image_stride_bytes, side_stream);
 }
 
 // Two (default) or three pyramid buffers.  With three, orbx_extract_batch_device_prefetch builds the next pyramid into a buffer of its
@@ -1238,6 +1310,35 @@ int orbx_internal_level(const orbx_extractor *h, int level, int *w, int *hgt, in
     return ORBX_OK;
 }
 
+// The layout of in-place input (include/orbx.h): level 0 of what plan_size decides for the size - nothing is restated here.  The feature
+// budget only sizes the quad-tree's LDS, so the geometry (and every refusal that comes from it) is that of any handle with these levels.
+extern "C" int orbx_level0_layout(int w, int hgt, int nlevels, float scale_factor, orbx_level0_layout_t *out) {
+    if (!out || nlevels < 1 || nlevels > ORBX_MAX_LEVELS || !(scale_factor > 1.0f)) { orbx_set_error("orbx_level0_layout: bad arguments"); return ORBX_ERR_ARG; }
+    SizeInput in = {};
+    in.w = w; in.h = hgt; in.nlevels = nlevels; in.scale_factor = scale_factor;
+    extractor_tables(1, in.scale_factor, nlevels, &in.tb);
+    SizePlan sp;
+    const int rc = plan_size(in, &sp);
+    if (rc) return rc;
+    const LevelGeom &g0 = sp.geom[0];
+    out->pstride = g0.pstride; out->prows = g0.prows;
+    out->pixel0_offset = g0.poff + (uint64_t)ORBX_EDGE * g0.pstride + ORBX_EDGE;
+    out->image_bytes = level0_image_bytes(g0);
+    return ORBX_OK;
+}
+
+// Level 0 of the last batch copied from the caller's images into the pyramid block (with its frame), for callers that look at the
+// padded buffers after a call that read it in place.  The kernels go on reading it in place: h->lv0 stays.
+static int ensure_level0(orbx_extractor *h) {
+    if (h->lv0Stale <= 0 || !h->lv0.base) return ORBX_OK;
+    const LevelGeom &g0 = h->sp.geom[0];
+    (void)hipGetLastError();
+    launch_pad0(h, h->lv0.base + (size_t)ORBX_EDGE * g0.pstride + ORBX_EDGE, h->d_pyr, h->lv0Stale, g0.pstride, h->lv0.imgBytes, h->last_stream);
+    ORBX_HIP(hipGetLastError());
+    h->lv0Stale = 0;
+    return ORBX_OK;
+}
+
 // copyMakeBorder of the levels >= 1 of the last batch, for callers that look at the padded buffers
 static int ensure_frames(orbx_extractor *h) {
     if (h->framesStale <= 0) return ORBX_OK;
@@ -1263,6 +1364,10 @@ extern "C" int orbx_pyramid_device(orbx_extractor_t *h, int b, int level, const 
         ORBX_HIP(hipSetDevice(h->device));
         const int rc = ensure_frames(h);
         if (rc) return rc;
+    } else {           // level 0 of a call that read the caller's images in place: copied into the pyramid block now
+        ORBX_HIP(hipSetDevice(h->device));
+        const int rc = ensure_level0(h);
+        if (rc) return rc;
     }
     const LevelGeom &g = h->sp.geom[level];
     *d_ptr = h->d_pyr + (size_t)b * h->sp.pyrImgBytes + g.poff + (size_t)ORBX_EDGE * g.pstride + ORBX_EDGE;
@@ -1286,6 +1391,7 @@ extern "C" int orbx_pyramid_host(orbx_extractor_t *h, int b, int level, int padd
     if (dst_stride < ow) { orbx_set_error("dst_stride < width"); return ORBX_ERR_ARG; }
     ORBX_HIP(hipSetDevice(h->device));
     if (padded && level > 0) { const int rc = ensure_frames(h); if (rc) return rc; }
+    if (level == 0) { const int rc = ensure_level0(h); if (rc) return rc; }
     if (h->last_valid) ORBX_HIP(hipStreamSynchronize(h->last_stream));
     const uint8_t *src = h->d_pyr + (size_t)b * h->sp.pyrImgBytes + g.poff +
                          (padded ? 0 : (size_t)ORBX_EDGE * g.pstride + ORBX_EDGE);
@@ -1468,6 +1574,11 @@ extern "C" int orbx_debug_last_plan(const orbx_extractor_t *h, int32_t *out, int
     if (!h || !out || n_out != ORBX_CHUNK_PLAN_INTS || !h->last_valid) { orbx_set_error("orbx_debug_last_plan: bad arguments or no call yet"); return ORBX_ERR_ARG; }
     memcpy(out, &h->lastPlan, sizeof(h->lastPlan));
     return ORBX_OK;
+}
+// which form the handle's last extraction call ran (include/orbx_dev_level0.h): 1 = level 0 read in place, 0 = copied into the pyramid block
+extern "C" int orbx_debug_level0_in_place(const orbx_extractor_t *h) {
+    if (!h || !h->last_valid) { orbx_set_error("orbx_debug_level0_in_place: bad arguments or no call yet"); return ORBX_ERR_ARG; }
+    return h->lv0.base != nullptr ? 1 : 0;
 }
 #endif
 

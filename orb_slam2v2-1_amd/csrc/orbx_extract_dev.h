@@ -99,7 +99,7 @@ __global__ void k_pyramid_fused(const uint8_t *src, int sstride, size_t simg, ui
                                 int maxPar, int l0);                                                             // orbx_pyramid.hip
 template <int RW, int SR>
 __global__ void k_pyr_level(uint8_t *pyr, size_t pyrImgBytes, const LevelGeom *geom, int l, const int32_t *tab, int nxc,
-                            int nbands, const PyrColRec *cols, const uint32_t *bands, uint32_t rcpNxc, uint32_t rcpNbx);   // orbx_pyramid.hip
+                            int nbands, const PyrColRec *cols, const uint32_t *bands, uint32_t rcpNxc, uint32_t rcpNbx, Level0 lv0);   // orbx_pyramid.hip
 template <bool FULL>
 __global__ void k_pyr_pad(const uint8_t *img, int sstride, size_t simg, uint8_t *pyr, size_t pyrImgBytes, const LevelGeom *geom,
                           int l0);                                                                               // orbx_pyramid.hip
@@ -118,10 +118,10 @@ __global__ void k_pyr_pad_rows(const uint8_t *img, int sstride, size_t simg, uin
 struct StripBases { int v[ORBX_MAX_LEVELS + 1]; };   // first strip of every level (levels with cells wider than 32 px own none)
 __global__ void k_fast_strips(const uint8_t *pyr, size_t pyrImgBytes, const LevelGeom *geom, int nlevels, int totalStrips, int totalCells,
                               uint32_t *cellCnt, uint32_t *cellRaw, uint32_t *slots, size_t slotsPerImg, int iniTh, int minTh,
-                              StripBases sb, const int32_t *sparseFlag, int strip0, int skipSparse);                                                                    // orbx_fast.hip
+                              StripBases sb, const int32_t *sparseFlag, int strip0, int skipSparse, Level0 lv0);                                                                    // orbx_fast.hip
 __global__ void k_fast_strips_sparse(const uint8_t *pyr, size_t pyrImgBytes, const LevelGeom *geom, int nlevels, int totalStrips, int totalCells,
                                      uint32_t *cellCnt, uint32_t *cellRaw, uint32_t *slots, size_t slotsPerImg, int iniTh, int minTh,
-                                     StripBases sb, const int32_t *sparseFlag);                                                               // orbx_fast.hip
+                                     StripBases sb, const int32_t *sparseFlag, Level0 lv0);                                                               // orbx_fast.hip
 // Small batches (B <= 4, round 5): the FAST stage also histograms what it emits - per (image, level), count and best key of every
 // cell of the quad-tree's count pyramid at its deepest depth - with atomics at the L2, spread over every CU that runs FAST cells;
 // k_octree_pyr then LOADS that histogram instead of sweeping the level's keys through the LDS atomics of its one CU (a 1241x376
@@ -131,7 +131,7 @@ template <int ES_T, bool SPARSE>   // SPARSE: the compaction form for the flagge
 __global__ void k_fast_cells(const uint8_t *pyr, size_t pyrImgBytes, const LevelGeom *geom, int nlevels, int totalCells,
                              uint32_t *cellCnt, uint32_t *cellRaw, uint32_t *slots, size_t slotsPerImg, int iniTh, int minTh, int ESrt,
                              int SSrt, int tileRows, int ldsPerWave, int phaseLimit, CellBases cb, unsigned stripLevels,
-                             const int32_t *sparseFlag, FastHist fh);  // orbx_fast.hip
+                             const int32_t *sparseFlag, FastHist fh, Level0 lv0);  // orbx_fast.hip
 __global__ void k_gather(const LevelGeom *geom, int nlevels, int totalCells, const uint32_t *cellCnt, const uint32_t *cellRaw,
                          const uint32_t *slots, size_t slotsPerImg, uint32_t *cand, size_t keysPerImg, int32_t *candCnt, int iniTh,
                          int minTh, CellBases cb, int32_t *sparseFlag, int sparsePerCell, int32_t *sparseSeen, int callSeq);                                                               // orbx_fast.hip
@@ -189,4 +189,4 @@ __global__ void k_octree_wide(const LevelGeom *geom, int nlevels, const uint32_t
 template <int GAUSS, bool SPLIT>   // ORBX_GAUSS_ROUND_* / ORBX_GAUSS_FIXED_TAPS: column rounding / taps of the fused Gaussian (orbx_flavour_t); SPLIT: a launch of a split call (DescGroup)
 __global__ void k_describe(const uint8_t *pyr, size_t pyrImgBytes, const LevelGeom *geom, int nlevels, const uint32_t *lvlKp,
                            int lvlKpCap, const int32_t *lvlCnt, orbx_keypoint_t *kps, uint8_t *desc, int32_t *counts,
-                           int cap, uint8_t *dbgBlur, const uint8_t *blur, unsigned blurMask, DescGroup grp);                                                                             // orbx_describe.hip
+                           int cap, uint8_t *dbgBlur, const uint8_t *blur, unsigned blurMask, DescGroup grp, Level0 lv0);                                                                             // orbx_describe.hip

@@ -137,7 +137,7 @@ __global__ __launch_bounds__(64 * FAST_WAVES) void k_fast_cells(
     const uint8_t *__restrict__ pyr, size_t pyrImgBytes, const LevelGeom *__restrict__ geom, int nlevels,
     int totalCells, uint32_t *__restrict__ cellCnt, uint32_t *__restrict__ cellRaw, uint32_t *__restrict__ slots, size_t slotsPerImg,
     int iniTh, int minTh, int ESrt, int SSrt, int tileRows, int ldsPerWave, int phaseLimit, CellBases cb, unsigned stripLevels,
-    const int32_t *__restrict__ sparseFlag, FastHist fh) {
+    const int32_t *__restrict__ sparseFlag, FastHist fh, Level0 lv0) {
     const int ES = ES_T ? ES_T : ESrt, SS = ES_T ? ES_T - 8 : SSrt;
     extern __shared__ __align__(16) uint8_t smem[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(64 * FAST_WAVES) void k_fast_cells(
     const size_t a = (size_t)(ORBX_EDGE + iniY) * g.pstride + ORBX_EDGE + iniX;
     const int sh = (int)(a & 3);
     {
-        const uint32_t *src = (const uint32_t *)(pyr + (size_t)b * pyrImgBytes + g.poff + (a - sh));
+        const uint32_t *src = (const uint32_t *)(level_base(pyr, pyrImgBytes, lv0, b, l, g.poff) + (a - sh));
         const int nd = (sh + tw + 3) >> 2, pstr4 = g.pstride >> 2, items = nd * th;
         // E column index = byte offset inside the aligned row (window column + sh): every item
         // is one aligned 16-byte LDS write, no bounds checks
@@ -406,7 +406,7 @@ __device__ __forceinline__ uint32_t dpp_row_shl1(uint32_t v) { return (uint32_t)
 __global__ __launch_bounds__(64 * FAST_WAVES) void k_fast_strips(
     const uint8_t *__restrict__ pyr, size_t pyrImgBytes, const LevelGeom *__restrict__ geom, int nlevels, int totalStrips,
     int totalCells, uint32_t *__restrict__ cellCnt, uint32_t *__restrict__ cellRaw, uint32_t *__restrict__ slots, size_t slotsPerImg,
-    int iniTh, int minTh, StripBases sb, const int32_t *__restrict__ sparseFlag, int strip0, int skipSparse) {
+    int iniTh, int minTh, StripBases sb, const int32_t *__restrict__ sparseFlag, int strip0, int skipSparse, Level0 lv0) {
     __shared__ __align__(16) uint32_t smem[FAST_WAVES * STRIP_SLOTS * STRIP_ES];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     int bx, b;
@@ -443,7 +443,7 @@ __global__ __launch_bounds__(64 * FAST_WAVES) void k_fast_strips(
     uint32_t *E = smem + wave * (STRIP_SLOTS * STRIP_ES);
     const size_t a = (size_t)(ORBX_EDGE + iniY) * g.pstride + ORBX_EDGE + Xs;
     const int sh = (int)(a & 3);
-    const uint8_t *src = pyr + (size_t)b * pyrImgBytes + g.poff + (a - sh);
+    const uint8_t *src = level_base(pyr, pyrImgBytes, lv0, b, l, g.poff) + (a - sh);
     const int nd = (sh + tws + 3) >> 2;                       // aligned source dwords per window row (<= 36)
     const int qi = min(lane, nd - 1);                         // lanes past the row repeat its last item (same value, same address)
     const uint32_t loff = (uint32_t)qi * 4u;
@@ -632,7 +632,7 @@ __device__ __forceinline__ uint32_t lds_pair(const uint8_t *p) { return (uint32_
 __global__ __launch_bounds__(64 * FAST_WAVES) __attribute__((amdgpu_waves_per_eu(7, 7))) void k_fast_strips_sparse(
     const uint8_t *__restrict__ pyr, size_t pyrImgBytes, const LevelGeom *__restrict__ geom, int nlevels, int totalStrips,
     int totalCells, uint32_t *__restrict__ cellCnt, uint32_t *__restrict__ cellRaw, uint32_t *__restrict__ slots, size_t slotsPerImg,
-    int iniTh, int minTh, StripBases sb, const int32_t *__restrict__ sparseFlag) {
+    int iniTh, int minTh, StripBases sb, const int32_t *__restrict__ sparseFlag, Level0 lv0) {
     __shared__ __align__(16) uint8_t smem[FAST_WAVES * SP_LDS_PER_WAVE];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     int bx, b;
@@ -668,7 +668,7 @@ __global__ __launch_bounds__(64 * FAST_WAVES) __attribute__((amdgpu_waves_per_eu
     uint32_t *RowHit = (uint32_t *)(Q + SP_K * 64);                           // bit r: row r of the block holds a score >= min(iniTh, minTh)
     const size_t a = (size_t)(ORBX_EDGE + iniY) * g.pstride + ORBX_EDGE + Xs;
     const int sh = (int)(a & 3);
-    const uint8_t *src = pyr + (size_t)b * pyrImgBytes + g.poff + (a - sh);
+    const uint8_t *src = level_base(pyr, pyrImgBytes, lv0, b, l, g.poff) + (a - sh);
     const int nd = (sh + tws + 3) >> 2;                       // aligned source dwords per window row (<= 36)
     const int qi = min(lane, nd - 1);                         // lanes past the row repeat its last item (same value, same address)
     const uint32_t loff = (uint32_t)qi * 4u;
@@ -904,7 +904,7 @@ __global__ __launch_bounds__(256) void k_gather(const LevelGeom *__restrict__ ge
 // the tile strides of the usual 30-px cell grids + the run-time-stride instance, each in the dense and the compaction form
 #define ORBX_FAST_INSTANCE(EST, SP)                                                                                              \
     template __global__ void k_fast_cells<EST, SP>(const uint8_t *, size_t, const LevelGeom *, int, int, uint32_t *, uint32_t *, \
-                                                   uint32_t *, size_t, int, int, int, int, int, int, int, CellBases, unsigned, const int32_t *, FastHist)
+                                                   uint32_t *, size_t, int, int, int, int, int, int, int, CellBases, unsigned, const int32_t *, FastHist, Level0)
 ORBX_FAST_INSTANCE(0, false);
 ORBX_FAST_INSTANCE(44, false);
 ORBX_FAST_INSTANCE(48, false);

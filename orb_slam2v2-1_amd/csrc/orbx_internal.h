@@ -50,6 +50,20 @@ template <class T> static inline hipError_t scratch_malloc(T **p, size_t bytes) 
 template <class T> static inline hipError_t scratch_host_malloc(T **p, size_t bytes, unsigned flags) { return hipHostMalloc((void **)p, bytes, flags); }
 #endif
 
+// Level 0 of a batch read IN PLACE from the caller's images (orbx_extract_batch_device_padded): image b's padded level 0 - the layout
+// of orbx_level0_layout, which is LevelGeom[0]'s - starts at base + b * imgBytes.  base == NULL: level 0 is in the pyramid block like
+// every other level (k_pyr_pad<true> copied it there).  A kernel argument of everything that addresses level 0 (level_base,
+// orbx_extract_dev.h), and a property of each pyramid buffer of the handle: it travels with the buffer when they rotate.
+struct Level0 { const uint8_t *base; size_t imgBytes; };
+// Where level l of image b starts.  Image and level are wave-uniform at every call site, so the choice is one select on the scalar
+// unit; levels >= 1 always live in the pyramid block.
+__device__ __forceinline__ const uint8_t *level_base(const uint8_t *pyr, size_t pyrImgBytes, const Level0 &z, int b, int l, unsigned long long poff) {
+    const bool ext = l == 0 && z.base != nullptr;
+    const uint8_t *base = ext ? z.base : pyr;
+    const size_t img = ext ? z.imgBytes : pyrImgBytes, off = ext ? 0 : (size_t)poff;
+    return base + (size_t)b * img + off;
+}
+
 struct orbx_extractor {
     int nfeatures, nlevels, ini_th, min_th, device;
     double scale_factor;
@@ -99,6 +113,9 @@ struct orbx_extractor {
     orbx_keypoint_t *d_kpsB; uint8_t *d_descB; size_t splitBytes; hipEvent_t evGather, evOctA;
     uint8_t *d_pyrNext; size_t pyrNextBytes; int pyrBuffers;   // three-buffer mode (orbx_set_pyramid_buffers): the pyramid built ahead gets a buffer of its own, the previous one survives it
     int prevPyrValid;   // d_pyrAlt still holds the pyramid of the call before the last one (orbm_stereo_batch_device_prev)
+    Level0 lv0, lv0Alt, lv0Next;   // where level 0 of d_pyr / d_pyrAlt / d_pyrNext lives (base NULL: in the buffer itself); swapped with the buffers
+    int lv0Stale;       // > 0: level 0 of that many images of d_pyr has not been copied from lv0 (test hooks copy it on demand, ensure_level0)
+    int pfPadded;       // the pyramid built ahead was asked for through the in-place entry point (part of what the next call must repeat)
     hipEvent_t evFastDone, evPrefetch;
     hipStream_t last_stream; // stream of the last batch call (NULL is a stream too: the HIP default stream)
     int last_valid;          // ... once there has been one

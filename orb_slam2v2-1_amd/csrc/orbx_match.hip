@@ -194,7 +194,7 @@ __global__ __launch_bounds__(64 * ST_WAVES) void k_stereo_match(
     const int32_t *__restrict__ nl, const orbx_keypoint_t *__restrict__ kr, const uint8_t *__restrict__ dr,
     const int32_t *__restrict__ nr, int cap, float mbf, float mb, float *__restrict__ uright,
     float *__restrict__ depth, int32_t *__restrict__ sad, const uint2 *__restrict__ rc, const int32_t *__restrict__ binStart,
-    const uint4 *__restrict__ binItems, int bhShift, int nbins) {
+    const uint4 *__restrict__ binItems, int bhShift, int nbins, Level0 lv0L, Level0 lv0R) {
     // Candidates = the right keypoints of this keypoint's row bin; the survivors of the exact tests are compacted
     // (ballot prefix) so that their descriptors are fetched by all lanes at once.
     __shared__ uint16_t s_cand[ST_WAVES][ST_CAND];
@@ -289,9 +289,10 @@ __global__ __launch_bounds__(64 * ST_WAVES) void k_stereo_match(
             const int w = 5, L = 5;
             const float iniu = scaleduR0 + L - w, endu = scaleduR0 + L + w + 1;
             if (!(iniu < 0 || endu >= lv.w[levelL])) {
-                const uint8_t *IL = pyrL + (size_t)b * pyrImgL + lv.poffL[levelL] +
+                // (level 0 of either camera may be the caller's images, read in place: the windows stay inside the image, guarded above)
+                const uint8_t *IL = level_base(pyrL, pyrImgL, lv0L, b, levelL, lv.poffL[levelL]) +
                                     (size_t)ORBX_EDGE * lv.pstrideL[levelL] + ORBX_EDGE;
-                const uint8_t *IR = pyrR + (size_t)b * pyrImgR + lv.poffR[levelL] +
+                const uint8_t *IR = level_base(pyrR, pyrImgR, lv0R, b, levelL, lv.poffR[levelL]) +
                                     (size_t)ORBX_EDGE * lv.pstrideR[levelL] + ORBX_EDGE;
                 const int sL = lv.pstrideL[levelL], sR = lv.pstrideR[levelL];
                 const int cy = (int)scaledvL, cxl = (int)scaleduL, cxr0 = (int)scaleduR0;
@@ -575,6 +576,11 @@ static int stereo_batch_impl(orbx_extractor_t *hl, orbx_extractor_t *hr, int B, 
         return ORBX_ERR_ARG;
     }
     const uint8_t *pyrL = prev ? hl->d_pyrAlt : hl->d_pyr, *pyrR = prev ? hr->d_pyrAlt : hr->d_pyr;
+    // level 0 of a pyramid whose extraction read its images in place is still the caller's buffer: the matcher reads it there too
+    // (the contract of orbx_extract_batch_device_padded keeps the images unchanged until this call has finished)
+    Level0 lv0L = prev ? hl->lv0Alt : hl->lv0, lv0R = prev ? hr->lv0Alt : hr->lv0;
+    if (lv0L.base) lv0L.base += (size_t)left_slot0 * lv0L.imgBytes;
+    if (lv0R.base) lv0R.base += (size_t)right_slot0 * lv0R.imgBytes;
     StereoLevels lv;
     int rc = fill_stereo_levels(hl, hr, &lv);
     if (rc) return rc;
@@ -602,7 +608,7 @@ static int stereo_batch_impl(orbx_extractor_t *hl, orbx_extractor_t *hr, int B, 
     hipLaunchKernelGGL(k_stereo_bins, dim3(B), dim3(SB_T), 0, st, lv, d_kr, hl->st_rc, d_nr, cap, bhShift, nbins, hl->st_binStart, hl->st_items);
     hipLaunchKernelGGL(k_stereo_match, grid, dim3(64 * ST_WAVES), 0, st, lv, pyrL + (size_t)left_slot0 * hl->sp.pyrImgBytes, hl->sp.pyrImgBytes,
                        pyrR + (size_t)right_slot0 * hr->sp.pyrImgBytes, hr->sp.pyrImgBytes, d_kl, d_dl, d_nl, d_kr, d_dr, d_nr, cap, mbf, mb, d_uright, d_depth,
-                       hl->st_sad, hl->st_rc, hl->st_binStart, hl->st_items, bhShift, nbins);
+                       hl->st_sad, hl->st_rc, hl->st_binStart, hl->st_items, bhShift, nbins, lv0L, lv0R);
     if (finish_rec)   // one frame, latency path: median step + the whole record to pinned host memory, one launch
     {
         const int uBegin = finish_tail_only ? (120 * cap) >> 4 : 0;

@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256) void k_pyr_level(uint8_t *__restrict__ pyr, si
                                                    const LevelGeom *__restrict__ geom, int l,
                                                    const int32_t *__restrict__ tab, int nxc, int nbands,
                                                    const PyrColRec *__restrict__ cols, const uint32_t *__restrict__ bands,
-                                                   uint32_t rcpNxc, uint32_t rcpNbx) {
+                                                   uint32_t rcpNxc, uint32_t rcpNbx, Level0 lv0) {
     static_assert((RW == 8 || RW == 16) && SR <= 32, "a 32-bit mask of source rows");
     constexpr int BW = PYR_BAND_HEAD + SR;   // words of a band record (pyr_band_words)
     // xcd_block_map (orbx_internal.h) with the division by the grid width done by udiv_rcp: everything here is blockIdx / argument
@@ -194,7 +194,8 @@ __global__ __launch_bounds__(256) void k_pyr_level(uint8_t *__restrict__ pyr, si
     const LevelGeom G = geom[l];
     const int sh = geom[l - 1].h, sps = geom[l - 1].pstride;
     uint8_t *base = pyr + (size_t)b * pyrImgBytes;
-    const uint8_t *srow0 = base + geom[l - 1].poff + (size_t)ORBX_EDGE * sps;   // padded row of source row 0
+    // (the source of level 1 may be the caller's images: the column records clamp to inner columns, the frame's bytes are never selected)
+    const uint8_t *srow0 = level_base(pyr, pyrImgBytes, lv0, (int)b, l - 1, geom[l - 1].poff) + (size_t)ORBX_EDGE * sps;   // padded row of source row 0
     uint8_t *drow0 = base + G.poff + (size_t)ORBX_EDGE * G.pstride + ORBX_EDGE;
     const int x0 = xc * 128 + 2 * lane - 1;
     // The pair store is 2-byte aligned (ORBX_EDGE + x0 is even).  Columns -1 and w fall on frame bytes
@@ -514,7 +515,7 @@ __global__ __launch_bounds__(256) void k_pyr_chain(uint8_t *__restrict__ pyr, si
     }
 }
 
-template __global__ void k_pyr_level<8, 12>(uint8_t *, size_t, const LevelGeom *, int, const int32_t *, int, int, const PyrColRec *, const uint32_t *, uint32_t, uint32_t);
-template __global__ void k_pyr_level<16, 22>(uint8_t *, size_t, const LevelGeom *, int, const int32_t *, int, int, const PyrColRec *, const uint32_t *, uint32_t, uint32_t);
+template __global__ void k_pyr_level<8, 12>(uint8_t *, size_t, const LevelGeom *, int, const int32_t *, int, int, const PyrColRec *, const uint32_t *, uint32_t, uint32_t, Level0);
+template __global__ void k_pyr_level<16, 22>(uint8_t *, size_t, const LevelGeom *, int, const int32_t *, int, int, const PyrColRec *, const uint32_t *, uint32_t, uint32_t, Level0);
 template __global__ void k_pyr_pad<true>(const uint8_t *, int, size_t, uint8_t *, size_t, const LevelGeom *, int);
 template __global__ void k_pyr_pad<false>(const uint8_t *, int, size_t, uint8_t *, size_t, const LevelGeom *, int);

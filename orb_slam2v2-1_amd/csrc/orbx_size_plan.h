@@ -138,6 +138,10 @@ static inline int pyr_depth(int nIni, int N, int cellCap) {
     return d;
 }
 static inline int pyr_deep_cells(const LevelGeom &g) { return g.nIni << (2 * g.pyrDepth); }
+// Bytes of one image a caller hands over in level 0's own layout (orbx_level0_layout): the padded level, plus 64 bytes so that a
+// load that starts on the level's last dword may be up to 16 bytes wide wherever the image sits in the caller's allocation (inside the
+// pyramid block the next level follows), rounded up to the 256 bytes the pyramid block's images are apart by
+static inline size_t level0_image_bytes(const LevelGeom &g0) { return ((size_t)g0.pstride * g0.prows + 64 + 255) & ~(size_t)255; }
 static inline size_t pow2_at_least(int n) { size_t p = 1; while (p < (size_t)n) p <<= 1; return p; }
 // Dynamic LDS of k_octree_pyr, term by term as octree_pyr_body carves it (orbx_octree.hip:233-241, :252, :264-265): the sort keys;
 // per list node cntA 8 + nidA 8 + hist 16 + pn 4 + xlist 2 + split 1; the count pyramid; the 16-bit path tables (regW + regH); the

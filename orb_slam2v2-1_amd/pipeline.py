@@ -63,7 +63,7 @@ def independent_stream(dev, busy, ncand=8):
 class FrontEnd:
     def __init__(self, w, h, nfeatures, stereo, B, device_index=0, nbuf=3, streams=1, world=1, gather=False,
                  gather_via_host=False, mbf=KITTI_BF, fx=KITTI_FX, scale_factor=1.2, nlevels=8, ini_th=20, min_th=7, prefetch=True, lag_stereo=True,
-                 stereo_late=None, gather_B=None, two_side=None, fast_alone=None, force_gather=False):
+                 stereo_late=None, gather_B=None, two_side=None, fast_alone=None, force_gather=False, level0_in_place=None):
         if not torch.cuda.is_available():
             raise RuntimeError("orb_slam2v2-1_amd.pipeline.FrontEnd needs a GPU: the HIP path has no CPU fallback")
         self.w, self.h, self.nf, self.stereo, self.B = w, h, nfeatures, stereo, B
@@ -110,6 +110,15 @@ class FrontEnd:
         # from the end of the descriptors to the end of the matcher: ~50 us of a 612-us step.  Without it the matcher runs beside FAST
         # (62 -> 285 us, hidden; FAST 265 -> 277 us) and the step takes 0.573 ms: 104.8 -> 111.8 k frames/s (three runs each, +-0.1).
         self.fast_alone = bool(int(_os.environ.get("ORBX_FAST_ALONE", "0")) if fast_alone is None else fast_alone)
+        # level0_in_place (the default): the resident batches are placed ONCE in the layout the library publishes for pyramid level 0
+        # (orbx_level0_layout) and every step reads level 0 there (orbx_extract_batch_device_padded) instead of copying each image into
+        # the pyramid block first.  False (or ORBX_LEVEL0_IN_PLACE=0): dense [nimg, h, w] batches through orbx_extract_batch_device, as
+        # a caller has them who cannot choose where its frames land.  Same results.  Resident batches never change, so the lifetime
+        # rule of the in-place form (images unchanged until the lagged matcher has read them) holds by construction; host streaming,
+        # which overwrites its image buffers, stays on the dense form (enable_host_streaming).
+        self.in_place = bool(int(_os.environ.get("ORBX_LEVEL0_IN_PLACE", "1")) if level0_in_place is None else level0_in_place)
+        self._lay = None
+        self._levels = (int(nlevels), float(scale_factor))
         self.two_side = bool(self.late and (int(_os.environ.get("ORBX_TWO_SIDE", "0")) if two_side is None else two_side))
         if self.two_side:
             self.fast_alone = True     # the pyramid of step i+2 (side) overwrites what matcher(i-1) (side2) reads: ordered through FAST(i+1)'s wait
@@ -132,7 +141,9 @@ class FrontEnd:
         for e in self.exs:
             e(imgs[0])                  # plan for this image size; max_keypoints() is now exact
         self.cap = self.ex.max_keypoints()
-        self.d_imgs = torch.from_numpy(np.ascontiguousarray(imgs)).to(self.dev)
+        if self.in_place:
+            self._lay = _pkg.level0_layout(self.w, self.h, *self._levels)
+        self.d_imgs = self._place(imgs)
         self.d_sets = [self.d_imgs]
         nbuf, world, gather, via_host, gB, force = self._ring_args
         self.ring = ResultRing(nbuf, self.B, self.nimg, self.cap, self.dev, world=world, gather=gather,
@@ -143,11 +154,38 @@ class FrontEnd:
         """One more resident batch of the same shape: step i then works on batch i % (number of batches)."""
         imgs = np.concatenate([left, right]) if self.stereo else left
         assert imgs.shape == (self.nimg, self.h, self.w) and imgs.dtype == np.uint8
-        self.d_sets.append(torch.from_numpy(np.ascontiguousarray(imgs)).to(self.dev))
+        self.d_sets.append(self._place(imgs))
         return self
+
+    def _place(self, imgs):
+        """One resident batch in HBM: dense [nimg, h, w], or - in-place form - [nimg, image_bytes] with every frame at its place in the
+        layout of pyramid level 0 (pixel (0,0) at pixel0_offset, rows pstride apart).  The margins keep what the allocation held: the
+        library neither reads results from them nor writes them."""
+        dense = torch.from_numpy(np.ascontiguousarray(imgs)).to(self.dev)
+        if self._lay is None:
+            return dense
+        lay = self._lay
+        buf = torch.empty((self.nimg, lay["image_bytes"]), dtype=torch.uint8, device=self.dev)
+        buf.as_strided((self.nimg, self.h, self.w), (lay["image_bytes"], lay["pstride"], 1), lay["pixel0_offset"]).copy_(dense)
+        return buf
 
     def _imgs(self, i):
         return self.d_sets[i % len(self.d_sets)].data_ptr()
+
+    def _extract(self, exi, i, j, st):
+        r = self.ring
+        if self._lay is not None and self._hs is None:
+            exi.extract_batch_device_padded(self._imgs(i), self.nimg, self.w, self.h, self._lay["image_bytes"], r.kps[j].data_ptr(),
+                                            r.desc[j].data_ptr(), r.cnt[j].data_ptr(), self.cap, st)
+        else:
+            exi.extract_batch_device(self._imgs(i), self.nimg, self.w, self.h, self.w, self.w * self.h, r.kps[j].data_ptr(), r.desc[j].data_ptr(),
+                                     r.cnt[j].data_ptr(), self.cap, st)
+
+    def _prefetch(self, exi, i, sd):
+        if self._lay is not None and self._hs is None:
+            exi.prefetch_batch_device_padded(self._imgs(i), self.nimg, self.w, self.h, self._lay["image_bytes"], sd)
+        else:
+            exi.prefetch_batch_device(self._imgs(i), self.nimg, self.w, self.h, self.w, self.w * self.h, sd)
 
     def _match(self, exi, j, st, prev=False):
         r, B, cap = self.ring, self.B, self.cap
@@ -199,7 +237,9 @@ class FrontEnd:
                                      been issued when the pipelined matcher is on: that is when step i's matcher is in the queue)
             wait(i)                  host blocks until fetch(i) has landed; returns the pinned arrays
         Three image buffers: the upload of batch i + 2 must not wait for the pyramid of batch i (two buffers would chain the copy
-        engine - the bottleneck, 60 MB per 64 stereo frames - to the compute queue).  Call after upload() (plans, result ring)."""
+        engine - the bottleneck, 60 MB per 64 stereo frames - to the compute queue).  Call after upload() (plans, result ring).
+        The image buffers are DENSE and the step copies level 0 (orbx_extract_batch_device): a buffer is free behind the extraction
+        (ev_free), which is too early for the in-place form, whose lagged matcher still reads level 0 in the caller's buffer."""
         assert self.ring is not None and self.S == 1
         # with the frames arriving over PCIe the step is upload-bound: the pyramid of batch i + 1 waits for its upload, and in the
         # pyramid-first order of the side stream that wait sits in front of the matcher of batch i - 1, which the next FAST waits for
@@ -285,7 +325,6 @@ class FrontEnd:
         j = r.acquire(i)
         exi, stream = self.exs[i % self.S], self.streams[i % self.S]
         st = stream.cuda_stream
-        B, cap, w, h = self.B, self.cap, self.w, self.h
         hs = self._hs
         if hs is not None:
             stream.wait_event(hs.ev_up[i % hs.n])            # this batch is in HBM (long since, when its pyramid was built ahead)
@@ -298,8 +337,7 @@ class FrontEnd:
             stream.wait_event(self._ev_side.pop(j))     # the matcher that last wrote buffer set j (nbuf steps ago) is long done
         if lag and self.fast_alone and self._ev_late is not None:
             stream.wait_event(self._ev_late)            # late order: the previous step's matcher is the last job of the side stream
-        exi.extract_batch_device(self._imgs(i), self.nimg, w, h, w, w * h, r.kps[j].data_ptr(), r.desc[j].data_ptr(),
-                                 r.cnt[j].data_ptr(), cap, st)
+        self._extract(exi, i, j, st)
         if hs is not None:
             k = i % hs.n
             if getattr(hs.ev_free[k], "_batch", None) != i:     # pyramid not built ahead: the buffer is free behind this extraction
@@ -353,14 +391,14 @@ class FrontEnd:
         hs = self._hs
         sd = side.cuda_stream if side is not None else None
         if hs is None:
-            exi.prefetch_batch_device(self._imgs(i + self.S), self.nimg, self.w, self.h, self.w, self.w * self.h, sd)
+            self._prefetch(exi, i + self.S, sd)
             return
         k = (i + 1) % hs.n
         ev = hs.ev_up[k]
         if ev is None or getattr(ev, "_batch", None) != i + 1:
             return                       # batch i + 1 has not been submitted yet: its own step builds the pyramid
         side.wait_event(ev)
-        exi.prefetch_batch_device(self._imgs(i + 1), self.nimg, self.w, self.h, self.w, self.w * self.h, sd)
+        self._prefetch(exi, i + 1, sd)
         fr = torch.cuda.Event()
         fr.record(side)
         fr._batch = i + 1
