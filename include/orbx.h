@@ -1228,6 +1228,95 @@ int orbg_optimize_essential_graph(const orbg_vertex_t *vertices, int N, const or
                                   int fix_scale, int iterations, float *Tcw_out16, float *pts_out3, double *est_out8, orbg_info_t *info,
                                   int device);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * Covisibility: KeyFrame::UpdateConnections (src/KeyFrame.cc:290-380), LocalMapping::KeyFrameCulling (src/LocalMapping.cc:640-704)
+ * and MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:340-383) over ONE observation table, the reference's
+ * std::map<KeyFrame*, size_t> of every map point laid out as rows.  DESIGN.md section 6, "k_cov_*".
+ *
+ * Keyframes are addressed by slot 0..K-1; slot order stands for the walk order of the reference's std::map<KeyFrame*, ...>, which is
+ * pointer order there (the host classes fill slots in ascending mnId: a stated difference).  Point p owns
+ * obs[obs_off[p] .. obs_off[p+1]), strictly ascending in kf.  Query q is keyframe slot query_kf[q] with the features
+ * feat[feat_off[q] .. feat_off[q+1]) in feature-slot order: GetMapPointMatches().  scale_factors[nlevels] is the one extractor's table
+ * every keyframe of the reference copies.
+ *
+ * PRECONDITION (not checked here; the Python wrappers check it by default): for a query keyframe, a feature that names point p
+ * implies that p's list holds an observation by that keyframe, and for orbc_keyframe_culling an observation (kf, idx) of p by a query
+ * keyframe implies that feature idx of that query names p (KeyFrame::SetBadFlag walks the features, src/KeyFrame.cc:470-472).  The
+ * query keyframes of a culling call are distinct.
+ *
+ * Every index range is checked on the host in the pass that packs the upload: kf, ref_kf, point, octave < nlevels, idx >= 0, offsets
+ * that start at 0 and do not decrease, kf strictly ascending inside a list, query_kf, a repeated culling query, th < 1, cap < 0:
+ * ORBX_ERR_ARG with a message, before a device is touched.  More than ORBC_MAX_CULL_KEYFRAMES keyframes in a culling call:
+ * ORBX_ERR_UNSUPPORTED.  No usable GPU: ORBX_ERR_NO_DEVICE; there is no CPU path.  Scratch, pinned mirror and stream are per host
+ * thread (orbx_thread_release_scratch); a call is one upload, its launches, one download and one stream synchronisation. */
+#define ORBC_LDS_KEYFRAMES 8192          /* k_cov_count keeps the counters of one query in LDS up to this K (32 KiB of the CU's 160); beyond: its row of a global block */
+#define ORBC_SORT_LDS 1024               /* k_cov_order sorts a list up to this length in LDS; beyond: the radix core of orbx_cloud_dev.h */
+#define ORBC_MAX_CULL_KEYFRAMES 262144   /* k_cull keeps the set of culled keyframes as one bit each in LDS (32 KiB) */
+typedef struct { int32_t id;            /* mnId: 0 is never culled (src/LocalMapping.cc:651, src/KeyFrame.cc:458) */
+                 uint8_t bad;           /* mbBad: carried, read by no kernel (src/KeyFrame.cc:310 tests the POINT, never the keyframe) */
+                 uint8_t not_erase;     /* mbNotErase (src/KeyFrame.cc:460-464) */
+                 uint8_t pad[2];
+                 float Ow[3];           /* GetCameraCenter() (src/MapPoint.cc:362) */
+                 float th_depth;        /* mThDepth (src/LocalMapping.cc:668) */
+} orbc_keyframe_t;                      /* 24 B */
+typedef struct { float pos[3];          /* mWorldPos (src/MapPoint.cc:357) */
+                 int32_t ref_kf;        /* slot of mpRefKF, -1 for none (src/MapPoint.cc:356) */
+                 uint8_t bad;           /* isBad() (src/KeyFrame.cc:310, src/LocalMapping.cc:664) */
+                 uint8_t pad[3];
+} orbc_point_t;                         /* 20 B */
+typedef struct { int32_t kf;            /* slot: the map's key */
+                 int32_t idx;           /* the map's value: the feature index in that keyframe */
+                 uint8_t octave;        /* mvKeysUn[idx].octave (src/LocalMapping.cc:683, src/MapPoint.cc:373) */
+                 uint8_t stereo;        /* mvuRight[idx] >= 0 (src/MapPoint.cc:121-127: nObs counts 2) */
+                 uint8_t pad[2];
+} orbc_observation_t;                   /* 12 B */
+typedef struct { int32_t point;         /* -1: a NULL slot of mvpMapPoints */
+                 int32_t octave;        /* mvKeysUn[i].octave (src/LocalMapping.cc:675) */
+                 float depth;           /* mvDepth[i] (src/LocalMapping.cc:668) */
+} orbc_feature_t;                       /* 12 B */
+typedef struct { float normal[3];       /* mNormalVector (src/MapPoint.cc:381) */
+                 float max_distance;    /* mfMaxDistance (src/MapPoint.cc:379) */
+                 float min_distance;    /* mfMinDistance (src/MapPoint.cc:380) */
+                 int32_t status;        /* ORBC_NORMAL_* ; nonzero: the five floats are 0 */
+} orbc_normal_t;                        /* 24 B */
+#define ORBC_NORMAL_OK 0
+#define ORBC_NORMAL_BAD 1                /* the point is bad (src/MapPoint.cc:349) */
+#define ORBC_NORMAL_NO_OBSERVATION 2     /* its list is empty (src/MapPoint.cc:359) */
+#define ORBC_NORMAL_NO_REFERENCE 3       /* ref_kf is -1 or not in its list: the reference is undefined there (observations[pRefKF] inserts 0, :373) */
+typedef struct { const orbc_keyframe_t *kf; int32_t K; const orbc_point_t *pts; int32_t P; const int32_t *obs_off /* [P + 1] */;
+                 const orbc_observation_t *obs; const float *scale_factors; int32_t nlevels; } orbc_table_t;
+typedef struct { const int32_t *query_kf; int32_t Q; const int32_t *feat_off /* [Q + 1] */; const orbc_feature_t *feat; } orbc_queries_t;
+/* UpdateConnections of Q keyframes, each independent of the others.  counter[k] = the number of (feature, observation) pairs of the
+ * query in which the feature's point is neither -1 nor bad and the observation's kf == k != the query's slot; a point named by two
+ * features counts twice (:303-321).  Every counter 0: n[q] = 0 (:324-325).  Otherwise the list is every k with counter[k] >= th (the
+ * reference: 15), or, if there is none, the one entry (nmax, the first slot in ascending order that reaches the strict maximum)
+ * (:335-353); ordered by descending weight and, among equal weights, descending slot: sort on (weight, pointer) and push_front
+ * (:355-362).  ids, weights [Q][cap]: the first min(n[q], cap) entries, the rest untouched; n[q]: the full length; counters [Q][K]
+ * (may be NULL): mConnectedKeyFrameWeights with 0 for an absent key. */
+typedef struct { int32_t th, cap; int32_t *ids, *weights, *n, *counters; } orbc_connections_t;
+/* KeyFrameCulling over the queries in the order of vpLocalKeyFrames: the result of the reference's SEQUENTIAL loop, in which
+ * pKF->SetBadFlag() changes what later keyframes see (src/KeyFrame.cc:454-472, src/MapPoint.cc:121-178).  With C the set of query
+ * keyframes culled so far: an observation by a keyframe in C is gone; a point's nObs is the sum over its remaining observations of
+ * stereo ? 2 : 1; a point is bad if it was bad on entry, or lost at least one observation and has nObs <= 2 left.  Per query: id == 0:
+ * verdict 0, counts 0.  A feature is skipped if its point is -1 or bad, or if !monocular && (depth > th_depth || depth < 0); otherwise
+ * n_mps++, and n_redundant++ if nObs > th_obs (the reference: 3) and at least th_obs remaining observations by other keyframes have
+ * octave_i <= octave + 1.  verdict = (double)n_redundant > 0.9 * (double)n_mps ? (not_erase ? 2 : 1) : 0; 1 joins C, 2 is
+ * mbToBeErased and does not.  point_bad [P] (may be NULL): every point's flag after the whole loop. */
+typedef struct { int32_t monocular, th_obs; int32_t *n_mps, *n_redundant, *verdict; uint8_t *point_bad; } orbc_culling_t;
+/* Any of the three results of one table in ONE upload: a NULL conn / cull / normals is not computed (the queries of a NULL result may
+ * be NULL too).  All three see the table as it is on entry.  normals [P]: what host/frame_shim.h's MapPoint::UpdateNormalAndDepth
+ * pins: normali = pos - Ow_i in float, its squared norm a double sum in the order 0 1 2, inv = (float)(1.0 / sqrt(s)),
+ * normal = normali * inv + normal as a separate multiply and add, the observations strictly in list order, dist = (float)norm(pos -
+ * Ow_ref), max = dist * sf[octave of the reference keyframe's observation], min = max / sf[nlevels - 1] correctly rounded,
+ * normal_out = (float)((double)normal * (1.0 / n)). */
+int orbc_covisibility(const orbc_table_t *table, const orbc_queries_t *conn_queries, const orbc_connections_t *conn,
+                      const orbc_queries_t *cull_queries, const orbc_culling_t *cull, orbc_normal_t *normals, int device);
+int orbc_update_connections(const orbc_table_t *table, const orbc_queries_t *queries, int th, int cap, int32_t *ids, int32_t *weights,
+                            int32_t *n, int32_t *counters, int device);
+int orbc_keyframe_culling(const orbc_table_t *table, const orbc_queries_t *queries, int monocular, int th_obs, int32_t *n_mps,
+                          int32_t *n_redundant, int32_t *verdict, uint8_t *point_bad, int device);
+int orbc_update_normal_and_depth(const orbc_table_t *table, orbc_normal_t *normals, int device);
+
 /* The host-array matcher entry points keep grow-only device scratch, a pinned mirror and one non-blocking stream
  * PER HOST THREAD (re-entrant without locks: the reference calls matchers from Tracking, LocalMapping and LoopClosing
  * threads at once, src/LocalMapping.cc:223, src/LoopClosing.cc:249).  Nothing is freed implicitly; a thread calls

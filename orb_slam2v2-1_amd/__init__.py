@@ -84,6 +84,15 @@ EG_VERTEX_DTYPE = np.dtype([("Scw", EG_SIM3_DTYPE), ("Snc", EG_SIM3_DTYPE), ("ha
 EG_EDGE_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("kind", "<i4")])      # kind 0: loop connection, 1: spanning tree / loop / covisibility
 EG_POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("ref", "<i4")])
 EG_MAX_ITERATIONS = 64
+# covisibility (include/orbx.h, orbc_*): the observation table's records
+COVIS_KEYFRAME_DTYPE = np.dtype([("id", "<i4"), ("bad", "u1"), ("not_erase", "u1"), ("pad", "u1", (2,)), ("Ow", "<f4", (3,)), ("th_depth", "<f4")])
+COVIS_POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("ref_kf", "<i4"), ("bad", "u1"), ("pad", "u1", (3,))])
+COVIS_OBSERVATION_DTYPE = np.dtype([("kf", "<i4"), ("idx", "<i4"), ("octave", "u1"), ("stereo", "u1"), ("pad", "u1", (2,))])
+COVIS_FEATURE_DTYPE = np.dtype([("point", "<i4"), ("octave", "<i4"), ("depth", "<f4")])
+COVIS_NORMAL_DTYPE = np.dtype([("normal", "<f4", (3,)), ("max_distance", "<f4"), ("min_distance", "<f4"), ("status", "<i4")])
+COVIS_LDS_KEYFRAMES = 8192           # ORBC_LDS_KEYFRAMES: k_cov_count's counters of one query live in LDS up to this K
+COVIS_SORT_LDS = 1024                # ORBC_SORT_LDS: k_cov_order sorts a list in LDS up to this length
+COVIS_MAX_CULL_KEYFRAMES = 262144    # ORBC_MAX_CULL_KEYFRAMES
 EG_INFO_DTYPE = np.dtype([("iterations", "<i4"), ("trials", "<i4"), ("end", "<i4"), ("free_vertices", "<i4"), ("blocks", "<i4"), ("levels", "<i4"),
                           ("launches", "<i4"), ("pad", "<i4"), ("chi2_first", "<f8"), ("chi2_last", "<f8"), ("trials_it", "<i4", (EG_MAX_ITERATIONS,))])
 EG_END_ITERATIONS, EG_END_QMAX, EG_END_RHO0, EG_END_SOLVER, EG_END_NBAD = 0, 1, 2, 3, 4      # info["end"]
@@ -149,6 +158,7 @@ NEWPOINTS_EXPORTS = ["orbl_triangulate", "orbl_triangulate_batch", "orbl_baselin
 LBA_EXPORTS = ["orbb_optimize", "orbb_local_bundle_adjustment", "orbb_bundle_adjustment", "orbb_optimize_blocked", "orbb_global_bundle_adjustment"]
 # the essential graph section (prefix orbg_), apart for the same reason
 ESSENTIAL_EXPORTS = ["orbg_optimize_essential_graph"]
+COVIS_EXPORTS = ["orbc_covisibility", "orbc_update_connections", "orbc_keyframe_culling", "orbc_update_normal_and_depth"]
 # what include/orbx_dev.h declares on top: exported by the developer build only
 DEV_EXPORTS = ["orbx_debug_level_points", "orbx_debug_sincosf", "orbx_debug_blur_patches", "orbm_debug_features_in_area",
                "orbx_debug_blurred_level", "orbx_debug_octree_fallbacks", "orbm_debug_match_path", "orbm_debug_resolve_plan",
@@ -490,6 +500,10 @@ def _load(path, dev):
     L.orbp_pnp_parameters.argtypes = [i32, C.c_double, i32, i32, i32, f32, C.POINTER(i32), C.POINTER(i32)]
     L.orbp_pnp_ransac.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
     L.orbp_pnp_ransac_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
+    L.orbc_covisibility.argtypes = [vp, vp, vp, vp, vp, vp, i32]
+    L.orbc_update_connections.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, i32]
+    L.orbc_keyframe_culling.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, i32]
+    L.orbc_update_normal_and_depth.argtypes = [vp, vp, i32]
     if dev:
         L.orbx_debug_level_points.argtypes = [vp, i32, i32, i32, vp, i32, C.POINTER(i32)]
         L.orbx_debug_sincosf.argtypes = [vp, i32, vp, vp, i32]
@@ -1576,6 +1590,145 @@ def optimize_essential_graph(vertices, edges, points, fix_scale, iterations=20, 
                                                        _p(est), _p(info), int(device)))
     inf = {k: (info[0][k].item() if info[0][k].ndim == 0 else [int(x) for x in info[0][k]]) for k in EG_INFO_DTYPE.names}
     return To, Po, est, inf
+
+
+class CovisTable(C.Structure):
+    """orbc_table_t; `keep` holds the arrays the pointers look into."""
+    _fields_ = [("kf", C.c_void_p), ("K", C.c_int32), ("pts", C.c_void_p), ("P", C.c_int32), ("obs_off", C.c_void_p), ("obs", C.c_void_p),
+                ("scale_factors", C.c_void_p), ("nlevels", C.c_int32)]
+
+
+class CovisQueries(C.Structure):
+    """orbc_queries_t"""
+    _fields_ = [("query_kf", C.c_void_p), ("Q", C.c_int32), ("feat_off", C.c_void_p), ("feat", C.c_void_p)]
+
+
+class CovisConnections(C.Structure):
+    """orbc_connections_t"""
+    _fields_ = [("th", C.c_int32), ("cap", C.c_int32), ("ids", C.c_void_p), ("weights", C.c_void_p), ("n", C.c_void_p), ("counters", C.c_void_p)]
+
+
+class CovisCulling(C.Structure):
+    """orbc_culling_t"""
+    _fields_ = [("monocular", C.c_int32), ("th_obs", C.c_int32), ("n_mps", C.c_void_p), ("n_redundant", C.c_void_p), ("verdict", C.c_void_p),
+                ("point_bad", C.c_void_p)]
+
+
+def covis_table(keyframes, points, rows, scale_factors):
+    """The observation table of the orbc_* entry points.  keyframes [K] COVIS_KEYFRAME_DTYPE in slot order, points [P] COVIS_POINT_DTYPE,
+    rows: (point, kf, idx, octave, stereo) per observation in any order, scale_factors [nlevels] -> dict with the CSR arrays: a point's
+    list is sorted by kf (the walk order of the reference's std::map).  Two rows of one point by one keyframe raise ValueError."""
+    kf = np.ascontiguousarray(keyframes, COVIS_KEYFRAME_DTYPE)
+    pt = np.ascontiguousarray(points, COVIS_POINT_DTYPE)
+    r = np.asarray(rows, np.int64).reshape(-1, 5)
+    if len(r) and (r[:, 0].min() < 0 or r[:, 0].max() >= len(pt)):
+        raise ValueError("covis_table: a row names a point outside [0, %d)" % len(pt))
+    order = np.lexsort((r[:, 1], r[:, 0]))
+    r = r[order]
+    if len(r) > 1 and ((r[1:, 0] == r[:-1, 0]) & (r[1:, 1] == r[:-1, 1])).any():
+        raise ValueError("covis_table: a point is observed twice by one keyframe")
+    obs = np.zeros(len(r), COVIS_OBSERVATION_DTYPE)
+    obs["kf"], obs["idx"], obs["octave"], obs["stereo"] = r[:, 1], r[:, 2], r[:, 3], r[:, 4] != 0
+    off = np.zeros(len(pt) + 1, np.int32)
+    off[1:] = np.cumsum(np.bincount(r[:, 0], minlength=len(pt)))
+    return {"kf": kf, "pts": pt, "obs_off": off, "obs": obs, "sf": np.ascontiguousarray(scale_factors, np.float32)}
+
+
+def covis_queries(query_kf, features):
+    """Query keyframes of an orbc_* call: query_kf [Q] slots, features: per query an array of COVIS_FEATURE_DTYPE in feature-slot order
+    (GetMapPointMatches()) -> dict with query_kf, feat_off, feat."""
+    qk = np.ascontiguousarray(query_kf, np.int32).reshape(-1)
+    fs = [np.ascontiguousarray(f, COVIS_FEATURE_DTYPE).reshape(-1) for f in features]
+    if len(fs) != len(qk):
+        raise ValueError("covis_queries: %d feature arrays for %d queries" % (len(fs), len(qk)))
+    off = np.zeros(len(qk) + 1, np.int32)
+    off[1:] = np.cumsum([len(f) for f in fs])
+    return {"query_kf": qk, "feat_off": off, "feat": np.concatenate(fs) if fs else np.zeros(0, COVIS_FEATURE_DTYPE)}
+
+
+def covis_check(table, queries, culling=False):
+    """The precondition of include/orbx.h that the library does not check: a query's feature that names point p has an observation of p
+    by that keyframe; with culling also the converse for (kf, idx), and distinct queries.  Raises ValueError."""
+    off, obs = table["obs_off"], table["obs"]
+    P = len(table["pts"])
+    for q, s in enumerate(queries["query_kf"]):
+        f = queries["feat"][queries["feat_off"][q]:queries["feat_off"][q + 1]]
+        for i in np.nonzero(f["point"] >= 0)[0]:
+            p = int(f["point"][i])
+            if p >= P:
+                continue   # the library reports it
+            if not (obs["kf"][off[p]:off[p + 1]] == s).any():
+                raise ValueError("covisibility: query %d (slot %d): feature %d names point %d, which has no observation by that keyframe" % (q, s, i, p))
+        if culling:
+            mine = np.nonzero(obs["kf"] == s)[0]
+            owner = np.searchsorted(off, mine, side="right") - 1
+            for o, p in zip(mine, owner):
+                i = int(obs["idx"][o])
+                if i >= len(f) or f["point"][i] != p:
+                    raise ValueError("covisibility: query %d (slot %d): point %d lists feature %d, which does not name it" % (q, s, p, i))
+
+
+def _covis_c_table(t):
+    return CovisTable(_p(t["kf"]), len(t["kf"]), _p(t["pts"]), len(t["pts"]), _p(t["obs_off"]), _p(t["obs"]), _p(t["sf"]), len(t["sf"]))
+
+
+def _covis_c_queries(q):
+    return CovisQueries(_p(q["query_kf"]), len(q["query_kf"]), _p(q["feat_off"]), _p(q["feat"]))
+
+
+def covisibility(table, connections=None, culling=None, normals=False, check=True, device=0):
+    """Any of the three covisibility results of one table with ONE upload (orbc_covisibility).  connections: dict(queries=covis_queries(..),
+    th=15, cap=None (K), counters=False); culling: dict(queries=.., monocular=.., th_obs=3, point_bad=True); normals: bool.
+    -> dict with "connections": (ids [Q, cap], weights [Q, cap] (-1 beyond n), n [Q], counters [Q, K] or None),
+    "culling": (n_mps [Q], n_redundant [Q], verdict [Q], point_bad [P] or None), "normals": [P] COVIS_NORMAL_DTYPE - those asked for."""
+    L = matcher_lib()
+    ct = _covis_c_table(table)
+    K, P = len(table["kf"]), len(table["pts"])
+    out = {}
+    cq = cc = kq = kc = None
+    nrm = np.zeros(P, COVIS_NORMAL_DTYPE) if normals else None
+    if connections is not None:
+        q = connections["queries"]
+        if check:
+            covis_check(table, q)
+        Q = len(q["query_kf"])
+        cap = connections.get("cap")
+        cap = K if cap is None else int(cap)
+        ids, w, n = np.full((Q, max(cap, 0)), -1, np.int32), np.full((Q, max(cap, 0)), -1, np.int32), np.zeros(Q, np.int32)
+        cnt = np.zeros((Q, K), np.int32) if connections.get("counters") else None
+        cq, cc = _covis_c_queries(q), CovisConnections(int(connections.get("th", 15)), cap, _p(ids), _p(w), _p(n), _p(cnt))
+        out["connections"] = (ids, w, n, cnt)
+    if culling is not None:
+        q = culling["queries"]
+        if check:
+            covis_check(table, q, culling=True)
+        Q = len(q["query_kf"])
+        nm, nr, v = np.zeros(Q, np.int32), np.zeros(Q, np.int32), np.zeros(Q, np.int32)
+        pb = np.zeros(P, np.uint8) if culling.get("point_bad", True) else None
+        kq, kc = _covis_c_queries(q), CovisCulling(int(bool(culling["monocular"])), int(culling.get("th_obs", 3)), _p(nm), _p(nr), _p(v), _p(pb))
+        out["culling"] = (nm, nr, v, pb)
+    _check(L.orbc_covisibility(C.addressof(ct), C.addressof(cq) if cq else None, C.addressof(cc) if cc else None, C.addressof(kq) if kq else None,
+                               C.addressof(kc) if kc else None, _p(nrm), int(device)), L)
+    if normals:
+        out["normals"] = nrm
+    return out
+
+
+def update_connections(table, queries, th=15, cap=None, counters=False, check=True, device=0):
+    """KeyFrame::UpdateConnections of the query keyframes (orbc_update_connections) -> (ids, weights, n, counters or None): row q holds the
+    first min(n[q], cap) entries of mvpOrderedConnectedKeyFrames / mvOrderedWeights as slots, -1 beyond."""
+    return covisibility(table, connections=dict(queries=queries, th=th, cap=cap, counters=counters), check=check, device=device)["connections"]
+
+
+def keyframe_culling(table, queries, monocular, th_obs=3, point_bad=True, check=True, device=0):
+    """LocalMapping::KeyFrameCulling over the queries in order (orbc_keyframe_culling) -> (n_mps, n_redundant, verdict, point_bad or None);
+    verdict 1: SetBadFlag erased the keyframe, 2: mbToBeErased."""
+    return covisibility(table, culling=dict(queries=queries, monocular=monocular, th_obs=th_obs, point_bad=point_bad), check=check, device=device)["culling"]
+
+
+def update_normal_and_depth(table, device=0):
+    """MapPoint::UpdateNormalAndDepth of every point (orbc_update_normal_and_depth) -> [P] COVIS_NORMAL_DTYPE."""
+    return covisibility(table, normals=True, device=device)["normals"]
 
 
 def essential_graph_edges(mnid, bad, parent, children, loop_edges, covisibles, weight, loop_connections, cur, loop, min_feat=100):

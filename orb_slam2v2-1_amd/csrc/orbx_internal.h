@@ -158,6 +158,7 @@ void orbx_internal_release_sim3opt_scratch();                // orbx_sim3opt.hip
 void orbx_internal_release_newpoints_scratch();              // orbx_newpoints.hip   (thread-local StagePair)
 void orbx_internal_release_lba_scratch();                    // orbx_lba.hip         (thread-local StagePair)
 void orbx_internal_release_essential_scratch();              // orbx_essential.hip   (thread-local StagePair)
+void orbx_internal_release_covis_scratch();                  // orbx_covis.hip       (thread-local StagePair)
 // orbx_bow.hip: ORBmatcher::SearchForTriangulation's node-list checks and its launch sequence on device-resident arrays, for its own
 // entry point and for orbl_create_new_map_points (orbx_newpoints.hip)
 int orbx_internal_tri_check(const char *fn, const int32_t *node_qstart, const int32_t *q_items, int nq, const int32_t *node_cstart,

@@ -1,5 +1,6 @@
-// LocalMapping.cc — ORB_SLAM2::LocalMapping::CreateNewMapPoints over include/orbx.h (see LocalMapping.h).
+// LocalMapping.cc — ORB_SLAM2::LocalMapping::CreateNewMapPoints and KeyFrameCulling over include/orbx.h (see LocalMapping.h).
 #include "LocalMapping.h"
+#include "Covisibility.h"
 #include <cstdlib>
 #include <cstring>
 #include <stdexcept>
@@ -145,6 +146,19 @@ void LocalMapping::CreateNewMapPoints() {
             mlpRecentAddedMapPoints.push_back(pMP);
         }
     }
+}
+
+void LocalMapping::KeyFrameCulling() {
+    const std::vector<KeyFrame *> vpLocalKeyFrames = mpCurrentKeyFrame->GetVectorCovisibleKeyFrames();   // :646
+    if (vpLocalKeyFrames.empty()) return;
+    CovisTables T;
+    T.Build(vpLocalKeyFrames, std::vector<MapPoint *>());
+    const size_t Q = vpLocalKeyFrames.size();
+    std::vector<int32_t> nMPs(Q), nRedundant(Q), verdict(Q);
+    if (orbc_keyframe_culling(&T.table, &T.queries, mbMonocular ? 1 : 0, 3, nMPs.data(), nRedundant.data(), verdict.data(), NULL, device) != ORBX_OK)
+        throw std::runtime_error(std::string("KeyFrameCulling: ") + orbx_last_error());
+    for (size_t q = 0; q < Q; q++)
+        if (verdict[q]) vpLocalKeyFrames[q]->SetBadFlag();   // :701-702; 2: the keyframe's mbNotErase turns it into mbToBeErased
 }
 
 }  // namespace ORB_SLAM2

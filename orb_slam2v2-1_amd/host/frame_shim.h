@@ -213,6 +213,30 @@ public:
     std::vector<float> mvuRight, mvDepth;
     // the covisibility graph reduced to its result: the ordered list (src/KeyFrame.cc:316-324 returns its first N entries)
     std::vector<KeyFrame *> mvpOrderedConnectedKeyFrames;
+    std::vector<int> mvOrderedWeights;   // include/KeyFrame.h: the weights of mvpOrderedConnectedKeyFrames (src/KeyFrame.cc:370)
+    // what LocalMapping::KeyFrameCulling reads and sets (include/KeyFrame.h)
+    bool mbNotErase = false, mbToBeErased = false;
+    float mThDepth = 0.f;
+    // src/KeyFrame.cc:454-472 plus mbBad = true (:540): the early returns, the neighbours forget this keyframe (EraseConnection, :554-569,
+    // whose re-sort of a consistent list is the list without the entry), then every map point does.  No spanning tree (:480-539), no
+    // map and no keyframe database (:544-545): the shim has none of them to repair
+    void SetBadFlag() {
+        if (mnId == 0) return;
+        else if (mbNotErase) { mbToBeErased = true; return; }
+        for (std::map<KeyFrame *, int>::iterator mit = mConnectedKeyFrameWeights.begin(), mend = mConnectedKeyFrameWeights.end(); mit != mend; mit++) {
+            KeyFrame *o = mit->first;
+            if (!o->mConnectedKeyFrameWeights.erase(this)) continue;
+            for (size_t i = 0; i < o->mvpOrderedConnectedKeyFrames.size(); i++)
+                if (o->mvpOrderedConnectedKeyFrames[i] == this) {
+                    o->mvpOrderedConnectedKeyFrames.erase(o->mvpOrderedConnectedKeyFrames.begin() + i);
+                    if (i < o->mvOrderedWeights.size()) o->mvOrderedWeights.erase(o->mvOrderedWeights.begin() + i);
+                    break;
+                }
+        }
+        for (size_t i = 0; i < mvpMapPoints.size(); i++)
+            if (mvpMapPoints[i]) mvpMapPoints[i]->EraseObservation(this);
+        mbBad = true;
+    }
     std::vector<KeyFrame *> GetBestCovisibilityKeyFrames(const int &n) {
         if ((int)mvpOrderedConnectedKeyFrames.size() < n) return mvpOrderedConnectedKeyFrames;
         return std::vector<KeyFrame *>(mvpOrderedConnectedKeyFrames.begin(), mvpOrderedConnectedKeyFrames.begin() + n);
