@@ -2,6 +2,7 @@
 // (part of the ORB extractor, see orbx_extract.hip for the pipeline and the C ABI)
 #include "orbx_extract_dev.h"
 #include "orbx_bufaddr.h"
+#include "orbx_fast_network.h"
 // ------------------------------------------------------------------------------------
 // K2: one wave per 30-px cell (:789-829).  The cell window (cell + 6 px) is staged in LDS
 // as one dword per pixel holding the pixel PAIR (p, p+1) in two 16-bit halves, so that the
@@ -40,35 +41,31 @@ __device__ __forceinline__ half2v pk_max3(half2v a, half2v b, half2v c) {
 // min_k (r[k] - v).  The centre is the same in every term, so it leaves the minima: dark = v - A, bright = B - v with
 //     A = min over arcs of (max of the arc's ring pixels),   B = max over arcs of (min of the arc's ring pixels)
 // computed on the ring values themselves: no per-position difference (16 packed subtractions per pair less).
-// Two neighbouring arcs share eight elements: min(max arc_2j, max arc_2j+1) = max(C_j, min(r[2j], r[2j+9])) with
-// C_j = max r[2j+1..2j+8], and C_j is two of the eight 4-windows q[t] = max r[2t+1..2t+4]: 36 packed ops per polarity.
+// A and B come from the network of orbx_fast_network.h (the arcs grouped by eight, two 3-windows reused inside each group):
+// 29 packed operations per polarity, 58 per pixel pair (pairing neighbouring arcs over eight 4-windows took 36 + 36); with the
+// two differences, their maximum and the caller's clamp this is "the 62-operation score" of the comments below.  Every operation
+// is PINNED to one v_pk_minimum3_f16 / v_pk_maximum3_f16: through the builtins the compiler
+// re-associates the nested maxima, recomputes the two shared 3-windows and keeps 6 of the 14 operations saved per row.  The asm
+// is not volatile, so the scheduler still moves the operations between the ring's LDS reads.
 // Returns the two values as signed 16-bit halves (negative = far from a corner).
+struct PkMin3 {
+    __device__ __forceinline__ uint32_t operator()(uint32_t a, uint32_t b, uint32_t c) const {
+        uint32_t r;
+        asm("v_pk_minimum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+        return r;
+    }
+};
+struct PkMax3 {
+    __device__ __forceinline__ uint32_t operator()(uint32_t a, uint32_t b, uint32_t c) const {
+        uint32_t r;
+        asm("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+        return r;
+    }
+};
 __device__ __forceinline__ half2v fast_ring_score(uint32_t vv, const uint32_t (&rr)[16]) {
     const half2v v = __builtin_bit_cast(half2v, vv);
-    half2v d[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) d[k] = __builtin_bit_cast(half2v, rr[k]);
-    half2v pmn[8], pmx[8];
-#pragma unroll
-    for (int t = 0; t < 8; t++) {
-        pmn[t] = __builtin_elementwise_minimum(d[2 * t + 1], d[(2 * t + 2) & 15]);
-        pmx[t] = __builtin_elementwise_maximum(d[2 * t + 1], d[(2 * t + 2) & 15]);
-    }
-    half2v qmn[8], qmx[8];
-#pragma unroll
-    for (int t = 0; t < 8; t++) {
-        qmn[t] = __builtin_elementwise_minimum(pmn[t], pmn[(t + 1) & 7]);
-        qmx[t] = __builtin_elementwise_maximum(pmx[t], pmx[(t + 1) & 7]);
-    }
-    half2v lo[8], hi[8];   // per arc pair: the larger of the two arc minima / the smaller of the two arc maxima
-#pragma unroll
-    for (int t = 0; t < 8; t++) {
-        const half2v e0 = d[2 * t], e1 = d[(2 * t + 9) & 15];
-        lo[t] = pk_min3(qmn[t], qmn[(t + 2) & 7], __builtin_elementwise_maximum(e0, e1));
-        hi[t] = pk_max3(qmx[t], qmx[(t + 2) & 7], __builtin_elementwise_minimum(e0, e1));
-    }
-    const half2v Bv = pk_max3(pk_max3(lo[0], lo[1], lo[2]), pk_max3(lo[3], lo[4], lo[5]), __builtin_elementwise_maximum(lo[6], lo[7]));
-    const half2v Av = pk_min3(pk_min3(hi[0], hi[1], hi[2]), pk_min3(hi[3], hi[4], hi[5]), __builtin_elementwise_minimum(hi[6], hi[7]));
+    const half2v Av = __builtin_bit_cast(half2v, fast_arc_extreme(rr, PkMax3(), PkMin3()));   // min over the arcs of the arc's max
+    const half2v Bv = __builtin_bit_cast(half2v, fast_arc_extreme(rr, PkMin3(), PkMax3()));   // max over the arcs of the arc's min
     return __builtin_elementwise_maximum(v - Av, Bv - v);
 }
 
@@ -123,10 +120,10 @@ __device__ __forceinline__ void fast_nms_pair(const uint8_t *Sc, int SS, int cw,
 // 21 of its 150 VALU instructions per pixel pair on address arithmetic.  ES_T == 0: run-time strides (any configuration).
 //
 // SPARSE (round 4): the same kernel for the corner-sparse levels of the strip kernel's range (cells up to 32 px wide whose
-// (image slot, level) the previous call flagged: a few candidates per cell, the regime of real footage).  There the 76-operation
+// (image slot, level) the previous call flagged: a few candidates per cell, the regime of real footage).  There the 62-operation
 // score is wasted on most pixels, and skipping it lane by lane saves nothing (an instruction issues for the whole wave), so the
 // work is COMPACTED: (1) every pixel pair goes through the exact five-pixel bound on score + 1 (every nine-arc of the ring holds
-// r[0] or r[8] and r[4] or r[12]; the necessary condition cv::FAST itself tests first), 9 packed operations instead of 76; (2) the
+// r[0] or r[8] and r[4] or r[12]; the necessary condition cv::FAST itself tests first), 9 packed operations instead of 62; (2) the
 // pairs that can reach min(iniTh, minTh) are appended to an LDS queue in row-major order (ballot prefix); (3) the queue is scored
 // 64 pairs at a time with per-lane ring addressing, the scores scattered into the zeroed score tile; (4) the 3x3 suppression and
 // the ordered emission run over the queue entries only.  A pair that fails the bound has a score below both thresholds: the dense
@@ -513,7 +510,7 @@ __global__ __launch_bounds__(64 * FAST_WAVES) void k_fast_strips(
                 // <= min(max(r0, r8), max(r4, r12)) - v and dark = v - (min over arcs of the arc's maximum) <= v - max(min(r0, r8),
                 // min(r4, r12)): an upper bound U of score + 1 from five pixels (the necessary condition cv::FAST itself tests first).
                 // A pixel with U <= min(iniTh, minTh) has a score below both thresholds: it is never emitted and never beats a
-                // neighbour that is, so its score may be taken as 0; when that holds for all 128 pixels of the row the 76-operation
+                // neighbour that is, so its score may be taken as 0; when that holds for all 128 pixels of the row the 62-operation
                 // score is skipped.  Same keypoints by construction.
                 const half2v v = __builtin_bit_cast(half2v, vv), a0 = __builtin_bit_cast(half2v, rr[0]), a4 = __builtin_bit_cast(half2v, rr[4]),
                              a8 = __builtin_bit_cast(half2v, rr[8]), a12 = __builtin_bit_cast(half2v, rr[12]);
@@ -607,7 +604,7 @@ __global__ __launch_bounds__(64 * FAST_WAVES) void k_fast_strips(
 // ------------------------------------------------------------------------------------
 // K2s: the strip kernel for CORNER-SPARSE levels (a few FAST candidates per cell: real footage; the (image slot, level)s the
 // previous call's quad-tree flagged).  Same wave = strip of four cells, same lane = pixel pair, same suppression in registers and
-// same ordered emission as k_fast_strips - but the 76-operation score is computed only where it can matter, and COMPACTED:
+// same ordered emission as k_fast_strips - but the 62-operation score is computed only where it can matter, and COMPACTED:
 //   * every pair of a row goes through the five-pixel bound on score + 1 (every nine-arc of the ring holds r[0] or r[8] and r[4]
 //     or r[12]: the necessary condition cv::FAST itself tests first; exact - a pair that fails it has a score below both thresholds,
 //     is never emitted and never beats a pixel that is, so its score may be taken as 0);
