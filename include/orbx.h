@@ -1317,6 +1317,71 @@ int orbc_keyframe_culling(const orbc_table_t *table, const orbc_queries_t *queri
                           int32_t *n_redundant, int32_t *verdict, uint8_t *point_bad, int device);
 int orbc_update_normal_and_depth(const orbc_table_t *table, orbc_normal_t *normals, int device);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * The local map: Tracking::UpdateLocalMap (src/Tracking.cc:1340-1484: UpdateLocalKeyFrames + UpdateLocalPoints) on a snapshot of the
+ * map that stays on the device (row a34, prefix orbt_).  DESIGN.md section 6, "k_lm_*".
+ *
+ * A handle holds one snapshot and the per-frame state; orbt_localmap_set_map replaces the snapshot with one upload when the map
+ * changed, orbt_update_local_map is the one call per tracked frame: N point indices up, the local lists down.  One handle is used by
+ * one thread at a time.  The handle's buffers only grow.  orbt_localmap_create touches no device.
+ *
+ * The snapshot: `table` is the observation table of the orbc_ section, unchanged (slot order stands for the reference's pointer
+ * order); `features` are every keyframe's GetMapPointMatches(): Q == K and query_kf[q] == q, and only feat[].point is read;
+ * parent[K]: slot of GetParent() or -1; cov_off[K + 1] / cov[]: GetVectorCovisibleKeyFrames() as slots, in the ordered list's order;
+ * child_off[K + 1] / child[]: GetChilds() as slots, ascending (the reference walks a std::set<KeyFrame*>: a stated difference of the
+ * same kind as the table's); views[P]; desc[P][32]: GetDescriptor().
+ * Every index range and offset array is checked on the host in the packing pass: ORBX_ERR_ARG with a message before a device is
+ * touched.  K > ORBC_MAX_CULL_KEYFRAMES (the marks are one bit per slot in LDS): ORBX_ERR_UNSUPPORTED.  No usable GPU:
+ * ORBX_ERR_NO_DEVICE; the handle then has no snapshot, and orbt_update_local_map still checks its arguments against that map's K and
+ * P (ORBX_ERR_ARG) before it returns ORBX_ERR_NO_DEVICE. */
+typedef struct { float normal[3];       /* GetNormal() */
+                 float max_distance;    /* mfMaxDistance */
+                 float min_distance;    /* mfMinDistance */
+                 int32_t observations;  /* Observations(): nObs */
+} orbt_pointview_t;                     /* 24 B */
+typedef struct { const orbc_table_t *table; const orbc_queries_t *features; const int32_t *parent; const int32_t *cov_off, *cov;
+                 const int32_t *child_off, *child; const orbt_pointview_t *views; const uint8_t *desc; } orbt_map_t;
+#define ORBT_END_RAN_OUT 0              /* every first-stage keyframe was visited */
+#define ORBT_END_LENGTH 1               /* the list was longer than max_keyframes (src/Tracking.cc:1430) */
+#define ORBT_END_PARENT 2               /* a parent was appended: the `break` at :1473 leaves the loop over the keyframes */
+typedef struct { int32_t empty_vote, n_voted, ref_kf, ref_votes, extension_end, launches, syncs, pad; } orbt_local_info_t;   /* 32 B */
+/* The result of one frame; the caller owns the arrays: frame_points, holder, ext_obs [N]; local_kf [K]; local_pts, pts [P];
+ * mp_desc [P][32].  Only the used prefix of local_kf / local_pts / pts / mp_desc is written. */
+typedef struct { int32_t *frame_points, *holder, *ext_obs; int32_t *local_kf; int32_t *local_pts; orbm_worldpoint_t *pts; uint8_t *mp_desc;
+                 int32_t n_local_kf, n_local_pts; orbt_local_info_t info; } orbt_local_t;
+typedef struct orbt_localmap orbt_localmap_t;
+int orbt_localmap_create(int device, orbt_localmap_t **out);
+void orbt_localmap_destroy(orbt_localmap_t *h);
+/* K, P, the total feature count and the snapshot's bytes of the last orbt_localmap_set_map whose checks passed; device_bytes: what
+ * the handle holds on the device.  Any pointer may be NULL */
+int orbt_localmap_info(const orbt_localmap_t *h, int *K, int *P, int64_t *features, size_t *snapshot_bytes, size_t *device_bytes);
+int orbt_localmap_set_map(orbt_localmap_t *h, const orbt_map_t *map);
+/* One frame.  frame_points[i]: the point index of mCurrentFrame.mvpMapPoints[i] or -1; prev_kf[n_prev]: the previous local
+ * keyframes, distinct slots.  The result is that of the reference's sequential code:
+ * 0. fp[i] = -1 if the point is bad, else frame_points[i] (:1382-1394, :1296-1299) -> out->frame_points.
+ * 1. counter[k] = the number of (feature i, observation o) pairs with fp[i] >= 0 and o in that point's list with o.kf == k; a point
+ *    named by two features counts twice; a bad keyframe's counter counts like any other (:1380-1396).
+ * 2. Every counter 0: info.empty_vote = 1, the local keyframes are prev_kf unchanged, n_voted = 0, ref_kf = -1 (the caller keeps
+ *    its reference keyframe); continue at 5 (:1398-1399).
+ * 3. The slots with counter > 0 and !bad in ascending slot order; n_voted = their number S; ref_kf = the largest counter's, among
+ *    equals the smallest slot, -1 if S == 0 (the list is then empty, not the previous one: :1404 cleared it); ref_votes its counter.
+ * 4. For j = 0 .. S-1 over the first-stage entries only (appended keyframes are never visited; where the reference's
+ *    reserve(3 * size) would be exceeded its iterators are undefined: the index walk is the stated reading): if the list is longer
+ *    than max_keyframes (the reference: 80) stop - a list of exactly 80 still runs, so it can end at 83.  With kf the j-th entry, in
+ *    order, each step seeing the marks of the ones before: (a) of the first min(nbest, len) entries (the reference: 10) of kf's
+ *    covisible list the first that is not bad and not in the list is appended; (b) of kf's children the first that is not bad and
+ *    not in the list is appended; (c) if parent >= 0 and it is not in the list it is appended, its bad flag NOT tested (:1466-1469),
+ *    and THE WHOLE LOOP ENDS: the `break` at :1473 stands in no inner loop.
+ * 5. UpdateLocalPoints (:1350-1373): the local keyframes in list order, each one's features in slot order; a point index >= 0 that is
+ *    not yet listed and not bad is appended.
+ * 6. What SearchLocalPointsHIP (host/ORBmatcher.cc) packs for orbm_search_local_points, byte for byte: pts[j].observations always;
+ *    valid = 1 and the nine floats only if the point is named by no fp[i] (mnLastFrameSeen, :1303, :1315), otherwise the record is 0
+ *    but for observations; mp_desc[j] the descriptor, or 32 zero bytes where valid == 0; holder[i] = -1 where fp[i] < 0, the local
+ *    index of fp[i] where it is listed, else -2 with ext_obs[i] = that point's observations; ext_obs[i] = 0 elsewhere.
+ * At most two stream synchronisations per call (info.syncs): the lengths, then the used prefixes. */
+int orbt_update_local_map(orbt_localmap_t *h, const int32_t *frame_points, int N, const int32_t *prev_kf, int n_prev, int max_keyframes,
+                          int nbest, orbt_local_t *out);
+
 /* The host-array matcher entry points keep grow-only device scratch, a pinned mirror and one non-blocking stream
  * PER HOST THREAD (re-entrant without locks: the reference calls matchers from Tracking, LocalMapping and LoopClosing
  * threads at once, src/LocalMapping.cc:223, src/LoopClosing.cc:249).  Nothing is freed implicitly; a thread calls

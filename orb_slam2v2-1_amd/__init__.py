@@ -93,6 +93,11 @@ COVIS_NORMAL_DTYPE = np.dtype([("normal", "<f4", (3,)), ("max_distance", "<f4"),
 COVIS_LDS_KEYFRAMES = 8192           # ORBC_LDS_KEYFRAMES: k_cov_count's counters of one query live in LDS up to this K
 COVIS_SORT_LDS = 1024                # ORBC_SORT_LDS: k_cov_order sorts a list in LDS up to this length
 COVIS_MAX_CULL_KEYFRAMES = 262144    # ORBC_MAX_CULL_KEYFRAMES
+# the local map (include/orbx.h, orbt_*): a point's view record and the rule fields of a frame's result
+LOCALMAP_VIEW_DTYPE = np.dtype([("normal", "<f4", (3,)), ("max_distance", "<f4"), ("min_distance", "<f4"), ("observations", "<i4")])
+LOCALMAP_INFO_DTYPE = np.dtype([("empty_vote", "<i4"), ("n_voted", "<i4"), ("ref_kf", "<i4"), ("ref_votes", "<i4"), ("extension_end", "<i4"),
+                                ("launches", "<i4"), ("syncs", "<i4"), ("pad", "<i4")])
+LOCALMAP_END_RAN_OUT, LOCALMAP_END_LENGTH, LOCALMAP_END_PARENT = 0, 1, 2      # ORBT_END_*
 EG_INFO_DTYPE = np.dtype([("iterations", "<i4"), ("trials", "<i4"), ("end", "<i4"), ("free_vertices", "<i4"), ("blocks", "<i4"), ("levels", "<i4"),
                           ("launches", "<i4"), ("pad", "<i4"), ("chi2_first", "<f8"), ("chi2_last", "<f8"), ("trials_it", "<i4", (EG_MAX_ITERATIONS,))])
 EG_END_ITERATIONS, EG_END_QMAX, EG_END_RHO0, EG_END_SOLVER, EG_END_NBAD = 0, 1, 2, 3, 4      # info["end"]
@@ -159,6 +164,8 @@ LBA_EXPORTS = ["orbb_optimize", "orbb_local_bundle_adjustment", "orbb_bundle_adj
 # the essential graph section (prefix orbg_), apart for the same reason
 ESSENTIAL_EXPORTS = ["orbg_optimize_essential_graph"]
 COVIS_EXPORTS = ["orbc_covisibility", "orbc_update_connections", "orbc_keyframe_culling", "orbc_update_normal_and_depth"]
+# the local map section (prefix orbt_), apart for the same reason
+LOCALMAP_EXPORTS = ["orbt_localmap_create", "orbt_localmap_destroy", "orbt_localmap_info", "orbt_localmap_set_map", "orbt_update_local_map"]
 # what include/orbx_dev.h declares on top: exported by the developer build only
 DEV_EXPORTS = ["orbx_debug_level_points", "orbx_debug_sincosf", "orbx_debug_blur_patches", "orbm_debug_features_in_area",
                "orbx_debug_blurred_level", "orbx_debug_octree_fallbacks", "orbm_debug_match_path", "orbm_debug_resolve_plan",
@@ -504,6 +511,12 @@ def _load(path, dev):
     L.orbc_update_connections.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, i32]
     L.orbc_keyframe_culling.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, i32]
     L.orbc_update_normal_and_depth.argtypes = [vp, vp, i32]
+    L.orbt_localmap_create.argtypes = [i32, C.POINTER(vp)]
+    L.orbt_localmap_destroy.argtypes = [vp]
+    L.orbt_localmap_destroy.restype = None
+    L.orbt_localmap_info.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.orbt_localmap_set_map.argtypes = [vp, vp]
+    L.orbt_update_local_map.argtypes = [vp, vp, i32, vp, i32, i32, i32, vp]
     if dev:
         L.orbx_debug_level_points.argtypes = [vp, i32, i32, i32, vp, i32, C.POINTER(i32)]
         L.orbx_debug_sincosf.argtypes = [vp, i32, vp, vp, i32]
@@ -1729,6 +1742,105 @@ def keyframe_culling(table, queries, monocular, th_obs=3, point_bad=True, check=
 def update_normal_and_depth(table, device=0):
     """MapPoint::UpdateNormalAndDepth of every point (orbc_update_normal_and_depth) -> [P] COVIS_NORMAL_DTYPE."""
     return covisibility(table, normals=True, device=device)["normals"]
+
+
+class LocalMapMap(C.Structure):       # orbt_map_t
+    _fields_ = [("table", C.c_void_p), ("features", C.c_void_p), ("parent", C.c_void_p), ("cov_off", C.c_void_p), ("cov", C.c_void_p),
+                ("child_off", C.c_void_p), ("child", C.c_void_p), ("views", C.c_void_p), ("desc", C.c_void_p)]
+
+
+class LocalMapResult(C.Structure):    # orbt_local_t
+    _fields_ = [("frame_points", C.c_void_p), ("holder", C.c_void_p), ("ext_obs", C.c_void_p), ("local_kf", C.c_void_p), ("local_pts", C.c_void_p),
+                ("pts", C.c_void_p), ("mp_desc", C.c_void_p), ("n_local_kf", C.c_int32), ("n_local_pts", C.c_int32), ("info", C.c_int32 * 8)]
+
+
+def localmap_graph(parent, covisibles, children):
+    """The keyframe graph of LocalMap.set_map.  parent [K]: slot of GetParent() or -1; covisibles [K]: GetVectorCovisibleKeyFrames() as
+    lists of slots in the ordered list's order; children [K]: GetChilds() as collections of slots (stored ascending)
+    -> dict(parent, cov_off, cov, child_off, child)."""
+    pa = np.ascontiguousarray(parent, np.int32).reshape(-1)
+    if len(covisibles) != len(pa) or len(children) != len(pa):
+        raise ValueError("localmap_graph: %d parents, %d covisible lists, %d child lists" % (len(pa), len(covisibles), len(children)))
+
+    def csr(lists):
+        off = np.zeros(len(lists) + 1, np.int32)
+        off[1:] = np.cumsum([len(x) for x in lists])
+        flat = [int(v) for x in lists for v in x]
+        return off, np.array(flat, np.int32).reshape(len(flat))
+    co, cv = csr([list(c) for c in covisibles])
+    ho, ch = csr([sorted(int(v) for v in c) for c in children])
+    return {"parent": pa, "cov_off": co, "cov": cv, "child_off": ho, "child": ch}
+
+
+class LocalMap:
+    """Tracking::UpdateLocalMap on a snapshot of the map that stays on the device (orbt_*).  set_map when the map changed, update once per
+    tracked frame.  One object is used by one thread at a time."""
+
+    def __init__(self, device=0):
+        self._L = matcher_lib()
+        h = C.c_void_p()
+        _check(self._L.orbt_localmap_create(int(device), C.byref(h)), self._L)
+        self._h, self.K, self.P = h, 0, 0
+
+    def close(self):
+        if self._h:
+            self._L.orbt_localmap_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def set_map(self, table, features, graph, views, desc):
+        """table: covis_table(..); features: covis_queries(arange(K), every keyframe's GetMapPointMatches()); graph: localmap_graph(..);
+        views [P] LOCALMAP_VIEW_DTYPE; desc [P, 32] uint8."""
+        views = np.ascontiguousarray(views, LOCALMAP_VIEW_DTYPE)
+        desc = np.ascontiguousarray(desc, np.uint8)
+        P = len(table["pts"])
+        if len(views) != P or desc.size != 32 * P:
+            raise ValueError("LocalMap.set_map: %d points, %d views, %d descriptor bytes" % (P, len(views), desc.size))
+        g = {k: np.ascontiguousarray(graph[k], np.int32) for k in ("parent", "cov_off", "cov", "child_off", "child")}
+        K = len(table["kf"])
+        if len(g["parent"]) != K or len(g["cov_off"]) != K + 1 or len(g["child_off"]) != K + 1 or len(features["feat_off"]) != len(features["query_kf"]) + 1:
+            raise ValueError("LocalMap.set_map: the graph's arrays do not have the table's %d keyframes" % K)
+        if (K and (g["cov_off"][K] > len(g["cov"]) or g["child_off"][K] > len(g["child"]))) or (len(features["query_kf"]) and features["feat_off"][-1] > len(features["feat"])):
+            raise ValueError("LocalMap.set_map: an offset array ends beyond its list")
+        ct, cq = _covis_c_table(table), _covis_c_queries(features)
+        m = LocalMapMap(C.addressof(ct), C.addressof(cq), _p(g["parent"]), _p(g["cov_off"]), _p(g["cov"]), _p(g["child_off"]), _p(g["child"]), _p(views), _p(desc))
+        rc = self._L.orbt_localmap_set_map(self._h, C.addressof(m))
+        k, p = C.c_int(), C.c_int()
+        self._L.orbt_localmap_info(self._h, C.addressof(k), C.addressof(p), None, None, None)
+        self.K, self.P = k.value, p.value
+        _check(rc, self._L)
+
+    def info(self):
+        """-> dict(K, P, features, snapshot_bytes, device_bytes)"""
+        k, p, f, sb, db = C.c_int(), C.c_int(), C.c_int64(), C.c_size_t(), C.c_size_t()
+        _check(self._L.orbt_localmap_info(self._h, C.addressof(k), C.addressof(p), C.addressof(f), C.addressof(sb), C.addressof(db)), self._L)
+        return {"K": k.value, "P": p.value, "features": f.value, "snapshot_bytes": sb.value, "device_bytes": db.value}
+
+    def update(self, frame_points, prev_kf=None, max_keyframes=80, nbest=10):
+        """One frame (orbt_update_local_map).  frame_points [N]: the point index of mCurrentFrame.mvpMapPoints[i] or -1; prev_kf: the previous
+        local keyframes -> dict: frame_points, holder, ext_obs [N]; local_kf; local_pts; pts (WORLDPOINT_DTYPE) and mp_desc [m, 32], the arrays
+        search_local_points takes; info (LOCALMAP_INFO_DTYPE record)."""
+        fp = np.ascontiguousarray(frame_points, np.int32).reshape(-1)
+        pk = np.ascontiguousarray(prev_kf if prev_kf is not None else [], np.int32).reshape(-1)
+        N, K, P = len(fp), self.K, self.P
+        o = {"frame_points": np.empty(N, np.int32), "holder": np.empty(N, np.int32), "ext_obs": np.empty(N, np.int32), "local_kf": np.empty(K, np.int32),
+             "local_pts": np.empty(P, np.int32), "pts": np.empty(P, WORLDPOINT_DTYPE), "mp_desc": np.empty((P, 32), np.uint8)}
+        r = LocalMapResult(_p(o["frame_points"]), _p(o["holder"]), _p(o["ext_obs"]), _p(o["local_kf"]), _p(o["local_pts"]), _p(o["pts"]), _p(o["mp_desc"]))
+        _check(self._L.orbt_update_local_map(self._h, _p(fp), N, _p(pk), len(pk), int(max_keyframes), int(nbest), C.addressof(r)), self._L)
+        nk, m = r.n_local_kf, r.n_local_pts
+        o["local_kf"] = o["local_kf"][:nk]
+        for k in ("local_pts", "pts", "mp_desc"):
+            o[k] = o[k][:m]
+        o["info"] = np.array([tuple(r.info)], LOCALMAP_INFO_DTYPE)[0]
+        return o
 
 
 def essential_graph_edges(mnid, bad, parent, children, loop_edges, covisibles, weight, loop_connections, cur, loop, min_feat=100):

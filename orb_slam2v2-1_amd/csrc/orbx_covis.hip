@@ -294,3 +294,7 @@ extern "C" int orbc_update_normal_and_depth(const orbc_table_t *table, orbc_norm
     if (!normals && table && table->P > 0) { orbx_set_error("orbc_update_normal_and_depth: bad arguments"); return ORBX_ERR_ARG; }
     return orbc_covisibility(table, nullptr, nullptr, nullptr, nullptr, normals, device);
 }
+
+// the two checks above for the other users of the table (orbx_localmap.hip)
+int orbx_internal_cov_check_table(const char *fn, const orbc_table_t *t) { return cov_check_table(fn, t); }
+int orbx_internal_cov_check_queries(const char *fn, const orbc_table_t *t, const orbc_queries_t *q, bool distinct) { return cov_check_queries(fn, t, q, distinct); }

@@ -80,6 +80,7 @@ public:
     bool mbBad;
     int nObs;
     long unsigned int mnLastFrameSeen = 0;   // include/MapPoint.h
+    long unsigned int mnTrackReferenceForFrame = 0;   // include/MapPoint.h: the mark of Tracking::UpdateLocalPoints
     int mnVisible = 1;
     void IncreaseVisible(int n = 1) { mnVisible += n; }
     float mfMinDistance = 0.f, mfMaxDistance = 0.f;
@@ -113,6 +114,7 @@ public:
     cv::Mat mDescriptors, mDescriptorsRight;
     std::vector<MapPoint *> mvpMapPoints;
     std::vector<bool> mvbOutlier;
+    KeyFrame *mpReferenceKF = nullptr;   // include/Frame.h: set by Tracking::UpdateLocalKeyFrames
     static float mfGridElementWidthInv, mfGridElementHeightInv;
     cv::Mat mTcw;
     void SetPose(cv::Mat Tcw) { mTcw = Tcw.clone(); }   // src/Frame.cc:262-266, without the derived Rcw / tcw / Ow the matchers do not read
@@ -170,6 +172,8 @@ public:
     std::set<KeyFrame *> mspChildrens, mspLoopEdges;
     std::map<KeyFrame *, int> mConnectedKeyFrameWeights;
     KeyFrame *GetParent() { return mpParent; }
+    std::set<KeyFrame *> GetChilds() { return mspChildrens; }   // src/KeyFrame.cc:398-402
+    long unsigned int mnTrackReferenceForFrame = 0;   // include/KeyFrame.h: the mark of Tracking::UpdateLocalKeyFrames
     bool hasChild(KeyFrame *pKF) { return mspChildrens.count(pKF) != 0; }
     std::set<KeyFrame *> GetLoopEdges() { return mspLoopEdges; }
     int GetWeight(KeyFrame *pKF) { return mConnectedKeyFrameWeights.count(pKF) ? mConnectedKeyFrameWeights[pKF] : 0; }
