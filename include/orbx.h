@@ -1382,6 +1382,62 @@ int orbt_localmap_set_map(orbt_localmap_t *h, const orbt_map_t *map);
 int orbt_update_local_map(orbt_localmap_t *h, const int32_t *frame_points, int N, const int32_t *prev_kf, int n_prev, int max_keyframes,
                           int nbest, orbt_local_t *out);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * Loop map correction: the two map-sized loops of LoopClosing (row a36, prefix orbr_).  DESIGN.md section 6, "k_mc_*".
+ * orbr_correct_loop is src/LoopClosing.cc:444-525 without the UpdateConnections() of :524, which reads no position (the caller runs
+ * orbc_update_connections on the same table); orbr_spread_global_ba is :685-746, what follows Optimizer::GlobalBundleAdjustemnt.
+ * Every index range is checked on the host in the packing pass: ORBX_ERR_ARG with a message before a device is touched.  No usable GPU:
+ * ORBX_ERR_NO_DEVICE after these checks; there is no CPU path.  Scratch, pinned mirror and stream are per host thread
+ * (orbx_thread_release_scratch).
+ *
+ * orbr_correct_loop.  table: the observation table of the orbc_ section, unchanged.  conn: mvpCurrentConnectedKFs with their
+ * GetMapPointMatches(); only feat[].point is read.  query_kf is STRICTLY ASCENDING: slot order stands for the pointer order of the
+ * reference's std::map<KeyFrame*, g2o::Sim3> CorrectedSim3 (the stated difference of the orbc_ section).  cur: the slot of mpCurrentKF,
+ * one of the queries.  Tiw16 [Q][16]: GetPose() of each query.  Scw: mg2oScw.
+ * Per query: Twc of cur as KeyFrame::SetPose derives it from Tiw16[cur] (Ow = -Rwc * tcw), Tic = Tiw * Twc (a float 4x4 product, each
+ * entry a double sum left to right narrowed once), corrected = Sim3(Ric, tic, 1.0) * Scw (Scw itself for cur), non_corrected =
+ * Sim3(Riw, tiw, 1.0), Tiw_new = [R(corrected.q), corrected.t * (1. / s); 0 0 0 1] narrowed, Ow_new = SetPose's centre of Tiw_new.
+ * Per point: a point that is not bad and that a query's feature names belongs to the query of the SMALLEST position that names it
+ * (what mnCorrectedByKF == mpCurrentKF->mnId leaves behind; a point named twice by one keyframe is corrected once).  There is no
+ * mnCorrectedByKF input: a point can only carry the current keyframe's id on entry if that id is 0, and keyframe 0 cannot close a loop.
+ * pos' = (float) corrected[owner]^-1.map(non_corrected[owner].map((double) pos)); then UpdateNormalAndDepth on pos' with the arithmetic
+ * of orbc_covisibility, in which an observer's (and the reference keyframe's) camera centre is Ow_new if that keyframe is a query at a
+ * position strictly below the owner's and the table's Ow otherwise: the owner's own SetPose comes after its point loop (:522).
+ * Outputs (all required): corrected, non_corrected [Q]; Tiw_new16 [Q][16]; Ow_new3 [Q][3]; pos3 [P][3] (the input where no query
+ * owns the point); corrected_ref [P]: the owner's slot (mnCorrectedReference), -1 for an untouched point; normals [P]: the ORBC_NORMAL_*
+ * codes apply to an owned point (a point with an empty list is still moved and reports ORBC_NORMAL_NO_OBSERVATION), and
+ * ORBR_NORMAL_UNTOUCHED marks a point that no query owns, the five floats 0.
+ * ORBX_ERR_ARG: what the orbc_ section checks of a table and a query set, query_kf not strictly ascending, cur not among the queries,
+ * a NULL pointer.  One call is one upload, three launches, one download and one stream synchronisation. */
+#define ORBR_NORMAL_UNTOUCHED 4
+typedef struct { orbg_sim3_t *corrected, *non_corrected; float *Tiw_new16, *Ow_new3, *pos3; int32_t *corrected_ref; orbc_normal_t *normals; } orbr_loop_out_t;
+int orbr_correct_loop(const orbc_table_t *table, const orbc_queries_t *conn, int32_t cur, const float *Tiw16, const orbg_sim3_t *Scw,
+                      const orbr_loop_out_t *out, int device);
+/* orbr_spread_global_ba.  Tcw16 [K][16]: GetPose(); TcwGBA16 [K][16]: mTcwGBA (read only where kf_in_gba); kf_in_gba [K]:
+ * mnBAGlobalForKF == nLoopKF; child_off [K + 1] / child: GetChilds() as slots, as in orbt_map_t; origins [n_origins]:
+ * mvpKeyFrameOrigins as slots; pos3, posGBA3 [P][3]; pt_in_gba [P]; ref_kf [P]: slot of GetReferenceKeyFrame() or -1; bad [P].
+ * The host finds the keyframes the reference's walk reaches from the origins THROUGH THE CHILD LISTS (a bad keyframe keeps its parent
+ * but is in nobody's child set, src/KeyFrame.cc:480-539, and is not reached) and, for each reached keyframe outside the global BA, its
+ * level: the distance to the nearest reached ancestor inside it.  One launch per level: TcwGBA_child = (Tcw_child * Twc_parent) *
+ * TcwGBA_parent, two float 4x4 products in that order, Twc_parent from the parent's pose on entry as SetPose left it.  A keyframe is
+ * marked if it is in the global BA or reached.  Then per point: bad: untouched; pt_in_gba: posGBA; reference keyframe marked and
+ * reached: Xc = Rcw_bef * pos + tcw_bef with the pose on entry, pos = Rwc * Xc + twc with the Twc SetPose derives from the new pose;
+ * otherwise untouched.
+ * Outputs (all required): Tcw_new16 [K][16]: TcwGBA_out of a reached keyframe, the input pose otherwise; TcwGBA_out16 [K][16];
+ * kf_marked [K]; kf_reached [K] (may be NULL): the keyframes the walk popped, whose mTcwBefGBA and SetPose the caller owes (:706-707);
+ * pos_out3 [P][3]; status [P]: ORBR_SPREAD_*; levels: written by the call, the number of launches over the tree.
+ * ORBX_ERR_ARG: an index out of range, offsets that do not start at 0 or decrease, a keyframe in two child lists or in its own, an
+ * origin that is in a child list, is repeated, or is outside the global BA (the reference would SetPose an empty matrix), a NULL
+ * pointer.  One call is one upload, one launch per level and one for the points, one download and one stream synchronisation. */
+#define ORBR_SPREAD_UNTOUCHED 0
+#define ORBR_SPREAD_GBA 1                /* took mPosGBA (:724) */
+#define ORBR_SPREAD_MOVED 2              /* moved with its reference keyframe (:735-744) */
+#define ORBR_SPREAD_UNDEFINED 3          /* ref_kf is -1, or a marked keyframe the walk did not reach (its mTcwBefGBA is empty): the reference is undefined there; untouched */
+typedef struct { int32_t K; const float *Tcw16, *TcwGBA16; const uint8_t *kf_in_gba; const int32_t *child_off, *child; const int32_t *origins;
+                 int32_t n_origins, P; const float *pos3, *posGBA3; const uint8_t *pt_in_gba; const int32_t *ref_kf; const uint8_t *bad; } orbr_spread_in_t;
+typedef struct { float *Tcw_new16, *TcwGBA_out16; uint8_t *kf_marked, *kf_reached; float *pos_out3; int32_t *status; int32_t levels; } orbr_spread_out_t;
+int orbr_spread_global_ba(const orbr_spread_in_t *in, orbr_spread_out_t *out, int device);
+
 /* The host-array matcher entry points keep grow-only device scratch, a pinned mirror and one non-blocking stream
  * PER HOST THREAD (re-entrant without locks: the reference calls matchers from Tracking, LocalMapping and LoopClosing
  * threads at once, src/LocalMapping.cc:223, src/LoopClosing.cc:249).  Nothing is freed implicitly; a thread calls

@@ -166,6 +166,10 @@ ESSENTIAL_EXPORTS = ["orbg_optimize_essential_graph"]
 COVIS_EXPORTS = ["orbc_covisibility", "orbc_update_connections", "orbc_keyframe_culling", "orbc_update_normal_and_depth"]
 # the local map section (prefix orbt_), apart for the same reason
 LOCALMAP_EXPORTS = ["orbt_localmap_create", "orbt_localmap_destroy", "orbt_localmap_info", "orbt_localmap_set_map", "orbt_update_local_map"]
+# loop map correction (prefix orbr_), apart for the same reason
+MAPCORRECT_EXPORTS = ["orbr_correct_loop", "orbr_spread_global_ba"]
+MAPCORRECT_NORMAL_UNTOUCHED = 4      # ORBR_NORMAL_UNTOUCHED: no query owns the point (the other codes of a normal's status are ORBC_NORMAL_*)
+MAPCORRECT_SPREAD_UNTOUCHED, MAPCORRECT_SPREAD_GBA, MAPCORRECT_SPREAD_MOVED, MAPCORRECT_SPREAD_UNDEFINED = 0, 1, 2, 3      # ORBR_SPREAD_*
 # what include/orbx_dev.h declares on top: exported by the developer build only
 DEV_EXPORTS = ["orbx_debug_level_points", "orbx_debug_sincosf", "orbx_debug_blur_patches", "orbm_debug_features_in_area",
                "orbx_debug_blurred_level", "orbx_debug_octree_fallbacks", "orbm_debug_match_path", "orbm_debug_resolve_plan",
@@ -517,6 +521,8 @@ def _load(path, dev):
     L.orbt_localmap_info.argtypes = [vp, vp, vp, vp, vp, vp]
     L.orbt_localmap_set_map.argtypes = [vp, vp]
     L.orbt_update_local_map.argtypes = [vp, vp, i32, vp, i32, i32, i32, vp]
+    L.orbr_correct_loop.argtypes = [vp, vp, i32, vp, vp, vp, i32]
+    L.orbr_spread_global_ba.argtypes = [vp, vp, i32]
     if dev:
         L.orbx_debug_level_points.argtypes = [vp, i32, i32, i32, vp, i32, C.POINTER(i32)]
         L.orbx_debug_sincosf.argtypes = [vp, i32, vp, vp, i32]
@@ -1742,6 +1748,71 @@ def keyframe_culling(table, queries, monocular, th_obs=3, point_bad=True, check=
 def update_normal_and_depth(table, device=0):
     """MapPoint::UpdateNormalAndDepth of every point (orbc_update_normal_and_depth) -> [P] COVIS_NORMAL_DTYPE."""
     return covisibility(table, normals=True, device=device)["normals"]
+
+
+class MapCorrectLoopOut(C.Structure):      # orbr_loop_out_t
+    _fields_ = [("corrected", C.c_void_p), ("non_corrected", C.c_void_p), ("Tiw_new16", C.c_void_p), ("Ow_new3", C.c_void_p), ("pos3", C.c_void_p),
+                ("corrected_ref", C.c_void_p), ("normals", C.c_void_p)]
+
+
+class MapCorrectSpreadIn(C.Structure):     # orbr_spread_in_t
+    _fields_ = [("K", C.c_int32), ("Tcw16", C.c_void_p), ("TcwGBA16", C.c_void_p), ("kf_in_gba", C.c_void_p), ("child_off", C.c_void_p), ("child", C.c_void_p),
+                ("origins", C.c_void_p), ("n_origins", C.c_int32), ("P", C.c_int32), ("pos3", C.c_void_p), ("posGBA3", C.c_void_p), ("pt_in_gba", C.c_void_p),
+                ("ref_kf", C.c_void_p), ("bad", C.c_void_p)]
+
+
+class MapCorrectSpreadOut(C.Structure):    # orbr_spread_out_t
+    _fields_ = [("Tcw_new16", C.c_void_p), ("TcwGBA_out16", C.c_void_p), ("kf_marked", C.c_void_p), ("kf_reached", C.c_void_p), ("pos_out3", C.c_void_p), ("status", C.c_void_p),
+                ("levels", C.c_int32)]
+
+
+MAPCORRECT_SIM3_DTYPE = EG_SIM3_DTYPE      # orbg_sim3_t: the entries of CorrectedSim3 / NonCorrectedSim3
+
+
+def correct_loop_map(table, queries, cur, Tiw, Scw, device=0):
+    """LoopClosing::CorrectLoop's pose and point correction (src/LoopClosing.cc:444-525 without :524; orbr_correct_loop).  table:
+    covis_table(..); queries: covis_queries(..) of the connected keyframes, slots strictly ascending; cur: the slot of mpCurrentKF, one
+    of them; Tiw [Q, 4, 4]: GetPose() of each query; Scw: one MAPCORRECT_SIM3_DTYPE record, mg2oScw.
+    -> dict: corrected, non_corrected [Q] MAPCORRECT_SIM3_DTYPE; Tiw_new [Q, 4, 4]; Ow_new [Q, 3]; pos [P, 3]; corrected_ref [P] (the
+    owner's slot, -1: untouched); normals [P] COVIS_NORMAL_DTYPE (status MAPCORRECT_NORMAL_UNTOUCHED where no query owns the point)."""
+    L = matcher_lib()
+    ct, cq = _covis_c_table(table), _covis_c_queries(queries)
+    Q, P = len(queries["query_kf"]), len(table["pts"])
+    T = np.ascontiguousarray(Tiw, np.float32)
+    if T.shape != (Q, 4, 4):
+        raise ValueError("correct_loop_map: Tiw has shape %s for %d queries" % (T.shape, Q))
+    S = np.ascontiguousarray(Scw, MAPCORRECT_SIM3_DTYPE).reshape(1)
+    out = {"corrected": np.zeros(Q, MAPCORRECT_SIM3_DTYPE), "non_corrected": np.zeros(Q, MAPCORRECT_SIM3_DTYPE), "Tiw_new": np.zeros((Q, 4, 4), np.float32),
+           "Ow_new": np.zeros((Q, 3), np.float32), "pos": np.zeros((P, 3), np.float32), "corrected_ref": np.full(P, -1, np.int32),
+           "normals": np.zeros(P, COVIS_NORMAL_DTYPE)}
+    co = MapCorrectLoopOut(*[_p(out[k]) for k in ("corrected", "non_corrected", "Tiw_new", "Ow_new", "pos", "corrected_ref", "normals")])
+    _check(L.orbr_correct_loop(C.addressof(ct), C.addressof(cq), int(cur), _p(T), _p(S), C.addressof(co), int(device)), L)
+    return out
+
+
+def spread_global_ba(Tcw, TcwGBA, kf_in_gba, child_off, child, origins, pos, posGBA, pt_in_gba, ref_kf, bad, device=0):
+    """What LoopClosing::RunGlobalBundleAdjustment does after the optimisation (src/LoopClosing.cc:685-746; orbr_spread_global_ba).
+    Tcw, TcwGBA [K, 4, 4]; kf_in_gba [K]; child_off [K + 1] / child: GetChilds() as slots (localmap_graph builds them); origins:
+    mvpKeyFrameOrigins as slots; pos, posGBA [P, 3]; pt_in_gba [P]; ref_kf [P] (-1: none); bad [P].
+    -> dict: Tcw_new, TcwGBA [K, 4, 4]; kf_marked, kf_reached [K]; pos [P, 3]; status [P] (MAPCORRECT_SPREAD_*); levels: the launches over the tree."""
+    L = matcher_lib()
+    a = {"Tcw": np.ascontiguousarray(Tcw, np.float32), "TcwGBA": np.ascontiguousarray(TcwGBA, np.float32), "kf_in_gba": np.ascontiguousarray(kf_in_gba, np.uint8),
+         "child_off": np.ascontiguousarray(child_off, np.int32), "child": np.ascontiguousarray(child, np.int32).reshape(-1),
+         "origins": np.ascontiguousarray(origins, np.int32).reshape(-1), "pos": np.ascontiguousarray(pos, np.float32), "posGBA": np.ascontiguousarray(posGBA, np.float32),
+         "pt_in_gba": np.ascontiguousarray(pt_in_gba, np.uint8), "ref_kf": np.ascontiguousarray(ref_kf, np.int32), "bad": np.ascontiguousarray(bad, np.uint8)}
+    K, P = len(a["kf_in_gba"]), len(a["bad"])
+    if a["Tcw"].shape != (K, 4, 4) or a["TcwGBA"].shape != (K, 4, 4) or len(a["child_off"]) != K + 1:
+        raise ValueError("spread_global_ba: %d keyframes, poses %s / %s, %d child offsets" % (K, a["Tcw"].shape, a["TcwGBA"].shape, len(a["child_off"])))
+    if a["pos"].shape != (P, 3) or a["posGBA"].shape != (P, 3) or len(a["pt_in_gba"]) != P or len(a["ref_kf"]) != P:
+        raise ValueError("spread_global_ba: %d points, positions %s / %s" % (P, a["pos"].shape, a["posGBA"].shape))
+    out = {"Tcw_new": np.zeros((K, 4, 4), np.float32), "TcwGBA": np.zeros((K, 4, 4), np.float32), "kf_marked": np.zeros(K, np.uint8), "kf_reached": np.zeros(K, np.uint8),
+           "pos": np.zeros((P, 3), np.float32), "status": np.zeros(P, np.int32)}
+    si = MapCorrectSpreadIn(K, _p(a["Tcw"]), _p(a["TcwGBA"]), _p(a["kf_in_gba"]), _p(a["child_off"]), _p(a["child"]), _p(a["origins"]), len(a["origins"]), P,
+                            _p(a["pos"]), _p(a["posGBA"]), _p(a["pt_in_gba"]), _p(a["ref_kf"]), _p(a["bad"]))
+    so = MapCorrectSpreadOut(_p(out["Tcw_new"]), _p(out["TcwGBA"]), _p(out["kf_marked"]), _p(out["kf_reached"]), _p(out["pos"]), _p(out["status"]), 0)
+    _check(L.orbr_spread_global_ba(C.addressof(si), C.addressof(so), int(device)), L)
+    out["levels"] = int(so.levels)
+    return out
 
 
 class LocalMapMap(C.Structure):       # orbt_map_t

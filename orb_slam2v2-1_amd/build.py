@@ -12,7 +12,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "liborbx_hip.so")
 SOURCES = ["orbx_extract.hip", "orbx_pyramid.hip", "orbx_fast.hip", "orbx_octree.hip", "orbx_octree_wide.hip", "orbx_describe.hip",
-           "orbx_match.hip", "orbx_match_fast.hip", "orbx_bow.hip", "orbx_rgbd.hip", "orbx_rectify.hip", "orbx_cloud.hip", "orbx_octomap.hip", "orbx_kfdb.hip", "orbx_poseopt.hip", "orbx_initializer.hip", "orbx_sim3.hip", "orbx_pnp.hip", "orbx_sim3opt.hip", "orbx_newpoints.hip", "orbx_lba.hip", "orbx_essential.hip", "orbx_covis.hip", "orbx_localmap.hip"]
+           "orbx_match.hip", "orbx_match_fast.hip", "orbx_bow.hip", "orbx_rgbd.hip", "orbx_rectify.hip", "orbx_cloud.hip", "orbx_octomap.hip", "orbx_kfdb.hip", "orbx_poseopt.hip", "orbx_initializer.hip", "orbx_sim3.hip", "orbx_pnp.hip", "orbx_sim3opt.hip", "orbx_newpoints.hip", "orbx_lba.hip", "orbx_essential.hip", "orbx_covis.hip", "orbx_localmap.hip", "orbx_mapcorrect.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared",
          "-Wall", "-Wno-unused-value", "-Wno-unused-result"]
 
@@ -27,7 +27,7 @@ HOST_LIB = os.path.join(HERE, "lib", "liborb_host.so")
 
 def build_host(force=False, verbose=False):
     """C++ host classes (ORB_SLAM2::ORBextractor / ORBmatcher mirrors) over the C ABI: g++ only."""
-    srcs = [os.path.join(HOST, f) for f in ("ORBextractor.cc", "ORBmatcher.cc", "ORBVocabulary.cc", "PointCloudMapping.cc", "KeyFrameDatabase.cc", "Optimizer.cc", "Initializer.cc", "Sim3Solver.cc", "PnPsolver.cc", "LocalMapping.cc", "Covisibility.cc", "Tracking.cc")]
+    srcs = [os.path.join(HOST, f) for f in ("ORBextractor.cc", "ORBmatcher.cc", "ORBVocabulary.cc", "PointCloudMapping.cc", "KeyFrameDatabase.cc", "Optimizer.cc", "Initializer.cc", "Sim3Solver.cc", "PnPsolver.cc", "LocalMapping.cc", "Covisibility.cc", "Tracking.cc", "LoopClosing.cc")]
     deps = srcs + [os.path.join(HOST, f) for f in os.listdir(HOST)] + [LIB]
     if not force and os.path.exists(HOST_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(HOST_LIB) for d in deps):
         return HOST_LIB

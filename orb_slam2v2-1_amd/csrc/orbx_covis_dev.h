@@ -208,11 +208,15 @@ __device__ __forceinline__ void cov_cull(const CovTable &T, const CovQueries &Qs
         for (int p = threadIdx.x; p < T.P; p += COV_CULL_THREADS) point_bad[p] = cov_point_bad(T, bits, p) ? 1 : 0;
 }
 
-// ---- k_normals: src/MapPoint.cc:340-383 for one point, the arithmetic of host/frame_shim.h's MapPoint::UpdateNormalAndDepth
-__device__ __forceinline__ orbc_normal_t cov_normal(const CovTable &T, int p) {
+// ---- k_normals: src/MapPoint.cc:340-383 for one point, the arithmetic of host/frame_shim.h's MapPoint::UpdateNormalAndDepth.
+// pos: the point's position; ow(k): GetCameraCenter() of slot k as this point sees it (the table's for k_normals; orbx_mapcorrect_dev.h
+// hands in the one that LoopClosing::CorrectLoop's sequential loop would have left there)
+template <class OwFn>
+__device__ __forceinline__ orbc_normal_t cov_normal_at(const CovTable &T, int p, const float *pos, OwFn ow) {
     orbc_normal_t r;
     r.normal[0] = 0.f; r.normal[1] = 0.f; r.normal[2] = 0.f; r.max_distance = 0.f; r.min_distance = 0.f; r.status = ORBC_NORMAL_OK;
-    const orbc_point_t pt = T.pts[p];
+    orbc_point_t pt = T.pts[p];
+    pt.pos[0] = pos[0]; pt.pos[1] = pos[1]; pt.pos[2] = pos[2];
     const int lo = T.obs_off[p], hi = T.obs_off[p + 1];
     if (pt.bad) { r.status = ORBC_NORMAL_BAD; return r; }
     if (hi == lo) { r.status = ORBC_NORMAL_NO_OBSERVATION; return r; }
@@ -220,7 +224,7 @@ __device__ __forceinline__ orbc_normal_t cov_normal(const CovTable &T, int p) {
     int n = 0, level = -1;
     for (int o = lo; o < hi; o++) {
         const orbc_observation_t ob = T.obs[o];
-        const float *Owi = T.kf[ob.kf].Ow;
+        const float *Owi = ow(ob.kf);
         float normali[3];
         double s = 0;
         for (int k = 0; k < 3; k++) { normali[k] = pt.pos[k] - Owi[k]; s += (double)normali[k] * (double)normali[k]; }
@@ -230,7 +234,7 @@ __device__ __forceinline__ orbc_normal_t cov_normal(const CovTable &T, int p) {
         if (ob.kf == pt.ref_kf) level = ob.octave;
     }
     if (level < 0) { r.status = ORBC_NORMAL_NO_REFERENCE; return r; }
-    const float *Or = T.kf[pt.ref_kf].Ow;
+    const float *Or = ow(pt.ref_kf);
     double s = 0;
     for (int k = 0; k < 3; k++) { const float d = pt.pos[k] - Or[k]; s += (double)d * (double)d; }
     const float dist = (float)sqrt(s);
@@ -238,4 +242,7 @@ __device__ __forceinline__ orbc_normal_t cov_normal(const CovTable &T, int p) {
     r.min_distance = (float)orbx_div_rn((double)r.max_distance, (double)T.sf[T.nlevels - 1]);   // two floats' quotient rounded to double, then to float, is the correctly rounded float quotient (53 >= 2 * 24 + 2)
     for (int k = 0; k < 3; k++) r.normal[k] = (float)((double)normal[k] * (1.0 / n));
     return r;
+}
+__device__ __forceinline__ orbc_normal_t cov_normal(const CovTable &T, int p) {
+    return cov_normal_at(T, p, T.pts[p].pos, [&T](int k) { return T.kf[k].Ow; });
 }

@@ -19,6 +19,12 @@ __host__ __device__ __forceinline__ void gemm33(const float *a, const float *b, 
         for (int j = 0; j < 3; j++)
             d[i * 3 + j] = (float)((((double)a[i * 3] * (double)b[j * bj] + (double)a[i * 3 + 1] * (double)b[bk + j * bj]) + (double)a[i * 3 + 2] * (double)b[2 * bk + j * bj]) * alpha);
 }
+// cv::gemm, d = a * b on 4x4 (the poses' Tiw * Twc): (((a_i0 b_0j + a_i1 b_1j) + a_i2 b_2j) + a_i3 b_3j).  d may be neither a nor b
+__host__ __device__ __forceinline__ void gemm44(const float *a, const float *b, float *d) {
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++)
+            d[i * 4 + j] = (float)((((double)a[i * 4] * (double)b[j] + (double)a[i * 4 + 1] * (double)b[4 + j]) + (double)a[i * 4 + 2] * (double)b[8 + j]) + (double)a[i * 4 + 3] * (double)b[12 + j]);
+}
 // cv::gemm, d = alpha * a * x on a 3-vector: ((a_i0 x_0 + a_i1 x_1) + a_i2 x_2) * alpha
 __host__ __device__ __forceinline__ void gemv3(const float *a, const float *x, float *d, double alpha = 1.0, int lda = 3, int ldd = 1) {
     for (int i = 0; i < 3; i++)

@@ -51,6 +51,7 @@ extern "C" int orbx_thread_release_scratch(void) {
     orbx_internal_release_lba_scratch();
     orbx_internal_release_essential_scratch();
     orbx_internal_release_covis_scratch();
+    orbx_internal_release_mapcorrect_scratch();
     return ORBX_OK;
 }
 #ifdef ORBX_DEVELOPER

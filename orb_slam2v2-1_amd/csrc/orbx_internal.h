@@ -159,6 +159,7 @@ void orbx_internal_release_newpoints_scratch();              // orbx_newpoints.h
 void orbx_internal_release_lba_scratch();                    // orbx_lba.hip         (thread-local StagePair)
 void orbx_internal_release_essential_scratch();              // orbx_essential.hip   (thread-local StagePair)
 void orbx_internal_release_covis_scratch();                  // orbx_covis.hip       (thread-local StagePair)
+void orbx_internal_release_mapcorrect_scratch();             // orbx_mapcorrect.hip  (thread-local StagePair)
 // orbx_covis.hip: the host checks of an observation table and of a query set (ORBX_ERR_ARG with a message), for orbx_localmap.hip too
 int orbx_internal_cov_check_table(const char *fn, const orbc_table_t *t);
 int orbx_internal_cov_check_queries(const char *fn, const orbc_table_t *t, const orbc_queries_t *q, bool distinct);

@@ -4,7 +4,7 @@
 // device-wide synchronisation, so other threads' extractors and matchers keep running (the reference's Tracking / LocalMapping /
 // LoopClosing threads call matchers and solvers concurrently, src/LocalMapping.cc:223, src/LoopClosing.cc:249).
 // Users, each with a `static thread_local StagePair` of its own: orbx_match.hip, orbx_poseopt.hip, orbx_initializer.hip,
-// orbx_sim3.hip, orbx_pnp.hip, orbx_sim3opt.hip, orbx_newpoints.hip, orbx_lba.hip, orbx_essential.hip, orbx_covis.hip.
+// orbx_sim3.hip, orbx_pnp.hip, orbx_sim3opt.hip, orbx_newpoints.hip, orbx_lba.hip, orbx_essential.hip, orbx_covis.hip, orbx_mapcorrect.hip.
 #pragma once
 #include "orbx_internal.h"
 #include "orbx_stage_plan.h"   // stage_align, StagePlan: no HIP in them

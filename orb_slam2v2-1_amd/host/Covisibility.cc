@@ -104,6 +104,11 @@ void UpdateConnectionsHIP(const std::vector<KeyFrame *> &vpKFs) {
     if (vpKFs.empty()) return;
     CovisTables T;
     T.Build(vpKFs, std::vector<MapPoint *>());
+    UpdateConnectionsHIP(T, vpKFs);
+}
+
+void UpdateConnectionsHIP(CovisTables &T, const std::vector<KeyFrame *> &vpKFs) {
+    if (vpKFs.empty()) return;
     const int Q = (int)vpKFs.size(), K = T.table.K;
     std::vector<int32_t> ids((size_t)Q * K), ws((size_t)Q * K), n(Q), counters((size_t)Q * K);
     if (orbc_update_connections(&T.table, &T.queries, 15, K, ids.data(), ws.data(), n.data(), counters.data(), Covisibility::device) != ORBX_OK)

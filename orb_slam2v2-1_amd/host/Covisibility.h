@@ -39,6 +39,8 @@ struct CovisTables {
 // A keyframe none of whose points is seen elsewhere is left as it is (:324-325).  Throws std::runtime_error with orbx_last_error()
 // when the library reports an error (no GPU among them).
 void UpdateConnectionsHIP(const std::vector<KeyFrame *> &vpKFs);
+// ... on a table the caller built with T.Build(vpKFs, ..) (LoopClosing::CorrectLoopPoses: positions do not enter the connections)
+void UpdateConnectionsHIP(CovisTables &T, const std::vector<KeyFrame *> &vpKFs);
 // UpdateNormalAndDepth of every point of the list with ONE device call: writes mNormalVector, mfMaxDistance and mfMinDistance of
 // the points the reference's early return (:349, :359) lets through.  Throws as above.
 void UpdateNormalAndDepthHIP(const std::vector<MapPoint *> &vpMPs);

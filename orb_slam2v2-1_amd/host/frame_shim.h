@@ -35,6 +35,7 @@ public:
     std::vector<MapPoint *> GetAllMapPoints() { return mvpMapPoints; }
     std::vector<MapPoint *> mvpMapPoints;
     inline long unsigned int GetMaxKFid();   // src/Map.cc:106-110 (kept as a member there; the largest mnId in the map here)
+    std::vector<KeyFrame *> mvpKeyFrameOrigins;   // include/Map.h: where LoopClosing::RunGlobalBundleAdjustment starts its walk of the spanning tree
 };
 
 class MapPoint {

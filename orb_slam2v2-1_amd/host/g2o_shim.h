@@ -125,12 +125,12 @@ protected:
 };
 }  // namespace g2o
 
+// ORB_SLAM2::LoopClosing with its KeyFrameAndPose (include/LoopClosing.h:50-51, without Eigen's allocator), the name
+// Optimizer::OptimizeEssentialGraph's signature needs.  LoopClosing.h includes this header first: whichever of the two comes first,
+// g2o::Sim3 is complete when the class is declared
+#include "LoopClosing.h"
+
 namespace ORB_SLAM2 {
-class KeyFrame;
-class LoopClosing {   // include/LoopClosing.h:50-51: the one name Optimizer::OptimizeEssentialGraph's signature needs (without Eigen's allocator)
-public:
-    typedef std::map<KeyFrame *, g2o::Sim3, std::less<KeyFrame *> > KeyFrameAndPose;
-};
 class Converter {   // src/Converter.cc:105-151
 public:
     static Eigen::Matrix3d toMatrix3d(const cv::Mat &cvMat3) {
